@@ -7,7 +7,13 @@ fixed pattern (update_precision_values! -> ensure_numeric!) followed by one 64-R
 (workspace_solve(ws, B)), with nzval and B already resident in HBM. Symbolic analysis is
 excluded from the step and reported separately.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--nrhs R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid G] [--nrhs R] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (headline, phases of the timed steps, logdet of the
+last step). --full adds everything else the benchmark measures: the separate-call steps, logpdf, host I/O, cfg 3, the
+rooflines, the CPU baseline and, for N > 1, the distributed-X step, the per-level probe and the cfg-4 line.
+--dump-outputs DIR writes what the last timed step returned (a fixed sample of the rows of X, the column norms of X, logdet)
+as DIR/<name>.npy in float64, so that two builds can be compared output for output; the inputs are seeded.
 
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL). The headline is ONE
 factorisation + 64-RHS solve SHARDED over the N GPUs (strong scaling: `value` = n / step time;
@@ -79,6 +85,27 @@ def measure_copy_peak(dev, nbytes=1 << 30):
     ms = e0.elapsed_time(e1) / 5
     del a, b
     return 2.0 * nbytes / (ms * 1e-3) / 1e9
+
+
+DUMP_X_BYTES = 32 << 20    # --dump-outputs: the rows of X written stay under this (the whole dump under 64 MB)
+
+
+def output_rows(n, nrhs):
+    """The rows of X that --dump-outputs writes: all of them when they fit DUMP_X_BYTES, else a fixed seeded sample (sorted)."""
+    import numpy as np
+    k = max(1, min(n, DUMP_X_BYTES // (8 * nrhs)))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(2024).choice(n, k, replace=False))
+
+
+def dump_outputs(outdir, X_rows, rows, col_norms, logdet):
+    """--dump-outputs: what the timed call returned, in float64 -- X at `rows` (len(rows) x nrhs), the indices `rows`, the 2-norm
+    of every column of X over all n rows, and logdet"""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in (("X_sample", X_rows), ("X_sample_rows", rows), ("X_column_norms", col_norms), ("logdet", [logdet])):
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def sweep_model_bound(be, nrhs, copy_gbs, floor_us=LAUNCH_FLOOR_US, small_rows=64):
@@ -232,11 +259,12 @@ def probe_level_ms(Q, mesh, local_rank):
         probe.close()
 
 
-def bench_sharded(args, Q, mesh, dist, rank, world, local_rank, steps=None, warmup=None, level_ms=None, probe=True):
+def bench_sharded(args, Q, mesh, dist, rank, world, local_rank, steps=None, warmup=None, level_ms=None, probe=True, keep=None):
     """Strong scaling: ONE refactorisation + 64-RHS solve sharded over the ranks (gmrfx/shard.py): subtrees
     per rank, every top front on one rank of its group, contribution blocks / update vectors point-to-point along the
     owner-crossing tree edges (RCCL over xGMI), x of the top fronts broadcast by their owners. Returns the result dict
-    on rank 0 (None elsewhere); timed exactly like the replica loop (barrier + sync on both sides, max over ranks)."""
+    on rank 0 (None elsewhere); timed exactly like the replica loop (barrier + sync on both sides, max over ranks).
+    The distributed-X step and the per-level probe only run with --full. `keep` (rank 0): receives X and logdet."""
     import numpy as np
     import torch
     from gmrfx import shard
@@ -279,9 +307,11 @@ def bench_sharded(args, Q, mesh, dist, rank, world, local_rank, steps=None, warm
     for _ in range(warmup):
         step(True)
     el, info = timed(True, steps)
-    for _ in range(min(warmup, 2)):
-        step(False)
-    el_dist, _ = timed(False, steps)
+    el_dist = None
+    if args.full:
+        for _ in range(min(warmup, 2)):
+            step(False)
+        el_dist, _ = timed(False, steps)
     sf.solve_dev(d_B.data_ptr(), n, args.nrhs, d_X.data_ptr(), n, gather=True)      # (untimed: all of X on rank 0 for the check)
     torch.cuda.synchronize()
     # how many ranks the collective library really spans: a device all-reduce of ones (RCCL unless --rehearse)
@@ -295,11 +325,13 @@ def bench_sharded(args, Q, mesh, dist, rank, world, local_rank, steps=None, warm
     mem_sum = mem.clone(); dist.all_reduce(mem_sum, op=dist.ReduceOp.SUM)
     out = None
     if rank == 0:
-        if level_ms is None and probe:
+        if level_ms is None and probe and args.full:
             level_ms = probe_level_ms(Q, mesh, local_rank)
         lstep = None if level_ms is None else (np.asarray(level_ms["factor"]) + np.asarray(level_ms["fwd"]) + np.asarray(level_ms["bwd"]))
         plan = shard.plan_summary(sf.be, lstep)
         X = d_X.cpu().numpy().T
+        if keep is not None:
+            keep.update(X=X, logdet=ld)
         resid = float(np.linalg.norm(Q @ X - Bh.numpy().T) / np.linalg.norm(Bh.numpy()))
         bounds = {"flop_bound_speedup": plan["flop_bound_speedup"]}
         if lstep is not None:
@@ -313,7 +345,8 @@ def bench_sharded(args, Q, mesh, dist, rank, world, local_rank, steps=None, warm
                "per_rank_hbm_bytes": {"max_total": float(mem_max[0]), "max_factor_panels": float(mem_max[1]), "sum_factor_panels": float(mem_sum[1])},
                "exchange": "gloo + host staging (rehearsal)" if args.rehearse else "RCCL point-to-point (batch_isend_irecv) + broadcast + all-reduce over xGMI, stream-ordered (no host synchronisation between phases)",
                "x": "gathered on rank 0 in every timed step (the headline: the same work as the N = 1 line)",
-               "ms_per_step_x_distributed": 1e3 * float(el_dist.item()) / steps, "value_x_distributed": n / (float(el_dist.item()) / steps),
+               "ms_per_step_x_distributed": 1e3 * float(el_dist.item()) / steps if el_dist is not None else None,
+               "value_x_distributed": n / (float(el_dist.item()) / steps) if el_dist is not None else None,
                "b": "row-sharded: every rank holds the rows shard.needed_rows() names, zeros elsewhere",
                "rccl_ranks": rccl_ranks, "collective_backend": dist.get_backend(), "world_size": dist.get_world_size(),
                "check": {"logdet": ld, "rel_residual": resid, "info": info}}
@@ -408,7 +441,14 @@ def main():
     ap.add_argument("--pool", type=int, default=0,
                     help="extra: throughput of P independent workspaces driven concurrently on this GPU "
                          "(the reference's WorkspacePool pattern; reported separately, never as `value`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline (separate-call steps, logpdf, host I/O, cfg 3, rooflines, CPU "
+                         "baseline; N > 1: distributed-X step, per-level probe, cfg-4 line); --extras and --pool imply it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (sampled rows of X, column norms of X, logdet) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.extras or args.pool > 1:
+        args.full = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes (one per GPU) before
@@ -509,10 +549,17 @@ def main():
     logdet_timed = be.compute_logdet()
     fail_col_timed = be.stats()["fail_col"]
     pipelined_equals_separate = None
+    # --dump-outputs: what the timed call returned (rank 0; an N > 1 run replaces it with the sharded X when that is the headline)
+    X_out = None
+    if args.dump_outputs and rank == 0:
+        rows_out = output_rows(n, args.nrhs)
+        X_out = (d_X_timed.index_select(1, torch.from_numpy(rows_out).to(dev)).T.cpu().numpy(), rows_out,
+                 torch.linalg.vector_norm(d_X_timed, dim=1).cpu().numpy(), logdet_timed)
     if not args.separate_calls:
         pipelined_phases = {"factor": float(np.median(t_factor)), "behind_factor": float(np.median(t_solve)),
                             "forward_left_behind_factor": float(np.median(t_fwd)), "backward": float(np.median(t_bwd)),
                             "syrk_launches": float(np.median(t_syrk))}
+    if args.full and not args.separate_calls:
         t_factor, t_solve, t_fwd, t_bwd, t_perm, t_syrk_sep = [], [], [], [], [], []
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -532,7 +579,7 @@ def main():
     # Untimed by `value`; wall clock of 5 evaluations including the two scalar read-backs each. Runs right after the
     # timed steps, before the host-side checks below (their BLAS / sparse products leave busy host threads behind).
     logpdf_ms = ms_quadform = logpdf_relerr = None
-    if rank == 0 and not args.no_logpdf:
+    if args.full and rank == 0 and not args.no_logpdf:
         d_z = d_B[0]
         def logpdf_eval():
             # ONE call: factorisation, r'Qr beside it, logdet behind it, one synchronisation (gmrfx_refactorize_logpdf_dev)
@@ -553,7 +600,7 @@ def main():
     # host_download); nothing is overlapped with the factorisation (a transfer beside it slows its launch chain by more than it hides).
     # Untimed by `value`; pageable arrays (a Julia Matrix) and page-locked ones.
     host_io = None
-    if rank == 0 and not args.no_host_io:
+    if args.full and rank == 0 and not args.no_host_io:
         nzh = np.ascontiguousarray(Q.data)
         host_io = {}
         for kind in ("pageable", "pinned"):
@@ -577,9 +624,11 @@ def main():
         be.refactorize_dev(d_nz.data_ptr())
 
     # ---- untimed correctness evidence on this very run: the output of the TIMED call ---------
-    X = d_X_timed.cpu().numpy().T            # n x nrhs
-    Bn = Bh.numpy().T
-    resid = float(np.linalg.norm(Q @ X - Bn) / np.linalg.norm(Bn))
+    resid = None
+    if args.full:
+        X = d_X_timed.cpu().numpy().T            # n x nrhs
+        Bn = Bh.numpy().T
+        resid = float(np.linalg.norm(Q @ X - Bn) / np.linalg.norm(Bn))
     logdet = logdet_timed
     st = be.stats()
     if logpdf_ms is not None:
@@ -590,7 +639,7 @@ def main():
 
     extras = {}
     cfg3 = None
-    if not args.no_cfg3 and rank == 0:
+    if args.full and not args.no_cfg3 and rank == 0:
         # BASELINE cfg 3 on the same factor (untimed by `value`; median of 3 each): Takahashi selected inverse on pattern(L)
         # (compute_selinv!, backend.jl:226-257) and 256 samples P' L^-T z (backend_backward_solve, backend.jl:281-284)
         t_sel, t_rand = [], []
@@ -693,132 +742,7 @@ def main():
 
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
-        med = lambda v: float(np.median(v))
-        mf, ms_, mfw, mbw = med(t_factor), med(t_solve), med(t_fwd), med(t_bwd)
-        # algorithmic bytes of one triangular sweep: 8 nnz(L) + 4 sum_s r_s + 2*8*n*nrhs
-        # (round 6: the TRUE nnz(L) -- amalgamation zeros and panel padding are this implementation's bytes, not the algorithm's; the
-        #  figure on the stored entries, which rounds 1-5 quoted, stays beside it as frac_on_stored_entries)
         nnzl = st["nnz_l_stored"]
-        bytes_sweep = 8.0 * st["nnz_l"] + 4.0 * st["sum_rows"] + 16.0 * n * args.nrhs
-        bytes_sweep_stored = 8.0 * nnzl + 4.0 * st["sum_rows"] + 16.0 * n * args.nrhs
-        sweep_ms = 0.5 * (mfw + mbw)
-        sweep_gbs = bytes_sweep / (sweep_ms * 1e-3) / 1e9
-        copy_gbs = measure_copy_peak(dev)
-        try:
-            smb = sweep_model_bound(be, args.nrhs, copy_gbs)
-            smb_guide = sweep_model_bound(be, args.nrhs, COPY_PEAK_GUIDE_GBS)       # the same sum at the guide's achievable copy rate
-        except Exception as ex:        # (the bound is a report, never a reason to lose the line)
-            smb = {"error": repr(ex)}
-        factor_tf = st["factor_flops"] / (mf * 1e-3) / 1e12
-        # HBM traffic from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate
-        # runs, gfx950 FETCH_SIZE x2 correction): only valid for the workload they were collected on
-        # The counters cannot be read inside this process, so `traffic` is a COMMITTED counter pass (tools/pmc_traffic.py,
-        # tools/cfg3_profile.py): each file names the source tree it was collected on (csrc_hash = gmrfx._lib.source_tree_hash()),
-        # and its figures are quoted only while the tree being timed is that tree -- otherwise traffic is null.
-        from gmrfx._lib import source_tree_hash
-        tree_hash = source_tree_hash()
-        pmc, pmc_note = None, "no counter pass for this workload under profiles/"
-        try:
-            with open(os.path.join(ROOT, "profiles", "r06_pmc_traffic.json")) as fh:
-                pj = json.load(fh)
-            if pj["workload"] == {"grid": args.grid, "nrhs": args.nrhs}:
-                if pj.get("csrc_hash") == tree_hash:
-                    pmc, pmc_note = pj, f"profiles/r06_pmc_traffic.json, collected on source tree {tree_hash} = the tree being timed"
-                else:
-                    pmc_note = (f"null: profiles/r06_pmc_traffic.json belongs to source tree {pj.get('csrc_hash')}, the tree being timed is "
-                                f"{tree_hash} (re-run tools/final_profile.sh)")
-        except Exception:
-            pmc = None
-        # ---- roofline of the DOMINANT KERNEL: k_syrk_cb_rec (contribution-block SYRK, ~18 % of the step) ----
-        # algorithmic flops: sum over the big fronts of c m (m + 1) (lower triangle of the m x m block,
-        # 2 c flops per entry), one launch per level; time: HIP events around every launch, recorded by
-        # the library on the stream the kernel runs on (gmrfx_stats.ms_syrk), median over the timed steps
-        ms_syrk = med(t_syrk)
-        n_launch = max(int(st["syrk_launches"]), 1)
-        syrk_tf = st["syrk_flops"] / (ms_syrk * 1e-3) / 1e12
-        per_k = (pmc or {}).get("per_kernel_GB_per_step", {})
-        # (round 6: two instantiations -- <true>: the software-pipelined product loop of the levels of wide fronts, <false>: the rest;
-        #  one launch per level, either one or the other: their bytes and launches add up to the kernel's)
-        inst = [v for k, v in per_k.items() if k == "k_syrk_cb_rec" or k.startswith("k_syrk_cb_rec<")]
-        pk = ({"fetch_x2": sum(v["fetch_x2"] for v in inst), "write": sum(v["write"] for v in inst)} if inst else per_k.get("k_syrk_cb"))
-        roof_kernel = {"bound": "mfma", "achieved": syrk_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                       "frac": syrk_tf / FP64_MFMA_PEAK_TF,
-                       "traffic": (1e9 * (pk["fetch_x2"] + pk["write"]) / n_launch) if pk else None,
-                       "peak_measured": FP64_MFMA_MEASURED_TF, "frac_of_measured_peak": syrk_tf / FP64_MFMA_MEASURED_TF,
-                       "kernel": "k_syrk_cb_rec", "instantiations": "k_syrk_cb_rec<true> (levels whose widest front has >= 128 columns: pipelined "
-                                                                     "product loop) + k_syrk_cb_rec<false> (the levels below)",
-                       "launches_per_step": n_launch, "avg_launch_ms": ms_syrk / n_launch,
-                       "flops_per_launch": st["syrk_flops"] / n_launch, "ms_per_step": ms_syrk,
-                       "note": "achieved = algorithmic flops of the launches of one step / their summed HIP-event time over the "
-                               "timed (pipelined) steps -- the forward sweep of the same step runs beside some of them; "
-                               "traffic = PMC HBM bytes per launch (" + pmc_note + ")"}
-        if pipelined_phases is not None:
-            alone = pipelined_phases["syrk_launches_separate"]
-            roof_kernel.update({"ms_per_step_alone": alone, "achieved_alone": st["syrk_flops"] / (alone * 1e-3) / 1e12,
-                                "frac_alone": st["syrk_flops"] / (alone * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF})
-        roof_factor = {"bound": "mfma", "achieved": factor_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                       "frac": factor_tf / FP64_MFMA_PEAK_TF, "traffic": pmc["factor"]["total_bytes"] if pmc else None,
-                       "peak_measured": FP64_MFMA_MEASURED_TF, "frac_of_measured_peak": factor_tf / FP64_MFMA_MEASURED_TF,
-                       "kernel": "numeric factorisation (all ~500 launches)", "ms": mf, "flops": st["factor_flops"], "note": "traffic: " + pmc_note}
-        roof_sweep = {"bound": "hbm", "achieved": sweep_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                      "frac": sweep_gbs / HBM_PEAK_GBS,
-                      "traffic": 0.5 * (pmc["sweep_forward"]["total_bytes"] + pmc["sweep_backward"]["total_bytes"]) if pmc else None,
-                      "kernel": "triangular sweep (mean of forward and backward, all launches)", "ms": sweep_ms, "bytes": bytes_sweep,
-                      "frac_on_stored_entries": bytes_sweep_stored / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                      "copy_peak_measured": copy_gbs, "frac_of_copy_peak": sweep_gbs / copy_gbs,
-                      "note": "bytes = 8 nnz(L) [true fill] + 4 sum r_s + 16 n nrhs (SURVEY 8d); traffic: " + pmc_note}
-        if "error" not in smb:
-            roof_sweep.update({
-                "model_bound_ms": {"fwd": smb["fwd_ms"], "bwd": smb["bwd_ms"], "mean": 0.5 * (smb["fwd_ms"] + smb["bwd_ms"])},
-                "model_bound_ms_at_guide_copy_peak": {"copy_peak_gbs": COPY_PEAK_GUIDE_GBS, "fwd": smb_guide["fwd_ms"], "bwd": smb_guide["bwd_ms"],
-                                                      "mean": 0.5 * (smb_guide["fwd_ms"] + smb_guide["bwd_ms"]),
-                                                      "frac_of_it": 0.5 * (smb_guide["fwd_ms"] + smb_guide["bwd_ms"]) / sweep_ms},
-                "frac_of_model_bound": 0.5 * (smb["fwd_ms"] + smb["bwd_ms"]) / sweep_ms,
-                "frac_of_model_bound_fwd": smb["fwd_ms"] / mfw, "frac_of_model_bound_bwd": smb["bwd_ms"] / mbw,
-                "model_bound": {"copy_peak_gbs": copy_gbs, "launch_floor_us": LAUNCH_FLOOR_US, "fwd_launches": smb["fwd_launches"],
-                                "bwd_launches": smb["bwd_launches"], "fwd_bytes": smb["fwd_bytes"], "bwd_bytes": smb["bwd_bytes"],
-                                "handoff_bytes_fwd": smb["handoff_bytes_fwd"], "handoff_bytes_bwd": smb["handoff_bytes_bwd"],
-                                # what the schedule itself forfeits of the 70 % target: the algorithmic bytes over the bound's time
-                                "ceiling_frac_of_hbm_peak": bytes_sweep / (0.5 * (smb["fwd_ms"] + smb["bwd_ms"]) * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                "note": "sum over the task launch and every level of (algorithmic + hand-off bytes) / measured copy peak "
-                                        "+ launches x floor (bench.py sweep_model_bound); ceiling_frac = the roofline fraction a sweep "
-                                        "running AT this bound would show"}})
-        else:
-            roof_sweep["model_bound_ms"] = None
-            roof_sweep["model_bound_error"] = smb["error"]
-        if roof_sweep["traffic"]:
-            # the bytes the sweeps really move (PMC), W / x hand-off between the levels included, against the same peak
-            roof_sweep["frac_of_peak_with_measured_traffic"] = roof_sweep["traffic"] / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        roof_cfg3 = {}
-        pmc3, pmc3_note = None, "no counter pass for this workload under profiles/"
-        try:
-            with open(os.path.join(ROOT, "profiles", "r06_cfg3_pmc_traffic.json")) as fh:
-                p3 = json.load(fh)
-            if p3["workload"]["grid"] == args.grid:
-                if p3.get("csrc_hash") == tree_hash:
-                    pmc3, pmc3_note = p3, f"profiles/r06_cfg3_pmc_traffic.json, collected on source tree {tree_hash} = the tree being timed"
-                else:
-                    pmc3_note = f"null: profiles/r06_cfg3_pmc_traffic.json belongs to source tree {p3.get('csrc_hash')}, the tree being timed is {tree_hash}"
-        except Exception:
-            pmc3 = None
-        if cfg3 is not None:
-            sel_tf = cfg3["sel_flops"] / (extras["ms_selinv"] * 1e-3) / 1e12
-            roof_cfg3["roofline_selinv"] = {
-                "bound": "mfma", "achieved": sel_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": sel_tf / FP64_MFMA_PEAK_TF,
-                "traffic": pmc3["selinv"]["total_bytes"] if pmc3 else None,
-                "kernel": "selected inversion on pattern(L) (all launches; dominant: k_sel_dense, Z21 = -Z22 Y of the big fronts)",
-                "ms": extras["ms_selinv"], "flops": cfg3["sel_flops"], "flops_over_factor_flops": cfg3["sel_flops"] / st["factor_flops"],
-                "bytes_min": 16.0 * nnzl, "gbs_on_bytes_min": 16.0 * nnzl / (extras["ms_selinv"] * 1e-3) / 1e9,
-                "note": "cfg 3: flops = sum_s 2 c m^2 + 4 c^2 m + 2 c^3 / 3 (Takahashi recursion through the dense inverse of L11); "
-                        "bytes_min = L read + Z written once; traffic: " + pmc3_note}
-            # 256 samples = 4 passes of 64 columns, each one backward sweep + the transposes of its columns (SURVEY 8d:
-            # bytes_backward_solve = bytes_sweep + 8 n nrhs)
-            rb = 4.0 * (8.0 * nnzl + 4.0 * st["sum_rows"] + 16.0 * n * 64 + 8.0 * n * 64)
-            roof_cfg3["roofline_rand256"] = {
-                "bound": "hbm", "achieved": rb / (extras["ms_rand256"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": rb / (extras["ms_rand256"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc3["rand256"]["total_bytes"] if pmc3 else None,
-                "kernel": "256 samples P' L^-T z: 4 backward sweeps of 64 columns on two lanes", "ms": extras["ms_rand256"], "bytes": rb,
-                "note": "traffic: " + pmc3_note}
         out = {
             "metric": "factor+solve(64 RHS) throughput", "value": world * n / (elapsed / args.steps), "unit": "DoF/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -828,35 +752,165 @@ def main():
                        "n": n, "nnz_Q": int(Q.nnz), "nnz_L": int(st["nnz_l"]), "nnz_L_stored": int(nnzl),
                        "nrhs": args.nrhs, "parallelism": "1 workspace per GPU (replicas)" if world > 1 else "1 GPU",
                        "ordering": "own geometric nested dissection"},
-            "roofline": roof_kernel,
-            "roofline_factor": roof_factor, "roofline_sweep": roof_sweep, **roof_cfg3,
             "step_call": "gmrfx_refactorize_dev + gmrfx_solve_dev" if args.separate_calls else
                          "gmrfx_refactorize_solve_dev (one pipelined call; include/gmrfx.h)",
-            "ms_per_step_separate_calls": ms_step_separate, "pipelined_phases_ms": pipelined_phases,
-            # the same step through the HOST entry point (what the reference's seam hands over): never `value`
-            "ms_per_step_host_io": host_io["pageable"]["ms_per_step"] if host_io else None,
-            "value_host_io": host_io["pageable"]["dof_per_s"] if host_io else None,
-            "host_io": ({**host_io, "call": "gmrfx_refactorize_solve(nzval, B, X): column-major HOST arrays, n x nrhs doubles each way over PCIe "
-                                            "inside the timed call; upload IN FRONT of the factorisation (staged by host threads when pageable), X out in slices behind the backward sweep"}
-                        if host_io else None),
-            "phases_ms": {"factor": mf, "solve": ms_, "solve_fwd": mfw, "solve_bwd": mbw, "solve_perm": med(t_perm),
-                          "symbolic_host": st0["ms_symbolic"], **extras},
-            "logpdf_per_s": (1e3 / logpdf_ms) if logpdf_ms else None, "logpdf_ms": logpdf_ms, "ms_quadform": ms_quadform,
-            "logpdf_relerr_vs_host": logpdf_relerr,
-            "check": {"rel_residual": resid, "logdet": logdet, "fail_col": fail_col_timed,
-                      "of": "the output of the timed call (copied out before any other call wrote d_X)",
-                      "pipelined_equals_separate": pipelined_equals_separate},
+            "pipelined_phases_ms": pipelined_phases,
+            "check": {"logdet": logdet, "fail_col": fail_col_timed,
+                      "of": "the output of the timed call (copied out before any other call wrote d_X)"},
             "supernodes": int(st["nsuper"]), "levels": int(st["nlevels"]),
-            "hbm_bytes_allocated": st["bytes_device_total"],
+            "hbm_bytes_allocated": st["bytes_device_total"], "full": args.full,
         }
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(Q, mesh, args.nrhs)
+        if args.full:
+            med = lambda v: float(np.median(v))
+            mf, ms_, mfw, mbw = med(t_factor), med(t_solve), med(t_fwd), med(t_bwd)
+            # algorithmic bytes of one triangular sweep: 8 nnz(L) + 4 sum_s r_s + 2*8*n*nrhs
+            # (round 6: the TRUE nnz(L) -- amalgamation zeros and panel padding are this implementation's bytes, not the algorithm's; the
+            #  figure on the stored entries, which rounds 1-5 quoted, stays beside it as frac_on_stored_entries)
+            bytes_sweep = 8.0 * st["nnz_l"] + 4.0 * st["sum_rows"] + 16.0 * n * args.nrhs
+            bytes_sweep_stored = 8.0 * nnzl + 4.0 * st["sum_rows"] + 16.0 * n * args.nrhs
+            sweep_ms = 0.5 * (mfw + mbw)
+            sweep_gbs = bytes_sweep / (sweep_ms * 1e-3) / 1e9
+            copy_gbs = measure_copy_peak(dev)
+            try:
+                smb = sweep_model_bound(be, args.nrhs, copy_gbs)
+                smb_guide = sweep_model_bound(be, args.nrhs, COPY_PEAK_GUIDE_GBS)       # the same sum at the guide's achievable copy rate
+            except Exception as ex:        # (the bound is a report, never a reason to lose the line)
+                smb = {"error": repr(ex)}
+            factor_tf = st["factor_flops"] / (mf * 1e-3) / 1e12
+            # HBM traffic from the committed PMC passes (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate
+            # runs, gfx950 FETCH_SIZE x2 correction): only valid for the workload they were collected on
+            # The counters cannot be read inside this process, so `traffic` is a COMMITTED counter pass (tools/pmc_traffic.py,
+            # tools/cfg3_profile.py): each file names the source tree it was collected on (csrc_hash = gmrfx._lib.source_tree_hash()),
+            # and its figures are quoted only while the tree being timed is that tree -- otherwise traffic is null.
+            from gmrfx._lib import source_tree_hash
+            tree_hash = source_tree_hash()
+            pmc, pmc_note = None, "no counter pass for this workload under profiles/"
+            try:
+                with open(os.path.join(ROOT, "profiles", "r06_pmc_traffic.json")) as fh:
+                    pj = json.load(fh)
+                if pj["workload"] == {"grid": args.grid, "nrhs": args.nrhs}:
+                    if pj.get("csrc_hash") == tree_hash:
+                        pmc, pmc_note = pj, f"profiles/r06_pmc_traffic.json, collected on source tree {tree_hash} = the tree being timed"
+                    else:
+                        pmc_note = (f"null: profiles/r06_pmc_traffic.json belongs to source tree {pj.get('csrc_hash')}, the tree being timed is "
+                                    f"{tree_hash} (re-run tools/final_profile.sh)")
+            except Exception:
+                pmc = None
+            # ---- roofline of the DOMINANT KERNEL: k_syrk_cb_rec (contribution-block SYRK, ~18 % of the step) ----
+            # algorithmic flops: sum over the big fronts of c m (m + 1) (lower triangle of the m x m block,
+            # 2 c flops per entry), one launch per level; time: HIP events around every launch, recorded by
+            # the library on the stream the kernel runs on (gmrfx_stats.ms_syrk), median over the timed steps
+            ms_syrk = med(t_syrk)
+            n_launch = max(int(st["syrk_launches"]), 1)
+            syrk_tf = st["syrk_flops"] / (ms_syrk * 1e-3) / 1e12
+            per_k = (pmc or {}).get("per_kernel_GB_per_step", {})
+            # (round 6: two instantiations -- <true>: the software-pipelined product loop of the levels of wide fronts, <false>: the rest;
+            #  one launch per level, either one or the other: their bytes and launches add up to the kernel's)
+            inst = [v for k, v in per_k.items() if k == "k_syrk_cb_rec" or k.startswith("k_syrk_cb_rec<")]
+            pk = ({"fetch_x2": sum(v["fetch_x2"] for v in inst), "write": sum(v["write"] for v in inst)} if inst else per_k.get("k_syrk_cb"))
+            roof_kernel = {"bound": "mfma", "achieved": syrk_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                           "frac": syrk_tf / FP64_MFMA_PEAK_TF,
+                           "traffic": (1e9 * (pk["fetch_x2"] + pk["write"]) / n_launch) if pk else None,
+                           "peak_measured": FP64_MFMA_MEASURED_TF, "frac_of_measured_peak": syrk_tf / FP64_MFMA_MEASURED_TF,
+                           "kernel": "k_syrk_cb_rec", "instantiations": "k_syrk_cb_rec<true> (levels whose widest front has >= 128 columns: pipelined "
+                                                                         "product loop) + k_syrk_cb_rec<false> (the levels below)",
+                           "launches_per_step": n_launch, "avg_launch_ms": ms_syrk / n_launch,
+                           "flops_per_launch": st["syrk_flops"] / n_launch, "ms_per_step": ms_syrk,
+                           "note": "achieved = algorithmic flops of the launches of one step / their summed HIP-event time over the "
+                                   "timed (pipelined) steps -- the forward sweep of the same step runs beside some of them; "
+                                   "traffic = PMC HBM bytes per launch (" + pmc_note + ")"}
+            if pipelined_phases is not None:
+                alone = pipelined_phases["syrk_launches_separate"]
+                roof_kernel.update({"ms_per_step_alone": alone, "achieved_alone": st["syrk_flops"] / (alone * 1e-3) / 1e12,
+                                    "frac_alone": st["syrk_flops"] / (alone * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF})
+            roof_factor = {"bound": "mfma", "achieved": factor_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                           "frac": factor_tf / FP64_MFMA_PEAK_TF, "traffic": pmc["factor"]["total_bytes"] if pmc else None,
+                           "peak_measured": FP64_MFMA_MEASURED_TF, "frac_of_measured_peak": factor_tf / FP64_MFMA_MEASURED_TF,
+                           "kernel": "numeric factorisation (all ~500 launches)", "ms": mf, "flops": st["factor_flops"], "note": "traffic: " + pmc_note}
+            roof_sweep = {"bound": "hbm", "achieved": sweep_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": sweep_gbs / HBM_PEAK_GBS,
+                          "traffic": 0.5 * (pmc["sweep_forward"]["total_bytes"] + pmc["sweep_backward"]["total_bytes"]) if pmc else None,
+                          "kernel": "triangular sweep (mean of forward and backward, all launches)", "ms": sweep_ms, "bytes": bytes_sweep,
+                          "frac_on_stored_entries": bytes_sweep_stored / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          "copy_peak_measured": copy_gbs, "frac_of_copy_peak": sweep_gbs / copy_gbs,
+                          "note": "bytes = 8 nnz(L) [true fill] + 4 sum r_s + 16 n nrhs (SURVEY 8d); traffic: " + pmc_note}
+            if "error" not in smb:
+                roof_sweep.update({
+                    "model_bound_ms": {"fwd": smb["fwd_ms"], "bwd": smb["bwd_ms"], "mean": 0.5 * (smb["fwd_ms"] + smb["bwd_ms"])},
+                    "model_bound_ms_at_guide_copy_peak": {"copy_peak_gbs": COPY_PEAK_GUIDE_GBS, "fwd": smb_guide["fwd_ms"], "bwd": smb_guide["bwd_ms"],
+                                                          "mean": 0.5 * (smb_guide["fwd_ms"] + smb_guide["bwd_ms"]),
+                                                          "frac_of_it": 0.5 * (smb_guide["fwd_ms"] + smb_guide["bwd_ms"]) / sweep_ms},
+                    "frac_of_model_bound": 0.5 * (smb["fwd_ms"] + smb["bwd_ms"]) / sweep_ms,
+                    "frac_of_model_bound_fwd": smb["fwd_ms"] / mfw, "frac_of_model_bound_bwd": smb["bwd_ms"] / mbw,
+                    "model_bound": {"copy_peak_gbs": copy_gbs, "launch_floor_us": LAUNCH_FLOOR_US, "fwd_launches": smb["fwd_launches"],
+                                    "bwd_launches": smb["bwd_launches"], "fwd_bytes": smb["fwd_bytes"], "bwd_bytes": smb["bwd_bytes"],
+                                    "handoff_bytes_fwd": smb["handoff_bytes_fwd"], "handoff_bytes_bwd": smb["handoff_bytes_bwd"],
+                                    # what the schedule itself forfeits of the 70 % target: the algorithmic bytes over the bound's time
+                                    "ceiling_frac_of_hbm_peak": bytes_sweep / (0.5 * (smb["fwd_ms"] + smb["bwd_ms"]) * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    "note": "sum over the task launch and every level of (algorithmic + hand-off bytes) / measured copy peak "
+                                            "+ launches x floor (bench.py sweep_model_bound); ceiling_frac = the roofline fraction a sweep "
+                                            "running AT this bound would show"}})
+            else:
+                roof_sweep["model_bound_ms"] = None
+                roof_sweep["model_bound_error"] = smb["error"]
+            if roof_sweep["traffic"]:
+                # the bytes the sweeps really move (PMC), W / x hand-off between the levels included, against the same peak
+                roof_sweep["frac_of_peak_with_measured_traffic"] = roof_sweep["traffic"] / (sweep_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+            roof_cfg3 = {}
+            pmc3, pmc3_note = None, "no counter pass for this workload under profiles/"
+            try:
+                with open(os.path.join(ROOT, "profiles", "r06_cfg3_pmc_traffic.json")) as fh:
+                    p3 = json.load(fh)
+                if p3["workload"]["grid"] == args.grid:
+                    if p3.get("csrc_hash") == tree_hash:
+                        pmc3, pmc3_note = p3, f"profiles/r06_cfg3_pmc_traffic.json, collected on source tree {tree_hash} = the tree being timed"
+                    else:
+                        pmc3_note = f"null: profiles/r06_cfg3_pmc_traffic.json belongs to source tree {p3.get('csrc_hash')}, the tree being timed is {tree_hash}"
+            except Exception:
+                pmc3 = None
+            if cfg3 is not None:
+                sel_tf = cfg3["sel_flops"] / (extras["ms_selinv"] * 1e-3) / 1e12
+                roof_cfg3["roofline_selinv"] = {
+                    "bound": "mfma", "achieved": sel_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": sel_tf / FP64_MFMA_PEAK_TF,
+                    "traffic": pmc3["selinv"]["total_bytes"] if pmc3 else None,
+                    "kernel": "selected inversion on pattern(L) (all launches; dominant: k_sel_dense, Z21 = -Z22 Y of the big fronts)",
+                    "ms": extras["ms_selinv"], "flops": cfg3["sel_flops"], "flops_over_factor_flops": cfg3["sel_flops"] / st["factor_flops"],
+                    "bytes_min": 16.0 * nnzl, "gbs_on_bytes_min": 16.0 * nnzl / (extras["ms_selinv"] * 1e-3) / 1e9,
+                    "note": "cfg 3: flops = sum_s 2 c m^2 + 4 c^2 m + 2 c^3 / 3 (Takahashi recursion through the dense inverse of L11); "
+                            "bytes_min = L read + Z written once; traffic: " + pmc3_note}
+                # 256 samples = 4 passes of 64 columns, each one backward sweep + the transposes of its columns (SURVEY 8d:
+                # bytes_backward_solve = bytes_sweep + 8 n nrhs)
+                rb = 4.0 * (8.0 * nnzl + 4.0 * st["sum_rows"] + 16.0 * n * 64 + 8.0 * n * 64)
+                roof_cfg3["roofline_rand256"] = {
+                    "bound": "hbm", "achieved": rb / (extras["ms_rand256"] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": rb / (extras["ms_rand256"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": pmc3["rand256"]["total_bytes"] if pmc3 else None,
+                    "kernel": "256 samples P' L^-T z: 4 backward sweeps of 64 columns on two lanes", "ms": extras["ms_rand256"], "bytes": rb,
+                    "note": "traffic: " + pmc3_note}
+            out.update({
+                "roofline": roof_kernel,
+                "roofline_factor": roof_factor, "roofline_sweep": roof_sweep, **roof_cfg3,
+                "ms_per_step_separate_calls": ms_step_separate,
+                # the same step through the HOST entry point (what the reference's seam hands over): never `value`
+                "ms_per_step_host_io": host_io["pageable"]["ms_per_step"] if host_io else None,
+                "value_host_io": host_io["pageable"]["dof_per_s"] if host_io else None,
+                "host_io": ({**host_io, "call": "gmrfx_refactorize_solve(nzval, B, X): column-major HOST arrays, n x nrhs doubles each way over PCIe "
+                                                "inside the timed call; upload IN FRONT of the factorisation (staged by host threads when pageable), X out in slices behind the backward sweep"}
+                            if host_io else None),
+                "phases_ms": {"factor": mf, "solve": ms_, "solve_fwd": mfw, "solve_bwd": mbw, "solve_perm": med(t_perm),
+                              "symbolic_host": st0["ms_symbolic"], **extras},
+                "logpdf_per_s": (1e3 / logpdf_ms) if logpdf_ms else None, "logpdf_ms": logpdf_ms, "ms_quadform": ms_quadform,
+                "logpdf_relerr_vs_host": logpdf_relerr,
+            })
+            out["check"].update({"rel_residual": resid, "pipelined_equals_separate": pipelined_equals_separate})
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(Q, mesh, args.nrhs)
 
     # ---- N > 1: ONE factorisation sharded over the ranks (the headline of a multi-GPU run), LAST and under a watchdog:
     # the replica line above is complete by now, and an exchange that never completes (the sharded path has not run on
     # a multi-GPU node yet) must not take it down. Every rank arms the same timer at the same barrier; when it fires,
     # rank 0 prints the replica line with the failure recorded and all ranks leave.
     sharded = None
+    sharded_out = {}
     shard_raised = False
     printed = [False]
     out_lock = None
@@ -891,7 +945,7 @@ def main():
         watchdog.daemon = True
         watchdog.start()
         try:
-            sharded = bench_sharded(args, Q, mesh, dist, rank, world, local_rank)
+            sharded = bench_sharded(args, Q, mesh, dist, rank, world, local_rank, keep=sharded_out)
         except Exception as e:           # the replica line must survive a failure of the sharded path
             sharded = {"error": repr(e)} if rank == 0 else None
             shard_raised = True
@@ -911,7 +965,7 @@ def main():
                 out["sharded"] = sharded
             out["replicas"] = replicas
 
-    if dist is not None and not args.no_shard and not args.no_cfg4:
+    if dist is not None and not args.no_shard and not args.no_cfg4 and args.full:
         # the configuration that CAN scale (3-D: the flops sit in a few huge fronts), next to the graded cfg-2 line; its
         # failure is recorded in the line but does not change the exit code (the headline is cfg 2)
         # every rank takes the same decision: 2 = the sharded cfg-2 run raised somewhere, 1 = some rank has less than --cfg4-budget
@@ -938,6 +992,11 @@ def main():
                 with out_lock:
                     out["cfg4_sharded"] = cfg4
 
+    if rank == 0 and X_out is not None:
+        if out["scaling"] == "strong" and "X" in sharded_out:          # the headline is the sharded step: its X and logdet
+            Xs = sharded_out["X"]
+            X_out = (Xs[X_out[1]], X_out[1], np.linalg.norm(Xs, axis=0), sharded_out["logdet"])
+        dump_outputs(args.dump_outputs, *X_out)
     if rank == 0:
         if out_lock is not None:
             with out_lock:

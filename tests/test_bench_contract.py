@@ -1,7 +1,8 @@
-"""The bench.py contract on a GPU box: ONE JSON line with the headline metric, the roofline of the dominant kernel (live HIP
-events), the secondary roofline objects, the phases and the correctness evidence -- on a reduced grid so that it runs in
-seconds (the driver runs the default 1000 x 1000 configuration). Also the two-rank rehearsal (two processes on this one GPU,
-gloo): the N > 1 line carries the sharded strong-scaling result as the headline and the replicas next to it."""
+"""The bench.py contract on a GPU box: ONE JSON line with the headline metric; with --full also the roofline of the dominant
+kernel (live HIP events), the secondary roofline objects, the phases and the correctness evidence -- on a reduced grid so that
+it runs in seconds (the driver runs the default 1000 x 1000 configuration). A plain run times the steps and nothing else, and
+--dump-outputs writes what the last timed step returned. Also the two-rank rehearsal (two processes on this one GPU, gloo): the
+N > 1 line carries the sharded strong-scaling result as the headline and the replicas next to it."""
 import json
 import os
 import subprocess
@@ -24,7 +25,7 @@ def _run(args, timeout=600, expect_rc=0, extra_env=None):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    d = _run(["--grid", "300", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"])
+    d = _run(["--grid", "300", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "roofline_factor", "roofline_sweep", "phases_ms", "check"):
         assert k in d, k
@@ -55,9 +56,41 @@ def test_single_gpu_line_has_the_contract_fields():
     assert d["roofline"]["achieved_alone"] > 0
 
 
+def test_plain_line_times_the_steps_only_and_dumps_the_last_step(tmp_path):
+    """A plain run: the headline fields, nothing of --full; --dump-outputs writes X at a fixed sample of rows, the column norms of
+    X and logdet of the last timed step in float64, and they are the solution of the seeded inputs."""
+    import numpy as np
+    import scipy.sparse.linalg as spla
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "gaussianmarkovrandomfields.jl_amd"))
+    from gmrfx import spde
+    out = tmp_path / "outputs"
+    d = _run(["--grid", "300", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["full"] is False and d["unit"] == "DoF/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and abs(d["value"] - d["config"]["n"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_sweep", "cpu_baseline", "ms_per_step_separate_calls", "host_io", "logpdf_ms", "phases_ms"):
+        assert k not in d, k
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert sorted(files) == ["X_column_norms.npy", "X_sample.npy", "X_sample_rows.npy", "logdet.npy"]
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    assert files["logdet.npy"][0] == d["check"]["logdet"]
+    # the same seeded inputs as bench.py, solved on the host
+    mesh = spde.grid_mesh_2d(300, 300, jitter=0.25, seed=0)
+    Q = spde.matern_precision(mesh, smoothness=0, range_=0.2)
+    n = Q.shape[0]
+    B = torch.randn((64, n), generator=torch.Generator(device="cpu").manual_seed(1), dtype=torch.float64).numpy().T
+    X = spla.splu(Q.tocsc()).solve(B)
+    rows = files["X_sample_rows.npy"].astype(np.int64)
+    assert files["X_sample.npy"].shape == (len(rows), 64) and len(rows) == len(set(rows.tolist())) and rows.max() < n
+    assert np.abs(files["X_sample.npy"] - X[rows]).max() < 1e-9 * np.abs(X).max()
+    assert np.abs(files["X_column_norms.npy"] - np.linalg.norm(X, axis=0)).max() < 1e-9 * np.linalg.norm(X, axis=0).max()
+
+
 def test_two_rank_rehearsal_line_is_sharded_strong_scaling():
     d = _run(["--gpus", "2", "--rehearse", "--grid", "200", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-logpdf", "--no-cfg3",
-              "--cfg4-grid", "14"])
+              "--cfg4-grid", "14", "--full"])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and "replicas" in d and d["replicas"]["scaling"] == "weak"
     sh = d["sharded"]
     assert "error" not in sh and sh["check"]["info"] == 0 and sh["check"]["rel_residual"] < 1e-10
@@ -93,6 +126,6 @@ def test_cfg4_line_is_skipped_and_says_so_when_the_deadline_leaves_no_room():
     left (the driver ends a bench run after 600 s; 126^3 nodes cost ~170 s of host work per rank before the first kernel): the cfg-2
     headline stays, the skip is recorded, rc == 0."""
     d = _run(["--gpus", "2", "--rehearse", "--grid", "200", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-logpdf", "--no-cfg3",
-              "--cfg4-grid", "14", "--cfg4-budget", "100000"])
+              "--cfg4-grid", "14", "--cfg4-budget", "100000", "--full"])
     assert d["scaling"] == "strong" and "error" not in d["sharded"]
     assert d["cfg4_sharded"]["status"].startswith("skipped") and "--deadline" in d["cfg4_sharded"]["status"]

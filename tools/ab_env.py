@@ -8,7 +8,7 @@ for setting in sys.argv[1:]:
     for kv in setting.split():
         k, v = kv.split("=", 1)
         env[k] = v
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-logpdf",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-logpdf",
                         "--no-cfg3", "--no-host-io"], env=env, capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])

@@ -3,9 +3,9 @@
 dependent launches grow) or loaded memory latency (DURATIONS grow)? (VERDICT r05 "Next round" #5.)
 
 From two kernel traces of bench.py steps (program directly behind `--`):
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/pg_sep -- python3 bench.py --steps 4 --warmup 2 --separate-calls --no-cpu-baseline --no-logpdf --no-cfg3 --no-host-io
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/pg_pip -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-logpdf --no-cfg3 --no-host-io
-    python3 tools/pipeline_gaps.py gpurun_out/pg_sep gpurun_out/pg_pip > gpurun_out/r06_pipeline_gaps.txt
+    rocprofv3 --kernel-trace --output-format csv -d prof_out/pg_sep -- python3 bench.py --full --steps 4 --warmup 2 --separate-calls --no-cpu-baseline --no-logpdf --no-cfg3 --no-host-io
+    rocprofv3 --kernel-trace --output-format csv -d prof_out/pg_pip -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-logpdf --no-cfg3 --no-host-io
+    python3 tools/pipeline_gaps.py prof_out/pg_sep prof_out/pg_pip > prof_out/r06_pipeline_gaps.txt
 For the panel-chain kernels of the top of the tree (the latency variants: k_potrf64_b<8, 4>, k_trsm<0, 1>, k_gemm_nt<1>) of every timed
 step: launches, mean / summed DURATION, and mean / summed GAP = start - end of the previous kernel of the same stream. Under the
 profiler the host is slower than the GPU at the top of the tree, so gaps are inflated in BOTH traces alike; what counts is the difference.

@@ -2,9 +2,11 @@
 # per-launch durations of the contribution-block SYRK for two settings of an environment variable
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 var=$1; shift
+OUT=${OUT:-prof_out}      # traces and per-launch tables
+mkdir -p $OUT
 for v in "$@"; do
   export $var=$v
-  rocprofv3 --kernel-trace --output-format csv -d gpurun_out/sl_$v -- python3 bench.py --no-cpu-baseline --steps 3 --warmup 2 --no-logpdf --no-cfg3 > gpurun_out/sl_$v.json 2> gpurun_out/sl_$v.err || { tail -5 gpurun_out/sl_$v.err; exit 1; }
-  python3 tools/timeline.py gpurun_out/sl_$v 0 | grep syrk > gpurun_out/sl_$v.txt
-  echo "== $var=$v"; cat gpurun_out/sl_$v.txt
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/sl_$v -- python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 2 --no-logpdf --no-cfg3 > $OUT/sl_$v.json 2> $OUT/sl_$v.err || { tail -5 $OUT/sl_$v.err; exit 1; }
+  python3 tools/timeline.py $OUT/sl_$v 0 | grep syrk > $OUT/sl_$v.txt
+  echo "== $var=$v"; cat $OUT/sl_$v.txt
 done
