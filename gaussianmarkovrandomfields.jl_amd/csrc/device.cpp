@@ -72,6 +72,9 @@ Device::~Device() {
     if (h_qf_) (void)hipHostFree(h_qf_);
     if (ev_qf_) (void)hipEventDestroy(ev_qf_);
     if (ev_logdet_) (void)hipEventDestroy(ev_logdet_);
+    if (h_bdiag_) (void)hipHostFree(h_bdiag_);
+    if (h_bqf_) (void)hipHostFree(h_bqf_);
+    if (ev_bdiag_) (void)hipEventDestroy(ev_bdiag_);
     if (ev_ready_) (void)hipEventDestroy(ev_ready_);
     if (ev_ready2_) (void)hipEventDestroy(ev_ready2_);
     if (ev_done1_) (void)hipEventDestroy(ev_done1_);
@@ -1648,9 +1651,11 @@ void Device::solve_phase(const double *d_B, long long ldb, long long nrhs, doubl
     last_nrhs = nrhs;
 }
 
-void Device::solve(const double *B, long long ldb, long long nrhs, double *X, long long ldx_out, bool on_device, int mode) {
+void Device::solve(const double *B, long long ldb, long long nrhs, double *X, long long ldx_out, bool on_device, int mode,
+                   const MemberLayout *ml) {
     HC(hipSetDevice(device));
     if (sharded()) throw std::invalid_argument("sharded handle: use gmrfx_solve_phase (phases with exchanges in between, gmrfx/shard.py)");
+    if (ml && !on_device) throw std::invalid_argument("member-strided solves take device arrays");
     if (nrhs <= 0) return;
     const long long n = S_->n;
     ensure_rhs_capacity(nrhs);
@@ -1710,14 +1715,17 @@ void Device::solve(const double *B, long long ldb, long long nrhs, double *X, lo
         hipEvent_t *ev = ev_lane_[ln];
         HC(hipEventRecord(ev[0], stream));
         // full solve: X = P b ; backward-only (F.UP \ z): z is taken in elimination order as is
-        launch_permute(stream, mode == 0 ? d_iperm_ : nullptr, (int)n, const_cast<double *>(dB) + j0 * ldin, ldin, d_X_, nr, ldx, 0);
+        if (ml) launch_batch_permute(stream, mode == 0 ? d_iperm_ : nullptr, (int)n, (int)ml->n_member, const_cast<double *>(dB) + j0 * ldin, ldin,
+                                     ml->sin, d_X_, nr, ldx, 0);
+        else launch_permute(stream, mode == 0 ? d_iperm_ : nullptr, (int)n, const_cast<double *>(dB) + j0 * ldin, ldin, d_X_, nr, ldx, 0);
         HC(hipEventRecord(ev[1], stream));
 
         if (mode == 0) forward(nr, ldx, 0, (int)levels_.size());
         HC(hipEventRecord(ev[2], stream));
         backward(nr, ldx, mode == 0, (int)levels_.size(), 0);
         HC(hipEventRecord(ev[3], stream));
-        launch_permute(stream, d_iperm_, (int)n, dXo + j0 * ldout, ldout, d_X_, nr, ldx, 1);
+        if (ml) launch_batch_permute(stream, d_iperm_, (int)n, (int)ml->n_member, dXo + j0 * ldout, ldout, ml->sout, d_X_, nr, ldx, 1);
+        else launch_permute(stream, d_iperm_, (int)n, dXo + j0 * ldout, ldout, d_X_, nr, ldx, 1);
         HC(hipEventRecord(ev[4], stream));
         busy[ln] = true;
         stream = main_stream; d_X_ = X0; d_X2_ = X20; d_W_ = W0;
@@ -2075,6 +2083,138 @@ void Device::transpose(const double *d_src, double *d_dst, long long rows, long 
 void Device::copy_factor(double *out_host) {
     HC(hipSetDevice(device));
     HC(hipMemcpy(out_host, d_L_, (size_t)l_size_ * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+// ---- batched handles (gmrfx_create_batched): the handle's structure is the forest of diag(Q_1 .. Q_B); these are the only places
+// that see the members one by one (batch.hip) --------------------------------------------------------------------------------------
+void Device::set_batch(int nbatch, long long n_member, long long nnz_member) {
+    HC(hipSetDevice(device));
+    const Symbolic &S = *S_;
+    if (nbatch < 1 || n_member * nbatch != S.n || nnz_member * nbatch != S.nnz_in) throw std::invalid_argument("set_batch: sizes do not match the forest");
+    nbatch_ = nbatch; nmember_ = n_member; nnz_member_ = nnz_member;
+    d_bpsum_ = dalloc<double>((size_t)nbatch * batch_diag_parts((int)n_member));
+    d_bpbad_ = dalloc<int>((size_t)nbatch * batch_diag_parts((int)n_member));
+    d_bdiag_ = dalloc<double>(2 * (size_t)nbatch);
+    HC(hipHostMalloc((void **)&h_bdiag_, 2 * (size_t)nbatch * sizeof(double), hipHostMallocDefault));
+    HC(hipEventCreateWithFlags(&ev_bdiag_, hipEventDisableTiming));
+    // the member's pattern = the forest's first n_member columns (rows unshifted)
+    d_bin_colptr_ = dalloc<long long>((size_t)n_member + 1);
+    d_bin_row_ = dalloc<int>((size_t)std::max<long long>(nnz_member, 1));
+    HC(hipMemcpyAsync(d_bin_colptr_, S.in_colptr.data(), ((size_t)n_member + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+    if (nnz_member > 0) HC(hipMemcpyAsync(d_bin_row_, S.in_row.data(), (size_t)nnz_member * sizeof(int), hipMemcpyHostToDevice, stream));
+    HC(hipStreamSynchronize(stream));
+}
+
+void Device::enqueue_batch_diag(hipStream_t st) {
+    double *ld = d_bdiag_;
+    long long *info = reinterpret_cast<long long *>(d_bdiag_ + nbatch_);
+    launch_batch_diag(st, d_L_, ds_.diagoff, (int)nmember_, nbatch_, d_bpsum_, d_bpbad_, ld, info);
+    HC(hipMemcpyAsync(h_bdiag_, d_bdiag_, 2 * (size_t)nbatch_ * sizeof(double), hipMemcpyDeviceToHost, st));
+    HC(hipEventRecord(ev_bdiag_, st));
+    bdiag_for_ = factor_serial_;
+}
+
+void Device::batch_diag(double *logdet_out, long long *info_out) {
+    HC(hipSetDevice(device));
+    if (!h_bdiag_) throw std::invalid_argument("not a batched handle");
+    if (bdiag_for_ != factor_serial_) enqueue_batch_diag(stream);
+    HC(hipEventSynchronize(ev_bdiag_));
+    HC(hipGetLastError());
+    const long long *hi = reinterpret_cast<const long long *>(h_bdiag_ + nbatch_);
+    for (int k = 0; k < nbatch_; k++) {
+        if (logdet_out) logdet_out[k] = h_bdiag_[k];
+        if (info_out) info_out[k] = hi[k];
+    }
+}
+
+void Device::prepare_batch_quadform(long long npairs) {
+    const long long nblk = batch_quadform_blocks((int)nmember_);
+    if (npairs > bqf_cap_) {
+        const long long cap = std::max<long long>(npairs, 2 * bqf_cap_);
+        bqf_cap_ = 0;
+        d_bqf_part_ = dregrow(d_bqf_part_, (size_t)(cap * nblk));
+        d_bqf_out_ = dregrow(d_bqf_out_, (size_t)cap);
+        bqf_cap_ = cap;
+    }
+    if (npairs > h_bqf_cap_) {
+        if (h_bqf_) HC(hipHostFree(h_bqf_));
+        h_bqf_ = nullptr; h_bqf_cap_ = 0;
+        const long long cap = std::max<long long>(npairs, 64);
+        HC(hipHostMalloc((void **)&h_bqf_, (size_t)cap * sizeof(double), hipHostMallocDefault));
+        h_bqf_cap_ = cap;
+    }
+}
+
+void Device::enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,
+                                    const double *d_mu) {
+    launch_batch_quadform(st, (int)nmember_, d_bin_colptr_, d_bin_row_, d_nz, nnz_member_, S_->in_use, d_X, ldx, sx, (int)nvec, nbatch_, d_mu,
+                          d_bqf_part_, d_bqf_out_);
+    HC(hipMemcpyAsync(h_bqf_, d_bqf_out_, (size_t)(nvec * nbatch_) * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+void Device::batch_quadform(const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu,
+                            double *quad_out) {
+    HC(hipSetDevice(device));
+    if (!h_bdiag_) throw std::invalid_argument("not a batched handle");
+    if (nvec <= 0) return;
+    if (!d_nz) {
+        if (!nz_held_) throw std::invalid_argument("batch_quadform: the handle does not hold Q's values (last refactorisation read a caller device buffer): pass them");
+        d_nz = d_nz_;
+    }
+    prepare_batch_quadform(nvec * nbatch_);
+    HC(hipEventRecord(ev_[0], stream));
+    enqueue_batch_quadform(stream, d_nz, d_X, ldx, sx, nvec, d_mu);
+    HC(hipEventRecord(ev_[1], stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    float ms; HC(hipEventElapsedTime(&ms, ev_[0], ev_[1])); ms_quadform = ms;
+    for (long long k = 0; k < nvec * nbatch_; k++) quad_out[k] = h_bqf_[k];
+}
+
+// One batched evaluation of the hyper-parameter loop (gmrfx_batch_refactorize_logpdf_dev), the batched twin of refactorize_logpdf:
+// the forest is refactored on the main stream, the members' quadratic forms run beside it on the side stream, the per-member log
+// det / pivot status follows the factorisation; ONE synchronisation. The same launches as batch_refactorize + batch_quadform +
+// batch_logdet: the same bits.
+void Device::batch_refactorize_logpdf(const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu,
+                                      double *quad_out, double *logdet_out, long long *info_out) {
+    HC(hipSetDevice(device));
+    if (!h_bdiag_) throw std::invalid_argument("not a batched handle");
+    if (stream != own_stream_) throw std::invalid_argument("batch_refactorize_logpdf: not on a caller's stream");
+    if (nvec > 0) {
+        prepare_batch_quadform(nvec * nbatch_);
+        HC(hipEventRecord(ev_ready_, stream));
+        HC(hipStreamWaitEvent(stream2, ev_ready_, 0));
+        enqueue_batch_quadform(stream2, d_nz, d_X, ldx, sx, nvec, d_mu);
+        if (!ev_qf_) HC(hipEventCreateWithFlags(&ev_qf_, hipEventDisableTiming));
+        HC(hipEventRecord(ev_qf_, stream2));
+    }
+    nz_held_ = false;
+    nz_src_ = d_nz;
+    factor_serial_++;
+    HC(hipEventRecord(ev_[0], stream));
+    factor_levels(0, (int)levels_.size());
+    HC(hipEventRecord(ev_[1], stream));
+    HC(hipEventRecord(ev_fact_, stream));
+    fact_event_valid_ = true;
+    inverse_pending = true;
+    HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
+    factorized = true;
+    selinv_valid = false;
+    enqueue_batch_diag(stream);
+    if (nvec > 0) HC(hipStreamWaitEvent(stream, ev_qf_, 0));
+    HC(hipStreamSynchronize(stream));
+    info_cached_ = true;
+    HC(hipGetLastError());
+    float tf = 0;
+    HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
+    ms_factor = tf;
+    syrk_times_pending_ = true;
+    for (long long k = 0; k < nvec * nbatch_; k++) quad_out[k] = h_bqf_[k];
+    const long long *hi = reinterpret_cast<const long long *>(h_bdiag_ + nbatch_);
+    for (int k = 0; k < nbatch_; k++) {
+        if (logdet_out) logdet_out[k] = h_bdiag_[k];
+        if (info_out) info_out[k] = hi[k];
+    }
 }
 
 }  // namespace gmrfx

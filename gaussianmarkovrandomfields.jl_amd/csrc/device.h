@@ -200,7 +200,21 @@ public:
     double *factor_panels() { return d_L_; }
     bool sharded() const { return S_ && S_->shard_plan; }
     // B: column-major n x nrhs (original ordering); mode 0: full solve, 1: backward only (P' L^-T Z)
-    void solve(const double *B, long long ldb, long long nrhs, double *X, long long ldx, bool on_device, int mode);
+    // ml (batched handles, device arrays only): member k's n_member x nrhs block of B / X at + k sin / + k sout, leading dimension ldb / ldx
+    struct MemberLayout { long long n_member, sin, sout; };
+    void solve(const double *B, long long ldb, long long nrhs, double *X, long long ldx, bool on_device, int mode,
+               const MemberLayout *ml = nullptr);
+    // ---- batched handles (gmrfx_create_batched): nbatch members of n_member nodes, the forest diag(Q_1 .. Q_B) -------------------
+    void set_batch(int nbatch, long long n_member, long long nnz_member);
+    bool batched() const { return h_bdiag_ != nullptr; }
+    // per-member log det / pivot status (1 + member-local column, 0 = fine) of the current factorisation, host arrays of nbatch
+    void batch_diag(double *logdet_out, long long *info_out);
+    // quad[k nvec + v] = (x_vk - mu_k)' Q_k (x_vk - mu_k), device operands: x_vk = d_X + k sx + v ldx, Q_k = d_nz + k nnz_member,
+    // mu_k = d_mu + k n_member (nullable); quad is a host array of nvec nbatch
+    void batch_quadform(const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu, double *quad_out);
+    // refactorisation + batch_quadform beside it + batch_diag, one synchronisation: same bits as the three calls
+    void batch_refactorize_logpdf(const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu,
+                                  double *quad_out, double *logdet_out, long long *info_out);
     double logdet();
     // q[v] = (x_v - mu)' Q (x_v - mu), v < nvec, on the device: x_v = d_X + v * ldx, d_mu nullable (zero mean).
     // d_nz = Q's values in the pattern's CSC order (device); nullptr = the values of the last refactorisation
@@ -392,6 +406,21 @@ private:
     hipEvent_t ev_[8] = {};
     std::vector<hipEvent_t> ev_syrk_;   // begin/end event of every k_syrk_cb launch
     long long l_size_ = 0, sum_trail_ = 0;
+    // batched handles (set_batch): members, member size / values; device partials + results of batch_diag / batch_quadform, pinned copies
+    int nbatch_ = 1;
+    long long nmember_ = 0, nnz_member_ = 0;
+    double *d_bpsum_ = nullptr, *d_bdiag_ = nullptr, *h_bdiag_ = nullptr;    // d_bdiag_ / h_bdiag_: nbatch log dets, then nbatch info words
+    int *d_bpbad_ = nullptr;
+    unsigned long long bdiag_for_ = 0;            // h_bdiag_ belongs to factorisation number bdiag_for_
+    hipEvent_t ev_bdiag_ = nullptr;
+    long long *d_bin_colptr_ = nullptr;           // the MEMBER's pattern (the forest's first n_member columns)
+    int *d_bin_row_ = nullptr;
+    double *d_bqf_part_ = nullptr, *d_bqf_out_ = nullptr, *h_bqf_ = nullptr;
+    long long bqf_cap_ = 0, h_bqf_cap_ = 0;
+    void enqueue_batch_diag(hipStream_t st);
+    void prepare_batch_quadform(long long npairs);
+    void enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,
+                                const double *d_mu);
 };
 
 void hip_check(hipError_t e, const char *what);

@@ -2,6 +2,8 @@
 #include "../../include/gmrfx.h"
 
 #include <algorithm>
+#include <chrono>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -24,6 +26,8 @@ struct gmrfx_handle {
     // lazily built pattern of the de-permuted selected inverse
     bool zpat_built = false;
     std::vector<i64> zcolptr, zrow, zoff;
+    // batched handles (gmrfx_create_batched): S is the forest of nbatch copies of the member's pattern; plain handles: 1, n, nnz
+    int64_t nbatch = 1, n_member = 0, nnz_member = 0;
 };
 
 static thread_local std::string g_create_err;
@@ -61,6 +65,31 @@ static int32_t need_device(gmrfx_handle *h, bool need_factor) {
     return GMRFX_OK;
 }
 
+// gmrfx_opts -> the analysis options (and the tuning / testing knobs of the environment)
+static void sym_options(const gmrfx_opts &o, SymOptions &so) {
+    so.uplo = o.uplo;
+    so.ordering = o.ordering;
+    so.nd_leaf = o.nd_leaf;
+    so.relax_cols = o.relax_cols;
+    so.relax_zeros = o.relax_zeros;
+    so.coord_dim = o.coords ? o.coord_dim : 0;
+    so.coords = o.coords;
+    if (so.coords && so.coord_dim != 2 && so.coord_dim != 3) throw std::invalid_argument("coord_dim must be 2 or 3");
+    if (const char *e = std::getenv("GMRFX_SMALL_ROWS")) so.small_front_rows = std::atoi(e);   // tuning/testing knob
+    if (const char *e = std::getenv("GMRFX_SUBTREE_MAX")) so.subtree_max = std::atoi(e);       // 0 disables subtree tasks
+    if (const char *e = std::getenv("GMRFX_SWEEP_TASK_ROWS")) so.sweep_task_rows = std::atoi(e);   // 0 disables sweep tasks
+    if (const char *e = std::getenv("GMRFX_MERGE_WIDE")) so.merge_wide = std::atoi(e);   // widest child with siblings that may still be merged into its parent
+    if (const char *e = std::getenv("GMRFX_TOP_BY_DEPTH")) so.top_by_depth = std::atoi(e);   // top levels levelled by depth below the root (0: none)
+    if (o.shard_world > 1 || (o.shard_world == 1 && o.shard_min_top > 0)) {
+        so.shard_min_top = std::max(0, o.shard_min_top);
+        if (o.shard_rank < 0 || o.shard_rank >= o.shard_world) throw std::invalid_argument("shard_rank out of range");
+        so.shard_rank = o.shard_rank;
+        so.shard_world = o.shard_world;
+        if (const char *e = std::getenv("GMRFX_DIST_MIN")) so.dist_min_cols = std::atoi(e);   // columns from which a top front is factored by its whole group (0: never)
+        so.subtree_max = 0;     // subtree tasks are not shard-aware
+    }
+}
+
 extern "C" int32_t gmrfx_create(int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t index_base,
                                 const int64_t *perm, const gmrfx_opts *opts, gmrfx_handle **out) {
     if (!out) { g_create_err = "out is null"; return GMRFX_ERR_INVALID_ARG; }
@@ -75,29 +104,10 @@ extern "C" int32_t gmrfx_create(int64_t n, const int64_t *colptr, const int64_t 
     }
     try {
         SymOptions so;
-        so.uplo = h->opts.uplo;
-        so.ordering = h->opts.ordering;
-        so.nd_leaf = h->opts.nd_leaf;
-        so.relax_cols = h->opts.relax_cols;
-        so.relax_zeros = h->opts.relax_zeros;
-        so.coord_dim = h->opts.coords ? h->opts.coord_dim : 0;
-        so.coords = h->opts.coords;
-        if (so.coords && so.coord_dim != 2 && so.coord_dim != 3) throw std::invalid_argument("coord_dim must be 2 or 3");
-        if (const char *e = std::getenv("GMRFX_SMALL_ROWS")) so.small_front_rows = std::atoi(e);   // tuning/testing knob
-        if (const char *e = std::getenv("GMRFX_SUBTREE_MAX")) so.subtree_max = std::atoi(e);       // 0 disables subtree tasks
-        if (const char *e = std::getenv("GMRFX_SWEEP_TASK_ROWS")) so.sweep_task_rows = std::atoi(e);   // 0 disables sweep tasks
-        if (const char *e = std::getenv("GMRFX_MERGE_WIDE")) so.merge_wide = std::atoi(e);   // widest child with siblings that may still be merged into its parent
-        if (const char *e = std::getenv("GMRFX_TOP_BY_DEPTH")) so.top_by_depth = std::atoi(e);   // top levels levelled by depth below the root (0: none)
-        if (h->opts.shard_world > 1 || (h->opts.shard_world == 1 && h->opts.shard_min_top > 0)) {
-            so.shard_min_top = std::max(0, h->opts.shard_min_top);
-            if (h->opts.shard_rank < 0 || h->opts.shard_rank >= h->opts.shard_world) throw std::invalid_argument("shard_rank out of range");
-            so.shard_rank = h->opts.shard_rank;
-            so.shard_world = h->opts.shard_world;
-            if (const char *e = std::getenv("GMRFX_DIST_MIN")) so.dist_min_cols = std::atoi(e);   // columns from which a top front is factored by its whole group (0: never)
-            so.subtree_max = 0;     // subtree tasks are not shard-aware
-        }
+        sym_options(h->opts, so);
         analyze(n, colptr, rowval, index_base, perm, so, h->S);
         h->opts.coords = nullptr;  // caller-owned, not kept
+        h->n_member = h->S.n; h->nnz_member = h->S.nnz_in;
     } catch (const std::invalid_argument &e) {
         g_create_err = e.what();
         return GMRFX_ERR_INVALID_ARG;
@@ -130,9 +140,11 @@ extern "C" int32_t gmrfx_clone(const gmrfx_handle *h, gmrfx_handle **out) {
     try {
         c->S = h->S;
         c->opts = h->opts;
+        c->nbatch = h->nbatch; c->n_member = h->n_member; c->nnz_member = h->nnz_member;
         if (h->D) {
             c->D.reset(new Device());
             c->D->clone_from(*h->D, c->S);
+            if (h->D->batched()) c->D->set_batch((int)c->nbatch, c->n_member, c->nnz_member);
         }
     } catch (const std::exception &e) {
         g_create_err = e.what();
@@ -987,5 +999,227 @@ extern "C" int32_t gmrfx_get_factor_values(gmrfx_handle *h, double *out) {
         if (!out) throw std::invalid_argument("out is null");
         h->D->copy_factor(out);
         return GMRFX_OK;
+    });
+}
+
+// ---- batched handles (include/gmrfx.h) ------------------------------------------------------------------------------------------
+// The member's pattern and order are analysed once; the handle itself is an ordinary handle of the block-diagonal forest
+// diag(Q_1 .. Q_B): pattern and elimination order replicated with offsets k n. Copies of the member's tree fall on the same levels
+// (levels are numbered by depth below each root), so every level launch does B times the work of one member.
+extern "C" int32_t gmrfx_create_batched(int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t index_base, const int64_t *perm,
+                                        int64_t nbatch, const gmrfx_opts *opts, gmrfx_handle **out) {
+    if (!out) { g_create_err = "out is null"; return GMRFX_ERR_INVALID_ARG; }
+    *out = nullptr;
+    // everything that can be refused is refused before anything is allocated
+    if (!colptr || !rowval) { g_create_err = "colptr/rowval is null"; return GMRFX_ERR_INVALID_ARG; }
+    if (nbatch < 1) { g_create_err = "nbatch must be >= 1"; return GMRFX_ERR_INVALID_ARG; }
+    if (n <= 0) { g_create_err = "n must be positive"; return GMRFX_ERR_INVALID_ARG; }
+    if (n > (int64_t)INT32_MAX / nbatch) { g_create_err = "nbatch * n exceeds INT32_MAX (32-bit node indices of the forest)"; return GMRFX_ERR_INVALID_ARG; }
+    gmrfx_opts o = default_opts();
+    if (opts) {
+        if (opts->struct_size <= 0) { g_create_err = "opts.struct_size not set"; return GMRFX_ERR_INVALID_ARG; }
+        std::memcpy(&o, opts, std::min<size_t>((size_t)opts->struct_size, sizeof(gmrfx_opts)));
+    }
+    if (o.shard_world > 1 || o.shard_min_top > 0) { g_create_err = "batched handles cannot be sharded (shard_world > 1 / shard_min_top > 0)"; return GMRFX_ERR_INVALID_ARG; }
+    const int64_t nnz = colptr[n] - index_base;
+    if (nnz < 0 || nnz > INT64_MAX / nbatch) { g_create_err = "colptr[n] out of range"; return GMRFX_ERR_INVALID_ARG; }
+    std::unique_ptr<gmrfx_handle> h(new gmrfx_handle());
+    h->opts = o;
+    try {
+        const auto t0 = std::chrono::steady_clock::now();
+        SymOptions so;
+        sym_options(h->opts, so);
+        Symbolic M;             // the member: its ordering (user perm, or nested dissection on its own coords) + postorder
+        analyze(n, colptr, rowval, index_base, perm, so, M);
+        const int64_t N = nbatch * n;
+        std::vector<i64> fcol((size_t)N + 1), frow((size_t)(nbatch * nnz)), fperm((size_t)N);
+        for (int64_t k = 0; k < nbatch; k++) {
+            for (int64_t j = 0; j < n; j++) fcol[k * n + j] = k * nnz + (colptr[j] - index_base);
+            for (int64_t p = 0; p < nnz; p++) frow[k * nnz + p] = k * n + (rowval[p] - index_base);
+            for (int64_t i = 0; i < n; i++) fperm[k * n + i] = k * n + M.perm[i];
+        }
+        fcol[N] = nbatch * nnz;
+        // the member's order is a postorder of its tree, so the forest's (copies one after the other, roots ascending) is one of the
+        // forest: the analysis keeps it as it is
+        so.coords = nullptr; so.coord_dim = 0;
+        analyze(N, fcol.data(), frow.data(), 0, fperm.data(), so, h->S);
+        h->S.flops = (double)nbatch * M.flops;      // the same sum, without the rounding of B copies added one by one
+        h->S.ms_symbolic = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        h->opts.coords = nullptr;
+        h->nbatch = nbatch; h->n_member = n; h->nnz_member = nnz;
+    } catch (const std::invalid_argument &e) {
+        g_create_err = e.what();
+        return GMRFX_ERR_INVALID_ARG;
+    } catch (const std::bad_alloc &) {
+        g_create_err = "out of host memory";
+        return GMRFX_ERR_ALLOC;
+    } catch (const std::exception &e) {
+        g_create_err = e.what();
+        return GMRFX_ERR_INVALID_ARG;
+    }
+    if (!h->opts.symbolic_only) {
+        try {
+            h->D.reset(new Device());
+            h->D->init(h->S, h->opts.device);
+            h->D->set_batch((int)nbatch, n, h->nnz_member);
+        } catch (const std::exception &e) {
+            g_create_err = e.what();
+            return std::string(e.what()).find("no HIP device") != std::string::npos ? GMRFX_ERR_NO_DEVICE : GMRFX_ERR_HIP;
+        }
+    }
+    *out = h.release();
+    return GMRFX_OK;
+}
+
+extern "C" int32_t gmrfx_batch_size(const gmrfx_handle *h, int64_t *nbatch, int64_t *n_member) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    if (nbatch) *nbatch = h->nbatch;
+    if (n_member) *n_member = h->n_member;
+    return GMRFX_OK;
+}
+
+// batch entry points on a plain handle: a batch of one (the device-side buffers are set up on first use)
+static int32_t need_batch(gmrfx_handle *h, bool need_factor) {
+    if (int32_t e = need_device(h, need_factor)) return e;
+    if (!h->D->batched()) {
+        if (h->S.shard_plan) throw std::invalid_argument("sharded handle: the batch entry points need an unsharded handle");
+        h->D->set_batch(1, h->S.n, h->S.nnz_in);
+    }
+    return GMRFX_OK;
+}
+
+static int32_t batch_status(gmrfx_handle *h, const std::vector<int64_t> &info) {
+    for (int64_t k = 0; k < h->nbatch; k++)
+        if (info[k] != 0 && h->opts.check_posdef) {
+            h->err = "member " + std::to_string(k) + " is not positive definite (non-positive pivot at elimination step " + std::to_string(info[k]) + ")";
+            return GMRFX_ERR_NOT_POSDEF;
+        }
+    return GMRFX_OK;
+}
+
+static int32_t batch_refactorize_impl(gmrfx_handle *h, const double *nz, int64_t *info, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = need_batch(h, false)) return e;
+        if (!nz) throw std::invalid_argument("nzval is null");
+        h->D->refactorize(nz, dev);
+        std::vector<int64_t> inf((size_t)h->nbatch);
+        h->D->batch_diag(nullptr, (long long *)inf.data());
+        if (info) std::copy(inf.begin(), inf.end(), info);
+        return batch_status(h, inf);
+    });
+}
+extern "C" int32_t gmrfx_batch_refactorize(gmrfx_handle *h, const double *nzval, int64_t *info) { return batch_refactorize_impl(h, nzval, info, false); }
+extern "C" int32_t gmrfx_batch_refactorize_dev(gmrfx_handle *h, const double *d_nzval, int64_t *info) { return batch_refactorize_impl(h, d_nzval, info, true); }
+
+extern "C" int32_t gmrfx_batch_logdet(gmrfx_handle *h, double *out) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = need_batch(h, true)) return e;
+        if (!out) throw std::invalid_argument("out is null");
+        h->D->batch_diag(out, nullptr);
+        return GMRFX_OK;
+    });
+}
+
+// member k's n x cnt block at A + k s: ld >= n, and the blocks of two members do not overlap (s >= ld cnt)
+static void check_member_layout(const gmrfx_handle *h, int64_t ld, int64_t s, int64_t cnt, const char *what) {
+    if (ld < h->n_member) throw std::invalid_argument(std::string(what) + ": leading dimension smaller than n");
+    if (h->nbatch > 1 && (s < 0 || s / ld < cnt)) throw std::invalid_argument(std::string(what) + ": member stride smaller than ld * columns");
+}
+
+static int32_t batch_solve_impl(gmrfx_handle *h, const double *B, int64_t ldb, int64_t sb, int64_t nrhs, double *X, int64_t ldx, int64_t sx,
+                                bool dev, int mode) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = need_batch(h, true)) return e;
+        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
+        if (nrhs == 0) return GMRFX_OK;
+        if (!B || !X) throw std::invalid_argument("B/X is null");
+        check_member_layout(h, ldb, sb, nrhs, "B");
+        check_member_layout(h, ldx, sx, nrhs, "X");
+        const int64_t n = h->n_member, nb = h->nbatch, N = h->S.n;
+        if (dev) {
+            const Device::MemberLayout ml{n, sb, sx};
+            h->D->solve(B, ldb, nrhs, X, ldx, true, mode, &ml);
+            return GMRFX_OK;
+        }
+        // host arrays: the members stacked into the forest's N x nrhs array (a host copy), the plain host path, and back
+        std::vector<double> buf((size_t)(N * nrhs));
+        for (int64_t j = 0; j < nrhs; j++)
+            for (int64_t k = 0; k < nb; k++) std::memcpy(&buf[(size_t)(j * N + k * n)], B + k * sb + j * ldb, (size_t)n * sizeof(double));
+        h->D->solve(buf.data(), N, nrhs, buf.data(), N, false, mode);
+        for (int64_t j = 0; j < nrhs; j++)
+            for (int64_t k = 0; k < nb; k++) std::memcpy(X + k * sx + j * ldx, &buf[(size_t)(j * N + k * n)], (size_t)n * sizeof(double));
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_batch_solve(gmrfx_handle *h, const double *B, int64_t ldb, int64_t sb, int64_t nrhs, double *X, int64_t ldx, int64_t sx) {
+    return batch_solve_impl(h, B, ldb, sb, nrhs, X, ldx, sx, false, 0);
+}
+extern "C" int32_t gmrfx_batch_solve_dev(gmrfx_handle *h, const double *d_B, int64_t ldb, int64_t sb, int64_t nrhs, double *d_X, int64_t ldx,
+                                         int64_t sx) {
+    return batch_solve_impl(h, d_B, ldb, sb, nrhs, d_X, ldx, sx, true, 0);
+}
+extern "C" int32_t gmrfx_batch_backward_solve(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t sz, int64_t nrhs, double *X, int64_t ldx,
+                                              int64_t sx) {
+    return batch_solve_impl(h, Z, ldz, sz, nrhs, X, ldx, sx, false, 1);
+}
+extern "C" int32_t gmrfx_batch_backward_solve_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t sz, int64_t nrhs, double *d_X,
+                                                  int64_t ldx, int64_t sx) {
+    return batch_solve_impl(h, d_Z, ldz, sz, nrhs, d_X, ldx, sx, true, 1);
+}
+
+static void check_batch_quadform(const gmrfx_handle *h, const double *X, int64_t ldx, int64_t sx, int64_t nvec, const double *quad) {
+    if (nvec < 0) throw std::invalid_argument("nvec < 0");
+    if (nvec > 0 && (!X || !quad)) throw std::invalid_argument("X / quad is null");
+    if (nvec > 0) check_member_layout(h, ldx, sx, nvec, "X");
+    if (nvec > INT32_MAX / h->nbatch) throw std::invalid_argument("nvec * nbatch exceeds INT32_MAX");
+}
+
+static int32_t batch_quadform_impl(gmrfx_handle *h, const double *nz, const double *X, int64_t ldx, int64_t sx, int64_t nvec,
+                                   const double *mu, double *quad, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = need_batch(h, false)) return e;
+        check_batch_quadform(h, X, ldx, sx, nvec, quad);
+        if (nvec == 0) return GMRFX_OK;
+        if (dev) { h->D->batch_quadform(nz, X, ldx, sx, nvec, mu, quad); return GMRFX_OK; }
+        // host operands: staged through plain device buffers (freed on return), members packed (ld = n, stride = n nvec)
+        const int64_t n = h->n_member, nb = h->nbatch;
+        struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } bx, bm, bn;
+        hip_check(hipSetDevice(h->D->device), "hipSetDevice");
+        std::vector<double> xs((size_t)(n * nvec * nb));
+        for (int64_t k = 0; k < nb; k++)
+            for (int64_t v = 0; v < nvec; v++) std::memcpy(&xs[(size_t)((k * nvec + v) * n)], X + k * sx + v * ldx, (size_t)n * sizeof(double));
+        hip_check(hipMalloc(&bx.p, xs.size() * sizeof(double)), "hipMalloc");
+        hip_check(hipMemcpy(bx.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+        if (mu) {
+            hip_check(hipMalloc(&bm.p, (size_t)(n * nb) * sizeof(double)), "hipMalloc");
+            hip_check(hipMemcpy(bm.p, mu, (size_t)(n * nb) * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        if (nz) {
+            hip_check(hipMalloc(&bn.p, (size_t)std::max<int64_t>(h->S.nnz_in, 1) * sizeof(double)), "hipMalloc");
+            hip_check(hipMemcpy(bn.p, nz, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+        }
+        h->D->batch_quadform((const double *)bn.p, (const double *)bx.p, n, n * nvec, nvec, (const double *)bm.p, quad);
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_batch_quadform(gmrfx_handle *h, const double *nzval, const double *X, int64_t ldx, int64_t sx, int64_t nvec,
+                                        const double *mu, double *quad) {
+    return batch_quadform_impl(h, nzval, X, ldx, sx, nvec, mu, quad, false);
+}
+extern "C" int32_t gmrfx_batch_quadform_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx, int64_t nvec,
+                                            const double *d_mu, double *quad) {
+    return batch_quadform_impl(h, d_nzval, d_X, ldx, sx, nvec, d_mu, quad, true);
+}
+
+extern "C" int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx,
+                                                      int64_t nvec, const double *d_mu, double *quad, double *logdet, int64_t *info) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = need_batch(h, false)) return e;
+        if (!d_nzval) throw std::invalid_argument("nzval is null");
+        check_batch_quadform(h, d_X, ldx, sx, nvec, quad);
+        std::vector<int64_t> inf((size_t)h->nbatch);
+        h->D->batch_refactorize_logpdf(d_nzval, d_X, ldx, sx, nvec, d_mu, quad, logdet, (long long *)inf.data());
+        if (info) std::copy(inf.begin(), inf.end(), info);
+        return batch_status(h, inf);
     });
 }

@@ -435,6 +435,21 @@ void launch_gather(hipStream_t st, const double *src, const long long *off, long
 void launch_gather_diag(hipStream_t st, const double *src, const long long *diagoff, const int *perm, int n, double *out);
 
 
+// batch.hip -- per-member kernels of a batched handle (B members of nm nodes each, forest of N = B nm nodes)
+int batch_diag_parts(int nm);
+// logdet[k] = 2 sum log L_jj and info[k] = 0 or 1 + first member-local column with !(L_jj > 0), over the columns [k nm, (k+1) nm);
+// psum / pbad: nbatch x batch_diag_parts(nm) partials
+void launch_batch_diag(hipStream_t st, const double *L, const long long *diagoff, int nm, int nbatch, double *psum, int *pbad,
+                       double *logdet, long long *info);
+// launch_permute with a member stride: member k's block of the caller's array at A + k s (leading dimension ld)
+void launch_batch_permute(hipStream_t st, const int *iperm, int N, int nm, double *A, long long ld, long long s, double *X, int nr, int ldx,
+                          int dir);
+int batch_quadform_blocks(int nm);
+// out[k nvec + v] = (x_vk - mu_k)' Q_k (x_vk - mu_k): x_vk = X + k sx + v ldx, Q_k's values val + k nnz, mu_k = mu + k nm (nullable);
+// part: nvec nbatch batch_quadform_blocks(nm) doubles
+void launch_batch_quadform(hipStream_t st, int nm, const long long *colptr, const int *row, const double *val, long long nnz, int use_lower,
+                           const double *X, long long ldx, long long sx, int nvec, int nbatch, const double *mu, double *part, double *out);
+
 // dense.hip -- the dense-operator leg of the Kronecker path: R = D T (row-major, D n1 x n1, T / R n1 x n2) and a transpose
 void launch_dense_apply(hipStream_t st, const double *D, const double *T, double *R, int n1, long long n2);
 void launch_transpose(hipStream_t st, const double *src, double *dst, long long rows, long long cols);

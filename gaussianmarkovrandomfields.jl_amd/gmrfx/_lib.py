@@ -67,6 +67,9 @@ EXPORTS = [
     "gmrfx_quadform", "gmrfx_quadform_dev", "gmrfx_selinv_dot", "gmrfx_selinv_row_diag", "gmrfx_kl_cholesky",
     "gmrfx_selinv_row_diag_plan", "gmrfx_selinv_row_diag_apply", "gmrfx_selinv_row_diag_free",
     "gmrfx_symbolic_sweep_tasks", "gmrfx_symbolic_sweep_chunks", "gmrfx_selinv_phase", "gmrfx_host_io_plan", "gmrfx_dist_front_block",
+    "gmrfx_create_batched", "gmrfx_batch_size", "gmrfx_batch_refactorize", "gmrfx_batch_refactorize_dev", "gmrfx_batch_logdet",
+    "gmrfx_batch_solve", "gmrfx_batch_solve_dev", "gmrfx_batch_backward_solve", "gmrfx_batch_backward_solve_dev",
+    "gmrfx_batch_quadform", "gmrfx_batch_quadform_dev", "gmrfx_batch_refactorize_logpdf_dev",
 ]
 
 
@@ -162,6 +165,16 @@ def lib():
         L.gmrfx_selinv_row_diag_free.argtypes = [vp, i64]
         L.gmrfx_host_io_plan.argtypes = [i64, i64, i32, vp]
         L.gmrfx_dist_front_block.argtypes = [vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+        L.gmrfx_create_batched.argtypes = [i64, vp, vp, i32, vp, i64, C.POINTER(GmrfxOpts), C.POINTER(vp)]
+        L.gmrfx_batch_size.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
+        L.gmrfx_batch_refactorize.argtypes = [vp, vp, vp]
+        L.gmrfx_batch_refactorize_dev.argtypes = [vp, vp, vp]
+        L.gmrfx_batch_logdet.argtypes = [vp, vp]
+        for nm in ("gmrfx_batch_solve", "gmrfx_batch_solve_dev", "gmrfx_batch_backward_solve", "gmrfx_batch_backward_solve_dev"):
+            getattr(L, nm).argtypes = [vp, vp, i64, i64, i64, vp, i64, i64]
+        L.gmrfx_batch_quadform.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
+        L.gmrfx_batch_quadform_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
+        L.gmrfx_batch_refactorize_logpdf_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

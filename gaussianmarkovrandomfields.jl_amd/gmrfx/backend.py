@@ -572,3 +572,211 @@ class MI355XBackend:
 
     def selinv_compute_dev(self) -> None:
         check(lib().gmrfx_selinv_compute(self._h), self._h)
+
+
+class MI355XBatchBackend:
+    """B precision matrices with ONE pattern, factored in one pass (gmrfx_create_batched, include/gmrfx.h): the hyper-parameter
+    loop of docs/src/literate-tutorials/workspace_factorization_reuse.jl evaluates logpdf for many values of one pattern, and
+    WorkspacePool (src/workspace/workspace_pool.jl:5-22) runs such evaluations side by side. The handle is an ordinary handle of
+    diag(Q_1 .. Q_B); the member's order is computed once (ordering / coords as in MI355XBackend) and replicated.
+
+    Shapes: member values NZ (nnz, B) (column k = Q_k's values in Q's CSC order); right-hand sides (n, B) or (n, r, B); results in
+    the same layout. Every shape is checked (ValueError) before the library is called."""
+
+    def __init__(self, Q, nbatch: int, ordering=None, coords=None, device: int = -1, symbolic_only: bool = False,
+                 check_posdef: bool = False, uplo: str = "U"):
+        Q = _as_csc(Q)
+        if isinstance(nbatch, bool) or not isinstance(nbatch, (int, np.integer)):
+            raise ValueError("nbatch must be an integer")
+        self.n = Q.shape[0]
+        self.nbatch = int(nbatch)
+        self._colptr = np.ascontiguousarray(Q.indptr, dtype=np.int64)
+        self._rowval = np.ascontiguousarray(Q.indices, dtype=np.int64)
+        self._nnz = int(self._colptr[-1])
+        opts = GmrfxOpts()
+        opts.struct_size = C.sizeof(GmrfxOpts)
+        opts.uplo = 0 if uplo.upper().startswith("U") else 1
+        opts.device = device
+        opts.symbolic_only = int(symbolic_only)
+        opts.check_posdef = int(check_posdef)
+        self.device, self.symbolic_only = device, symbolic_only
+        from .ordering import ordering_permutation as _resolve
+        perm = _resolve(Q, ordering, coords)
+        if isinstance(perm, str):           # "natural"
+            opts.ordering = 1
+            perm = None
+        cr = None
+        if coords is not None:
+            cr = np.ascontiguousarray(coords, dtype=np.float64)
+            if cr.ndim != 2 or cr.shape[0] != self.n:
+                raise ValueError("coords must be n x dim")
+            opts.coord_dim = cr.shape[1]
+            opts.coords = cr.ctypes.data
+        h = C.c_void_p()
+        check(lib().gmrfx_create_batched(self.n, ptr(self._colptr), ptr(self._rowval), 0, ptr(perm), self.nbatch, C.byref(opts),
+                                         C.byref(h)))
+        self._h = h
+        self._info = np.zeros(self.nbatch, np.int64)
+
+    # -- lifetime ------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().gmrfx_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clone(self) -> "MI355XBatchBackend":
+        other = object.__new__(MI355XBatchBackend)
+        other.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
+        other._info = self._info.copy()
+        h = C.c_void_p()
+        check(lib().gmrfx_clone(self._h, C.byref(h)))
+        other._h = h
+        return other
+
+    # -- shape checks (before any ctypes call) ---------------------------------------------
+    def _values(self, NZ) -> np.ndarray:
+        NZ = np.asarray(NZ, dtype=np.float64)
+        if NZ.shape != (self._nnz, self.nbatch):
+            raise ValueError(f"NZ must have shape (nnz, nbatch) = ({self._nnz}, {self.nbatch}), got {NZ.shape}")
+        return np.asfortranarray(NZ)
+
+    def _members(self, R, what: str):
+        """(n, B) or (n, r, B) -> Fortran array, columns per member, member stride"""
+        R = np.asarray(R, dtype=np.float64)
+        if R.ndim == 2 and R.shape == (self.n, self.nbatch):
+            return np.asfortranarray(R), 1, self.n
+        if R.ndim == 3 and R.shape[0] == self.n and R.shape[2] == self.nbatch:
+            return np.asfortranarray(R), R.shape[1], self.n * R.shape[1]
+        raise ValueError(f"{what} must have shape (n, nbatch) or (n, r, nbatch) with n = {self.n}, nbatch = {self.nbatch}, got {R.shape}")
+
+    def _mean(self, mean):
+        if mean is None:
+            return None
+        mu = np.asarray(mean, dtype=np.float64)
+        if mu.shape == (self.n,):
+            mu = np.repeat(mu[:, None], self.nbatch, axis=1)
+        if mu.shape != (self.n, self.nbatch):
+            raise ValueError(f"mean must have shape (n,) or (n, nbatch), got {mu.shape}")
+        return np.asfortranarray(mu)
+
+    # -- numeric ---------------------------------------------------------------------------
+    def refactorize_values(self, NZ) -> np.ndarray:
+        """All members from their values; returns info (B,): 0, or 1 + the member's first failing pivot (elimination order)."""
+        nz = self._values(NZ)
+        info = np.zeros(self.nbatch, np.int64)
+        code = lib().gmrfx_batch_refactorize(self._h, ptr(nz), ptr(info))
+        self._info = info
+        check(code, self._h)
+        return info.copy()
+
+    def info(self) -> np.ndarray:
+        return self._info.copy()
+
+    def logdet(self) -> np.ndarray:
+        out = np.empty(self.nbatch)
+        check(lib().gmrfx_batch_logdet(self._h, ptr(out)), self._h)
+        return out
+
+    def _solve(self, R, name: str):
+        Rf, r, s = self._members(R, "R" if name == "gmrfx_batch_solve" else "Z")
+        X = np.empty_like(Rf, order="F")
+        check(getattr(lib(), name)(self._h, Rf.ctypes.data, self.n, s, r, X.ctypes.data, self.n, s), self._h)
+        return X
+
+    def solve(self, R) -> np.ndarray:
+        """X_k = Q_k^-1 R_k for R of shape (n, B) or (n, r, B)."""
+        return self._solve(R, "gmrfx_batch_solve")
+
+    def backward_solve(self, Z) -> np.ndarray:
+        """X_k = P' L_k^-T Z_k (samples of member k) for Z of shape (n, B) or (n, r, B)."""
+        return self._solve(Z, "gmrfx_batch_backward_solve")
+
+    def sqmahal(self, X, mean=None, nzval=None) -> np.ndarray:
+        """(x_vk - mu_k)' Q_k (x_vk - mu_k): X (n, B) -> (1, B), X (n, nvec, B) -> (nvec, B). mean: (n,) for every member or
+        (n, B); nzval: (nnz, B), None = the values of the last refactorize_values."""
+        Xf, nvec, s = self._members(X, "X")
+        mu = self._mean(mean)
+        nz = None if nzval is None else self._values(nzval)
+        out = np.empty((nvec, self.nbatch), order="F")
+        check(lib().gmrfx_batch_quadform(self._h, ptr(nz), ptr(Xf), self.n, s, nvec, ptr(mu), out.ctypes.data), self._h)
+        return out
+
+    def refactorize_logpdf(self, NZ, X, mean=None):
+        """The logpdf terms of every member with new values: (logdet (B,), quad (nvec, B), info (B,));
+        logpdf_k = -quad / 2 + logdet_k / 2 - n log(2 pi) / 2 (workspace_gmrf.jl:288-292)."""
+        nz = self._values(NZ)
+        Xf, _, _ = self._members(X, "X")
+        mu = self._mean(mean)
+        info = self.refactorize_values(nz)
+        return self.logdet(), self.sqmahal(Xf, mu), info
+
+    def selinv_diag(self) -> np.ndarray:
+        """diag(Q_k^-1) of every member: (n, B)."""
+        out = np.empty((self.n, self.nbatch), order="F")
+        check(lib().gmrfx_selinv_diag(self._h, out.ctypes.data), self._h)
+        return out
+
+    # -- extras ----------------------------------------------------------------------------
+    def batch_size(self):
+        nb, nm = C.c_int64(0), C.c_int64(0)
+        check(lib().gmrfx_batch_size(self._h, C.byref(nb), C.byref(nm)))
+        return nb.value, nm.value
+
+    def ordering_permutation(self) -> np.ndarray:
+        """The MEMBER's elimination order (0-based); the handle's is this one replicated with offsets k n."""
+        p = np.empty(self.n * self.nbatch, np.int64)
+        check(lib().gmrfx_get_perm(self._h, 0, ptr(p)))
+        return p[:self.n].copy()
+
+    def forest_permutation(self) -> np.ndarray:
+        p = np.empty(self.n * self.nbatch, np.int64)
+        check(lib().gmrfx_get_perm(self._h, 0, ptr(p)))
+        return p
+
+    def stats(self) -> dict:
+        st = GmrfxStats()
+        check(lib().gmrfx_get_stats(self._h, C.byref(st), C.sizeof(GmrfxStats)))
+        return st.asdict()
+
+    def factor_values(self) -> np.ndarray:
+        sizes = np.zeros(8, np.int64)
+        check(lib().gmrfx_symbolic_sizes(self._h, ptr(sizes)))
+        out = np.empty(int(sizes[2]))
+        check(lib().gmrfx_get_factor_values(self._h, ptr(out)), self._h)
+        return out
+
+    # -- device-resident entry points (HBM in, HBM out) -------------------------------------
+    def refactorize_dev(self, d_nzval: int) -> np.ndarray:
+        info = np.zeros(self.nbatch, np.int64)
+        code = lib().gmrfx_batch_refactorize_dev(self._h, d_nzval, ptr(info))
+        self._info = info
+        check(code, self._h)
+        return info.copy()
+
+    def solve_dev(self, d_B: int, ldb: int, sb: int, nrhs: int, d_X: int, ldx: int, sx: int) -> None:
+        check(lib().gmrfx_batch_solve_dev(self._h, d_B, ldb, sb, nrhs, d_X, ldx, sx), self._h)
+
+    def backward_solve_dev(self, d_Z: int, ldz: int, sz: int, nrhs: int, d_X: int, ldx: int, sx: int) -> None:
+        check(lib().gmrfx_batch_backward_solve_dev(self._h, d_Z, ldz, sz, nrhs, d_X, ldx, sx), self._h)
+
+    def quadform_dev(self, d_nzval: int, d_X: int, ldx: int, sx: int, nvec: int, d_mu: int = 0) -> np.ndarray:
+        out = np.empty((max(nvec, 0), self.nbatch), order="F")
+        check(lib().gmrfx_batch_quadform_dev(self._h, d_nzval or None, d_X, ldx, sx, nvec, d_mu or None, out.ctypes.data), self._h)
+        return out
+
+    def refactorize_logpdf_dev(self, d_nzval: int, d_X: int, ldx: int, sx: int, nvec: int, d_mu: int = 0):
+        """gmrfx_batch_refactorize_logpdf_dev: (logdet (B,), quad (nvec, B), info (B,)) in one call, one synchronisation."""
+        quad = np.empty((max(nvec, 0), self.nbatch), order="F")
+        ld = np.empty(self.nbatch)
+        info = np.zeros(self.nbatch, np.int64)
+        code = lib().gmrfx_batch_refactorize_logpdf_dev(self._h, d_nzval, d_X or None, ldx, sx, nvec, d_mu or None, quad.ctypes.data,
+                                                        ptr(ld), ptr(info))
+        self._info = info
+        check(code, self._h)
+        return ld, quad, info.copy()

@@ -9,6 +9,7 @@
 module GMRFX
 
 using LinearAlgebra, SparseArrays, Random
+import LinearAlgebra: logdet      # extended for the owned MI355XBatch only (batched handles below)
 import Distributions
 import GaussianMarkovRandomFields as G
 import GaussianMarkovRandomFields: WorkspaceBackend, refactorize!, backend_solve, compute_logdet,
@@ -410,6 +411,103 @@ end
 
 function solve! end       # ROCArray methods: julia/ext/GMRFXAMDGPUExt.jl
 
+# ---------------------------------------------------------------------------------- batched handles
+# B precisions with ONE pattern factored in one pass (include/gmrfx.h, gmrfx_create_batched): the hyper-parameter loop of
+# docs/src/literate-tutorials/workspace_factorization_reuse.jl evaluates logpdf for many values of one pattern, and WorkspacePool
+# (src/workspace/workspace_pool.jl:5-22) runs such evaluations side by side. Member k's values are column k of an nnz x B matrix
+# (the pattern's CSC order), right-hand sides are n x B or n x r x B arrays.
+mutable struct MI355XBatch
+    h::Handle
+    n::Int           # nodes per member
+    nbatch::Int
+    nnz::Int         # stored entries per member
+    info::Vector{Int64}
+end
+
+function MI355XBatch(Q::SparseMatrixCSC{Float64, Int}, nbatch::Integer; ordering = nothing, coords = nothing, device = -1)
+    n = size(Q, 1)
+    perm = resolve_ordering(Q, ordering)
+    perm === nothing || isperm(perm) && length(perm) == n || throw(ArgumentError("ordering is not a permutation of 1:$n"))
+    C = coords === nothing ? nothing : Matrix{Float64}(transpose(coords))
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve Q perm C begin
+        o = Opts(struct_size = sizeof(Opts), device = device, ordering = ordering === :natural ? 1 : 0,
+            coord_dim = C === nothing ? 0 : size(C, 1), coords = C === nothing ? C_NULL : pointer(C))
+        check(ccall((:gmrfx_create_batched, LIB), Int32,
+            (Int64, Ptr{Int64}, Ptr{Int64}, Int32, Ptr{Int64}, Int64, Ref{Opts}, Ref{Ptr{Cvoid}}),
+            n, SparseArrays.getcolptr(Q), rowvals(Q), 1, perm === nothing ? C_NULL : pointer(perm), nbatch, Ref(o), out))
+    end
+    return MI355XBatch(Handle(out[]), n, Int(nbatch), nnz(Q), zeros(Int64, nbatch))
+end
+
+function refactorize!(bb::MI355XBatch, NZ::Matrix{Float64})
+    size(NZ) == (bb.nnz, bb.nbatch) || throw(DimensionMismatch("NZ must be nnz x nbatch"))
+    GC.@preserve NZ check(ccall((:gmrfx_batch_refactorize, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, NZ, bb.info), bb.h)
+    return bb
+end
+
+# per-member pivot status of the last refactorize!: 0, or 1 + the first failing column of that member (elimination order)
+info(bb::MI355XBatch) = copy(bb.info)
+
+function logdet(bb::MI355XBatch)
+    out = Vector{Float64}(undef, bb.nbatch)
+    GC.@preserve out check(ccall((:gmrfx_batch_logdet, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, out), bb.h)
+    return out
+end
+
+function _batch_solve(bb::MI355XBatch, R::Array{Float64}, name::Symbol)
+    (ndims(R) == 2 && size(R) == (bb.n, bb.nbatch)) || (ndims(R) == 3 && size(R, 1) == bb.n && size(R, 3) == bb.nbatch) ||
+        throw(DimensionMismatch("expected n x nbatch or n x r x nbatch"))
+    r = ndims(R) == 3 ? size(R, 2) : 1
+    X = similar(R)
+    code = GC.@preserve R X if name === :solve
+        ccall((:gmrfx_batch_solve, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64),
+            bb.h.ptr, R, bb.n, bb.n * r, r, X, bb.n, bb.n * r)
+    else
+        ccall((:gmrfx_batch_backward_solve, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Int64, Int64),
+            bb.h.ptr, R, bb.n, bb.n * r, r, X, bb.n, bb.n * r)
+    end
+    check(code, bb.h)
+    return X
+end
+# X_k = Q_k \ R_k
+solve(bb::MI355XBatch, R::Union{Matrix{Float64}, Array{Float64, 3}}) = _batch_solve(bb, R, :solve)
+# X_k = P' L_k^-T Z_k (samples)
+backward_solve(bb::MI355XBatch, Z::Union{Matrix{Float64}, Array{Float64, 3}}) = _batch_solve(bb, Z, :backward)
+
+# diag(Q_k^-1) of every member: n x nbatch
+function selinv_diag(bb::MI355XBatch)
+    out = Matrix{Float64}(undef, bb.n, bb.nbatch)
+    GC.@preserve out check(ccall((:gmrfx_selinv_diag, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, out), bb.h)
+    return out
+end
+
+# the terms of logpdf for every member (src/workspace/workspace_gmrf.jl:288-292): new values -> (log det Q_k, (z_k - mu_k)' Q_k (z_k - mu_k));
+# Z: n x nbatch, mean: n x nbatch or nothing
+function logpdf_terms(bb::MI355XBatch, NZ::Matrix{Float64}, Z::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing)
+    size(Z) == (bb.n, bb.nbatch) || throw(DimensionMismatch("Z must be n x nbatch"))
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    refactorize!(bb, NZ)
+    quad = Vector{Float64}(undef, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve NZ Z mean quad check(ccall((:gmrfx_batch_quadform, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+        bb.h.ptr, NZ, Z, bb.n, bb.n, 1, mu, quad), bb.h)
+    return logdet(bb), quad, info(bb)
+end
+
+# deepcopy(bb) (Newton loops copy their caches) reaches the owning Handle: a copy of a handle is a clone of the native one
+# (gmrfx_clone), never a second owner of the same pointer
+function Base.deepcopy_internal(h::Handle, stackdict::IdDict)
+    haskey(stackdict, h) && return stackdict[h]::Handle
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:gmrfx_clone, LIB), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}), h.ptr, out))
+    c = Handle(out[])
+    stackdict[h] = c
+    return c
+end
+
 # ---------------------------------------------------------------------------------- seam A
 # LinearSolve algorithm; GMRF-side hooks exactly as the Pardiso extension (ext/GaussianMarkovRandomFieldsPardiso.jl:10-80).
 import LinearSolve, SciMLBase
@@ -478,5 +576,5 @@ G.configure_algorithm(alg::MI355XCholesky) = alg
 G.algorithm_applicable(::MI355XCholesky, ::Union{SparseMatrixCSC, Symmetric{<:Any, <:SparseMatrixCSC}}) = Val{true}()
 G.algorithm_applicable(::MI355XCholesky, ::AbstractMatrix) = Val{false}()
 
-export MI355XBackend, MI355XCholesky, MI355XCacheval, ordering_permutation, ShardedMI355X, rccl_unique_id
+export MI355XBackend, MI355XCholesky, MI355XCacheval, ordering_permutation, ShardedMI355X, rccl_unique_id, MI355XBatch
 end # module

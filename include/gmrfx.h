@@ -365,6 +365,55 @@ int32_t gmrfx_symbolic_sweep_chunks(const gmrfx_handle *h, int64_t *nchunks, int
                                     int64_t *slot, int64_t *fwd, int64_t *bwd, int64_t *rows);
 int32_t gmrfx_get_factor_values(gmrfx_handle *h, double *out);
 
+/* ---- batched handles: B precisions with ONE pattern, factored in one pass ------------------------------------------------------
+ * The hyper-parameter loop evaluates logpdf for many values of one pattern (docs/src/literate-tutorials/workspace_factorization_reuse.jl:
+ * 50 values of a 100 x 100 grid; INLA / marginal-likelihood / HMC loops), and WorkspacePool (src/workspace/workspace_pool.jl:5-22)
+ * exists to run such evaluations side by side -- CHOLMOD serialises them behind a global lock. A batched handle holds B MEMBERS:
+ * one pattern Q and one elimination order, B sets of values. Internally it is an ordinary handle of the block-diagonal matrix
+ * diag(Q_1 .. Q_B), whose elimination forest is B copies of the member's tree on the same levels: every level launch does B times
+ * the work of one member, with the same kernels.
+ * gmrfx_create_batched: n, colptr, rowval, perm and opts.coords describe ONE member (the order is computed once, on the member, and
+ * replicated: perm[k n + i] = k n + perm_1[i]). INVALID_ARG (message in gmrfx_last_create_error, nothing allocated) for nbatch < 1,
+ * nbatch n > INT32_MAX, or sharding options (shard_world > 1, shard_min_top > 0). gmrfx_stats then describe the forest: n, nnz_l,
+ * nsuper, factor_flops, bytes_factor and bytes_cb_arena are B times the member's (also for symbolic_only handles: size B with them
+ * before building a numeric handle), nlevels is the member's.
+ * gmrfx_batch_size: *nbatch = B, *n_member = n (1 and n for a plain handle; the batch entry points treat it as a batch of one).
+ * gmrfx_batch_refactorize(_dev): nzval = nnz x B column-major, member k's values in the member's CSC order at nzval + k nnz (which
+ *   is the forest's CSC value array). info[k] <- 0, or 1 + the first member-local pivot column (elimination order) that failed --
+ *   what a plain handle reports for that member's values alone. A failing member does not disturb the others. check_posdef = 1:
+ *   GMRFX_ERR_NOT_POSDEF when any member fails; info is filled in either way.
+ * gmrfx_batch_logdet: out[k] = log det Q_k.
+ * gmrfx_batch_solve(_dev): X_k = Q_k^-1 B_k; gmrfx_batch_backward_solve(_dev): X_k = P' L_k^-T Z_k (Z_k in the member's elimination
+ *   order). Member k's n x nrhs block of B (Z) / X at B + k sb / X + k sx, leading dimension ldb / ldx >= n, stride >= ld nrhs.
+ * gmrfx_batch_quadform(_dev): quad[k nvec + v] = (x_vk - mu_k)' Q_k (x_vk - mu_k) (quad: host array nvec x B), x_vk at X + k sx + v ldx,
+ *   mu_k at mu + k n (mu: n x B, nullable), Q_k's values at nzval + k nnz (NULL: the values of the last host refactorisation), the
+ *   stored triangle chosen by opts.uplo as in gmrfx_quadform; one launch for all members.
+ * gmrfx_batch_refactorize_logpdf_dev: the batched gmrfx_refactorize_logpdf_dev -- refactorisation of all members, their quadratic forms
+ *   beside it on the side stream, per-member log det and info, one synchronisation; quad (nvec x B), logdet (B), info (B) are host
+ *   arrays. Same bits as gmrfx_batch_refactorize_dev + gmrfx_batch_quadform_dev + gmrfx_batch_logdet.
+ * Every other entry point keeps its meaning on a batched handle and acts on the block-diagonal matrix of size B n: gmrfx_logdet is
+ * the sum over the members, gmrfx_selinv_diag returns the n x B matrix of member variances, gmrfx_get_perm the forest's order,
+ * gmrfx_clone copies the batch (Newton loops clone). The Newton entry points (gmrfx_set_prior, gmrfx_refactorize_update*) take
+ * forest-wide index maps. */
+int32_t gmrfx_create_batched(int64_t n, const int64_t *colptr, const int64_t *rowval, int32_t index_base, const int64_t *perm,
+                             int64_t nbatch, const gmrfx_opts *opts, gmrfx_handle **out);
+int32_t gmrfx_batch_size(const gmrfx_handle *h, int64_t *nbatch, int64_t *n_member);
+int32_t gmrfx_batch_refactorize(gmrfx_handle *h, const double *nzval, int64_t *info /* nbatch, nullable */);
+int32_t gmrfx_batch_refactorize_dev(gmrfx_handle *h, const double *d_nzval, int64_t *info /* nbatch, nullable */);
+int32_t gmrfx_batch_logdet(gmrfx_handle *h, double *out /* nbatch */);
+int32_t gmrfx_batch_solve(gmrfx_handle *h, const double *B, int64_t ldb, int64_t sb, int64_t nrhs, double *X, int64_t ldx, int64_t sx);
+int32_t gmrfx_batch_solve_dev(gmrfx_handle *h, const double *d_B, int64_t ldb, int64_t sb, int64_t nrhs, double *d_X, int64_t ldx, int64_t sx);
+int32_t gmrfx_batch_backward_solve(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t sz, int64_t nrhs, double *X, int64_t ldx, int64_t sx);
+int32_t gmrfx_batch_backward_solve_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t sz, int64_t nrhs, double *d_X, int64_t ldx,
+                                       int64_t sx);
+int32_t gmrfx_batch_quadform(gmrfx_handle *h, const double *nzval, const double *X, int64_t ldx, int64_t sx, int64_t nvec,
+                             const double *mu, double *quad);
+int32_t gmrfx_batch_quadform_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx, int64_t nvec,
+                                 const double *d_mu, double *quad);
+int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx, int64_t nvec,
+                                           const double *d_mu, double *quad /* host, nvec x nbatch */, double *logdet /* host, nbatch */,
+                                           int64_t *info /* host, nbatch, nullable */);
+
 /* KL-optimal sparse approximate Cholesky factor, L L' ~ Theta^-1: a batch of small dense problems, one
  * workgroup each. A task = local rows R (task_rows[task_rowptr[t] .. task_rowptr[t+1]), in the caller's local order)
  * + the columns of L it fills (task_cols[task_colptr[t] ..)): M = Theta[R, R] + reg I = U'U, and for every member
