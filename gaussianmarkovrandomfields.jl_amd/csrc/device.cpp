@@ -13,6 +13,7 @@
 #include <functional>
 #include <stdexcept>
 #include <thread>
+#include <type_traits>
 
 #include "kernels.h"
 
@@ -98,8 +99,6 @@ void Device::set_external_stream(hipStream_t s, bool use, bool async) {
     async_phases_ = use && async;
 }
 
-template <class T, class U> static std::vector<T> conv(const std::vector<U> &v) { return std::vector<T>(v.begin(), v.end()); }
-
 void Device::init(const Symbolic &S, int dev) {
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -119,12 +118,22 @@ void Device::init(const Symbolic &S, int dev) {
         own_stream_ = stream;
         HC(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, lo));
         HC(hipStreamCreateWithPriority(&stream3, hipStreamNonBlocking, hi));
-        if (const char *c = std::getenv("GMRFX_INV_CAP")) {      // testing knob: power of two >= 64
-            int v = std::atoi(c), p2 = NB;
-            while (p2 < v) p2 *= 2;
-            inv_cap_ = p2;
-        }
     }
+    // the environment's testing / A/B / profiling knobs
+    if (const char *c = std::getenv("GMRFX_INV_CAP")) {      // testing knob: power of two >= 64
+        int v = std::atoi(c), p2 = NB;
+        while (p2 < v) p2 *= 2;
+        inv_cap_ = p2;
+    }
+    if (const char *e = std::getenv("GMRFX_TASK_MODE")) {       // A/B knob: "wg" / "wave" force one form for every width
+        const std::string m(e);
+        wave_max_nr_ = m == "wg" ? 0 : m == "wave" ? 64 : wave_max_nr_;
+    }
+    if (const char *e = std::getenv("GMRFX_LEVEL_MARK")) level_mark_ = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GMRFX_BWD_FRONT")) bwd_front_min_ = std::atoi(e);    // fronts a level needs for the one-workgroup backward step (0: never)
+    if (const char *e = std::getenv("GMRFX_FWD_FRONT")) fwd_front_min_ = std::atoi(e);    // ... and for the one-workgroup forward step
+    if (const char *e = std::getenv("GMRFX_SYRK_XCD")) syrk_xcd_ = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GMRFX_SYRK_PIPED")) syrk_piped_min_ = std::atoi(e);
     HC(hipEventCreateWithFlags(&ev_fact_, hipEventDisableTiming));
     HC(hipEventCreateWithFlags(&ev_inv_, hipEventDisableTiming));
     for (auto &ev : ev_) HC(hipEventCreate(&ev));
@@ -140,528 +149,70 @@ void Device::init(const Symbolic &S, int dev) {
 
 void Device::upload(const Symbolic &S) {
     S_ = &S;
-    const int ns = S.nsuper;
-    if (S.nnz_in >= (i64)INT_MAX) throw std::runtime_error("nnz(Q) >= 2^31 not supported by the device scatter map yet");
-    auto up = [&](auto *&dst, const auto &host) {
-        using T = typename std::remove_const<typename std::remove_reference<decltype(host[0])>::type>::type;
-        T *p = dalloc<T>(host.size());
+    const DevicePlan P = build_device_plan(S, PlanOptions{syrk_xcd_});
+    // a device copy of a host vector (the analysis' int64_t offsets become the kernels' long long: the same bytes). The copies
+    // read the host vectors until the synchronisation at the end, while P and S still hold them.
+    auto up = [&](const auto &host) {
+        using T = typename std::decay_t<decltype(host)>::value_type;
+        using D = std::conditional_t<std::is_same<T, i64>::value, long long, T>;
+        static_assert(sizeof(D) == sizeof(T), "a device array holds the same bytes as its host vector");
+        D *p = dalloc<D>(host.size());
         if (!host.empty()) HC(hipMemcpyAsync(p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-        dst = p;
+        return p;
     };
+    levels_ = P.levels; swlevels_ = P.swlevels; sel_max_cols_ = P.sel_max_cols; sel_max_trail_ = P.sel_max_trail;
+    inv_maxc_ = P.inv_maxc; inv_nact_ = P.inv_nact; inv_lvl_first_ = P.inv_lvl_first; inv_lvl_maxc_ = P.inv_lvl_maxc; inv_lvl_nact_ = P.inv_lvl_nact;
+    fc_levelptr_ = P.fc_levelptr; fc_maxtrail_ = P.fc_maxtrail;
+    std::copy_n(P.wave_first, kWaveClasses, wave_first_); std::copy_n(P.wave_count, kWaveClasses, wave_count_); std::copy_n(P.nsub_cls, 3, nsub_cls_);
+    bottom_top_level_ = P.bottom_top_level; fused_gate_level_ = P.fused_gate_level; first_multiblock_level_ = P.first_multiblock_level;
+    syrk_flops = P.syrk_flops; sum_trail_ = P.sum_trail; l_size_ = P.l_size; nq_ = P.nq; nswt_ = P.nswt; nswc_ = P.nswc;
+
     ds_.n = (int)S.n;
-    ds_.nsuper = ns;
-    const int *ip; const long long *lp;
-    up(ip, S.sfirst); ds_.sfirst = ip;
-    std::vector<long long> tmp64;
-    tmp64 = conv<long long>(S.rowptr); up(lp, tmp64); ds_.rowptr = lp; HC(hipStreamSynchronize(stream));
-    up(ip, S.rows); ds_.rows = ip;
-    up(ip, S.rel); ds_.rel = ip;
-    tmp64 = conv<long long>(S.panelptr); up(lp, tmp64); ds_.panelptr = lp; HC(hipStreamSynchronize(stream));
-    up(ip, S.ld); ds_.ld = ip;
-    tmp64 = conv<long long>(S.cbptr); up(lp, tmp64); ds_.cbptr = lp; HC(hipStreamSynchronize(stream));
-    tmp64 = conv<long long>(S.zbptr); up(lp, tmp64); d_zbptr_ = lp; HC(hipStreamSynchronize(stream));
-    {   // selected inversion: one gather record per supernode
-        std::vector<SelRec> sr((size_t)ns);
-        for (i32 s = 0; s < ns; s++) {
-            SelRec t{};
-            const i32 p = S.sparent[s];
-            t.p = (int)p;
-            t.rel = (long long)S.rowptr[s] + S.ncols(s);
-            t.m = S.nrows(s) - S.ncols(s);
-            t.out = (long long)S.zbptr[s];
-            if (p >= 0) {
-                t.zp = (long long)S.panelptr[p]; t.zbp = (long long)S.zbptr[p];
-                t.cp = S.ncols(p); t.mp = S.nrows(p) - S.ncols(p); t.ldp = (int)S.ld[p];
-            }
-            t.foreign = (S.shard_plan && p >= 0 && S.owner[p] != S.shard_rank) ? 1 : 0;   // (= DevSym::foreign_parent)
-            sr[(size_t)s] = t;
-        }
-        const SelRec *sp; up(sp, sr); d_selrec_ = sp;
-        HC(hipStreamSynchronize(stream));
-    }
-    tmp64 = conv<long long>(S.childptr); up(lp, tmp64); ds_.childptr = lp; HC(hipStreamSynchronize(stream));
-    up(ip, S.children); ds_.children = ip;
-    up(ip, S.sparent); ds_.sparent = ip;
-    tmp64 = conv<long long>(S.qptr); up(lp, tmp64); ds_.qptr = lp; HC(hipStreamSynchronize(stream));
-    {
-        std::vector<int> qs(S.qsrc.size()), qd(S.qdst.size()), qc(S.qdst.size());
-        for (i32 s = 0; s < ns; s++)
-            for (i64 q = S.qptr[s]; q < S.qptr[s + 1]; q++) {
-                qs[q] = (int)S.qsrc[q];
-                const i64 rel = S.qdst[q] - S.panelptr[s];      // column-major offset inside the panel (may exceed 2^31)
-                qc[q] = (int)(rel / S.ld[s]);
-                qd[q] = (int)(rel % S.ld[s]);
-            }
-        up(ip, qs); ds_.qsrc = ip;
-        nq_ = (long long)qs.size();
-        d_nzp_ = dalloc<double>((size_t)std::max<long long>(nq_, 1));
-        HC(hipEventCreateWithFlags(&ev_nzp_, hipEventDisableTiming));
-        HC(hipEventCreateWithFlags(&ev_nzp0_, hipEventDisableTiming));
-        up(ip, qd); ds_.qdst = ip;
-        up(ip, qc); ds_.qcol = ip;
-        // entries are sorted by column inside a front: one pointer per column of L replaces a search per panel column
-        std::vector<int> qcp((size_t)S.n + 1);
-        for (i32 s = 0; s < ns; s++) {
-            i64 q = S.qptr[s];
-            for (i32 tc = 0; tc < S.ncols(s); tc++) {
-                qcp[(size_t)S.sfirst[s] + tc] = (int)q;
-                while (q < S.qptr[s + 1] && qc[q] == tc) q++;
-            }
-            if (q != S.qptr[s + 1]) throw std::runtime_error("scatter map of a front is not sorted by column");
-        }
-        qcp[(size_t)S.n] = (int)S.qptr[ns];
-        up(ip, qcp); ds_.qcolptr = ip;
-        HC(hipStreamSynchronize(stream));
-    }
-    {
-        const std::vector<long long> wptr = conv<long long>(S.wptr);     // (Symbolic::wptr: per-rank layout on sharded handles)
-        sum_trail_ = wptr[ns];
-        up(lp, wptr); ds_.wptr = lp;
-        h_wptr_ = wptr;
-        HC(hipStreamSynchronize(stream));
-    }
-    {
-        const std::vector<long long> wptr = conv<long long>(S.wptr);
-        std::vector<EdgeRec> edges(S.children.size());
-        std::vector<int> etile;
-        std::vector<int> erow;
-        for (i32 p = 0; p < ns; p++) {
-            const int cp = S.ncols(p), mp = S.nrows(p) - cp, nT = (mp + 31) / 32;
-            for (i64 ch = S.childptr[p]; ch < S.childptr[p + 1]; ch++) {
-                const i32 d = S.children[ch];
-                const int cd = S.ncols(d), md = S.nrows(d) - cd;
-                const i64 reloff = S.rowptr[d] + cd;
-                if (etile.size() + (size_t)nT + 1 >= (size_t)INT_MAX) throw std::runtime_error("edge tile table too large");
-                EdgeRec e{d, md, (int)etile.size(), 0, (long long)reloff, wptr[d], (long long)S.cbptr[d], (long long)erow.size()};
-                int a = 0;
-                for (int T = 0; T <= nT; T++) {
-                    const int key = cp + 32 * T;
-                    while (a < md && S.rel[reloff + a] < key) a++;
-                    etile.push_back(a);
-                }
-                e.nown = etile[e.tptr];
-                erow.resize(erow.size() + (size_t)cp, -1);      // which child row lands in own column tc of the parent
-                for (int a2 = 0; a2 < e.nown; a2++) erow[(size_t)e.eoff + (size_t)S.rel[reloff + a2]] = a2;
-                edges[ch] = e;
-            }
-        }
-        const EdgeRec *ep; up(ep, edges); ds_.edge = ep;
-        if (etile.empty()) etile.push_back(0);
-        up(ip, etile); ds_.etile = ip;
-        if (erow.empty()) erow.push_back(-1);
-        up(ip, erow); ds_.erow = ip;
-        HC(hipStreamSynchronize(stream));
-        h_edges_.swap(edges);      // read once more by the tile records of the contribution-block SYRK (init)
-        h_etile_.swap(etile);
-    }
-    tmp64 = conv<long long>(S.diagoff); up(lp, tmp64); ds_.diagoff = lp; HC(hipStreamSynchronize(stream));
-    up(ip, S.perm); ds_.perm = ip;
-    up(ip, S.iperm); d_iperm_ = ip;
+    ds_.nsuper = S.nsuper;
+    ds_.sfirst = up(S.sfirst); ds_.rowptr = up(S.rowptr); ds_.rows = up(S.rows); ds_.rel = up(S.rel);
+    ds_.panelptr = up(S.panelptr); ds_.ld = up(S.ld); ds_.cbptr = up(S.cbptr);
+    d_zbptr_ = up(S.zbptr);
+    d_selrec_ = up(P.selrec);
+    ds_.childptr = up(S.childptr); ds_.children = up(S.children); ds_.sparent = up(S.sparent);
+    ds_.qptr = up(S.qptr); ds_.qsrc = up(P.qsrc); ds_.qdst = up(P.qdst); ds_.qcol = up(P.qcol); ds_.qcolptr = up(P.qcolptr);
+    d_nzp_ = dalloc<double>((size_t)std::max<long long>(nq_, 1));
+    HC(hipEventCreateWithFlags(&ev_nzp_, hipEventDisableTiming));
+    HC(hipEventCreateWithFlags(&ev_nzp0_, hipEventDisableTiming));
+    ds_.wptr = up(S.wptr);
+    ds_.edge = up(P.edge); ds_.etile = up(P.etile); ds_.erow = up(P.erow);
+    ds_.diagoff = up(S.diagoff); ds_.perm = up(S.perm);
+    d_iperm_ = up(S.iperm);
     if (S.shard_plan) {
-        std::vector<unsigned char> own(S.n, 0);
-        for (i32 s = 0; s < ns; s++) {
-            const bool mine = S.owner[s] == S.shard_rank;
-            if (mine) for (i32 j = S.sfirst[s]; j < S.sfirst[s + 1]; j++) own[j] = 1;
-        }
-        const unsigned char *op; up(op, own); d_owncol_ = op;
-        HC(hipStreamSynchronize(stream));
-        // selected inversion across ranks: which of my fronts get their trailing inverse block from another rank, and
-        // which fronts of other ranks get theirs from me (gathered here, level by level, then sent)
-        std::vector<unsigned char> fp(ns, 0);
-        std::vector<std::vector<int>> fc(S.nlevels);
-        for (i32 s = 0; s < ns; s++) {
-            const i32 pr = S.sparent[s];
-            if (pr < 0) continue;
-            if (S.owner[pr] != S.shard_rank) fp[s] = 1;
-            if (S.owner[pr] == S.shard_rank && S.owner[s] != S.shard_rank) fc[S.level[s]].push_back(s);
-        }
-        const unsigned char *fpp; up(fpp, fp); ds_.foreign_parent = fpp;
-        std::vector<int> flat;
-        fc_levelptr_.assign(S.nlevels + 1, 0);
-        fc_maxtrail_.assign(S.nlevels, 0);
-        for (i32 l = 0; l < S.nlevels; l++) {
-            for (int s : fc[l]) { flat.push_back(s); fc_maxtrail_[l] = std::max(fc_maxtrail_[l], S.nrows(s) - S.ncols(s)); }
-            fc_levelptr_[l + 1] = (int)flat.size();
-        }
-        const int *fl; up(fl, flat); d_fchild_ = const_cast<int *>(fl);
-        HC(hipStreamSynchronize(stream));
+        d_owncol_ = up(P.owncol);
+        ds_.foreign_parent = up(P.foreign_parent);
+        d_fchild_ = up(P.fchild);
     }
-    up(ip, S.lrow); ds_.lrow = ip;
-    {
-        const int *a; up(a, S.sw_levellist); d_sw_levellist_ = const_cast<int *>(a);
-        nswt_ = (int)S.swt_first.size();
-        const std::vector<long long> wp = conv<long long>(S.wptr);
-        std::vector<SweepTask> tk((size_t)nswt_);
-        for (int t = 0; t < nswt_; t++) {
-            const i32 f = S.swt_first[t], r = S.swt_last[t];
-            SweepTask &T = tk[t];
-            T.s0 = f; T.s1 = r; T.col0 = S.sfirst[f]; T.nt = S.sfirst[r + 1] - S.sfirst[f];
-            T.mroot = S.nrows(r) - S.ncols(r); T.pad = 0;
-            T.p0 = S.panelptr[f]; T.p1 = S.panelptr[r + 1];
-            T.rp0 = S.rowptr[f]; T.rp1 = S.rowptr[r + 1];
-            T.rroot = S.rowptr[r] + S.ncols(r);
-            T.woff = wp[r];
-            T.c0 = S.swc_ptr[t]; T.nch = S.swc_ptr[t + 1] - S.swc_ptr[t];
-            T.b0 = S.swc_bptr[t]; T.nbw = S.swc_bptr[t + 1] - S.swc_bptr[t];
-            for (int q = 0; q < 4; q++) { T.scnt[q] = S.swc_slot[(size_t)8 * t + q]; T.sbar[q] = S.swc_slot[(size_t)8 * t + 4 + q]; }
-        }
-        // chunk records and their target-row lists. The kernels take a target row as the BYTE offset of its column 0 in the
-        // local vector (row-major, NC columns, odd rows with their 16-column tiles swapped: sweep_chunk.hip, vbyte) and add
-        // the lane's column with one XOR; padding rows go to the spare row. Forward order per 32-row pair: [lk][tile][rr] =
-        // pair row 2 (lk + 4 rr) + tile; backward order per 16-row k-tile: [lk][h][e] = row 8 h + 2 lk + e.
-        nswc_ = S.swc_nchunks;
-        if (nswc_ > 0) {
-            const Symbolic::SwChunk *cp; up(cp, S.swc_fwd); d_swc_fwd_ = const_cast<Symbolic::SwChunk *>(cp);
-            up(cp, S.swc_bwd); d_swc_bwd_ = const_cast<Symbolic::SwChunk *>(cp);
-            const int nc = sweep_chunk_nc(), spare = sweep_chunk_spare_row();
-            auto enc = [&](i32 row) { const int r = row < 0 ? spare : row; return (r * nc + (nc >= 32 ? (r & 1) << 4 : 0)) * 8; };
-            // (64 entries of slack: the backward kernel requests a fixed number of k-tiles per chunk, the last chunk's past its list)
-            std::vector<int> lf(S.swc_rows.size() + 64, 0), lb(S.swc_rows.size() + 64, 0);
-            for (size_t b0 = 0; b0 < S.swc_rows.size(); b0 += 32) {
-                const i32 *src = S.swc_rows.data() + b0;
-                for (int lk = 0; lk < 4; lk++)
-                    for (int tl = 0; tl < 2; tl++)
-                        for (int rr = 0; rr < 4; rr++) lf[b0 + lk * 8 + tl * 4 + rr] = enc(src[2 * (lk + 4 * rr) + tl]);
-                for (int kt = 0; kt < 2; kt++)
-                    for (int lk = 0; lk < 4; lk++)
-                        for (int h = 0; h < 2; h++)
-                            for (int e = 0; e < 2; e++) lb[b0 + 16 * kt + lk * 4 + h * 2 + e] = enc(src[16 * kt + 8 * h + 2 * lk + e]);
-            }
-            const int *a; up(a, lf); d_swc_listf_ = const_cast<int *>(a);
-            up(a, lb); d_swc_listb_ = const_cast<int *>(a);
-            HC(hipStreamSynchronize(stream));          // (the host vectors go out of scope)
-            d_dtile_ = dalloc<double>((size_t)nswc_ * 256);
-        }
-        const SweepTask *tp; up(tp, tk); d_swt_ = const_cast<SweepTask *>(tp);
-        // wave tasks (sweep_wave.hip): the tasks by LDS class -- rows of the local vector <= kWaveRows[k] -- heaviest first inside
-        // a class (the list is already sorted by work); the big class is launched first
-        {
-            if (const char *e = std::getenv("GMRFX_TASK_MODE")) {       // A/B knob: "wg" / "wave" force one form for every width
-                const std::string m(e);
-                wave_max_nr_ = m == "wg" ? 0 : m == "wave" ? 64 : wave_max_nr_;
-            }
-            std::vector<int> ord;
-            for (int k = 0; k < kWaveClasses; k++) {
-                wave_first_[k] = (int)ord.size();
-                for (int t = 0; t < nswt_; t++) {
-                    const int rows = tk[t].nt + tk[t].mroot;
-                    if (rows <= kWaveRows[k] && (k == 0 || rows > kWaveRows[k - 1])) ord.push_back(t);
-                }
-                wave_count_[k] = (int)ord.size() - wave_first_[k];
-            }
-            if ((int)ord.size() != nswt_) throw std::runtime_error("internal: a sweep task exceeds the largest wave-task class");
-            for (int t = 0; t < nswt_; t++) ord.push_back(t);       // ... and all of them, heaviest first (passes of at most 4 columns: one launch)
-            const int *op; up(op, ord); d_wave_order_ = op;
-        }
-        HC(hipStreamSynchronize(stream));
+    ds_.lrow = up(S.lrow);
+    d_sw_levellist_ = up(S.sw_levellist);
+    if (nswc_ > 0) {
+        d_swc_fwd_ = up(S.swc_fwd); d_swc_bwd_ = up(S.swc_bwd);
+        d_swc_listf_ = up(P.swc_listf); d_swc_listb_ = up(P.swc_listb);
+        d_dtile_ = dalloc<double>((size_t)nswc_ * 256);
     }
-    {
-        const int *ll; up(ll, S.levellist); d_levellist_ = const_cast<int *>(ll);
-        {   // the same lists with every level's big fronts split into their even / odd positions
-            std::vector<int> l2(S.levellist.begin(), S.levellist.end());
-            for (i32 l = 0; l < S.nlevels; l++) {
-                const i64 f = S.levelptr[l] + S.level_nsmall[l], e = S.levelptr[l + 1];
-                i64 w = f;
-                for (i64 k = f; k < e; k += 2) l2[w++] = S.levellist[k];
-                for (i64 k = f + 1; k < e; k += 2) l2[w++] = S.levellist[k];
-            }
-            const int *l2p; up(l2p, l2); d_levellist2_ = const_cast<int *>(l2p);
-            if (const char *e = std::getenv("GMRFX_LEVEL_MARK")) level_mark_ = std::atoi(e) != 0;
-            if (const char *e = std::getenv("GMRFX_BWD_FRONT")) bwd_front_min_ = std::atoi(e);    // fronts a level needs for the one-workgroup backward step (0: never)
-            if (const char *e = std::getenv("GMRFX_FWD_FRONT")) fwd_front_min_ = std::atoi(e);    // ... and for the one-workgroup forward step
-        }
-        const int *a; up(a, S.sub_first); d_sub_first_ = const_cast<int *>(a);
-        const int *b; up(b, S.sub_last); d_sub_last_ = const_cast<int *>(b);
-        for (int k = 0; k < 3; k++) nsub_cls_[k] = S.nsub_cls[k];
-        const int *sl; up(sl, S.sel_levellist); d_sel_levellist_ = const_cast<int *>(sl);
-        // one 32-byte geometry record per position of the level lists (kernels.h, front_view)
-        auto frecs = [&](const std::vector<i32> &lst, FrontView *&dst) {
-            std::vector<FrontView> v(lst.size());
-            for (size_t k = 0; k < lst.size(); k++) {
-                const i32 s = lst[k];
-                v[k] = FrontView{(int)s, S.ncols(s), S.nrows(s), (int)S.ld[s], (int)S.sfirst[s], 0, (long long)S.panelptr[s]};
-            }
-            const FrontView *p; up(p, v); dst = const_cast<FrontView *>(p);
-        };
-        frecs(S.levellist, d_frec_);
-        frecs(S.sel_levellist, d_sel_frec_);
-        {   // ... and of the even / odd re-ordering of the big fronts (two panel chains per level)
-            std::vector<i32> l2(S.levellist.begin(), S.levellist.end());
-            for (i32 l = 0; l < S.nlevels; l++) {
-                const i64 f = S.levelptr[l] + S.level_nsmall[l], e = S.levelptr[l + 1];
-                i64 w = f;
-                for (i64 k = f; k < e; k += 2) l2[w++] = S.levellist[k];
-                for (i64 k = f + 1; k < e; k += 2) l2[w++] = S.levellist[k];
-            }
-            frecs(l2, d_frec2_);
-        }
-        HC(hipStreamSynchronize(stream));
-    }
-    HC(hipStreamSynchronize(stream));
-
-    sel_max_cols_.assign(S.nlevels, 0);
-    sel_max_trail_.assign(S.nlevels, 0);
-    for (i32 l = 0; l < S.nlevels; l++)
-        for (i64 k = S.sel_levelptr[l] + S.sel_level_nsmall[l]; k < S.sel_levelptr[l + 1]; k++) {
-            const i32 s = S.sel_levellist[k];
-            sel_max_cols_[l] = std::max(sel_max_cols_[l], (int)S.ncols(s));
-            sel_max_trail_[l] = std::max(sel_max_trail_[l], (int)(S.nrows(s) - S.ncols(s)));
-        }
-    auto build_levels = [&](std::vector<LevelInfo> &LV, const std::vector<i64> &lptr, const std::vector<i32> &llist,
-                            const std::vector<i32> &lnsmall, const std::vector<i32> &lncls, bool count_flops) {
-        LV.clear();
-        LV.resize(S.nlevels);
-        for (i32 l = 0; l < S.nlevels; l++) {
-            LevelInfo &L = LV[l];
-            L.first = (int)lptr[l];
-            L.count = (int)(lptr[l + 1] - lptr[l]);
-            L.nsmall = lnsmall[l];
-            for (int k = 0; k < 4; k++) L.ncls[k] = lncls[(size_t)l * 4 + k];
-            L.max_rows = L.max_cols = 0;
-            int max_trail = 0, min_trail = INT_MAX;
-            for (int k = L.nsmall; k < L.count; k++) {
-                i32 s = llist[L.first + k];
-                L.max_rows = std::max(L.max_rows, S.nrows(s));
-                L.max_cols = std::max(L.max_cols, S.ncols(s));
-                max_trail = std::max(max_trail, S.nrows(s) - S.ncols(s));
-                if (S.nrows(s) > S.ncols(s)) min_trail = std::min(min_trail, S.nrows(s) - S.ncols(s));
-                const double cc = S.ncols(s), mm = S.nrows(s) - S.ncols(s);
-                if (count_flops) syrk_flops += cc * mm * (mm + 1);   // lower triangle of the contribution block: 2 c flops per entry
-            }
-            int nblk = (L.max_cols + NB - 1) / NB;
-            L.active.assign(nblk + 1, 0);
-            for (int b = 0; b <= nblk; b++) {
-                int cnt = 0;
-                for (int k = L.nsmall; k < L.count; k++) {
-                    if (S.ncols(llist[L.first + k]) > b * NB) cnt++; else break;  // sorted by decreasing columns
-                }
-                L.active[b] = cnt;
-            }
-            for (int q = 0; q < 3; q++) {
-                const int lim = 48 - 16 * q;
-                int cnt = 0;
-                for (int k = L.nsmall; k < L.count; k++) {
-                    if (S.ncols(llist[L.first + k]) > lim) cnt++; else break;
-                }
-                L.wider[q] = cnt;
-            }
-            L.min_trail = min_trail == INT_MAX ? 0 : min_trail;
-            L.active.push_back(max_trail);  // stash: last element = max trailing rows of the level
-        }
-    };
-    syrk_flops = 0;
-    build_levels(levels_, S.levelptr, S.levellist, S.level_nsmall, S.level_ncls, true);
-    build_levels(swlevels_, S.sw_levelptr, S.sw_levellist, S.sw_level_nsmall, S.sw_level_ncls, false);
-
-    // fronts with more than one 64-column block, by decreasing width: dense-inverse stages
-    {
-        std::vector<int> il;
-        for (i32 s = 0; s < ns; s++) {
-            const bool mine = !S.shard_plan || S.owner[s] == S.shard_rank;
-            if (S.ncols(s) > NB && mine) il.push_back(s);     // sharded handles only hold the panels they factored
-        }
-        std::sort(il.begin(), il.end(), [&](int a, int b) { return S.ncols(a) != S.ncols(b) ? S.ncols(a) > S.ncols(b) : a < b; });
-        inv_maxc_ = il.empty() ? 0 : S.ncols(il[0]);
-        const int *p; up(p, il); d_invlist_ = const_cast<int *>(p);
-        long long tmax = 0;
-        for (int B = NB; B < inv_maxc_; B *= 2) {
-            int na = 0;
-            std::vector<long long> off;
-            long long acc = 0;
-            for (int s : il) {
-                if (S.ncols(s) <= B) break;
-                off.push_back(acc);
-                acc += (long long)((S.ncols(s) + 2 * B - 1) / (2 * B)) * B * B;
-                na++;
-            }
-            inv_nact_.push_back(na);
-            const long long *lq; up(lq, off); d_inv_toff_.push_back(const_cast<long long *>(lq));
-            HC(hipStreamSynchronize(stream));
-            tmax = std::max(tmax, acc);
-        }
-        d_invT_ = dalloc<double>((size_t)std::max<long long>(tmax, 1));
-        HC(hipStreamSynchronize(stream));
-        // the same stages level by level (pipelined factor + solve: the inverses of a level are built right behind its
-        // factorisation; the levels follow each other on one stream, so they share the workspace)
-        std::vector<int> cat;
-        inv_lvl_first_.assign(S.nlevels + 1, 0); inv_lvl_maxc_.assign(S.nlevels, 0); inv_lvl_nact_.assign(S.nlevels, {});
-        std::vector<std::vector<int>> per(S.nlevels);
-        for (int s : il) per[S.level[s]].push_back(s);      // (il is sorted by decreasing width: so is every level's list)
-        for (i32 l = 0; l < S.nlevels; l++) {
-            inv_lvl_first_[l] = (int)cat.size();
-            inv_lvl_maxc_[l] = per[l].empty() ? 0 : S.ncols(per[l][0]);
-            cat.insert(cat.end(), per[l].begin(), per[l].end());
-        }
-        inv_lvl_first_[S.nlevels] = (int)cat.size();
-        if (!cat.empty()) {
-            const int *cp; up(cp, cat); d_inv_lvl_list_ = const_cast<int *>(cp);
-            for (int B = NB; B < inv_maxc_; B *= 2) {
-                std::vector<long long> off(cat.size(), 0);
-                for (i32 l = 0; l < S.nlevels; l++) {
-                    long long acc = 0;
-                    int na = 0;
-                    for (int s : per[l]) {
-                        if (S.ncols(s) <= B) break;
-                        off[(size_t)inv_lvl_first_[l] + na] = acc;
-                        acc += (long long)((S.ncols(s) + 2 * B - 1) / (2 * B)) * B * B;
-                        na++;
-                    }
-                    inv_lvl_nact_[l].push_back(na);
-                }
-                const long long *lq; up(lq, off); d_inv_lvl_toff_.push_back(const_cast<long long *>(lq));
-            }
-            HC(hipStreamSynchronize(stream));
-        }
-    }
-    {   // the highest level a sweep task or a one-workgroup subtree reaches: the bottom of the forward sweep starts behind it
-        bottom_top_level_ = 0;
-        for (size_t t = 0; t < S.swt_last.size(); t++) bottom_top_level_ = std::max<int>(bottom_top_level_, S.level[S.swt_last[t]]);
-        for (i32 s = 0; s < ns; s++) if (S.in_subtree[s]) bottom_top_level_ = std::max<int>(bottom_top_level_, S.level[s]);
-        bottom_top_level_ = std::min<int>(bottom_top_level_, std::max<int>(S.nlevels - 1, 0));
-        // The bottom of the forward sweep is throughput work whose workgroups hold a CU's LDS for their whole life; started
-        // while the factorisation still is throughput work itself (the wide middle of the tree) it only takes the chip away
-        // from it. It is held back until the factorisation reaches its latency-bound top: the first level from which on every
-        // level has at most 32 fronts (re-swept in round 4: 4 .. 10 levels below the root are within 0.2 ms of it).
-        int gate = S.nlevels - 1;
-        while (gate > 0 && levels_[gate - 1].count <= 32) gate--;
-        fused_gate_level_ = std::min<int>(std::max(gate, bottom_top_level_), std::max<int>(S.nlevels - 1, 0));
-    }
-
-    // Contribution-block tiles of every level in hand-out order: front by front (the level list's order), inside a
-    // front by 8 x 8-tile squares of the lower triangle (row-major inside a square), then cut into 8 runs of equal
-    // estimated cost -- one per XCD. One self-contained record per tile (kernels.hip, k_syrk_cb_rec).
-    {
-        if (const char *e = std::getenv("GMRFX_SYRK_XCD")) syrk_xcd_ = std::atoi(e) != 0;
-        if (const char *e = std::getenv("GMRFX_SYRK_PIPED")) syrk_piped_min_ = std::atoi(e);
-        std::vector<SyrkTile> recs;
-        std::vector<double> cost;
-        constexpr int SQ = 8;
-        for (i32 l = 0; l < S.nlevels; l++) {
-            LevelInfo &L = levels_[l];
-            cost.clear();
-            L.syrk_off = (long long)recs.size();
-            for (int k = L.nsmall; syrk_xcd_ && k < L.count; k++) {
-                const i32 s = S.levellist[L.first + k];
-                const int c = S.ncols(s), m = S.nrows(s) - c;
-                const int T = (m + 63) / 64, nT = (m + 31) / 32;
-                const i64 ch0 = S.childptr[s];
-                const int nch = (int)(S.childptr[s + 1] - ch0);
-                for (int I = 0; I < T; I += SQ)
-                    for (int J = 0; J <= I; J += SQ)
-                        for (int bi = I; bi < std::min(I + SQ, T); bi++)
-                            for (int bj = J; bj < std::min(J + SQ, bi + 1); bj++) {
-                                // k-loop of 3 (diagonal tile) or 4 waves + the gather / epilogue of a tile, in columns of K
-                                cost.push_back((double)(c + 48) * (bi == bj ? 3 : 4));
-                                SyrkTile t{};
-                                t.pa = (long long)S.panelptr[s] + c;
-                                t.cb = (long long)S.cbptr[s];
-                                t.ch0 = (long long)ch0;
-                                t.c = c; t.m = m; t.ld = (int)S.ld[s]; t.nch = nch;
-                                t.bi = bi; t.bj = bj;
-                                for (int q = 0; q < std::min(nch, 2); q++) {
-                                    const EdgeRec &e = h_edges_[ch0 + q];
-                                    const int *et = h_etile_.data() + e.tptr;
-                                    t.reloff[q] = e.reloff; t.cboff[q] = e.cboff; t.md[q] = e.md;
-                                    t.a0[q] = et[2 * bi]; t.a1[q] = et[std::min(2 * bi + 2, nT)];
-                                    t.b0[q] = et[2 * bj]; t.b1[q] = et[std::min(2 * bj + 2, nT)];
-                                }
-                                recs.push_back(t);
-                            }
-            }
-            const size_t nt = cost.size();
-            if (nt >= (size_t)INT_MAX / 8) throw std::runtime_error("too many contribution-block tiles in one level");
-            double tot = 0, acc = 0;
-            for (size_t t = 0; t < nt; t++) tot += cost[t];
-            int x = 0;
-            L.syrk_split.start[0] = 0;
-            for (size_t t = 0; t < nt; t++) {
-                while (x < 7 && acc >= tot * (x + 1) / 8) L.syrk_split.start[++x] = (int)t;
-                acc += cost[t];
-            }
-            while (x < 8) L.syrk_split.start[++x] = (int)nt;
-            L.syrk_per = 0;
-            for (int q = 0; q < 8; q++) L.syrk_per = std::max(L.syrk_per, L.syrk_split.start[q + 1] - L.syrk_split.start[q]);
-        }
-        if (recs.empty()) recs.push_back(SyrkTile{});
-        const SyrkTile *rp; up(rp, recs); d_syrk_recs_ = const_cast<SyrkTile *>(rp);
-        HC(hipStreamSynchronize(stream));
-        // forward update: one record per 32-row tile of the trailing rows of every big front of the SWEEP levels, front
-        // by front, cut into 8 runs of equal cost (a front's tiles share its y and its children's update vectors)
-        std::vector<FwdTile> ft;
-        for (i32 l = 0; l < S.nlevels; l++) {
-            LevelInfo &L = swlevels_[l];
-            cost.clear();
-            L.fwd_off = (long long)ft.size();
-            for (int k = L.nsmall; syrk_xcd_ && k < L.count; k++) {
-                const i32 s = S.sw_levellist[L.first + k];
-                const int c = S.ncols(s), r = S.nrows(s), m = r - c;
-                const i64 ch0 = S.childptr[s];
-                const int nch = (int)(S.childptr[s + 1] - ch0);
-                for (int T = 0; T * 32 < m; T++) {
-                    FwdTile t{};
-                    t.pp = (long long)S.panelptr[s]; t.xoff = S.sfirst[s]; t.woff = h_wptr_[s]; t.ch0 = (long long)ch0;
-                    t.c = c; t.r = r; t.ld = (int)S.ld[s]; t.i0 = c + 32 * T; t.nch = nch; t.tile = T;
-                    for (int q = 0; q < std::min(nch, 2); q++) {
-                        const EdgeRec &e = h_edges_[ch0 + q];
-                        t.md[q] = e.md; t.reloff[q] = e.reloff; t.cwoff[q] = e.woff;
-                        t.a0[q] = h_etile_[(size_t)e.tptr + T]; t.a1[q] = h_etile_[(size_t)e.tptr + T + 1];
-                    }
-                    ft.push_back(t);
-                    cost.push_back((double)(c + 64));
-                }
-            }
-            const size_t nt = cost.size();
-            if (nt >= (size_t)INT_MAX / 8) throw std::runtime_error("too many update-vector tiles in one level");
-            double tot = 0, acc = 0;
-            for (size_t t = 0; t < nt; t++) tot += cost[t];
-            int x = 0;
-            L.fwd_split.start[0] = 0;
-            for (size_t t = 0; t < nt; t++) {
-                while (x < 7 && acc >= tot * (x + 1) / 8) L.fwd_split.start[++x] = (int)t;
-                acc += cost[t];
-            }
-            while (x < 8) L.fwd_split.start[++x] = (int)nt;
-            L.fwd_per = 0;
-            for (int q = 0; q < 8; q++) L.fwd_per = std::max(L.fwd_per, L.fwd_split.start[q + 1] - L.fwd_split.start[q]);
-        }
-        if (ft.empty()) ft.push_back(FwdTile{});
-        const FwdTile *fp; up(fp, ft); d_fwd_recs_ = const_cast<FwdTile *>(fp);
-        HC(hipStreamSynchronize(stream));
-        std::vector<long long>().swap(h_wptr_);
-        {   // panel-assembly records, one per level-list position
-            std::vector<AsmRec> ar(S.levellist.size());
-            for (size_t k = 0; k < S.levellist.size(); k++) {
-                const i32 s = S.levellist[k];
-                AsmRec a{};
-                a.pp = (long long)S.panelptr[s];
-                a.ch0 = (long long)S.childptr[s];
-                a.c = S.ncols(s); a.ld = (int)S.ld[s]; a.first = (int)S.sfirst[s];
-                a.nch = (int)(S.childptr[s + 1] - S.childptr[s]);
-                for (int q = 0; q < std::min(a.nch, 2); q++) {
-                    const EdgeRec &e = h_edges_[a.ch0 + q];
-                    a.reloff[q] = e.reloff; a.cboff[q] = e.cboff; a.eoff[q] = e.eoff; a.md[q] = e.md;
-                }
-                ar[k] = a;
-            }
-            if (ar.empty()) ar.push_back(AsmRec{});
-            const AsmRec *ap; up(ap, ar); d_arec_ = const_cast<AsmRec *>(ap);
-            HC(hipStreamSynchronize(stream));
-        }
-        std::vector<EdgeRec>().swap(h_edges_);
-        std::vector<int>().swap(h_etile_);
-    }
+    d_swt_ = up(P.swt);
+    d_wave_order_ = up(P.wave_order);
+    d_levellist_ = up(S.levellist); d_levellist2_ = up(P.levellist2);
+    d_sub_first_ = up(S.sub_first); d_sub_last_ = up(S.sub_last);
+    d_sel_levellist_ = up(S.sel_levellist);
+    d_frec_ = up(P.frec); d_sel_frec_ = up(P.sel_frec); d_frec2_ = up(P.frec2);
+    d_invlist_ = up(P.invlist);
+    for (const auto &off : P.inv_toff) d_inv_toff_.push_back(up(off));
+    d_invT_ = dalloc<double>((size_t)std::max<long long>(P.inv_tsize, 1));
+    if (!P.inv_lvl_list.empty()) d_inv_lvl_list_ = up(P.inv_lvl_list);
+    for (const auto &off : P.inv_lvl_toff) d_inv_lvl_toff_.push_back(up(off));
+    d_syrk_recs_ = up(P.syrk_recs); d_fwd_recs_ = up(P.fwd_recs); d_arec_ = up(P.arec);
     ev_syrk_.resize(2 * (size_t)S.nlevels);
     for (auto &e : ev_syrk_) HC(hipEventCreate(&e));
-    first_multiblock_level_ = S.nlevels;
-    // (over the SWEEP lists: the forward sweep waits there for the dense inverses, and a sharded handle's factor lists leave
-    //  out the distributed root, which its owner still sweeps)
-    for (i32 l = 0; l < S.nlevels; l++) if (swlevels_[l].max_cols > NB) { first_multiblock_level_ = l; break; }
 
     // INVARIANT (pair loads): the kernels that read operand rows in 16-byte pairs (sweep_front.hip, k_syrk_cb_rec, selinv.hip)
     // may read ONE double past a column's last row; for the last column of the last panel that is element l_size_ of the
     // buffer. Every buffer that holds panels (d_L_, d_Z_, a clone) is therefore allocated through dalloc (16 bytes of
     // slack) and zeroed INCLUDING the slack, so the extra element is mapped and finite (it only ever meets a 0.0 mask).
-    l_size_ = S.panelptr[ns];
     static_assert(kPairSlackBytes >= sizeof(double), "pair loads read one element past the end");
     // (the chunk kernels of the sweep tasks read whole 16-column / 16-row tiles from a chunk's first element without clamps: for
     //  the last task panel of the buffer that is up to 16 columns of <= 304 rows past its end -- mapped, zero, never used)

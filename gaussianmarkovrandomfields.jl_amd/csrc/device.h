@@ -6,24 +6,11 @@
 #include <string>
 #include <vector>
 
-#include "symbolic.h"
+#include "device_plan.h"
 
 namespace gmrfx { constexpr int kSyrkPipedMinCols = 128; }     // see DeviceFactor::syrk_piped_min_
 
 namespace gmrfx {
-
-// One record per (child -> parent) edge of the assembly tree, in childptr order: everything a
-// parent's workgroup needs to gather from that child, in ONE load instead of a chain of dependent
-// index loads (children[ch] -> sfirst/rowptr/cbptr/wptr[d] -> ...).
-struct EdgeRec {
-    int d, md;         // child supernode and its number of trailing rows
-    int tptr;          // offset of this edge's tile table in DevSym::etile
-    int nown;          // child rows that map into the parent's OWN columns (= etile[tptr])
-    long long reloff;  // offset of the child's trailing rows in DevSym::rel
-    long long woff;    // DevSym::wptr[d]
-    long long cboff;   // DevSym::cbptr[d]
-    long long eoff;    // offset of this edge's column table in DevSym::erow
-};
 
 // Pointers to the symbolic structure in HBM; passed to kernels by value.
 struct DevSym {
@@ -59,102 +46,11 @@ struct DevSym {
                                            // (its trailing inverse block arrives over the wire: no local gather); else null
 };
 
-// One sweep task (Symbolic::swt_*): everything its workgroup needs in ONE load.
-struct SweepTask {
-    int s0, s1;            // first / last (= root) supernode
-    int col0, nt;          // first own column of the subtree, number of own columns (= local rows 0 .. nt-1)
-    int mroot, pad;        // trailing rows of the root (= local rows nt .. nt+mroot-1)
-    long long p0, p1;      // the subtree's panels in the factor storage (contiguous: postorder)
-    long long rp0, rp1;    // its range in the row / local-row lists
-    long long rroot;       // offset of the root's trailing rows in DevSym::rows
-    long long woff;        // DevSym::wptr[root]
-    // chunk form (sweep_chunk.hip; Symbolic::swc_*): first chunk record / number of chunks, the backward programs of the four
-    // row-tile slots (chunks per slot, barriers behind a slot's last chunk)
-    int c0, nch;           // forward records
-    int b0, nbw;           // backward records (every chunk once)
-    int scnt[4], sbar[4];
-};
-
-// geometry of one front for the panel kernels: in the kernel arguments (FrontArg) or one record per level-list position
+// geometry of one front for the panel kernels in the kernel arguments (FrontView: the same as one record per level-list position)
 // ppa (round 6): where the K operand columns of a panel update live when they are NOT in the panel itself -- the received block of a
 // distributed front with block-cyclic storage sits in a window (Device::dist_front_phase); kNoPpa = in the panel, as everywhere else
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
-struct FrontView { int s, c, r, ld, first, pad; long long pp; };   // 32 bytes
-
-// Everything a column of the panel assembly (k_assemble_lds) needs to know about its front and the front's first two children,
-// in ONE 96-byte record per level-list position (one scalar load) instead of front -> geometry arrays -> edge records.
-struct AsmRec {
-    long long pp;            // panel offset in the factor storage
-    long long ch0;           // first child edge (children beyond the second go the long way)
-    int c, ld, first, nch;   // columns, leading dimension, first global column, number of children
-    long long reloff[2], cboff[2], eoff[2];     // per child: rel[] offset of its trailing rows, arena offset of its contribution block, erow offset
-    int md[2];               // per child: trailing rows
-    int pad[2];
-};
-
-struct SyrkSplit { int start[9]; };   // tile runs of the 8 XCDs inside a level's tile list
-
-// Everything a workgroup of k_syrk_cb_rec needs for one 64 x 64 contribution-block tile, in ONE 128-byte record (one
-// scalar load) instead of four rounds of dependent index loads (tile -> front geometry -> edge records -> tile ranges):
-// the levels with narrow fronts spend their time in exactly that chain.
-struct SyrkTile {
-    long long pa;            // offset of L21 (panel + c rows down) in the factor storage
-    long long cb;            // offset of the front's contribution block in the arena
-    long long ch0;           // first child edge of the front (children beyond the second go the long way)
-    int c, m, ld, nch;       // columns, trailing rows, leading dimension, number of children
-    int bi, bj, pad0, pad1;  // tile row / column
-    long long reloff[2], cboff[2];   // first two children: relative-row list, contribution block
-    int md[2];                       //   trailing rows of the child
-    int a0[2], a1[2], b0[2], b1[2];  //   the child's rows that fall into the tile's rows [a0, a1) / columns [b0, b1)
-};
-static_assert(sizeof(SyrkTile) == 128, "SyrkTile is one 128-byte record");
-
-// The same idea for the forward update of a big front (k_fwd_update_rec): one record per 32-row tile of the trailing rows.
-struct FwdTile {
-    long long pp;            // offset of the front's panel in the factor storage
-    long long xoff;          // first own row of the front in X (= sfirst)
-    long long woff;          // first row of the front's update vector in W (= wptr)
-    long long ch0;           // first child edge (children beyond the second go the long way)
-    int c, r, ld, i0;        // columns, rows, leading dimension, first front row of the tile (>= c)
-    int nch, tile;           // number of children, 32-row tile index (for the long way)
-    int md[2], a0[2], a1[2]; // first two children: trailing rows, and the rows [a0, a1) that fall into this tile
-    int pad[4];
-    long long reloff[2], cwoff[2];   // their relative-row lists and update vectors
-};
-static_assert(sizeof(FwdTile) == 128, "FwdTile is one 128-byte record");
-
-// What k_sel_gather needs about a front and its parent, in one 64-byte record per supernode (selected inversion).
-struct SelRec {
-    long long rel;           // offset of the front's trailing rows in DevSym::rel
-    long long zp;            // parent's panel in Z
-    long long zbp;           // parent's trailing inverse block in the arena (selected-inversion layout)
-    long long out;           // this front's trailing inverse block
-    int m, cp, mp, ldp;      // trailing rows; parent's columns, trailing rows, leading dimension
-    int p, foreign, pad[2];  // parent (-1: root), 1 = the block arrives over the wire (sharded)
-};
-static_assert(sizeof(SelRec) == 64, "SelRec is 64 bytes");
-
-struct LevelInfo {
-    int first;        // offset into levellist
-    int count;        // fronts in level
-    int nsmall;       // prefix handled by the fused small-front kernels
-    int ncls[4];      // of which r <= 48 / 64 / 96 / 128 (in this order)
-    int max_rows;     // over big fronts
-    int max_cols;     // over big fronts (they are sorted by decreasing column count)
-    int min_trail = 0; // fewest trailing rows of a big front with any (0: none has)
-    std::vector<int> active;  // active[k] = number of big fronts with ncols > k*NB
-    int wider[3] = {0, 0, 0}; // big fronts with more than 48 / 32 / 16 columns (first 64-column block: the diagonal-block kernel's shapes)
-    // contribution-block SYRK: the level's 64 x 64 tiles in the order they are handed out, cut into one run per XCD
-    long long syrk_off = 0;   // offset of the level's tiles in Device::d_syrk_recs_
-    SyrkSplit syrk_split{};   // run of XCD x = [start[x], start[x + 1])
-    int syrk_per = 0;         // longest run: the grid is 8 * syrk_per workgroups
-    // forward update (sweep levels only): 32-row tiles of the trailing rows, same per-XCD hand-out
-    long long fwd_off = 0;
-    SyrkSplit fwd_split{};
-    int fwd_per = 0;
-};
-
 class Device {
 public:
     Device() = default;
@@ -288,17 +184,12 @@ private:
     hipEvent_t ev_nzp_ = nullptr, ev_nzp0_ = nullptr;
     AsmRec *d_arec_ = nullptr;          // one per position of the level lists (Symbolic::levellist order)
     SyrkTile *d_syrk_recs_ = nullptr;   // one record per contribution-block tile, level by level, in hand-out order
-    std::vector<EdgeRec> h_edges_;      // host copies of the edge records / tile tables between upload() and init()
-    std::vector<int> h_etile_;
-    std::vector<long long> h_wptr_;
     int syrk_piped_min_ = kSyrkPipedMinCols;      // GMRFX_SYRK_PIPED=N: levels whose widest front has >= N columns take the software-pipelined
                                                   // product loop of k_syrk_cb_rec (0: every level; a huge N: none) -- same bits either way
     bool syrk_xcd_ = true;          // GMRFX_SYRK_XCD=0: k_syrk_cb on a plain 3-D grid (front, tile row, tile column) instead
     FrontView *d_frec_ = nullptr, *d_frec2_ = nullptr, *d_sel_frec_ = nullptr;   // geometry records parallel to the level lists
     int *d_levellist2_ = nullptr;   // per level: the big fronts re-ordered [even positions..., odd positions...] (two-stream panel chains)
-    // wave tasks (sweep_wave.hip): task ids by LDS class
-    static constexpr int kWaveClasses = 2;
-    static constexpr int kWaveRows[kWaveClasses] = {160, 288};
+    // wave tasks (sweep_wave.hip): task ids by LDS class (kWaveRows, device_plan.h)
     int wave_max_nr_ = 16;        // passes of up to this many right-hand sides use the wave tasks (0: never)
     const int *d_wave_order_ = nullptr;
     int wave_first_[kWaveClasses] = {0, 0}, wave_count_[kWaveClasses] = {0, 0};

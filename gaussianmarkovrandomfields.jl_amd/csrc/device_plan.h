@@ -1,0 +1,170 @@
+// device_plan.h -- the host images of the tables the kernels read and the level schedule the drivers keep, built from the
+// symbolic analysis on the host (device_plan.cpp, no HIP); Device::upload copies the tables to the device as they are.
+#pragma once
+#include <vector>
+
+#include "symbolic.h"
+
+namespace gmrfx {
+
+constexpr int NB = 64;       // block-column width of the dense partial factorisation / sweeps
+// chunk form of the sweep tasks (sweep_chunk.hip): right-hand-side columns of a workgroup's local vector, and its spare row
+// (row 288 of 289: target rows of padding land there)
+constexpr int kChunkNc = 16;
+constexpr int kChunkSpareRow = 288;
+// wave tasks (sweep_wave.hip): the LDS classes of the tasks, by rows of the local vector
+constexpr int kWaveClasses = 2;
+constexpr int kWaveRows[kWaveClasses] = {160, 288};
+
+// One record per (child -> parent) edge of the assembly tree, in childptr order: everything a
+// parent's workgroup needs to gather from that child, in ONE load instead of a chain of dependent
+// index loads (children[ch] -> sfirst/rowptr/cbptr/wptr[d] -> ...).
+struct EdgeRec {
+    int d, md;         // child supernode and its number of trailing rows
+    int tptr;          // offset of this edge's tile table in DevSym::etile
+    int nown;          // child rows that map into the parent's OWN columns (= etile[tptr])
+    long long reloff;  // offset of the child's trailing rows in DevSym::rel
+    long long woff;    // DevSym::wptr[d]
+    long long cboff;   // DevSym::cbptr[d]
+    long long eoff;    // offset of this edge's column table in DevSym::erow
+};
+
+// One sweep task (Symbolic::swt_*): everything its workgroup needs in ONE load.
+struct SweepTask {
+    int s0, s1;            // first / last (= root) supernode
+    int col0, nt;          // first own column of the subtree, number of own columns (= local rows 0 .. nt-1)
+    int mroot, pad;        // trailing rows of the root (= local rows nt .. nt+mroot-1)
+    long long p0, p1;      // the subtree's panels in the factor storage (contiguous: postorder)
+    long long rp0, rp1;    // its range in the row / local-row lists
+    long long rroot;       // offset of the root's trailing rows in DevSym::rows
+    long long woff;        // DevSym::wptr[root]
+    // chunk form (sweep_chunk.hip; Symbolic::swc_*): first chunk record / number of chunks, the backward programs of the four
+    // row-tile slots (chunks per slot, barriers behind a slot's last chunk)
+    int c0, nch;           // forward records
+    int b0, nbw;           // backward records (every chunk once)
+    int scnt[4], sbar[4];
+};
+
+// geometry of one front for the panel kernels, one record per level-list position (the panel chain gets it in the kernel
+// arguments instead: FrontArg, device.h)
+struct FrontView { int s, c, r, ld, first, pad; long long pp; };   // 32 bytes
+
+// Everything a column of the panel assembly (k_assemble_lds) needs to know about its front and the front's first two children,
+// in ONE 96-byte record per level-list position (one scalar load) instead of front -> geometry arrays -> edge records.
+struct AsmRec {
+    long long pp;            // panel offset in the factor storage
+    long long ch0;           // first child edge (children beyond the second go the long way)
+    int c, ld, first, nch;   // columns, leading dimension, first global column, number of children
+    long long reloff[2], cboff[2], eoff[2];     // per child: rel[] offset of its trailing rows, arena offset of its contribution block, erow offset
+    int md[2];               // per child: trailing rows
+    int pad[2];
+};
+
+struct SyrkSplit { int start[9]; };   // tile runs of the 8 XCDs inside a level's tile list
+
+// Everything a workgroup of k_syrk_cb_rec needs for one 64 x 64 contribution-block tile, in ONE 128-byte record (one
+// scalar load) instead of four rounds of dependent index loads (tile -> front geometry -> edge records -> tile ranges):
+// the levels with narrow fronts spend their time in exactly that chain.
+struct SyrkTile {
+    long long pa;            // offset of L21 (panel + c rows down) in the factor storage
+    long long cb;            // offset of the front's contribution block in the arena
+    long long ch0;           // first child edge of the front (children beyond the second go the long way)
+    int c, m, ld, nch;       // columns, trailing rows, leading dimension, number of children
+    int bi, bj, pad0, pad1;  // tile row / column
+    long long reloff[2], cboff[2];   // first two children: relative-row list, contribution block
+    int md[2];                       //   trailing rows of the child
+    int a0[2], a1[2], b0[2], b1[2];  //   the child's rows that fall into the tile's rows [a0, a1) / columns [b0, b1)
+};
+static_assert(sizeof(SyrkTile) == 128, "SyrkTile is one 128-byte record");
+
+// The same idea for the forward update of a big front (k_fwd_update_rec): one record per 32-row tile of the trailing rows.
+struct FwdTile {
+    long long pp;            // offset of the front's panel in the factor storage
+    long long xoff;          // first own row of the front in X (= sfirst)
+    long long woff;          // first row of the front's update vector in W (= wptr)
+    long long ch0;           // first child edge (children beyond the second go the long way)
+    int c, r, ld, i0;        // columns, rows, leading dimension, first front row of the tile (>= c)
+    int nch, tile;           // number of children, 32-row tile index (for the long way)
+    int md[2], a0[2], a1[2]; // first two children: trailing rows, and the rows [a0, a1) that fall into this tile
+    int pad[4];
+    long long reloff[2], cwoff[2];   // their relative-row lists and update vectors
+};
+static_assert(sizeof(FwdTile) == 128, "FwdTile is one 128-byte record");
+
+// What k_sel_gather needs about a front and its parent, in one 64-byte record per supernode (selected inversion).
+struct SelRec {
+    long long rel;           // offset of the front's trailing rows in DevSym::rel
+    long long zp;            // parent's panel in Z
+    long long zbp;           // parent's trailing inverse block in the arena (selected-inversion layout)
+    long long out;           // this front's trailing inverse block
+    int m, cp, mp, ldp;      // trailing rows; parent's columns, trailing rows, leading dimension
+    int p, foreign, pad[2];  // parent (-1: root), 1 = the block arrives over the wire (sharded)
+};
+static_assert(sizeof(SelRec) == 64, "SelRec is 64 bytes");
+
+struct LevelInfo {
+    int first;        // offset into levellist
+    int count;        // fronts in level
+    int nsmall;       // prefix handled by the fused small-front kernels
+    int ncls[4];      // of which r <= 48 / 64 / 96 / 128 (in this order)
+    int max_rows;     // over big fronts
+    int max_cols;     // over big fronts (they are sorted by decreasing column count)
+    int min_trail = 0; // fewest trailing rows of a big front with any (0: none has)
+    std::vector<int> active;  // active[k] = number of big fronts with ncols > k*NB
+    int wider[3] = {0, 0, 0}; // big fronts with more than 48 / 32 / 16 columns (first 64-column block: the diagonal-block kernel's shapes)
+    // contribution-block SYRK: the level's 64 x 64 tiles in the order they are handed out, cut into one run per XCD
+    long long syrk_off = 0;   // offset of the level's tiles in Device::d_syrk_recs_
+    SyrkSplit syrk_split{};   // run of XCD x = [start[x], start[x + 1])
+    int syrk_per = 0;         // longest run: the grid is 8 * syrk_per workgroups
+    // forward update (sweep levels only): 32-row tiles of the trailing rows, same per-XCD hand-out
+    long long fwd_off = 0;
+    SyrkSplit fwd_split{};
+    int fwd_per = 0;
+};
+
+// What changes the tables besides the analysis.
+struct PlanOptions {
+    bool syrk_xcd = true;       // GMRFX_SYRK_XCD: tile records of the contribution-block SYRK and the forward update (false: none)
+    int chunk_nc = kChunkNc, chunk_spare_row = kChunkSpareRow;   // layout of the local vector the chunk target rows address
+};
+
+struct DevicePlan {
+    // tables: every array Device::upload builds, in its device form (arrays of the analysis that already have it go up directly)
+    std::vector<SelRec> selrec;                   // one per supernode
+    std::vector<int> qsrc, qdst, qcol, qcolptr;   // the scatter map split into row and column (DevSym)
+    std::vector<EdgeRec> edge;
+    std::vector<int> etile, erow;
+    std::vector<unsigned char> owncol, foreign_parent;   // sharded handles only
+    std::vector<int> fchild;                             //   (grouped by level: fc_levelptr)
+    std::vector<SweepTask> swt;
+    std::vector<int> swc_listf, swc_listb;        // chunk target rows as LDS byte offsets (only with chunks)
+    std::vector<int> wave_order;
+    std::vector<int> levellist2;                  // the level lists with every level's big fronts split into even / odd positions
+    std::vector<FrontView> frec, frec2, sel_frec; // parallel to levellist, levellist2, sel_levellist
+    std::vector<int> invlist;                     // dense-inverse stages: fronts by decreasing width ...
+    std::vector<std::vector<long long>> inv_toff; // ... the T-buffer offsets of each stage
+    std::vector<int> inv_lvl_list;                // the same level by level (empty: no multi-block front)
+    std::vector<std::vector<long long>> inv_lvl_toff;
+    std::vector<SyrkTile> syrk_recs;
+    std::vector<FwdTile> fwd_recs;
+    std::vector<AsmRec> arec;
+    // schedule: what the drivers read on the host (Device keeps each in its member of that name: levels -> levels_)
+    std::vector<LevelInfo> levels, swlevels;
+    std::vector<int> sel_max_cols, sel_max_trail;
+    int inv_maxc = 0;
+    long long inv_tsize = 0;                      // doubles of the dense-inverse workspace
+    std::vector<int> inv_nact, inv_lvl_first, inv_lvl_maxc;
+    std::vector<std::vector<int>> inv_lvl_nact;
+    std::vector<int> fc_levelptr, fc_maxtrail;
+    int wave_first[kWaveClasses] = {}, wave_count[kWaveClasses] = {};
+    int nsub_cls[3] = {};
+    int bottom_top_level = 0, fused_gate_level = 0, first_multiblock_level = 0;
+    double syrk_flops = 0;
+    long long sum_trail = 0, l_size = 0, nq = 0;
+    int nswt = 0, nswc = 0;
+};
+
+// Throws std::runtime_error when a table outgrows its index type.
+DevicePlan build_device_plan(const Symbolic &S, const PlanOptions &o);
+
+}  // namespace gmrfx

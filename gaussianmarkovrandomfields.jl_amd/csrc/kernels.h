@@ -6,11 +6,10 @@
 
 namespace gmrfx {
 
-constexpr int NB = 64;       // block-column width of the dense partial factorisation / sweeps
 constexpr int ASM_CW = 4;    // front columns owned by one assembly workgroup
 constexpr int FWD_RB = 32;    // front rows owned by one forward-assembly workgroup
 
-// (FrontArg / FrontView -- the geometry of one front for the panel kernels -- live in device.h. The panel chain at the top
+// (FrontArg / FrontView -- the geometry of one front for the panel kernels -- live in device.h / device_plan.h. The panel chain at the top
 // of the tree, potrf -> trsm -> gemm, ~120 dependent launches on a single front, gets it in the kernel arguments; everything
 // else reads one record at its position in the level list.)
 // two doubles that are only known to be 8-byte aligned (one 16-byte load; the hardware takes unaligned addresses)
@@ -480,8 +479,6 @@ void launch_pack_diag(hipStream_t st, const Symbolic::SwChunk *recs, int nchunks
 void launch_sweep_chunks(hipStream_t st, const DevSym &S, int phase, const SweepTask *tasks, int ntasks, const Symbolic::SwChunk *recs_fwd,
                          const Symbolic::SwChunk *recs_bwd, const int *listf, const int *listb, const double *dtile, const double *L,
                          double *X, double *W, int nr, int ldx, size_t extra_lds);
-int sweep_chunk_nc();
-int sweep_chunk_spare_row();
 
 // sweep_wave.hip -- the same tasks, one wave per (task, 16 right-hand sides); order = task ids of one LDS class
 void launch_wave_tasks(hipStream_t st, const DevSym &S, int phase, const SweepTask *tasks, const int *order, int ntasks, int rows_cap,

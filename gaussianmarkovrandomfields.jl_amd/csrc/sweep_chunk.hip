@@ -17,7 +17,7 @@
 // its own -- a 16 x 16 diagonal block whose inverse is a diagonal block of L11^-1, K = its columns, targets = the panel
 // rows below the block (own rows of the front's later chunks, then the trailing rows), which are CONTIGUOUS in the panel.
 //  * No clamps, no masks: the analysis pads every target-row list to a multiple of 32 with a spare row of the local vector
-//    (row CH_SPARE: results of padding rows land there in the forward sweep; it stays zero in the backward sweep, where it
+//    (row kChunkSpareRow: results of padding rows land there in the forward sweep; it stays zero in the backward sweep, where it
 //    meets the operand rows read past the panel), panels are followed by zero columns up to a multiple of 4 and by >= 16
 //    zero doubles (symbolic.cpp: panel_span -- reads past those reach the next panel's first entries: mapped, finite, and
 //    multiplied into discarded rows only, see there), and the inverse diagonal blocks come PACKED in MFMA operand order with
@@ -47,10 +47,8 @@ typedef Symbolic::SwChunk Chunk;
 static_assert(sizeof(Chunk) == 32, "chunk records are read as two 16-byte words");
 
 constexpr int CH_ROWS = 289;         // 288 rows of the local vector (a chunk reads the 16 rows from its first own row: the analysis keeps
-constexpr int CH_SPARE = 288;        // own columns + max(root's trailing rows, 15) <= 288) + the spare row
+                                     // own columns + max(root's trailing rows, 15) <= 288) + the spare row (kChunkSpareRow, device_plan.h)
 constexpr int CH_MAXC = 96;          // chunk records per task (symbolic.cpp enforces)
-
-int sweep_chunk_spare_row() { return CH_SPARE; }
 
 // byte offset of (row, column) of the local vector: row-major, NC columns. From 32 columns on the 16-column tiles of odd
 // rows are swapped pairwise, so that the two k-rows a ds_read_b64 lane group (lanes 0-31 = two k-rows x 16 columns) touches
@@ -526,11 +524,6 @@ __global__ __launch_bounds__(256) void k_pack_diag(const Chunk *__restrict__ rec
     }
 }
 
-// 16 columns of the right-hand sides per workgroup, one 16-column tile per wave: 4 waves, four workgroups per compute unit.
-// (Measured at cfg 2, round 5: 32 columns / 8 waves / two workgroups per CU 0.61 / 0.67 ms forward / backward against 0.56 / 0.64;
-//  two tiles per wave, 32 or 64 columns: 0.74-0.75 / 0.86-0.87 ms.)
-int sweep_chunk_nc() { return 16; }
-
 #ifdef GMRFX_CYC
 // tools/chunk_cycles.py: [kernel 0 = forward, 1 = backward][slot 0..3][category 0..9] (see the CY_ macros above); reset != 0 zeroes the counters
 extern "C" int gmrfx_debug_chunk_cycles(unsigned long long *out, int reset) {
@@ -561,12 +554,15 @@ void launch_pack_diag(hipStream_t st, const Symbolic::SwChunk *recs, int nchunks
     hipLaunchKernelGGL(k_pack_diag, dim3((nchunks + 3) / 4), dim3(256), 0, st, recs, nchunks, L, dtile);
 }
 
+// kChunkNc = 16 columns of the right-hand sides per workgroup, one 16-column tile per wave: 4 waves, four workgroups per compute unit.
+// (Measured at cfg 2, round 5: 32 columns / 8 waves / two workgroups per CU 0.61 / 0.67 ms forward / backward against 0.56 / 0.64;
+//  two tiles per wave, 32 or 64 columns: 0.74-0.75 / 0.86-0.87 ms.)
 void launch_sweep_chunks(hipStream_t st, const DevSym &S, int phase, const SweepTask *tasks, int ntasks, const Symbolic::SwChunk *recs_fwd,
                          const Symbolic::SwChunk *recs_bwd, const int *listf, const int *listb, const double *dtile, const double *L,
                          double *X, double *W, int nr, int ldx, size_t extra_lds) {
     if (ntasks <= 0) return;
     const int grid = ((ntasks + 7) / 8) * 32;       // blocks b, b + 8, b + 16, b + 24 (same XCD): the four column slices of one task
-    if (phase == 1) hipLaunchKernelGGL((k_fwd_chunks<16, 1>), dim3(grid), dim3(256), extra_lds, st, tasks, ntasks, recs_fwd, listf, dtile, L, X, W, nr, ldx);
-    else hipLaunchKernelGGL((k_bwd_chunks<16, 1, 3>), dim3(grid), dim3(256), 0, st, S, tasks, ntasks, recs_bwd, listb, dtile, L, X, nr, ldx);
+    if (phase == 1) hipLaunchKernelGGL((k_fwd_chunks<kChunkNc, 1>), dim3(grid), dim3(256), extra_lds, st, tasks, ntasks, recs_fwd, listf, dtile, L, X, W, nr, ldx);
+    else hipLaunchKernelGGL((k_bwd_chunks<kChunkNc, 1, 3>), dim3(grid), dim3(256), 0, st, S, tasks, ntasks, recs_bwd, listb, dtile, L, X, nr, ldx);
 }
 }  // namespace gmrfx

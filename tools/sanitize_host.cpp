@@ -1,8 +1,10 @@
 // sanitize_host.cpp -- CPU-only sanitizer job for the host C++ of libgmrfx: the symbolic phase
-// (ordering.cpp, symbolic.cpp) spawns threads, gmrfx_api.cpp parses caller arrays. Built twice by
+// (ordering.cpp, symbolic.cpp) spawns threads, gmrfx_api.cpp parses caller arrays, device_plan.cpp builds the device
+// tables with index arithmetic over the analysis (called directly: it needs no device). Built twice by
 // `make -C gaussianmarkovrandomfields.jl_amd sanitize` (AddressSanitizer + UBSan, ThreadSanitizer) from the SAME
 // sources as the product, driven through the C ABI with symbolic_only handles (no GPU is touched; the HIP kernel
 // launch wrappers stay unresolved and are never called). Exit code 0 = clean. Run by tests/test_sanitizers.py.
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -10,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "../gaussianmarkovrandomfields.jl_amd/csrc/device_plan.h"
 #include "../include/gmrfx.h"
 
 // 19-point pattern of (5-point Laplacian)^2 on an nx x ny grid, both triangles, 0-based
@@ -100,6 +103,42 @@ static void sharded_handles(const std::vector<int64_t> &cp, const std::vector<in
     unsetenv("GMRFX_DIST_MIN");
 }
 
+// The per-XCD runs of the tile records (contribution-block SYRK, forward update), as the kernels take them: every level's
+// split starts at 0 and is monotone, its longest run is `per`, and the levels' records follow each other up to the end of the
+// table (a table without records holds one empty record).
+static void check_runs(const std::vector<gmrfx::LevelInfo> &LV, bool fwd, size_t nrec, bool any) {
+    long long end = 0;
+    for (const gmrfx::LevelInfo &L : LV) {
+        const gmrfx::SyrkSplit &sp = fwd ? L.fwd_split : L.syrk_split;
+        const long long off = fwd ? L.fwd_off : L.syrk_off;
+        int per = 0;
+        EXPECT(sp.start[0] == 0 && off == end);
+        for (int x = 0; x < 8; x++) { EXPECT(sp.start[x] <= sp.start[x + 1]); per = std::max(per, sp.start[x + 1] - sp.start[x]); }
+        EXPECT(per == (fwd ? L.fwd_per : L.syrk_per));
+        end = off + sp.start[8];
+    }
+    EXPECT(end == (long long)nrec || (end == 0 && nrec == 1));
+    EXPECT(any || end == 0);
+}
+
+// the device tables of every rank of a (sharded, world > 1) analysis, with and without the tile records (GMRFX_SYRK_XCD=0)
+static void device_plans(const std::vector<int64_t> &cp, const std::vector<int64_t> &ri, const double *coords, int64_t n, int world) {
+    for (int rank = 0; rank < world; rank++) {
+        gmrfx::SymOptions so;
+        if (coords) { so.coord_dim = 2; so.coords = coords; }
+        if (world > 1) { so.shard_rank = rank; so.shard_world = world; so.subtree_max = 0; so.dist_min_cols = 128; }   // (as gmrfx_create)
+        gmrfx::Symbolic S;
+        gmrfx::analyze(n, cp.data(), ri.data(), 0, nullptr, so, S);
+        for (bool xcd : {true, false}) {
+            const gmrfx::DevicePlan P = gmrfx::build_device_plan(S, gmrfx::PlanOptions{xcd});
+            check_runs(P.levels, false, P.syrk_recs.size(), xcd);
+            check_runs(P.swlevels, true, P.fwd_recs.size(), xcd);
+            EXPECT(P.edge.size() == S.children.size() && (int)P.levels.size() == S.nlevels);
+            EXPECT(S.shard_plan ? P.owncol.size() == (size_t)n && P.fc_levelptr.back() == (int)P.fchild.size() : P.owncol.empty());
+        }
+    }
+}
+
 int main() {
     std::vector<int64_t> cp, ri;
     std::vector<double> xy;
@@ -112,6 +151,8 @@ int main() {
     sharded_handles(cp, ri, xy.data(), n, 2);
     sharded_handles(cp, ri, xy.data(), n, 4);
     sharded_handles(cp, ri, xy.data(), n, 8);      // the width the driver scales to
+    device_plans(cp, ri, xy.data(), n, 1);
+    device_plans(cp, ri, xy.data(), n, 2);         // owner columns, foreign parents, other ranks' children
     // distinct handles are used concurrently from different host threads (WorkspacePool contract)
     {
         std::vector<int64_t> cp2, ri2; std::vector<double> xy2;
@@ -120,6 +161,7 @@ int main() {
         th.reserve(4);
         for (int t = 0; t < 4; t++) th.emplace_back([&, t] { one_handle(cp2, ri2, t % 2 ? xy2.data() : nullptr, 90 * 70, 0); });
         for (auto &x : th) x.join();
+        device_plans(cp2, ri2, xy2.data(), 90 * 70, 1);
     }
     // malformed input is rejected, not read out of bounds
     {
