@@ -1129,12 +1129,15 @@ static void check_member_layout(const gmrfx_handle *h, int64_t ld, int64_t s, in
 static int32_t batch_solve_impl(gmrfx_handle *h, const double *B, int64_t ldb, int64_t sb, int64_t nrhs, double *X, int64_t ldx, int64_t sx,
                                 bool dev, int mode) {
     return guarded(h, [&]() -> int32_t {
-        if (int32_t e = need_batch(h, true)) return e;
+        // the arguments first: they are checked against the handle's sizes, with or without device state
         if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
+        if (nrhs > 0) {
+            if (!B || !X) throw std::invalid_argument("B/X is null");
+            check_member_layout(h, ldb, sb, nrhs, "B");
+            check_member_layout(h, ldx, sx, nrhs, "X");
+        }
+        if (int32_t e = need_batch(h, true)) return e;
         if (nrhs == 0) return GMRFX_OK;
-        if (!B || !X) throw std::invalid_argument("B/X is null");
-        check_member_layout(h, ldb, sb, nrhs, "B");
-        check_member_layout(h, ldx, sx, nrhs, "X");
         const int64_t n = h->n_member, nb = h->nbatch, N = h->S.n;
         if (dev) {
             const Device::MemberLayout ml{n, sb, sx};
@@ -1177,8 +1180,8 @@ static void check_batch_quadform(const gmrfx_handle *h, const double *X, int64_t
 static int32_t batch_quadform_impl(gmrfx_handle *h, const double *nz, const double *X, int64_t ldx, int64_t sx, int64_t nvec,
                                    const double *mu, double *quad, bool dev) {
     return guarded(h, [&]() -> int32_t {
-        if (int32_t e = need_batch(h, false)) return e;
         check_batch_quadform(h, X, ldx, sx, nvec, quad);
+        if (int32_t e = need_batch(h, false)) return e;
         if (nvec == 0) return GMRFX_OK;
         if (dev) { h->D->batch_quadform(nz, X, ldx, sx, nvec, mu, quad); return GMRFX_OK; }
         // host operands: staged through plain device buffers (freed on return), members packed (ld = n, stride = n nvec)
@@ -1214,9 +1217,9 @@ extern "C" int32_t gmrfx_batch_quadform_dev(gmrfx_handle *h, const double *d_nzv
 extern "C" int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx,
                                                       int64_t nvec, const double *d_mu, double *quad, double *logdet, int64_t *info) {
     return guarded(h, [&]() -> int32_t {
-        if (int32_t e = need_batch(h, false)) return e;
         if (!d_nzval) throw std::invalid_argument("nzval is null");
         check_batch_quadform(h, d_X, ldx, sx, nvec, quad);
+        if (int32_t e = need_batch(h, false)) return e;
         std::vector<int64_t> inf((size_t)h->nbatch);
         h->D->batch_refactorize_logpdf(d_nzval, d_X, ldx, sx, nvec, d_mu, quad, logdet, (long long *)inf.data());
         if (info) std::copy(inf.begin(), inf.end(), info);

@@ -112,3 +112,102 @@ def test_python_binding_rejects_misshaped_operands():
     # well-shaped operands reach the library, which reports the missing device state (symbolic_only) instead
     with pytest.raises(gmrfx.NoDeviceError):
         bb.solve(np.zeros((n, B)))
+
+
+# ---- level widths: the preconditions of the wide-level GPU tests (tests/test_gpu_batch_edges.py) ------------------------------
+
+def _level_counts(be, min_rows=0):
+    s = gmrfx.MI355XBackend.symbolic(be)
+    return np.bincount(s.level[np.diff(s.row_ptr) > min_rows], minlength=int(s.level.max()) + 1)
+
+
+@pytest.mark.parametrize("B", [2, 7, 64])
+def test_forest_level_counts_are_b_times_the_members(B):
+    from test_gpu_batch_edges import _arrow
+    for Q, kw in ((_matern30()[0], {}), (_arrow(300), {"ordering": "natural"})):
+        one = gmrfx.MI355XBackend(Q, symbolic_only=True, **kw)
+        bb = gmrfx.MI355XBatchBackend(Q, B, symbolic_only=True, **kw)
+        for m in (0, 128):
+            assert np.array_equal(_level_counts(bb, m), B * _level_counts(one, m))
+
+
+def test_wide_level_preconditions():
+    """the GPU tests' batches and the arrow-star matrix really have a level of more than 65535 fronts (grid y > 65535), and the
+    arrow's fronts are taller than 128 rows (the generic front path, not the small-front kernels)"""
+    from test_gpu_batch_edges import _arrow, _grid
+    Q, pts = _grid(20, 20)
+    one = gmrfx.MI355XBackend(Q, coords=pts, symbolic_only=True)
+    assert _level_counts(one).max() * 6000 > 65535
+    assert _level_counts(one).max() * 6000 < 2 * 65535            # wide, not needlessly big
+    bb = gmrfx.MI355XBatchBackend(_arrow(1100), 64, ordering="natural", symbolic_only=True)
+    assert _level_counts(bb, 128).max() > 65535
+    plain = gmrfx.MI355XBackend(_arrow(70000), ordering="natural", symbolic_only=True)
+    assert _level_counts(plain, 128).max() > 65535
+    assert np.array_equal(plain.ordering_permutation(), np.arange(70128))
+
+
+# ---- argument checks of the batch entry points: refused before any device state is needed ------------------------------------
+
+def _code(h, name, *args):
+    code = getattr(lib(), name)(h, *args)
+    return code, (lib().gmrfx_last_error(h) or b"").decode()
+
+
+@pytest.mark.parametrize("dev", [False, True], ids=["host", "dev"])
+@pytest.mark.parametrize("backward", [False, True], ids=["solve", "backward"])
+def test_batch_solve_layout_is_checked(dev, backward):
+    Q, _ = _matern30()
+    n, B, r = Q.shape[0], 3, 4
+    bb = gmrfx.MI355XBatchBackend(Q, B, symbolic_only=True)
+    name = "gmrfx_batch_" + ("backward_solve" if backward else "solve") + ("_dev" if dev else "")
+    buf = np.zeros((n + 8) * r * B + 64)
+    p = buf.ctypes.data
+    good = (n, n * r)
+    bad = {"ld < n": ((n - 1, n * r), "leading dimension"),
+           "stride < ld * nrhs": ((n, n * r - 1), "member stride"),
+           "negative stride": ((n, -n * r), "member stride"),
+           "padded ld, stride too small": ((n + 8, n * r), "member stride")}
+    for label, ((ld, s), msg) in bad.items():
+        for side in ("B", "X"):
+            a = (ld, s) if side == "B" else good
+            x = good if side == "B" else (ld, s)
+            code, err = _code(bb._h, name, p, a[0], a[1], r, p, x[0], x[1])
+            assert code == _lib.ERR_INVALID_ARG and msg in err and err.startswith(side), (label, side, err)
+    code, err = _code(bb._h, name, p, n, n * r, -1, p, n, n * r)
+    assert code == _lib.ERR_INVALID_ARG and "nrhs" in err
+    code, err = _code(bb._h, name, None, n, n * r, r, p, n, n * r)
+    assert code == _lib.ERR_INVALID_ARG and "null" in err
+    # a well-formed layout (padded ld, a gap between members) reaches the missing device state
+    assert _code(bb._h, name, p, n + 3, (n + 3) * r + 5, r, p, n + 1, (n + 1) * r)[0] == _lib.ERR_NO_DEVICE
+    # a plain handle is a batch of one: ld < n is refused, the member stride is not used
+    one = gmrfx.MI355XBackend(Q, symbolic_only=True)
+    assert _code(one._h, name, p, n - 1, 0, r, p, n, 0)[0] == _lib.ERR_INVALID_ARG
+    assert _code(one._h, name, p, n, 0, r, p, n, 0)[0] == _lib.ERR_NO_DEVICE
+
+
+@pytest.mark.parametrize("name", ["gmrfx_batch_quadform", "gmrfx_batch_quadform_dev", "gmrfx_batch_refactorize_logpdf_dev"])
+def test_batch_quadform_arguments_are_checked(name):
+    Q, _ = _matern30()
+    n, B = Q.shape[0], 3
+    bb = gmrfx.MI355XBatchBackend(Q, B, symbolic_only=True)
+    buf = np.zeros(4 * n * B + 64)
+    p = buf.ctypes.data
+    fused = name.endswith("logpdf_dev")
+
+    def call(ldx, sx, nvec, X=p, quad=p):
+        args = (p, X, ldx, sx, nvec, None, quad) + ((p, None) if fused else ())
+        return _code(bb._h, name, *args)
+
+    big = (2**31 - 1) // B + 1                   # nvec * nbatch > INT32_MAX: the pair index of k_batch_quadform is 32-bit
+    code, err = call(n, n * big, big)
+    assert code == _lib.ERR_INVALID_ARG and "INT32_MAX" in err
+    assert call(n, n * (big - 1), big - 1)[0] == _lib.ERR_NO_DEVICE
+    for (ldx, sx, nvec), msg in (((n - 1, 2 * n, 2), "leading dimension"), ((n, 2 * n - 1, 2), "member stride"),
+                                 ((n, 2 * n, -1), "nvec")):
+        code, err = call(ldx, sx, nvec)
+        assert code == _lib.ERR_INVALID_ARG and msg in err, err
+    code, err = call(n, 2 * n, 2, X=None)
+    assert code == _lib.ERR_INVALID_ARG and "null" in err
+    code, err = call(n, 2 * n, 2, quad=None)
+    assert code == _lib.ERR_INVALID_ARG and "null" in err
+    assert call(n, 2 * n, 2)[0] == _lib.ERR_NO_DEVICE
