@@ -227,6 +227,9 @@ void Device::upload(const Symbolic &S) {
 
 void Device::clone_from(const Device &o, const Symbolic &S) {
     init(S, o.device);
+    inv_cap_ = o.inv_cap_;
+    inv_cap_decided_ = o.inv_cap_decided_;
+    ms_inv_decide = o.ms_inv_decide;
     if (o.factorized) {
         HC(hipMemcpyAsync(d_L_, o.d_L_, (size_t)l_size_ * sizeof(double), hipMemcpyDeviceToDevice, stream));
         HC(hipMemcpyAsync(d_info_, o.d_info_, sizeof(int), hipMemcpyDeviceToDevice, stream));
@@ -602,6 +605,27 @@ void Device::start_inverse_async() {
 }
 void Device::wait_inverse() { HC(hipStreamWaitEvent(stream, ev_inv_, 0)); }
 
+// Called behind the synchronisation of a factorisation, before anything reads the inverses (see device.h).
+void Device::decide_inverse_cap() {
+    if (inv_cap_decided_ || sharded() || *h_info_ != INT_MAX) return;     // a failed pivot: the next good factorisation decides
+    inv_cap_decided_ = true;
+    const int nf = inv_nact_.empty() ? 0 : inv_nact_[0];                   // the fronts wider than NB
+    if (nf <= 0 || inv_cap_ <= NB) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t cnt = (size_t)nf * (size_t)((inv_maxc_ + 255) / 256);     // partial maxima: row blocks x fronts
+    if (!d_pivgrowth_) d_pivgrowth_ = dalloc<double>(cnt);
+    launch_pivot_growth(stream, ds_, d_invlist_, nf, inv_maxc_, d_L_, d_pivgrowth_);
+    std::vector<double> r(cnt);
+    HC(hipMemcpyAsync(r.data(), d_pivgrowth_, cnt * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    ms_inv_decide = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (double v : r)
+        if (!(v <= kInvGrowthMax)) {
+            inv_cap_ = NB;
+            break;
+        }
+}
+
 void Device::invert_diag_blocks(hipStream_t stream, int b_from, int b_to) {
     int stage = 0;
     for (int B = NB; B < std::min(inv_maxc_, b_to); B *= 2, stage++) {
@@ -636,7 +660,9 @@ void Device::refactorize_solve(const double *nzval, bool nz_on_device, const dou
                                bool b_on_device) {
     HC(hipSetDevice(device));
     if (sharded()) throw std::invalid_argument("sharded handle: use the phase entry points (gmrfx/shard.py)");
-    if (nrhs <= 0 || stream != own_stream_) {      // nothing to pipeline / the caller's stream: the plain sequence
+    // nothing to pipeline / the caller's stream / the inverse cap is not decided yet (the handle's first factorisation): the plain
+    // sequence
+    if (nrhs <= 0 || stream != own_stream_ || !inv_cap_decided_) {
         refactorize(nzval, nz_on_device);
         if (nrhs > 0) solve(B, ldb, nrhs, X, ldx_out, b_on_device, 0);
         return;
@@ -758,6 +784,7 @@ void Device::refactorize(const double *nzval, bool on_device) {
     HC(hipStreamSynchronize(stream));
     info_cached_ = true;
     HC(hipGetLastError());
+    decide_inverse_cap();
     float ms = 0;
     HC(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
     ms_factor = ms;
@@ -1396,6 +1423,7 @@ void Device::refactorize_logpdf(const double *d_nz, const double *d_X, long long
     HC(hipStreamSynchronize(stream));
     info_cached_ = true;
     HC(hipGetLastError());
+    decide_inverse_cap();
     HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
     ms_factor = tf;
     syrk_times_pending_ = true;
@@ -1756,6 +1784,7 @@ void Device::batch_refactorize_logpdf(const double *d_nz, const double *d_X, lon
     HC(hipStreamSynchronize(stream));
     info_cached_ = true;
     HC(hipGetLastError());
+    decide_inverse_cap();
     float tf = 0;
     HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
     ms_factor = tf;

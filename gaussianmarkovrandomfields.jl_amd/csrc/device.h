@@ -142,6 +142,8 @@ public:
     double ms_factor = 0, ms_solve = 0, ms_fwd = 0, ms_bwd = 0, ms_perm = 0, ms_bsolve = 0, ms_logdet = 0, ms_selinv = 0;
     long long last_nrhs = 0;
     double ms_quadform = 0;
+    double ms_inv_decide = 0;      // host wall time of the one-time inverse-cap decision (decide_inverse_cap), 0 before / without it
+    int inv_cap() const { return inv_cap_; }
     bool syrk_times_pending_ = false;
     double syrk_ms();                 // summed HIP-event time of the SYRK launches of the last factorisation (read lazily)
     double ms_syrk = 0, syrk_flops = 0;   // dominant kernel (k_syrk_cb): live HIP-event time per refactorisation, flops
@@ -238,6 +240,18 @@ private:
     // front costs O(c^3): most of a 3-D solve); wider fronts substitute block by block in the sweeps. The selected
     // inversion needs the full inverses and runs the remaining stages on demand (B from inv_cap_ up).
     int inv_cap_ = 2048;     // measured: cfg 2 flat between 1024 and 4096 (6.18 vs 6.26 ms), 3-D 100^3 solve 44 vs 54 ms
+    // An explicit inverse of an ill-conditioned L11 is not backward stable (inverse.hip, "Conditioning"): the handle's first
+    // successful factorisation measures the pivot growth max_j sqrt(A11_jj) / L_jj of every front wider than NB, and above
+    // kInvGrowthMax the cap drops to NB for the rest of the handle's life. One cap per handle, decided before any sweep runs
+    // (refactorize_solve takes the plain sequence until then), keeps the pipelined and the separate calls bit-identical; the
+    // measure is the same bits for D Q D (D of powers of two) as for Q, so both take the same path. Sharded handles never
+    // decide (their fronts are spread over ranks): they keep the cap they were created with. Costs one pass over the
+    // lower triangles of those fronts, O(c^2) each, and one synchronisation, once per handle (stats: ms_inv_decide; measured
+    // 2.5 ms on the 1000 x 1000 2-D benchmark mesh, 14 ms on a 100^3 3-D grid whose top front has 30 000 columns).
+    static constexpr double kInvGrowthMax = 1e4;
+    bool inv_cap_decided_ = false;
+    double *d_pivgrowth_ = nullptr;
+    void decide_inverse_cap();
     bool inverse_full_ = false;
     // pipelined factor + solve: per-level "level is factored" events, the dense-inverse stages per level, the highest level a
     // sweep task / small subtree reaches

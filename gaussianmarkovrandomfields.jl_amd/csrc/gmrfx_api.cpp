@@ -907,6 +907,8 @@ extern "C" int32_t gmrfx_get_stats(const gmrfx_handle *h, gmrfx_stats *out, int3
         st.last_nrhs = D.last_nrhs;
         st.ms_syrk = const_cast<gmrfx::Device &>(D).syrk_ms(); st.syrk_flops = D.syrk_flops; st.syrk_launches = D.syrk_launches;
         st.ms_quadform = D.ms_quadform;
+        st.inv_cap = D.inv_cap();
+        st.ms_inv_decide = D.ms_inv_decide;
         if (D.factorized) st.fail_col = const_cast<Device &>(D).fail_col();
     }
     std::memcpy(out, &st, std::min<size_t>((size_t)struct_size, sizeof(st)));

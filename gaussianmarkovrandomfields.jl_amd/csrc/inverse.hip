@@ -3,9 +3,19 @@
 //
 // Why: with 64-column blocks the triangular sweeps of the top separator fronts are a chain of
 // ~c/64 dependent (diagonal solve, update) launch pairs per level and direction -- ~120 latency-
-// bound steps of 30-40 us each on the 1M-node benchmark. L11 of a separator front is well
-// conditioned (cond ~ 1e2 on SPDE precisions), so its explicit inverse turns the whole diagonal
+// bound steps of 30-40 us each on the 1M-node benchmark. An explicit inverse turns the whole diagonal
 // solve of a level into ONE triangular matrix product that parallelises over row tiles.
+//
+// Conditioning. One-off measurements (numpy's cond(L11) and the pivot growth below, computed on the CPU oracle's factor in
+// the handle's elimination order, for the fronts wider than 64 columns): cond(L11) ~1e1 - 2e2 and pivot growth <= 16 on
+// SPDE precisions (Matern, ranges 0.3 - 0.5, 2-D and 3-D); cond up to ~7e4, growth ~3e3 on intrinsic models (Besag on a
+// 2-D / 3-D torus + 1e-10 I), where the solves keep the backward error of plain substitution (tests/test_gpu_intrinsic.py
+// checks the backward errors, not these numbers); cond ~2.5e7, growth 4.5e5 at the top front of a Matern precision of range
+// 20 on [-1, 1]^2, whose inverse raised the normwise backward error of a solve from 2.4e-16 to 1.3e-13. So the handle's first
+// factorisation measures the pivot growth of every front wider than 64 columns (k_pivot_growth); above 1e4 the handle's
+// inverse cap drops to 64 columns for good, and such fronts substitute block by block with inverses of their 64 x 64
+// diagonal blocks (Device::decide_inverse_cap). Sharded handles never lower the cap. The selected inversion still uses
+// the full inverses.
 //
 // Storage: X[k][q] (k > q) lives at P[q + k*ld], i.e. transposed in the strict upper triangle of
 // the c x c diagonal block of the panel, which the factorisation never touches (the 64 x 64
@@ -252,6 +262,55 @@ void launch_inv_stage(hipStream_t st, const DevSym &S, const int *list, int nact
     // workgroup would land on the same XCD (linear workgroup id mod 8)
     hipLaunchKernelGGL(k_inv_stage, dim3(ntile, npair | 1, nactive), dim3(256), 0, st, S, list, B, phase, L, T, toff);
 }
+// Pivot growth of every front of `list` (workgroup (x, y): rows 256 x .. 256 x + 255 of front y; the host takes the max over
+// x): max over its columns j of sqrt(A11_jj) / L_jj =
+// sqrt(sum_{k <= j} (L_jk / L_jj)^2), where A11_jj = sum_{k <= j} L_jk^2 is the diagonal of the assembled front that L11 L11'
+// reproduces; NaN when a pivot is not positive. Row j is divided by its own pivot before it is squared: no overflow or underflow
+// of the squares at any scale of Q, and the result is the same bits for D A11 D when D holds powers of two (x d * (1 / (p d))
+// = x * (1 / p) exactly), unlike max / min L_jj.
+__global__ __launch_bounds__(256) void k_pivot_growth(DevSym S, const int *__restrict__ list, const double *__restrict__ L,
+                                                      double *__restrict__ out) {
+    const int s = list[blockIdx.y];
+    const int c = S.sfirst[s + 1] - S.sfirst[s];
+    const int ld = S.ld[s];
+    const double *P = L + S.panelptr[s];
+    double g = 0.0;
+    int bad = 0;
+    const int j = blockIdx.x * 256 + threadIdx.x;       // one row per thread, 256 rows per workgroup
+    if (j < c) {
+        const double p = P[j + (long long)j * ld];
+        if (!(p > 0.0)) {
+            bad = 1;
+        } else {
+            const double r = 1.0 / p;
+            double a = 0.0;
+            for (int k = 0; k <= j; k++) {
+                const double v = P[j + (long long)k * ld] * r;
+                a = fma(v, v, a);
+            }
+            g = sqrt(a);
+        }
+    }
+    __shared__ double sg[256];
+    __shared__ int sbad[256];
+    sg[threadIdx.x] = g;
+    sbad[threadIdx.x] = bad;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) {
+            sg[threadIdx.x] = fmax(sg[threadIdx.x], sg[threadIdx.x + h]);
+            sbad[threadIdx.x] |= sbad[threadIdx.x + h];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(long long)blockIdx.y * gridDim.x + blockIdx.x] = sbad[0] ? __builtin_nan("") : sg[0];
+}
+
+void launch_pivot_growth(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_c, const double *L, double *out) {
+    if (nfronts <= 0 || max_c <= 0) return;
+    hipLaunchKernelGGL(k_pivot_growth, dim3(cdiv(max_c, 256), nfronts), dim3(256), 0, st, S, list, L, out);
+}
+
 void launch_xmul(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_c, int trans, const double *L,
                  const double *Xin, double *Xout, int nr, int ldx, int blk, int cap) {
     if (nfronts <= 0 || max_c <= 0) return;

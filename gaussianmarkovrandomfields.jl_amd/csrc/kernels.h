@@ -393,6 +393,8 @@ __device__ __forceinline__ void splitk_reduce4_pairs(gmrfx_d4 (&acc)[2][4], doub
 // inverse.hip -- dense L11^-1 of big fronts (recursive doubling) and the sweeps that use it
 void launch_inv_stage(hipStream_t st, const DevSym &S, const int *list, int nactive, int B, int max_c, int phase,
                       double *L, double *T, const long long *toff);
+// out: nfronts x cdiv(max_c, 256) partial maxima (front-major)
+void launch_pivot_growth(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_c, const double *L, double *out);
 void launch_xmul(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_c, int trans, const double *L,
                  const double *Xin, double *Xout, int nr, int ldx, int blk = 0, int cap = 1 << 30);
 void launch_copy_own(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_c, const double *Xsrc,

@@ -32,7 +32,7 @@ class GmrfxStats(C.Structure):
         "ms_solve", "ms_solve_fwd", "ms_solve_bwd", "ms_solve_perm", "ms_backward_solve", "ms_logdet",
         "ms_selinv")] + [("last_nrhs", C.c_int64), ("fail_col", C.c_int64), ("ms_syrk", C.c_double),
                          ("syrk_flops", C.c_double), ("syrk_launches", C.c_int64),
-                         ("ms_quadform", C.c_double)]
+                         ("ms_quadform", C.c_double), ("inv_cap", C.c_int64), ("ms_inv_decide", C.c_double)]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

@@ -95,6 +95,10 @@ typedef struct gmrfx_stats {
     double  ms_syrk, syrk_flops;
     int64_t syrk_launches;
     double  ms_quadform;           /* most recent gmrfx_quadform(_dev): kernels only             */
+    /* widest diagonal block the sweeps use as an explicit inverse (2048 by default; 64 once the handle's first factorisation
+     * found a front with pivot growth above 1e4), and the host wall time that one-time check took (0 before it ran) */
+    int64_t inv_cap;
+    double  ms_inv_decide;
 } gmrfx_stats;
 
 /* Message for the most recent failed gmrfx_create on this thread. */
