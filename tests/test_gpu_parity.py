@@ -3,7 +3,8 @@ through the C ABI (ctypes -> libgmrfx.so), is compared with the CPU oracle on th
 same permutation, and with the dense identities the reference's own tests use
 (test/workspace/test_gmrf_workspace.jl:26-224, test_backend_ordering.jl:25-68,
 test_precision_logdet.jl:198-204). Tolerances: factor/solve/logdet 1e-10 relative (north_star
-asks 1e-8), selinv diag 1e-8, full selinv 1e-6, as in the reference's tests."""
+asks 1e-8), selinv diag 1e-8, full selinv 1e-6, as in the reference's tests.
+The entrywise check of the selected inverse, on fronts of prescribed shape, is in test_gpu_selinv_shapes.py."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
