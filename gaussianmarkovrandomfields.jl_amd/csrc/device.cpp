@@ -57,6 +57,8 @@ template <class T> T *Device::dregrow(T *old, size_t count) {
 Device::~Device() {
     for (size_t k = 0; k < rd_plans_.size(); k++) rowdiag_plan_free((long long)k);
     if (stream) { (void)hipStreamSynchronize(stream); }
+    if (con_.ev0) (void)hipEventDestroy(con_.ev0);
+    if (con_.ev1) (void)hipEventDestroy(con_.ev1);
     for (auto &p : allocs_) (void)hipFree(p.first);
     for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto &v : ev_level_) for (auto &e : v) (void)hipEventDestroy(e);

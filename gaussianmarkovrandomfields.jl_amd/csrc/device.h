@@ -49,6 +49,16 @@ struct DevSym {
 // geometry of one front for the panel kernels in the kernel arguments (FrontView: the same as one record per level-list position)
 // ppa (round 6): where the K operand columns of a panel update live when they are NOT in the panel itself -- the received block of a
 // distributed front with block-cyclic storage sits in a window (Device::dist_front_phase); kNoPpa = in the panel, as everywhere else
+// Linear equality constraints A x = e as the handle keeps them on the host (gmrfx_constraints_set): m sparse rows, 0-based 32-bit
+// columns sorted and unique within a row, the right-hand side e and log det(A A').
+struct ConHost {
+    int m = 0;
+    std::vector<long long> rowptr;
+    std::vector<int> col;
+    std::vector<double> val, e;
+    double logdet_AAt = 0;
+};
+
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
 class Device {
@@ -136,6 +146,23 @@ public:
     void dense_apply(const double *d_D, const double *d_T, double *d_R, long long n1, long long n2);
     void transpose(const double *d_src, double *d_dst, long long rows, long long cols);
     long long fail_col();
+    // ---- linear equality constraints (device_constraint.cpp, constraint.hip) ------------------------------------------------------
+    // con_set uploads A / e (m = 0: none) and drops everything derived. con_prepare (lazy, once per factorisation) builds
+    // At = Q^-1 A' (scatter + ONE blocked solve), W = A At, L_c, L_c^-1 (host, m <= 64) and B = At L_c^-T; false = W is not positive definite.
+    void con_set(const ConHost &c);
+    int con_m() const { return con_.m; }
+    bool con_prepare();
+    double con_logdet_w() const { return con_.logdet_w; }
+    double con_ms() const { return con_.ms; }
+    void con_get(double *At_host, long long ld, double *W_host);
+    // X <- X (+ mu) - At W^-1 (A (X + mu) - e) on nvec columns of a device array (d_mu nullable); without constraints X += mu
+    void con_correct(double *d_X, long long ldx, long long nvec, const double *d_mu);
+    double ms_con_correct = 0;         // GPU time of the kernels of the most recent con_correct
+    // A mu - e of the most recent con_correct (its first column), host copy of m values
+    void con_residual(double *out_host);
+    const std::vector<double> &con_linv() const { return con_.h_linv; }
+    // max(diag Sigma - rowsum(B^2), 0) (selected inverse computed if absent); without constraints = selinv_diag
+    void con_var(double *out_host);
 
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
@@ -323,6 +350,21 @@ private:
     double *d_bqf_part_ = nullptr, *d_bqf_out_ = nullptr, *h_bqf_ = nullptr;
     long long bqf_cap_ = 0, h_bqf_cap_ = 0;
     void enqueue_batch_diag(hipStream_t st);
+    // constraint state: A (CSR) and e on the device, chunk offsets of the reduction, the cached operands of factorisation con_.serial
+    struct ConDev {
+        int m = 0, maxchunks = 0;
+        long long nnz = 0, maxlen = 0, totchunks = 0, colcap = 0;
+        long long *rowptr = nullptr;
+        int *col = nullptr, *choff = nullptr;
+        double *val = nullptr, *e = nullptr, *At = nullptr, *B = nullptr, *Linv = nullptr, *R = nullptr, *amu = nullptr, *part = nullptr, *sig = nullptr;
+        std::vector<double> h_w, h_linv;
+        double logdet_w = 0, ms = 0;
+        unsigned long long serial = 0;      // 0: nothing cached
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    } con_;
+    void *con_alloc(size_t bytes);
+    void con_release(void *p);
+    void con_drop();
     void prepare_batch_quadform(long long npairs);
     void enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,
                                 const double *d_mu);

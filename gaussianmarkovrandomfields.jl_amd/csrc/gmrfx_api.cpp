@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <chrono>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -28,6 +29,8 @@ struct gmrfx_handle {
     std::vector<i64> zcolptr, zrow, zoff;
     // batched handles (gmrfx_create_batched): S is the forest of nbatch copies of the member's pattern; plain handles: 1, n, nnz
     int64_t nbatch = 1, n_member = 0, nnz_member = 0;
+    // linear equality constraints A x = e (gmrfx_constraints_set): host copy, also on symbolic_only handles; con.m = 0: none
+    ConHost con;
 };
 
 static thread_local std::string g_create_err;
@@ -146,6 +149,8 @@ extern "C" int32_t gmrfx_clone(const gmrfx_handle *h, gmrfx_handle **out) {
             c->D->clone_from(*h->D, c->S);
             if (h->D->batched()) c->D->set_batch((int)c->nbatch, c->n_member, c->nnz_member);
         }
+        c->con = h->con;        // A and e travel; the clone recomputes what is derived from them
+        if (c->D && c->con.m > 0) c->D->con_set(c->con);
     } catch (const std::exception &e) {
         g_create_err = e.what();
         return GMRFX_ERR_HIP;
@@ -1227,4 +1232,219 @@ extern "C" int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const dou
         if (info) std::copy(inf.begin(), inf.end(), info);
         return batch_status(h, inf);
     });
+}
+
+// ---- linear equality constraints A x = e (include/gmrfx.h; Device::con_*, csrc/constraint.hip) --------------------------------------
+// log det(A A') on the host: the m x m Gram matrix of the sparse rows through one dense scratch row, then a plain Cholesky
+// (-inf when A A' is not positive definite: a rank-deficient A is reported by the numeric entry points, as the reference does)
+static double logdet_gram(const ConHost &c, int64_t n) {
+    const int m = c.m;
+    std::vector<double> G((size_t)m * m, 0.0), row((size_t)n, 0.0);
+    for (int r = 0; r < m; r++) {
+        for (long long p = c.rowptr[r]; p < c.rowptr[r + 1]; p++) row[c.col[p]] = c.val[p];
+        for (int s = 0; s <= r; s++) {
+            double acc = 0.0;
+            for (long long p = c.rowptr[s]; p < c.rowptr[s + 1]; p++) acc += c.val[p] * row[c.col[p]];
+            G[(size_t)r * m + s] = acc;
+        }
+        for (long long p = c.rowptr[r]; p < c.rowptr[r + 1]; p++) row[c.col[p]] = 0.0;
+    }
+    double ld = 0.0;
+    for (int j = 0; j < m; j++) {
+        double d = G[(size_t)j * m + j];
+        for (int q = 0; q < j; q++) d -= G[(size_t)j * m + q] * G[(size_t)j * m + q];
+        if (!(d > 0.0)) return -HUGE_VAL;
+        const double dj = std::sqrt(d);
+        G[(size_t)j * m + j] = dj;
+        ld += 2.0 * std::log(dj);
+        for (int i = j + 1; i < m; i++) {
+            double t = G[(size_t)i * m + j];
+            for (int q = 0; q < j; q++) t -= G[(size_t)i * m + q] * G[(size_t)j * m + q];
+            G[(size_t)i * m + j] = t / dj;
+        }
+    }
+    return ld;
+}
+
+extern "C" int32_t gmrfx_constraints_set(gmrfx_handle *h, int64_t m, const int64_t *rowptr, const int64_t *colind, const double *values,
+                                         int32_t base, const double *e) {
+    return guarded(h, [&]() -> int32_t {
+        // everything is checked and built aside first: a refused call changes nothing
+        if (m < 0) throw std::invalid_argument("constraints: m < 0");
+        if (m > 64) throw std::invalid_argument("constraints: more than 64 rows (the limit of the device path: one sweep pass, m x m operands in LDS)");
+        if (h->nbatch > 1) throw std::invalid_argument("constraints: batched handles are not supported");
+        if (h->S.shard_plan) throw std::invalid_argument("constraints: sharded handles are not supported");
+        ConHost c;
+        if (m > 0) {
+            if (!rowptr || !colind || !values || !e) throw std::invalid_argument("constraints: null argument");
+            if (base != 0 && base != 1) throw std::invalid_argument("index_base must be 0 or 1");
+            check_compressed_ptr(rowptr, m, base, "rowptr");
+            const int64_t n = h->S.n;
+            c.m = (int)m;
+            c.rowptr.assign((size_t)m + 1, 0);
+            c.e.assign(e, e + m);
+            std::vector<std::pair<int, double>> ent;
+            for (int64_t r = 0; r < m; r++) {
+                if (rowptr[r + 1] == rowptr[r]) throw std::invalid_argument("constraints: row " + std::to_string(r) + " of A is empty");
+                ent.clear();
+                for (int64_t p = rowptr[r] - base; p < rowptr[r + 1] - base; p++) {
+                    const int64_t j = colind[p] - base;
+                    if (j < 0 || j >= n) throw std::invalid_argument("constraints: column index out of range");
+                    ent.push_back({(int)j, values[p]});
+                }
+                std::stable_sort(ent.begin(), ent.end(), [](const std::pair<int, double> &a, const std::pair<int, double> &b) { return a.first < b.first; });
+                for (size_t t = 0; t < ent.size(); t++) {
+                    if (t > 0 && ent[t].first == ent[t - 1].first) c.val.back() += ent[t].second;      // duplicates are summed
+                    else { c.col.push_back(ent[t].first); c.val.push_back(ent[t].second); }
+                }
+                c.rowptr[(size_t)r + 1] = (long long)c.col.size();
+            }
+            c.logdet_AAt = logdet_gram(c, n);
+        }
+        if (h->D) h->D->con_set(c);
+        h->con = std::move(c);
+        return GMRFX_OK;
+    });
+}
+
+// the cached operands of the current factorisation (built on first use)
+static int32_t con_ready(gmrfx_handle *h) {
+    if (int32_t e = need_device(h, true)) return e;
+    if (h->con.m > 0 && !h->D->con_prepare()) {
+        h->err = "constraints: A Q^-1 A' is not positive definite (rank-deficient constraint matrix)";
+        return GMRFX_ERR_NOT_POSDEF;
+    }
+    return GMRFX_OK;
+}
+
+extern "C" int32_t gmrfx_constraints_info(gmrfx_handle *h, int64_t *m, double *logdet_W, double *logdet_AAt, double *ms) {
+    return guarded(h, [&]() -> int32_t {
+        if (m) *m = h->con.m;
+        if (logdet_AAt) *logdet_AAt = h->con.m > 0 ? h->con.logdet_AAt : 0.0;
+        if (logdet_W) *logdet_W = 0.0;
+        if (ms) *ms = 0.0;
+        if (h->con.m == 0 || (!logdet_W && !ms)) return GMRFX_OK;
+        if (int32_t e = con_ready(h)) return e;
+        if (logdet_W) *logdet_W = h->D->con_logdet_w();
+        if (ms) *ms = h->D->con_ms();
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_constraints_get(gmrfx_handle *h, double *A_tilde_T, int64_t ld, double *W) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = con_ready(h)) return e;
+        if (A_tilde_T && ld < h->S.n) throw std::invalid_argument("constraints: ld < n");
+        h->D->con_get(A_tilde_T, ld, W);
+        return GMRFX_OK;
+    });
+}
+
+// a device copy of an n x nvec host block (ld = n), freed on return
+namespace {
+struct DevBlock {
+    double *p = nullptr;
+    ~DevBlock() { if (p) (void)hipFree(p); }
+    void alloc(int64_t count) { hip_check(hipMalloc((void **)&p, (size_t)std::max<int64_t>(count, 1) * sizeof(double) + 16), "hipMalloc"); }
+    void up(const double *src, int64_t ld, int64_t n, int64_t nvec) {
+        hip_check(hipMemcpy2D(p, (size_t)n * sizeof(double), src, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
+    }
+    void down(double *dst, int64_t ld, int64_t n, int64_t nvec) {
+        hip_check(hipMemcpy2D(dst, (size_t)ld * sizeof(double), p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
+    }
+};
+}  // namespace
+
+extern "C" int32_t gmrfx_constraints_mean(gmrfx_handle *h, const double *mu, double *mean_c, double *log_correction) {
+    return guarded(h, [&]() -> int32_t {
+        if (int32_t e = con_ready(h)) return e;
+        const int64_t n = h->S.n;
+        const int m = h->con.m;
+        hip_check(hipSetDevice(h->D->device), "hipSetDevice");
+        DevBlock x;
+        x.alloc(n);
+        if (mu) x.up(mu, n, n, 1);
+        else hip_check(hipMemset(x.p, 0, (size_t)n * sizeof(double)), "hipMemset");
+        h->D->con_correct(x.p, n, 1, nullptr);
+        if (mean_c) x.down(mean_c, n, n, 1);
+        if (log_correction) {
+            *log_correction = 0.0;
+            if (m > 0) {
+                // 0.5 (m log 2 pi + log det W + r' W^-1 r) - 0.5 log det(A A'), r = e - A mu: r' W^-1 r = |L_c^-1 r|^2
+                std::vector<double> r((size_t)m);
+                h->D->con_residual(r.data());
+                const std::vector<double> &Li = h->D->con_linv();
+                double quad = 0.0;
+                for (int l = 0; l < m; l++) {
+                    double t = 0.0;
+                    for (int q = 0; q <= l; q++) t += Li[(size_t)l * m + q] * r[q];
+                    quad += t * t;
+                }
+                *log_correction = 0.5 * (m * std::log(2.0 * 3.14159265358979323846) + h->D->con_logdet_w() + quad) - 0.5 * h->con.logdet_AAt;
+            }
+        }
+        return GMRFX_OK;
+    });
+}
+
+static int32_t constraints_correct_impl(gmrfx_handle *h, double *X, int64_t ldx, int64_t nvec, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        if (nvec < 0) throw std::invalid_argument("nvec < 0");
+        if (nvec > 0 && !X) throw std::invalid_argument("X is null");
+        if (nvec > 0 && ldx < h->S.n) throw std::invalid_argument("leading dimension smaller than n");
+        if (int32_t e = con_ready(h)) return e;
+        if (nvec == 0 || h->con.m == 0) return GMRFX_OK;
+        if (dev) { h->D->con_correct(X, ldx, nvec, nullptr); return GMRFX_OK; }
+        const int64_t n = h->S.n;
+        hip_check(hipSetDevice(h->D->device), "hipSetDevice");
+        DevBlock x;
+        x.alloc(n * nvec);
+        x.up(X, ldx, n, nvec);
+        h->D->con_correct(x.p, n, nvec, nullptr);
+        x.down(X, ldx, n, nvec);
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_constraints_correct(gmrfx_handle *h, double *X, int64_t ldx, int64_t nvec) { return constraints_correct_impl(h, X, ldx, nvec, false); }
+extern "C" int32_t gmrfx_constraints_correct_dev(gmrfx_handle *h, double *d_X, int64_t ldx, int64_t nvec) { return constraints_correct_impl(h, d_X, ldx, nvec, true); }
+
+extern "C" int32_t gmrfx_constraints_var(gmrfx_handle *h, double *out) {
+    return guarded(h, [&]() -> int32_t {
+        if (!out) throw std::invalid_argument("out is null");
+        if (int32_t e = con_ready(h)) return e;
+        h->D->con_var(out);
+        return GMRFX_OK;
+    });
+}
+
+static int32_t sample_impl(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t nrhs, const double *mu, double *X, int64_t ldx, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
+        if (nrhs > 0 && (!Z || !X)) throw std::invalid_argument("Z/X is null");
+        if (nrhs > 0 && (ldz < h->S.n || ldx < h->S.n)) throw std::invalid_argument("leading dimension smaller than n");
+        if (int32_t e = con_ready(h)) return e;
+        if (nrhs == 0) return GMRFX_OK;
+        if (dev) {
+            h->D->solve(Z, ldz, nrhs, X, ldx, true, 1);
+            h->D->con_correct(X, ldx, nrhs, mu);
+            return GMRFX_OK;
+        }
+        if (h->con.m == 0 && !mu) { h->D->solve(Z, ldz, nrhs, X, ldx, false, 1); return GMRFX_OK; }     // = gmrfx_backward_solve
+        const int64_t n = h->S.n;
+        hip_check(hipSetDevice(h->D->device), "hipSetDevice");
+        DevBlock x, dm;
+        x.alloc(n * nrhs);
+        x.up(Z, ldz, n, nrhs);
+        if (mu) { dm.alloc(n); dm.up(mu, n, n, 1); }
+        h->D->solve(x.p, n, nrhs, x.p, n, true, 1);
+        h->D->con_correct(x.p, n, nrhs, dm.p);
+        x.down(X, ldx, n, nrhs);
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_sample(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t nrhs, const double *mu, double *X, int64_t ldx) {
+    return sample_impl(h, Z, ldz, nrhs, mu, X, ldx, false);
+}
+extern "C" int32_t gmrfx_sample_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t nrhs, const double *d_mu, double *d_X, int64_t ldx) {
+    return sample_impl(h, d_Z, ldz, nrhs, d_mu, d_X, ldx, true);
 }

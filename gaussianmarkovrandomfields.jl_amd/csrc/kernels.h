@@ -455,6 +455,20 @@ void launch_batch_quadform(hipStream_t st, int nm, const long long *colptr, cons
 void launch_dense_apply(hipStream_t st, const double *D, const double *T, double *R, int n1, long long n2);
 void launch_transpose(hipStream_t st, const double *src, double *dst, long long rows, long long cols);
 
+// constraint.hip -- linear equality constraints A x = e (m <= 64 sparse rows; At, B: n x m column-major, ld n)
+constexpr int kConChunk = 4096;        // entries of a row of A per partial sum of A X (fixed: the sums' order depends on it)
+constexpr int kConColTile = 8;         // columns of X per workgroup of the reduction
+constexpr int kConApplyGroups = 2048;  // row-tile workgroups of the correction kernel per column block (they walk the tiles)
+void launch_con_scatter(hipStream_t st, const long long *rowptr, const int *col, const double *val, int n, int m, long long maxlen, double *out);
+// R[r + j m] = (A X)[r, j] (- e[r]) (+ add[r]); part: choff[m] k doubles, choff = prefix sum of the rows' chunk counts
+void launch_con_ax(hipStream_t st, const long long *rowptr, const int *col, const double *val, const int *choff, int maxchunks, int m,
+                   const double *X, long long ldx, int k, double *part, const double *e, const double *add, double *R);
+void launch_con_trsm(hipStream_t st, const double *At, const double *Linv, int n, int m, double *B);
+void launch_con_var(hipStream_t st, const double *B, int n, int m, double *sig);
+// X <- X (+ mu) - B (Linv R); m = 0 with a mean: X += mu
+void launch_con_apply(hipStream_t st, const double *B, const double *Linv, const double *R, const double *mu, double *X, long long ldx, int n,
+                      int m, int k);
+
 // small.hip -- fused kernels for fronts with r <= 96 / 128 rows and c <= 64 columns
 void launch_factor_small(hipStream_t st, const DevSym &S, const int *list, int nfronts, int rmax,
                          const double *nzval, double *L, double *CB, int *info);

@@ -70,6 +70,8 @@ EXPORTS = [
     "gmrfx_create_batched", "gmrfx_batch_size", "gmrfx_batch_refactorize", "gmrfx_batch_refactorize_dev", "gmrfx_batch_logdet",
     "gmrfx_batch_solve", "gmrfx_batch_solve_dev", "gmrfx_batch_backward_solve", "gmrfx_batch_backward_solve_dev",
     "gmrfx_batch_quadform", "gmrfx_batch_quadform_dev", "gmrfx_batch_refactorize_logpdf_dev",
+    "gmrfx_constraints_set", "gmrfx_constraints_info", "gmrfx_constraints_get", "gmrfx_constraints_mean",
+    "gmrfx_constraints_correct", "gmrfx_constraints_correct_dev", "gmrfx_constraints_var", "gmrfx_sample", "gmrfx_sample_dev",
 ]
 
 
@@ -175,6 +177,15 @@ def lib():
         L.gmrfx_batch_quadform.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
         L.gmrfx_batch_quadform_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp]
         L.gmrfx_batch_refactorize_logpdf_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp]
+        L.gmrfx_constraints_set.argtypes = [vp, i64, vp, vp, vp, i32, vp]
+        L.gmrfx_constraints_info.argtypes = [vp, C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]
+        L.gmrfx_constraints_get.argtypes = [vp, vp, i64, vp]
+        L.gmrfx_constraints_mean.argtypes = [vp, vp, vp, C.POINTER(dbl)]
+        L.gmrfx_constraints_correct.argtypes = [vp, vp, i64, i64]
+        L.gmrfx_constraints_correct_dev.argtypes = [vp, vp, i64, i64]
+        L.gmrfx_constraints_var.argtypes = [vp, vp]
+        L.gmrfx_sample.argtypes = [vp, vp, i64, i64, vp, vp, i64]
+        L.gmrfx_sample_dev.argtypes = [vp, vp, i64, i64, vp, vp, i64]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

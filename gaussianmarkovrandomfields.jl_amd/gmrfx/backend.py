@@ -573,6 +573,104 @@ class MI355XBackend:
     def selinv_compute_dev(self) -> None:
         check(lib().gmrfx_selinv_compute(self._h), self._h)
 
+    # -- linear equality constraints A x = e, computed on the device (include/gmrfx.h "linear equality constraints") ------------
+    def set_constraints(self, A, e) -> None:
+        """`ConstraintInfo(ws, mu, A, e)`'s A and e (workspace_gmrf.jl:22-40) become state of the handle: m <= 64 sparse rows.
+        Everything derived (A~' = Q^-1 A', W = A A~', L_c, B) is built lazily on the device, once per factorisation."""
+        A = sp.csr_matrix(A, dtype=np.float64)
+        e = np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+        if A.shape[1] != self.n:
+            raise ValueError(f"Constraint matrix size {A.shape} incompatible with workspace size {self.n}")
+        if A.shape[0] != e.shape[0]:
+            raise ValueError(f"Constraint matrix rows {A.shape[0]} != constraint vector length {e.shape[0]}")
+        self.set_constraints_csr(A.shape[0], A.indptr, A.indices, A.data, e)
+
+    def set_constraints_csr(self, m: int, rowptr, colind, values, e) -> None:
+        """The raw form: CSR arrays as given (0-based), checked by the library."""
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+        ci = np.ascontiguousarray(colind, dtype=np.int64)
+        va = np.ascontiguousarray(values, dtype=np.float64)
+        ev = np.ascontiguousarray(e, dtype=np.float64)
+        if rp.shape != (m + 1,) or ev.shape != (m,) or ci.shape != va.shape or (m > 0 and ci.shape[0] < rp[-1]):
+            raise ValueError("constraints: array lengths do not match m")
+        check(lib().gmrfx_constraints_set(self._h, m, ptr(rp), ptr(ci), ptr(va), 0, ptr(ev)), self._h)
+
+    def clear_constraints(self) -> None:
+        check(lib().gmrfx_constraints_set(self._h, 0, None, None, None, 0, None), self._h)
+
+    def constraint_info(self) -> dict:
+        """m, log det(A A') and -- on a numeric handle, building the cached operands if needed -- log det W = logdet(L_c) and the
+        GPU time of the most recent preparation."""
+        m, ldw, lda, ms = C.c_int64(0), C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+        if self.symbolic_only:
+            check(lib().gmrfx_constraints_info(self._h, C.byref(m), None, C.byref(lda), None), self._h)
+            return {"m": m.value, "logdet_AAt": lda.value}
+        check(lib().gmrfx_constraints_info(self._h, C.byref(m), C.byref(ldw), C.byref(lda), C.byref(ms)), self._h)
+        return {"m": m.value, "logdet_W": ldw.value, "logdet_AAt": lda.value, "ms": ms.value}
+
+    def _con_m(self) -> int:
+        m = C.c_int64(0)
+        check(lib().gmrfx_constraints_info(self._h, C.byref(m), None, None, None), self._h)
+        return m.value
+
+    def constraint_fields(self):
+        """(A_tilde_T, W): the n x m solve Q^-1 A' and W = A A~' (ConstraintInfo.A_tilde_T; L_c = cholesky(Symmetric(W)))."""
+        m = self._con_m()
+        At = np.empty((self.n, m), order="F")
+        W = np.empty((m, m), order="F")
+        check(lib().gmrfx_constraints_get(self._h, ptr(At), self.n, ptr(W)), self._h)
+        return At, W
+
+    def constrained_mean(self, mu=None):
+        """(mean_c, log_constraint_correction) of workspace_gmrf.jl:43-51; mu None = zero mean."""
+        mu = None if mu is None else np.ascontiguousarray(mu, dtype=np.float64)
+        if mu is not None and mu.shape != (self.n,):
+            raise ValueError("dimension mismatch")
+        out = np.empty(self.n)
+        lc = C.c_double(0.0)
+        check(lib().gmrfx_constraints_mean(self._h, ptr(mu), ptr(out), C.byref(lc)), self._h)
+        return out, lc.value
+
+    def constrained_var(self) -> np.ndarray:
+        """var(d) of workspace_gmrf.jl:260-273: max(diag Sigma - rowsum(B^2), 0); without constraints = get_selinv_diag()."""
+        out = np.empty(self.n)
+        check(lib().gmrfx_constraints_var(self._h, ptr(out)), self._h)
+        return out
+
+    def constraint_correct(self, X):
+        """x - A~' (L_c \\ (A x - e)) on every column (workspace_gmrf.jl:280-284). Returns a fresh array; input untouched."""
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim not in (1, 2) or X.shape[0] != self.n:
+            raise ValueError("dimension mismatch")
+        vec = X.ndim == 1
+        Xf = np.array(X.reshape(self.n, -1), order="F", copy=True)
+        check(lib().gmrfx_constraints_correct(self._h, ptr(Xf), self.n, Xf.shape[1]), self._h)
+        return Xf[:, 0].copy() if vec else Xf
+
+    def constraint_correct_dev(self, d_X: int, ldx: int, nvec: int) -> None:
+        if nvec < 0 or (nvec > 0 and (not d_X or ldx < self.n)):
+            raise ValueError("constraint_correct_dev: null pointer, nvec < 0 or ldx < n")
+        check(lib().gmrfx_constraints_correct_dev(self._h, d_X, ldx, nvec), self._h)
+
+    def sample(self, Z, mean=None):
+        """`_rand!` on given standard-normal draws (workspace_gmrf.jl:275-286): P' L^-T Z + mean, then the constraint correction."""
+        Z = np.asarray(Z, dtype=np.float64)
+        if Z.ndim not in (1, 2) or Z.shape[0] != self.n:
+            raise ValueError("dimension mismatch")
+        mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        if mu is not None and mu.shape != (self.n,):
+            raise ValueError("dimension mismatch")
+        vec = Z.ndim == 1
+        Zf = np.asfortranarray(Z.reshape(self.n, -1))
+        X = np.empty_like(Zf, order="F")
+        check(lib().gmrfx_sample(self._h, ptr(Zf), self.n, Zf.shape[1], ptr(mu), ptr(X), self.n), self._h)
+        return X[:, 0].copy() if vec else X
+
+    def sample_dev(self, d_Z: int, ldz: int, nrhs: int, d_X: int, ldx: int, d_mu: int = 0) -> None:
+        if nrhs < 0 or (nrhs > 0 and (not d_Z or not d_X or ldz < self.n or ldx < self.n)):
+            raise ValueError("sample_dev: null pointer, nrhs < 0 or leading dimension < n")
+        check(lib().gmrfx_sample_dev(self._h, d_Z, ldz, nrhs, d_mu or None, d_X, ldx), self._h)
+
 
 class MI355XBatchBackend:
     """B precision matrices with ONE pattern, factored in one pass (gmrfx_create_batched, include/gmrfx.h): the hyper-parameter

@@ -249,14 +249,101 @@ function Distributions._rand!(rng::AbstractRNG, d::G.WorkspaceGMRF{<:Any, MI355X
     G.ensure_loaded!(d)
     Z = randn!(rng, Matrix{Float64}(undef, size(X, 1), size(X, 2)))
     G.ensure_numeric!(d.workspace)
+    b = d.workspace.backend
+    if d.constraints === nothing || size(d.constraints.matrix, 1) <= MAX_DEVICE_CONSTRAINTS
+        # mean and constraint correction on the device, in the same call as the sweep (gmrfx_sample): nothing but Z and X crosses
+        sync_constraints!(b, d.constraints)
+        X .= sample(b, Z, Vector{Float64}(d.mean))
+        return X
+    end
+    # more than 64 constraint rows: the generic host arithmetic (workspace_gmrf.jl:280-284 on all columns at once)
+    sync_constraints!(b, nothing)
     Y = backend_backward_solve(d.workspace.backend, Z)
     Y .+= d.mean
-    if d.constraints !== nothing
-        ci = d.constraints
-        Y .-= ci.A_tilde_T * (ci.L_c \ (ci.matrix * Y .- ci.vector))
-    end
+    ci = d.constraints
+    Y .-= ci.A_tilde_T * (ci.L_c \ (ci.matrix * Y .- ci.vector))
     X .= Y
     return X
+end
+
+# ---- linear equality constraints on the device (include/gmrfx.h "linear equality constraints") ----------------------------------
+# The reference keeps A, e and what it derives from them in ConstraintInfo (src/workspace/workspace_gmrf.jl:22-56) and applies them on
+# the host. Here A and e become state of the handle (gmrfx_constraints_set: m <= 64 rows); A~' = Q^-1 A', W = A A~', L_c and
+# B = A~' L_c^-T are built on the device once per factorisation, and the corrections of `_rand!` (:280-284) and `var` (:260-273) run there.
+const MAX_DEVICE_CONSTRAINTS = 64
+const CONSTRAINT_KEYS = WeakKeyDict{Any, UInt}()      # backend -> objectid of the ConstraintInfo its handle holds (0: none)
+
+function set_constraints!(b::MI355XBackend, A::AbstractMatrix, e::AbstractVector)
+    At = sparse(transpose(sparse(A)))                 # CSC of A' = CSR of A
+    cp = Vector{Int}(SparseArrays.getcolptr(At)); rv = Vector{Int}(rowvals(At)); nz = Vector{Float64}(nonzeros(At))
+    ev = Vector{Float64}(e)
+    size(A, 2) == b.n || throw(ArgumentError("Constraint matrix size $(size(A)) incompatible with workspace size $(b.n)"))
+    size(A, 1) == length(ev) || throw(ArgumentError("Constraint matrix rows $(size(A, 1)) != constraint vector length $(length(ev))"))
+    GC.@preserve cp rv nz ev check(ccall((:gmrfx_constraints_set, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}), b.h.ptr, size(A, 1), cp, rv, nz, 1, ev), b.h)
+    return nothing
+end
+function clear_constraints!(b::MI355XBackend)
+    check(ccall((:gmrfx_constraints_set, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}),
+        b.h.ptr, 0, C_NULL, C_NULL, C_NULL, 1, C_NULL), b.h)
+    return nothing
+end
+# the handle holds the constraint of `ci` (a ConstraintInfo, or nothing): set once per (backend, ConstraintInfo) pair
+function sync_constraints!(b::MI355XBackend, ci)
+    key = ci === nothing ? UInt(0) : objectid(ci)
+    get(CONSTRAINT_KEYS, b, UInt(0)) == key && return nothing
+    ci === nothing ? clear_constraints!(b) : set_constraints!(b, ci.matrix, ci.vector)
+    CONSTRAINT_KEYS[b] = key
+    return nothing
+end
+function constraint_info(b::MI355XBackend)
+    m = Ref{Int64}(0); ldw = Ref{Float64}(0); lda = Ref{Float64}(0); ms = Ref{Float64}(0)
+    check(ccall((:gmrfx_constraints_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Float64}, Ref{Float64}, Ref{Float64}),
+        b.h.ptr, m, ldw, lda, ms), b.h)
+    return (m = Int(m[]), logdet_W = ldw[], logdet_AAt = lda[], ms = ms[])
+end
+# (A_tilde_T, W): the fields of ConstraintInfo; L_c = cholesky(Symmetric(W))
+function constraint_fields(b::MI355XBackend)
+    m = constraint_info(b).m
+    At = Matrix{Float64}(undef, b.n, m); W = Matrix{Float64}(undef, m, m)
+    GC.@preserve At W check(ccall((:gmrfx_constraints_get, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}),
+        b.h.ptr, At, b.n, W), b.h)
+    return At, W
+end
+function constrained_mean(b::MI355XBackend, mu::Vector{Float64})
+    out = Vector{Float64}(undef, b.n); lc = Ref{Float64}(0)
+    GC.@preserve mu out check(ccall((:gmrfx_constraints_mean, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+        b.h.ptr, mu, out, lc), b.h)
+    return out, lc[]
+end
+function constraint_correct!(b::MI355XBackend, X::StridedVecOrMat{Float64})
+    GC.@preserve X check(ccall((:gmrfx_constraints_correct, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64),
+        b.h.ptr, X, X isa AbstractVector ? b.n : stride(X, 2), size(X, 2)), b.h)
+    return X
+end
+function constrained_var(b::MI355XBackend)
+    out = Vector{Float64}(undef, b.n)
+    GC.@preserve out check(ccall((:gmrfx_constraints_var, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h.ptr, out), b.h)
+    return out
+end
+# `_rand!` on given draws: X = P' L^-T Z + mean, then the constraint correction when the handle holds one
+function sample(b::MI355XBackend, Z::Matrix{Float64}, mean::Union{Nothing, Vector{Float64}} = nothing)
+    X = similar(Z)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve Z X mean check(ccall((:gmrfx_sample, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64),
+        b.h.ptr, Z, stride(Z, 2), size(Z, 2), mu, X, stride(X, 2)), b.h)
+    return X
+end
+# var(d) (workspace_gmrf.jl:260-273) with the subtraction of rowsum(B^2) on the device; more than 64 rows: the reference's method
+function G.var(d::G.WorkspaceGMRF{<:Any, MI355XBackend})
+    G.ensure_loaded!(d)
+    G.ensure_numeric!(d.workspace)
+    b = d.workspace.backend
+    if d.constraints !== nothing && size(d.constraints.matrix, 1) > MAX_DEVICE_CONSTRAINTS
+        return invoke(G.var, Tuple{G.WorkspaceGMRF}, d)
+    end
+    sync_constraints!(b, d.constraints)
+    return constrained_var(b)
 end
 
 ordering_permutation(b::MI355XBackend) = (p = Vector{Int}(undef, b.n);

@@ -418,6 +418,52 @@ int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const double *d_nzva
                                            const double *d_mu, double *quad /* host, nvec x nbatch */, double *logdet /* host, nbatch */,
                                            int64_t *info /* host, nbatch, nullable */);
 
+/* ---- linear equality constraints A x = e, computed on the device -----------------------------------------------------------------
+ * Conditioning by kriging (Rue & Held 2005, section 2.3.3) as `ConstraintInfo` / `WorkspaceGMRF` do it on the host,
+ * src/workspace/workspace_gmrf.jl:22-56 (the blocked solve A~' = Q^-1 A', the m x m Cholesky L_c of W = A A~', the constrained mean and
+ * the log-density correction), :260-273 (variance correction), :280-284 (per-sample correction). A constraint is STATE of a handle,
+ * like the prior of the Newton loop: set once, everything derived from it is computed lazily on the device once per factorisation
+ * (zero + scatter of A' on the device, ONE blocked solve through the gmrfx_solve_dev path -- gmrfx_stats.last_nrhs then reads m --,
+ * W by a deterministic reduction, L_c and L_c^-1 on the host, B = A~' L_c^-T on the device), kept there (A~' and B, 2 x 8 n m bytes)
+ * and dropped by every refactorisation, like the selected-inverse cache. A handle without constraints behaves exactly as before.
+ * LIMIT: m <= 64 rows -- the blocked solve is then one sweep pass and the m x m operands of the correction kernels live in LDS.
+ * Callers with more rows keep their host path. Every sum is formed in a fixed order without atomics: results are bit-reproducible
+ * from run to run and do not depend on leading dimensions or on the alignment of the caller's arrays.
+ *
+ * gmrfx_constraints_set: A as m sparse rows (CSR arrays = the CSC arrays of A', what `sparse(A')` holds), e: m values; duplicates within
+ *   a row are summed; m = 0 removes the constraint. The handle keeps A (on the device with 32-bit columns), e and the host-computed
+ *   log det(A A') (:51). GMRFX_ERR_INVALID_ARG with a message and NOTHING changed for: a column outside [0, n), a non-monotone rowptr,
+ *   m > 64, an empty row, a batched handle (gmrfx_batch_size > 1), a sharded handle. Works on symbolic_only handles (validation;
+ *   numeric use there returns GMRFX_ERR_NO_DEVICE). gmrfx_clone carries A and e; the clone recomputes what is derived.
+ * gmrfx_constraints_info: *m (0 without a constraint, the other outputs are then 0), *logdet_AAt, and -- these two trigger the
+ *   preparation when they are asked for (non-null) -- *logdet_W = log det(A Q^-1 A') = logdet(L_c) (:50) and *ms = GPU time of the most
+ *   recent preparation. Any pointer may be NULL. gmrfx_stats is unchanged.
+ * gmrfx_constraints_get: host copies of A~' (n x m column-major, leading dimension ld) and W (m x m), either nullable: the fields
+ *   A_tilde_T and L_c (= cholesky(Symmetric(W))) of the Julia ConstraintInfo (:37-40).
+ * gmrfx_constraints_mean: mean_c = mu - A~' W^-1 (A mu - e) (:43-44; mu NULL = 0, mean_c nullable) and *log_correction =
+ *   0.5 (m log 2 pi + log det W + r' W^-1 r) - 0.5 log det(A A'), r = e - A mu (:46-51). Host arrays.
+ * gmrfx_constraints_correct(_dev): in place X <- X - A~' W^-1 (A X - e) on all nvec >= 1 columns (column-major, ldx >= n): :280-284
+ *   applied to a block. A no-op without a constraint.
+ * gmrfx_constraints_var: out[i] = max(Sigma_ii - sum_j B_ij^2, 0), B = A~' L_c^-T (:260-273); uses the cached selected inverse and
+ *   computes it if absent. Without a constraint: gmrfx_selinv_diag, bit for bit.
+ * gmrfx_sample(_dev): `_rand!` (:275-286) in one call: X = P' L^-T Z + mu (mu nullable, n values), then the correction when a
+ *   constraint is set. Without a constraint and with mu = NULL the result has the bits of gmrfx_backward_solve(_dev).
+ * Errors: GMRFX_ERR_NOT_FACTORIZED before the first factorisation; GMRFX_ERR_NOT_POSDEF when W is not positive definite -- a
+ *   rank-deficient A, where the reference throws PosDefException from cholesky (:40); a pivot below 16 m eps W_jj counts as zero.
+ *   The handle stays usable. */
+int32_t gmrfx_constraints_set(gmrfx_handle *h, int64_t m, const int64_t *rowptr, const int64_t *colind, const double *values,
+                              int32_t index_base, const double *e);
+int32_t gmrfx_constraints_info(gmrfx_handle *h, int64_t *m, double *logdet_W, double *logdet_AAt, double *ms);
+int32_t gmrfx_constraints_get(gmrfx_handle *h, double *A_tilde_T /* n x m, nullable */, int64_t ld, double *W /* m x m, nullable */);
+int32_t gmrfx_constraints_mean(gmrfx_handle *h, const double *mu /* n, nullable = 0 */, double *mean_c /* n, nullable */,
+                               double *log_correction /* nullable */);
+int32_t gmrfx_constraints_correct(gmrfx_handle *h, double *X, int64_t ldx, int64_t nvec);
+int32_t gmrfx_constraints_correct_dev(gmrfx_handle *h, double *d_X, int64_t ldx, int64_t nvec);
+int32_t gmrfx_constraints_var(gmrfx_handle *h, double *out /* n */);
+int32_t gmrfx_sample(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t nrhs, const double *mu /* nullable */, double *X, int64_t ldx);
+int32_t gmrfx_sample_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t nrhs, const double *d_mu /* nullable */, double *d_X,
+                         int64_t ldx);
+
 /* KL-optimal sparse approximate Cholesky factor, L L' ~ Theta^-1: a batch of small dense problems, one
  * workgroup each. A task = local rows R (task_rows[task_rowptr[t] .. task_rowptr[t+1]), in the caller's local order)
  * + the columns of L it fills (task_cols[task_colptr[t] ..)): M = Theta[R, R] + reg I = U'U, and for every member

@@ -60,7 +60,32 @@ static void one_handle(const std::vector<int64_t> &cp, const std::vector<int64_t
     // a second handle with the first one's permutation (user-permutation path), cloned and destroyed
     gmrfx_handle *h2 = nullptr, *h3 = nullptr;
     EXPECT(gmrfx_create(n, cp.data(), ri.data(), 0, perm.data(), &o, &h2) == GMRFX_OK);
-    if (h2) { EXPECT(gmrfx_clone(h2, &h3) == GMRFX_OK); gmrfx_destroy(h3); gmrfx_destroy(h2); }
+    if (h2) {
+        // linear equality constraints on a symbolic handle: the host side of gmrfx_constraints_set (sorting, summed duplicates,
+        // log det(A A')), each refused form, and the copy a clone carries
+        std::vector<int64_t> rp = {0, n, n + 3}, ci((size_t)n + 3);
+        std::vector<double> va((size_t)n + 3, 1.0), e = {0.0, 1.0};
+        for (int64_t j = 0; j < n; j++) ci[(size_t)j] = n - 1 - j;
+        ci[(size_t)n] = 2; ci[(size_t)n + 1] = 0; ci[(size_t)n + 2] = 2;
+        int64_t m = -1;
+        double lda = 0, ldw = 0;
+        EXPECT(gmrfx_constraints_set(h2, 2, rp.data(), ci.data(), va.data(), 0, e.data()) == GMRFX_OK);
+        EXPECT(gmrfx_constraints_info(h2, &m, nullptr, &lda, nullptr) == GMRFX_OK && m == 2 && lda > 0);
+        EXPECT(gmrfx_constraints_info(h2, &m, &ldw, nullptr, nullptr) == GMRFX_ERR_NO_DEVICE);
+        EXPECT(gmrfx_constraints_var(h2, va.data()) == GMRFX_ERR_NO_DEVICE);
+        ci[1] = n;
+        EXPECT(gmrfx_constraints_set(h2, 2, rp.data(), ci.data(), va.data(), 0, e.data()) == GMRFX_ERR_INVALID_ARG);
+        std::vector<int64_t> rp2 = {0, 2, 2}, rp3 = {0, 2, 1};
+        EXPECT(gmrfx_constraints_set(h2, 2, rp2.data(), ci.data() + n, va.data(), 0, e.data()) == GMRFX_ERR_INVALID_ARG);
+        EXPECT(gmrfx_constraints_set(h2, 2, rp3.data(), ci.data() + n, va.data(), 0, e.data()) == GMRFX_ERR_INVALID_ARG);
+        EXPECT(gmrfx_constraints_set(h2, 65, rp.data(), ci.data(), va.data(), 0, e.data()) == GMRFX_ERR_INVALID_ARG);
+        EXPECT(gmrfx_constraints_info(h2, &m, nullptr, nullptr, nullptr) == GMRFX_OK && m == 2);
+        EXPECT(gmrfx_clone(h2, &h3) == GMRFX_OK);
+        if (h3) EXPECT(gmrfx_constraints_info(h3, &m, nullptr, nullptr, nullptr) == GMRFX_OK && m == 2);
+        EXPECT(gmrfx_constraints_set(h2, 0, nullptr, nullptr, nullptr, 0, nullptr) == GMRFX_OK);
+        EXPECT(gmrfx_constraints_info(h2, &m, nullptr, nullptr, nullptr) == GMRFX_OK && m == 0);
+        gmrfx_destroy(h3); gmrfx_destroy(h2);
+    }
     gmrfx_destroy(h);
 }
 
