@@ -452,7 +452,7 @@ static const int OBK = 4;   // 64-column blocks per outer (256-column) block of 
 static inline int level_max_trail(const LevelInfo &L) { return L.active.back(); }
 static inline int level_nblk(const LevelInfo &L) { return (int)L.active.size() - 2; }
 
-void Device::factor_levels(int lo, int hi) {
+void Device::factor_levels(int lo, int hi, bool record_level_events) {
     if (lo == 0) {
         const int big = INT_MAX;
         HC(hipMemcpyAsync(d_info_, &big, sizeof(int), hipMemcpyHostToDevice, stream));
@@ -477,7 +477,7 @@ void Device::factor_levels(int lo, int hi) {
     int nsy = (int)syrk_launches;
     for (int lev = lo; lev < hi; lev++) {
         auto &L = levels_[lev];
-        if (level_mark_) { launch_level_mark(stream, 3, lev); level_event(0, lev); }
+        if (level_mark_) { launch_level_mark(stream, 3, lev); level_event(stream, 0, lev); }
         const int *list = d_levellist_ + L.first + L.nsmall;
         const int nf = L.count - L.nsmall;
         // The small fronts of a level (fused one-workgroup kernels) and its big fronts (assembly -> panel chain -> SYRK)
@@ -582,11 +582,11 @@ void Device::factor_levels(int lo, int hi) {
             HC(hipEventRecord(ev_done1_, stream3));
             HC(hipStreamWaitEvent(stream, ev_done1_, 0));
         }
-        if (fused_) HC(hipEventRecord(ev_flevel_[lev], stream));      // the panels of this level are final: its sweep may start
+        if (record_level_events) HC(hipEventRecord(ev_flevel_[lev], stream));      // the panels of this level are final: its sweep may start
     }
     syrk_launches = nsy;
     if (lo == 0 && nzp_pending_) { HC(hipStreamWaitEvent(stream, ev_nzp_, 0)); nzp_pending_ = false; }     // (see above)
-    if (level_mark_) level_event(0, hi);
+    if (level_mark_) level_event(stream, 0, hi);
 }
 
 // The dense inverses are only needed by the sweeps and the selected inversion of the big
@@ -605,7 +605,7 @@ void Device::start_inverse_async() {
     inverse_pending = false;
     inverse_full_ = inv_maxc_ <= inv_cap_;
 }
-void Device::wait_inverse() { HC(hipStreamWaitEvent(stream, ev_inv_, 0)); }
+void Device::wait_inverse(hipStream_t st) { HC(hipStreamWaitEvent(st, ev_inv_, 0)); }
 
 // Called behind the synchronisation of a factorisation, before anything reads the inverses (see device.h).
 void Device::decide_inverse_cap() {
@@ -676,114 +676,89 @@ void Device::refactorize_solve(const double *nzval, bool nz_on_device, const dou
         host_upload_values(nzval);
         src = d_nz_;
     }
-    nz_held_ = (src == d_nz_);
-    nz_src_ = src;
     ensure_rhs_capacity(nrhs);
     const double *dB = B;
     double *dXo = X;
     long long ldin = ldb, ldout = ldx_out;
     if (!b_on_device) {
-        const long long need = n * nrhs;
-        if (need > io_cap_) { const long long cap = std::max(need, 2 * io_cap_); d_io_ = dregrow(d_io_, (size_t)cap); io_cap_ = cap; }
+        ensure_io(n * nrhs);
         dB = d_io_; dXo = d_io_; ldin = n; ldout = n;
     }
     while ((int)ev_flevel_.size() < nl + 1) { hipEvent_t e; HC(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_flevel_.push_back(e); }
-    factor_serial_++;
     // host right-hand sides: in FRONT of the factorisation (see the measurements above host_upload): the transfers are serial --
     // B in, the pipelined step, X out -- never beside the factorisation
     if (!b_on_device) {
         host_upload(B, ldb, nrhs, d_io_);
         HC(hipStreamWaitEvent(stream, ev_up_, 0));
     }
-    HC(hipEventRecord(ev_[0], stream));
+    begin_factor(src);
     HC(hipEventRecord(ev_ready_, stream));                 // the side stream starts behind the uploads / whatever precedes this call
-    struct Flag { bool &f; ~Flag() { f = false; } } f1{fused_}, f2{fused_fwd_};
-    fused_ = true;
-    factor_levels(0, nl);
-    fused_ = false;
-    HC(hipEventRecord(ev_[1], stream));
-    HC(hipEventRecord(ev_fact_, stream));
-    fact_event_valid_ = true;
-    HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
-    factorized = true;
-    selinv_valid = false;
+    factor_levels(0, nl, true);
+    enqueue_factor_tail();
     // ---- first pass (pass_width(): up to 64 columns, 16 for 17 .. 32 right-hand sides -- the widths solve() uses, so that the two
     // forms of the step give the same bits): forward sweep on the side stream, behind the level events
     const int PW = pass_width(nrhs);
     const int nr = (int)std::min<long long>(PW, nrhs), ldx = nr;
     hipEvent_t *ev = ev_lane_[0];
-    {
-        const hipStream_t main_stream = stream;
-        struct Restore { Device &D; hipStream_t st; ~Restore() { D.stream = st; } } restore{*this, main_stream};
-        stream = stream2;
-        HC(hipStreamWaitEvent(stream, ev_ready_, 0));
-        if (!b_on_device) HC(hipStreamWaitEvent(stream, ev_up_, 0));
-        HC(hipEventRecord(ev[0], stream));
-        launch_permute(stream, d_iperm_, (int)n, const_cast<double *>(dB), ldin, d_X_, nr, ldx, 0);
-        HC(hipEventRecord(ev[1], stream));
-        fused_fwd_ = true;
-        forward(nr, ldx, 0, nl);
-        fused_fwd_ = false;
-        HC(hipEventRecord(ev_inv_, stream));             // every level's inverses exist: later solves pass wait_inverse() at once
-        HC(hipEventRecord(ev[2], stream));
-    }
+    // lane 0's buffers on the side stream for the forward half, on the main stream for the rest
+    const SweepLane ln0 = lane(0), side{stream2, ln0.X, ln0.X2, ln0.W};
+    HC(hipStreamWaitEvent(side.st, ev_ready_, 0));
+    if (!b_on_device) HC(hipStreamWaitEvent(side.st, ev_up_, 0));
+    HC(hipEventRecord(ev[0], side.st));
+    launch_permute(side.st, d_iperm_, (int)n, const_cast<double *>(dB), ldin, side.X, nr, ldx, 0);
+    HC(hipEventRecord(ev[1], side.st));
+    forward(side, nr, ldx, 0, nl, true);
+    HC(hipEventRecord(ev_inv_, side.st));                // every level's inverses exist: later solves pass wait_inverse() at once
+    HC(hipEventRecord(ev[2], side.st));
     inverse_pending = false;
     inverse_full_ = inv_maxc_ <= inv_cap_;
     enqueue_logdet(stream2, false);                     // behind the forward sweep on the side stream: beside the backward sweep
     HC(hipStreamWaitEvent(stream, ev[2], 0));
-    backward(nr, ldx, true, nl, 0);
+    backward(ln0, nr, ldx, true, nl, 0);
     HC(hipEventRecord(ev[3], stream));
-    launch_permute(stream, d_iperm_, (int)n, dXo, ldout, d_X_, nr, ldx, 1);
+    launch_permute(stream, d_iperm_, (int)n, dXo, ldout, ln0.X, nr, ldx, 1);
     HC(hipEventRecord(ev[4], stream));
-    // ---- further passes: the factor is complete, plain sweeps on the main stream
-    for (long long j0 = PW; j0 < nrhs; j0 += PW) {
-        const int nr2 = (int)std::min<long long>(PW, nrhs - j0);
-        launch_permute(stream, d_iperm_, (int)n, const_cast<double *>(dB) + j0 * ldin, ldin, d_X_, nr2, nr2, 0);
-        forward(nr2, nr2, 0, nl);
-        backward(nr2, nr2, true, nl, 0);
-        launch_permute(stream, d_iperm_, (int)n, dXo + j0 * ldout, ldout, d_X_, nr2, nr2, 1);
-    }
+    // ---- further passes: the factor is complete, plain sweeps on the main stream (no per-pass events)
+    for (long long j0 = PW; j0 < nrhs; j0 += PW)
+        sweep_pass(ln0, nullptr, dB + j0 * ldin, ldin, dXo + j0 * ldout, ldout, (int)std::min<long long>(PW, nrhs - j0), 0, nullptr);
     HC(hipEventRecord(ev_lane_[1][0], stream));
     if (!b_on_device) host_download(d_io_, nrhs, X, ldx_out, stream);
     HC(hipStreamSynchronize(stream));
-    info_cached_ = true;
-    HC(hipGetLastError());
-    float tf = 0, a = 0, b = 0, c = 0, d = 0, tail = 0;
-    HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
+    finish_factor();                                    // (the inverse cap was decided before this call could be taken)
+    float a = 0, b = 0, c = 0, d = 0, tail = 0;
     HC(hipEventElapsedTime(&a, ev[0], ev[1]));
     HC(hipEventElapsedTime(&b, ev_[1], ev[2]));          // what is left of the forward sweep once the factor is complete
     HC(hipEventElapsedTime(&c, ev[2], ev[3]));
     HC(hipEventElapsedTime(&d, ev[3], ev[4]));
     HC(hipEventElapsedTime(&tail, ev_[1], ev_lane_[1][0]));
-    ms_factor = tf;
     ms_perm = a + d; ms_fwd = std::max(b, 0.0f); ms_bwd = b >= 0 ? c : c + b;
     ms_solve = tail;                                     // device time behind the factorisation: ms_factor + ms_solve = the step
-    syrk_times_pending_ = true;
     last_nrhs = nrhs;
 }
 
-void Device::refactorize(const double *nzval, bool on_device) {
-    HC(hipSetDevice(device));
-    const double *src = nzval;
-    if (!on_device) {
-        HC(hipMemcpyAsync(d_nz_, nzval, (size_t)S_->nnz_in * sizeof(double), hipMemcpyHostToDevice, stream));
-        src = d_nz_;
-    }
-    nz_held_ = (src == d_nz_);
-    // a device-resident nzval is read in place (the Q scatter happens inside the assembly kernels, and
-    // this call only returns once they have finished): no private copy
-    nz_src_ = src;
-    if (sharded()) throw std::invalid_argument("sharded handle: use gmrfx_refactorize_phase (two phases with an exchange in between)");
+// ---- what every numeric factorisation of an unsharded handle shares (refactorize, refactorize_solve, refactorize_logpdf,
+// batch_refactorize_logpdf): begin_factor -> factor_levels -> enqueue_factor_tail -> [whatever else the call enqueues] -> the
+// call's ONE synchronisation -> finish_factor. The caller says what becomes of the dense inverses (inverse_pending, or complete).
+// d_src: Q's values on the device (d_nz_ or the caller's buffer). A caller's buffer is read in place (the Q scatter happens
+// inside the assembly kernels, and the call only returns once they have finished): no private copy.
+void Device::begin_factor(const double *d_src) {
+    nz_src_ = d_src;
+    nz_held_ = (d_src == d_nz_);
     factor_serial_++;
     HC(hipEventRecord(ev_[0], stream));
-    factor_levels(0, (int)levels_.size());
+}
+// behind the last level: the timing / "factor is final" events, and the pivot report on its way to the pinned host word (it
+// travels with the factorisation: no blocking copy after the synchronisation)
+void Device::enqueue_factor_tail() {
     HC(hipEventRecord(ev_[1], stream));
     HC(hipEventRecord(ev_fact_, stream));
     fact_event_valid_ = true;
-    inverse_pending = true;
-    // the pivot report travels with the factorisation (pinned host word): no blocking copy after the synchronisation
     HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
-    HC(hipStreamSynchronize(stream));
+}
+// behind the synchronisation. `factorized` is set HERE for every caller, once the synchronisation has succeeded: a call that
+// throws on the way leaves the handle as it found it. (decide_inverse_cap returns at once when the cap is decided -- always so in
+// the pipelined call.)
+void Device::finish_factor() {
     info_cached_ = true;
     HC(hipGetLastError());
     decide_inverse_cap();
@@ -793,6 +768,22 @@ void Device::refactorize(const double *nzval, bool on_device) {
     syrk_times_pending_ = true;      // the per-launch event times are only read when somebody asks for the statistics
     factorized = true;
     selinv_valid = false;
+}
+
+void Device::refactorize(const double *nzval, bool on_device) {
+    HC(hipSetDevice(device));
+    if (sharded()) throw std::invalid_argument("sharded handle: use gmrfx_refactorize_phase (two phases with an exchange in between)");
+    const double *src = nzval;
+    if (!on_device) {
+        HC(hipMemcpyAsync(d_nz_, nzval, (size_t)S_->nnz_in * sizeof(double), hipMemcpyHostToDevice, stream));
+        src = d_nz_;
+    }
+    begin_factor(src);
+    factor_levels(0, (int)levels_.size(), false);
+    enqueue_factor_tail();
+    inverse_pending = true;
+    HC(hipStreamSynchronize(stream));
+    finish_factor();
 }
 
 void Device::refactorize_phase(const double *d_nzval, int phase) {
@@ -808,11 +799,11 @@ void Device::refactorize_phase(const double *d_nzval, int phase) {
         nz_src_ = d_nzval;
         nz_held_ = false;       // the values live in the caller's device buffer
         factorized = false;
-        factor_levels(0, split);
+        factor_levels(0, split, false);
     } else {                        // top level split + phase - 1: the fronts of that level this rank owns
         const int lev = split + phase - 1;
         if (lev >= nl) throw std::invalid_argument("refactorize phase beyond the last level");
-        factor_levels(lev, lev + 1);
+        factor_levels(lev, lev + 1, false);
     }
     HC(hipEventRecord(ev_[1], stream));
     if (!async_phases_) {
@@ -909,8 +900,8 @@ void Device::set_prior(const double *prior_nzval, const long long *map, long lon
     if (cnt > 0) HC(hipMemcpyAsync(d_hmap_, map, (size_t)cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
     HC(hipStreamSynchronize(stream));
 }
-void Device::refactorize_update(const double *h, bool on_device) {
-    HC(hipSetDevice(device));
+// the Hessian values to the device (when they are the host's), then d_nz_ = prior, d_nz_[map[k]] -= h[k]
+void Device::newton_values(const double *h, bool on_device) {
     if (!d_prior_) throw std::invalid_argument("gmrfx_set_prior has not been called");
     const double *dh = h;
     if (!on_device && hmap_cnt_ > 0) {
@@ -918,6 +909,10 @@ void Device::refactorize_update(const double *h, bool on_device) {
         dh = d_h_;
     }
     launch_newton_update(stream, d_prior_, d_nz_, S_->nnz_in, d_hmap_, dh, hmap_cnt_);
+}
+void Device::refactorize_update(const double *h, bool on_device) {
+    HC(hipSetDevice(device));
+    newton_values(h, on_device);
     refactorize(d_nz_, true);
 }
 
@@ -926,13 +921,7 @@ void Device::refactorize_update(const double *h, bool on_device) {
 void Device::refactorize_update_solve(const double *h, bool h_on_device, const double *B, long long ldb, long long nrhs, double *X, long long ldx,
                                       bool b_on_device) {
     HC(hipSetDevice(device));
-    if (!d_prior_) throw std::invalid_argument("gmrfx_set_prior has not been called");
-    const double *dh = h;
-    if (!h_on_device && hmap_cnt_ > 0) {
-        HC(hipMemcpyAsync(d_h_, h, (size_t)hmap_cnt_ * sizeof(double), hipMemcpyHostToDevice, stream));
-        dh = d_h_;
-    }
-    launch_newton_update(stream, d_prior_, d_nz_, S_->nnz_in, d_hmap_, dh, hmap_cnt_);
+    newton_values(h, h_on_device);
     refactorize_solve(d_nz_, true, B, ldb, nrhs, X, ldx, b_on_device);
 }
 
@@ -976,76 +965,84 @@ void Device::ensure_rhs_capacity(long long nrhs) {
     }
 }
 
+// the staging buffer of host right-hand sides (solve, refactorize_solve): grown geometrically
+void Device::ensure_io(long long need) {
+    if (need <= io_cap_) return;
+    const long long cap = std::max(need, 2 * io_cap_);
+    d_io_ = dregrow(d_io_, (size_t)cap);
+    io_cap_ = cap;
+}
+
 // The bottom subtrees. Up to wave_max_nr_ (16) right-hand sides: one wave per (task, 16 columns), sweep_wave.hip, biggest LDS
 // class first; wider passes: the chunk form, four waves per (task, 16 columns), sweep_chunk.hip. Measured at cfg 2, round 5
 // (tools/nrhs_sweep.py, ms per solve, wave form / chunk form): 1 RHS 2.88 / 3.22, 16: 3.00 / 3.36, 32: 3.71 / 3.47, 64: - / 3.90 at the
 // time of the choice; with the narrow level kernels and the local vector as wide as the pass: 1 RHS 1.65, 16: 2.28.
 // GMRFX_TASK_MODE = wg / wave forces one form.
-void Device::sweep_tasks(int phase, int nr, int ldx) {
+void Device::sweep_tasks(const SweepLane &ln, int phase, int nr, int ldx, bool follows_factor) {
     if (nr > wave_max_nr_) {
         // pipelined call: the forward task kernel runs beside the top of the factorisation -- TWO resident workgroups per CU
         // instead of four (16 KB of unused dynamic LDS on top of its 40 KB), so that the panel chain's kernels find LDS
         // (measured at cfg 2, round 5: pad 0 / 8 / 16 / 42 KB -> step 12.59 / 12.61 / 12.38 / 12.91 ms)
         constexpr int pad_kb = 16;
-        const size_t extra = (fused_fwd_ && phase == 1) ? (size_t)pad_kb * 1024 : 0;
-        ensure_dtile();
-        launch_sweep_chunks(stream, ds_, phase, d_swt_, nswt_, d_swc_fwd_, d_swc_bwd_, d_swc_listf_, d_swc_listb_, d_dtile_, d_L_, d_X_,
-                            phase == 1 ? d_W_ : nullptr, nr, ldx, extra);
+        const size_t extra = (follows_factor && phase == 1) ? (size_t)pad_kb * 1024 : 0;
+        ensure_dtile(ln.st);
+        launch_sweep_chunks(ln.st, ds_, phase, d_swt_, nswt_, d_swc_fwd_, d_swc_bwd_, d_swc_listf_, d_swc_listb_, d_dtile_, d_L_, ln.X,
+                            phase == 1 ? ln.W : nullptr, nr, ldx, extra);
         return;
     }
-    ensure_rdiag();
+    ensure_rdiag(ln.st);
     if (nr <= 4) {      // the local vector of such a pass is 9 KB at most whatever the class: one launch, no tail of the big class before the small one starts
-        launch_wave_tasks(stream, ds_, phase, d_swt_, d_wave_order_ + nswt_, nswt_, kWaveRows[kWaveClasses - 1], d_L_, d_rdiag_, d_rdiag_ + S_->n, d_X_,
-                          d_W_, nr, ldx);
+        launch_wave_tasks(ln.st, ds_, phase, d_swt_, d_wave_order_ + nswt_, nswt_, kWaveRows[kWaveClasses - 1], d_L_, d_rdiag_, d_rdiag_ + S_->n, ln.X,
+                          ln.W, nr, ldx);
         return;
     }
     for (int k = kWaveClasses - 1; k >= 0; k--)
-        launch_wave_tasks(stream, ds_, phase, d_swt_, d_wave_order_ + wave_first_[k], wave_count_[k], kWaveRows[k], d_L_, d_rdiag_,
-                          d_rdiag_ + S_->n, d_X_, d_W_, nr, ldx);
+        launch_wave_tasks(ln.st, ds_, phase, d_swt_, d_wave_order_ + wave_first_[k], wave_count_[k], kWaveRows[k], d_L_, d_rdiag_,
+                          d_rdiag_ + S_->n, ln.X, ln.W, nr, ldx);
 }
 
-// 1 / L_jj (+ the zero word masked operand elements are read from), once per factorisation, on the current `stream`:
-// solve() calls this BEFORE its lanes fork, so that a second lane never reads it half-written
-void Device::ensure_rdiag() {
+// 1 / L_jj (+ the zero word masked operand elements are read from), once per factorisation, on stream st:
+// solve() calls this on the main stream BEFORE its lanes fork, so that a second lane never reads it half-written
+void Device::ensure_rdiag(hipStream_t st) {
     if (wave_max_nr_ <= 0 || nswt_ <= 0) return;
     if (!d_rdiag_) { d_rdiag_ = dalloc<double>((size_t)S_->n + 2); rdiag_for_ = 0; }
     if (rdiag_for_ == factor_serial_) return;
-    launch_rdiag(stream, d_L_, ds_.diagoff, (int)S_->n, d_rdiag_);
-    HC(hipMemsetAsync(d_rdiag_ + S_->n, 0, 2 * sizeof(double), stream));
+    launch_rdiag(st, d_L_, ds_.diagoff, (int)S_->n, d_rdiag_);
+    HC(hipMemsetAsync(d_rdiag_ + S_->n, 0, 2 * sizeof(double), st));
     rdiag_for_ = factor_serial_;
 }
 
-// the chunks' inverse diagonal blocks in MFMA operand order, once per factorisation, on the current `stream` (solve() calls
-// this BEFORE its lanes fork; the pipelined call behind the gate event, when the task fronts are final)
-void Device::ensure_dtile() {
+// the chunks' inverse diagonal blocks in MFMA operand order, once per factorisation, on stream st (solve() calls this on the
+// main stream BEFORE its lanes fork; the pipelined call on the side stream behind the gate event, when the task fronts are final)
+void Device::ensure_dtile(hipStream_t st) {
     if (nswc_ <= 0 || dtile_for_ == factor_serial_) return;
-    launch_pack_diag(stream, d_swc_bwd_, nswc_, d_L_, d_dtile_);      // (the backward records hold every chunk once)
+    launch_pack_diag(st, d_swc_bwd_, nswc_, d_L_, d_dtile_);      // (the backward records hold every chunk once)
     dtile_for_ = factor_serial_;
 }
 
-void Device::forward(int nr, int ldx, int lo, int hi) {
-    if (level_mark_ && lo == 0) { launch_level_mark(stream, 1, -1); level_event(1, 0); }
+void Device::forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor) {
+    if (level_mark_ && lo == 0) { launch_level_mark(ln.st, 1, -1); level_event(ln.st, 1, 0); }
     // pipelined factor + solve (refactorize_solve): the bottom waits for the highest level a task / subtree reaches, every level
     // above for its own "factored" event; the dense inverses are built level by level instead of all at once
-    if (fused_fwd_) {
-        HC(hipStreamWaitEvent(stream, ev_flevel_[fused_gate_level_], 0));
+    if (follows_factor) {
+        HC(hipStreamWaitEvent(ln.st, ev_flevel_[fused_gate_level_], 0));
         if (nr <= wave_max_nr_ && nswt_ > 0) rdiag_for_ = 0;      // 1 / L_jj of the task fronts: their diagonals are final now, the rest is never read
         dtile_for_ = 0;                                            // (the same for the chunks' inverse diagonal blocks)
     }
-    if (lo == 0) sweep_tasks(1, nr, ldx);
+    if (lo == 0) sweep_tasks(ln, 1, nr, ldx, follows_factor);
     if (lo == 0)
         for (int k = 0, off = 0; k < 3; off += nsub_cls_[k], k++)
-            launch_subtree(stream, ds_, 1, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
-                           nullptr, d_X_, d_W_, nr, ldx);
+            launch_subtree(ln.st, ds_, 1, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
+                           nullptr, ln.X, ln.W, nr, ldx);
     for (int lev = lo; lev < hi; lev++) {
         auto &L = swlevels_[lev];
-        if (level_mark_) { launch_level_mark(stream, 1, lev); level_event(1, 1 + lev); }
-        if (fused_fwd_) {
-            if (lev > fused_gate_level_) HC(hipStreamWaitEvent(stream, ev_flevel_[lev], 0));
-            invert_level(stream, lev);
-        } else if (lev == std::max(lo, first_multiblock_level_)) wait_inverse();
+        if (level_mark_) { launch_level_mark(ln.st, 1, lev); level_event(ln.st, 1, 1 + lev); }
+        if (follows_factor) {
+            if (lev > fused_gate_level_) HC(hipStreamWaitEvent(ln.st, ev_flevel_[lev], 0));
+            invert_level(ln.st, lev);
+        } else if (lev == std::max(lo, first_multiblock_level_)) wait_inverse(ln.st);
         for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++)
-            launch_fwd_small(stream, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, d_X_, d_W_, nr, ldx);
+            launch_fwd_small(ln.st, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, ln.X, ln.W, nr, ldx);
         const int *list = d_sw_levellist_ + L.first + L.nsmall;
         int nf = L.count - L.nsmall;
         // fronts of at most 128 columns (the tail of the list: sorted by decreasing width): the WHOLE step -- own rows assembled,
@@ -1056,13 +1053,13 @@ void Device::forward(int nr, int ldx, int lo, int hi) {
             const size_t kq = (size_t)std::min(bwd_front_max_cols(), inv_cap_) / NB;       // (a front needs its WHOLE inverse for this)
             const int nwide = kq + 1 < L.active.size() ? L.active[kq] : 0;
             if (nf - nwide >= fwd_front_min_) {
-                launch_fwd_front(stream, ds_, list + nwide, nf - nwide, d_L_, d_X_, d_X2_, d_W_, nr, ldx);
+                launch_fwd_front(ln.st, ds_, list + nwide, nf - nwide, d_L_, ln.X, ln.X2, ln.W, nr, ldx);
                 nf = nwide;
                 cmin_front = (int)kq * NB;       // the record-driven update below skips the fronts taken here (its records cover the level)
                 if (nf == 0) continue;
             }
         }
-        launch_fwd_assemble(stream, ds_, list, nf, L.max_cols, d_X_, d_W_, nr, ldx);   // own rows only
+        launch_fwd_assemble(ln.st, ds_, list, nf, L.max_cols, ln.X, ln.W, nr, ldx);   // own rows only
         // y = L11^-1 b as one triangular product per front (dense inverse, inverse.hip), then the
         // trailing update W -= L21 y with K = all columns of the front
         // y of the big fronts stays in X2 (no copy back): the update below and the backward sweep read it there
@@ -1071,8 +1068,8 @@ void Device::forward(int nr, int ldx, int lo, int hi) {
         for (int j = 0; j < nbk; j++) {
             // (nf: k_fwd_front may have taken the narrow tail of the list above -- block 0's count is "every big front" otherwise)
             const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-            launch_xmul(stream, ds_, list, na, L.max_cols, 0, d_L_, d_X_, d_X2_, nr, ldx, j, inv_cap_);
-            if (j + 1 < nbk) launch_fwd_own_update(stream, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, d_X2_, d_X_, nr, ldx, j, inv_cap_);
+            launch_xmul(ln.st, ds_, list, na, L.max_cols, 0, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
+            if (j + 1 < nbk) launch_fwd_own_update(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X2, ln.X, nr, ldx, j, inv_cap_);
         }
         // levels with many tiles: record-driven, per-XCD runs; the handful-of-fronts levels keep the 16-row latency variant
         // Passes of at most 16 right-hand sides: the fronts up to kFwdWaveCols columns wide go one WAVE per 32-row tile (no LDS, no
@@ -1082,30 +1079,30 @@ void Device::forward(int nr, int ldx, int lo, int hi) {
         const int cwave = syrk_xcd_ && nr <= narrow_pass_max() ? kFwdWaveCols : 0;
         const int cmin = std::max(cwave, cmin_front);          // fronts up to this width are not the split-K kernels' (wave kernel / k_fwd_front)
         const int nwider = (size_t)(kFwdWaveCols / NB + 1) < L.active.size() ? L.active[kFwdWaveCols / NB] : 0;      // fronts wider than that
-        if (cwave > 0 && nwider < nf) launch_fwd_update_wave(stream, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, d_X2_, d_W_, nr, ldx, cwave,
+        if (cwave > 0 && nwider < nf) launch_fwd_update_wave(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, cwave,
                                                               L.max_cols > launch_wave_split_cols());
         if (L.max_cols > cmin) {
             if (syrk_xcd_ && (long long)((level_max_trail(L) + 31) / 32) * nf > 128)
-                launch_fwd_update_recs(stream, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, d_X2_, d_W_, nr, ldx, cmin);
+                launch_fwd_update_recs(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, cmin);
             else
-                launch_fwd_update(stream, ds_, list, nf, level_max_trail(L), d_L_, d_X2_, d_W_, nr, ldx, cmin);
+                launch_fwd_update(ln.st, ds_, list, nf, level_max_trail(L), d_L_, ln.X2, ln.W, nr, ldx, cmin);
         }
     }
-    if (level_mark_) level_event(1, 1 + hi);
+    if (level_mark_) level_event(ln.st, 1, 1 + hi);
 }
 
 // y_in_x2: the forward sweep left y of the big fronts in X2 (full solve). The backward sweep then turns it
 // into t = y - L21' x in place there and writes x = L11^-T t straight into X -- no copies. A backward-only
 // solve (F.UP \ z) gets z in X: classic path with one copy per level.
-void Device::backward(int nr, int ldx, bool y_in_x2, int hi, int lo) {
-    wait_inverse();   // (a no-op event wait once the forward sweep has passed it)
+void Device::backward(const SweepLane &ln, int nr, int ldx, bool y_in_x2, int hi, int lo) {
+    wait_inverse(ln.st);   // (a no-op event wait once the forward sweep has passed it)
     for (int l = hi - 1; l >= lo; l--) {
         auto &L = swlevels_[l];
-        if (level_mark_) { launch_level_mark(stream, 2, l); level_event(2, (int)levels_.size() - 1 - l); }
+        if (level_mark_) { launch_level_mark(ln.st, 2, l); level_event(ln.st, 2, (int)levels_.size() - 1 - l); }
         const int *list = d_sw_levellist_ + L.first + L.nsmall;
         int nf = L.count - L.nsmall;
         for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++)
-            launch_bwd_small(stream, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, d_X_, nr, ldx);
+            launch_bwd_small(ln.st, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, ln.X, nr, ldx);
         // fronts of at most 128 columns (the tail of the list: sorted by decreasing width): the whole step as one workgroup and
         // one launch (sweep_front.hip); in place when y sits in X (own rows are read and written by their front alone)
         // Only on levels with enough such fronts to fill the chip: a workgroup walks its front's trailing rows batch after batch,
@@ -1120,51 +1117,51 @@ void Device::backward(int nr, int ldx, bool y_in_x2, int hi, int lo) {
             const size_t kq = (size_t)std::min(bwd_front_max_cols(), inv_cap_) / NB;
             const int nwide = kq + 1 < L.active.size() ? L.active[kq] : 0;   // fronts with more than kq NB columns (the last entry of `active` is the stash of level_max_trail)
             if (nf - nwide >= bwd_front_min_) {
-                launch_bwd_front(stream, ds_, list + nwide, nf - nwide, d_L_, d_X_, y_in_x2 ? d_X2_ : d_X_, d_X_, nr, ldx);
+                launch_bwd_front(ln.st, ds_, list + nwide, nf - nwide, d_L_, ln.X, y_in_x2 ? ln.X2 : ln.X, ln.X, nr, ldx);
                 nf = nwide;
                 if (nf == 0) continue;
             }
         }
         const int nbk = std::max(1, (L.max_cols + inv_cap_ - 1) / inv_cap_);
-        double *const Xt = y_in_x2 ? d_X2_ : d_X_;
+        double *const Xt = y_in_x2 ? ln.X2 : ln.X;
         const int mmin = narrow ? kBwdWaveRows : 0;
-        if (narrow && level_max_trail(L) > 0 && L.min_trail <= kBwdWaveRows) launch_bwd_wave(stream, ds_, list, nf, L.max_cols, d_L_, d_X_, Xt, nr, ldx, kBwdWaveRows,
+        if (narrow && level_max_trail(L) > 0 && L.min_trail <= kBwdWaveRows) launch_bwd_wave(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, Xt, nr, ldx, kBwdWaveRows,
                                                                                                   level_max_trail(L) > launch_wave_split_rows());
         if (y_in_x2) {
-            if (level_max_trail(L) > mmin) launch_bwd_gemm(stream, ds_, list, nf, L.max_cols, d_L_, d_X_, d_X2_, nr, ldx, -1, 1 << 30, mmin);
+            if (level_max_trail(L) > mmin) launch_bwd_gemm(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, ln.X2, nr, ldx, -1, 1 << 30, mmin);
             // fronts wider than inv_cap_: from the last block up, t_j -= L[own rows below, block j]' x, x_j = X_jj' t_j
             for (int j = nbk - 1; j >= 0; j--) {
                 // (nf: k_bwd_front may have taken the narrow tail of the list above -- block 0's count is "every big front" otherwise)
                 const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-                if (j + 1 < nbk) launch_bwd_gemm(stream, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, d_X_, d_X2_, nr, ldx, j, inv_cap_);
-                launch_xmul(stream, ds_, list, na, L.max_cols, 1, d_L_, d_X2_, d_X_, nr, ldx, j, inv_cap_);
+                if (j + 1 < nbk) launch_bwd_gemm(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
+                launch_xmul(ln.st, ds_, list, na, L.max_cols, 1, d_L_, ln.X2, ln.X, nr, ldx, j, inv_cap_);
             }
         } else {
-            if (level_max_trail(L) > mmin) launch_bwd_gemm(stream, ds_, list, nf, L.max_cols, d_L_, d_X_, d_X_, nr, ldx, -1, 1 << 30, mmin);
+            if (level_max_trail(L) > mmin) launch_bwd_gemm(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, ln.X, nr, ldx, -1, 1 << 30, mmin);
             for (int j = nbk - 1; j >= 0; j--) {
                 const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-                if (j + 1 < nbk) launch_bwd_gemm(stream, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, d_X_, d_X_, nr, ldx, j, inv_cap_);
-                launch_xmul(stream, ds_, list, na, L.max_cols, 1, d_L_, d_X_, d_X2_, nr, ldx, j, inv_cap_);
+                if (j + 1 < nbk) launch_bwd_gemm(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X, ln.X, nr, ldx, j, inv_cap_);
+                launch_xmul(ln.st, ds_, list, na, L.max_cols, 1, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
                 // x_j has to be back in X before the block above reads it
-                launch_copy_own(stream, ds_, list, na, L.max_cols, d_X2_, d_X_, nr, ldx, j, inv_cap_);
+                launch_copy_own(ln.st, ds_, list, na, L.max_cols, ln.X2, ln.X, nr, ldx, j, inv_cap_);
             }
         }
     }
-    if (level_mark_ && lo == 0) { launch_level_mark(stream, 2, -1); level_event(2, (int)levels_.size()); }
+    if (level_mark_ && lo == 0) { launch_level_mark(ln.st, 2, -1); level_event(ln.st, 2, (int)levels_.size()); }
     if (lo == 0)
         for (int k = 0, off = 0; k < 3; off += nsub_cls_[k], k++)
-            launch_subtree(stream, ds_, 2, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
-                           nullptr, d_X_, nullptr, nr, ldx);
-    if (lo == 0) sweep_tasks(2, nr, ldx);
-    if (level_mark_ && lo == 0) level_event(2, (int)levels_.size() + 1);
+            launch_subtree(ln.st, ds_, 2, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
+                           nullptr, ln.X, nullptr, nr, ldx);
+    if (lo == 0) sweep_tasks(ln, 2, nr, ldx, false);
+    if (level_mark_ && lo == 0) level_event(ln.st, 2, (int)levels_.size() + 1);
 }
 
 // GMRFX_LEVEL_MARK=1: HIP events at the level boundaries of the most recent factorisation / forward / backward sweep
 // (slot numbering in level_times()); a profiling aid behind gmrfx_level_times, never on in production runs
-void Device::level_event(int phase, int slot) {
+void Device::level_event(hipStream_t st, int phase, int slot) {
     auto &v = ev_level_[phase];
     while ((int)v.size() <= slot) { hipEvent_t e; HC(hipEventCreate(&e)); v.push_back(e); }
-    HC(hipEventRecord(v[slot], stream));
+    HC(hipEventRecord(v[slot], st));
     level_slots_[phase] = std::max(level_slots_[phase], slot + 1);
 }
 // out[0] = the sweep tasks (0 for the factorisation), out[1 + l] = tree level l, milliseconds; returns the count
@@ -1191,34 +1188,34 @@ void Device::solve_phase(const double *d_B, long long ldb, long long nrhs, doubl
     const int split = std::min<int>(S_->shard_level, nl);
     const long long n = S_->n;
     HC(hipEventRecord(ev_[0], stream));
+    if (phase == 0 || phase == 10) ensure_rhs_capacity(nrhs);
+    const SweepLane ln = lane(0);
     if (phase == 0) {                                     // transpose in + forward over the own subtrees
-        ensure_rhs_capacity(nrhs);
         start_inverse_async();
-        ensure_rdiag();
-        ensure_dtile();
-        launch_permute(stream, d_iperm_, (int)n, const_cast<double *>(d_B), ldb, d_X_, nr, ldx, 0);
-        forward(nr, ldx, 0, split);
+        ensure_rdiag(stream);
+        ensure_dtile(stream);
+        launch_permute(stream, d_iperm_, (int)n, const_cast<double *>(d_B), ldb, ln.X, nr, ldx, 0);
+        forward(ln, nr, ldx, 0, split, false);
     } else if (phase >= 100 && phase < 100 + (nl - split)) {       // forward, top level split + (phase - 100)
         const int lev = split + phase - 100;
-        forward(nr, ldx, lev, lev + 1);
+        forward(ln, nr, ldx, lev, lev + 1, false);
     } else if (phase >= 200 && phase < 200 + (nl - split)) {       // backward, top level split + (phase - 200)
         const int lev = split + phase - 200;
-        backward(nr, ldx, true, lev + 1, lev);
+        backward(ln, nr, ldx, true, lev + 1, lev);
     } else if (phase == 2) {                              // backward over the own subtrees
-        backward(nr, ldx, true, split, 0);
+        backward(ln, nr, ldx, true, split, 0);
     } else if (phase == 10) {                             // F.UP \ z: z is taken in elimination order as is, no forward sweep
-        ensure_rhs_capacity(nrhs);
         start_inverse_async();
-        ensure_rdiag();
-        ensure_dtile();
-        launch_permute(stream, nullptr, (int)n, const_cast<double *>(d_B), ldb, d_X_, nr, ldx, 0);
+        ensure_rdiag(stream);
+        ensure_dtile(stream);
+        launch_permute(stream, nullptr, (int)n, const_cast<double *>(d_B), ldb, ln.X, nr, ldx, 0);
     } else if (phase >= 300 && phase < 300 + (nl - split)) {       // backward-only solve, top level split + (phase - 300)
         const int lev = split + phase - 300;
-        backward(nr, ldx, false, lev + 1, lev);
+        backward(ln, nr, ldx, false, lev + 1, lev);
     } else if (phase == 12) {                             // backward-only solve over the own subtrees
-        backward(nr, ldx, false, split, 0);
+        backward(ln, nr, ldx, false, split, 0);
     } else if (phase == 3) {                              // transpose out (rank 0, after the gather)
-        launch_permute(stream, d_iperm_, (int)n, d_Xout, ldx_out, d_X_, nr, ldx, 1);
+        launch_permute(stream, d_iperm_, (int)n, d_Xout, ldx_out, ln.X, nr, ldx, 1);
     } else throw std::invalid_argument("solve phase must be 0, 2, 3, 10, 12, 100 + k, 200 + k or 300 + k (k = top level)");
     HC(hipEventRecord(ev_[1], stream));
     if (!async_phases_) {
@@ -1231,6 +1228,25 @@ void Device::solve_phase(const double *d_B, long long ldb, long long nrhs, doubl
     last_nrhs = nrhs;
 }
 
+// One pass of at most 64 columns on lane ln: dB (column-major, original ordering) -> ln.X (elimination order, row-major), the
+// sweeps, and back to dXo. mode 0: full solve, X = P b; 1: backward only (F.UP \ z), z is taken in elimination order as is.
+void Device::sweep_pass(const SweepLane &ln, hipEvent_t *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
+                        const MemberLayout *ml) {
+    const int n = (int)S_->n, ldx = nr, nl = (int)levels_.size();
+    auto mark = [&](int k) { if (ev) HC(hipEventRecord(ev[k], ln.st)); };
+    mark(0);
+    if (ml) launch_batch_permute(ln.st, mode == 0 ? d_iperm_ : nullptr, n, (int)ml->n_member, const_cast<double *>(dB), ldin, ml->sin, ln.X, nr, ldx, 0);
+    else launch_permute(ln.st, mode == 0 ? d_iperm_ : nullptr, n, const_cast<double *>(dB), ldin, ln.X, nr, ldx, 0);
+    mark(1);
+    if (mode == 0) forward(ln, nr, ldx, 0, nl, false);
+    mark(2);
+    backward(ln, nr, ldx, mode == 0, nl, 0);
+    mark(3);
+    if (ml) launch_batch_permute(ln.st, d_iperm_, n, (int)ml->n_member, dXo, ldout, ml->sout, ln.X, nr, ldx, 1);
+    else launch_permute(ln.st, d_iperm_, n, dXo, ldout, ln.X, nr, ldx, 1);
+    mark(4);
+}
+
 void Device::solve(const double *B, long long ldb, long long nrhs, double *X, long long ldx_out, bool on_device, int mode,
                    const MemberLayout *ml) {
     HC(hipSetDevice(device));
@@ -1240,27 +1256,23 @@ void Device::solve(const double *B, long long ldb, long long nrhs, double *X, lo
     const long long n = S_->n;
     ensure_rhs_capacity(nrhs);
     start_inverse_async();
-    ensure_rdiag();
-    ensure_dtile();
+    ensure_rdiag(stream);      // (on the main stream, before the lanes fork)
+    ensure_dtile(stream);
     const double *dB = B;
     double *dXo = X;
     long long ldin = ldb, ldout = ldx_out;
     if (!on_device) {
         const long long need = n * nrhs;
-        if (need > io_cap_) { const long long cap = std::max(need, 2 * io_cap_); d_io_ = dregrow(d_io_, (size_t)cap); io_cap_ = cap; }
+        ensure_io(need);
         if (ldb == n) HC(hipMemcpyAsync(d_io_, B, (size_t)need * sizeof(double), hipMemcpyHostToDevice, stream));
         else HC(hipMemcpy2DAsync(d_io_, n * sizeof(double), B, ldb * sizeof(double), n * sizeof(double), nrhs, hipMemcpyHostToDevice, stream));
         dB = d_io_; dXo = d_io_; ldin = n; ldout = n;
     }
     double t_perm = 0, t_fwd = 0, t_bwd = 0;
-    // 64-column passes, alternating between the two lanes when there is more than one pass. forward() / backward()
-    // enqueue on the members `stream`, d_X_, d_X2_, d_W_: a lane is selected by swapping them in for the duration
-    // of the (asynchronous) enqueue.
     // passes of pass_width() = 64 columns, alternating between the two lanes when there is more than one pass
     const int PW = pass_width(nrhs);
     const bool two = nrhs > PW && d_Xb_ != nullptr;
-    struct LaneState { hipStream_t st; double *X, *X2, *W; };
-    LaneState lanes[2] = {{stream, d_X_, d_X2_, d_W_}, {stream3, d_Xb_, d_X2b_, d_Wb_}};
+    const SweepLane lanes[2] = {lane(0), lane(1)};
     if (two) {
         // lane 1 starts after everything already enqueued on the main stream (factorisation, upload of B)
         HC(hipEventRecord(ev_ready_, stream));
@@ -1278,37 +1290,13 @@ void Device::solve(const double *B, long long ldb, long long nrhs, double *X, lo
         t_perm += a + d; t_fwd += b; t_bwd += c;
         busy[ln] = false;
     };
-    const hipStream_t main_stream = stream;
-    double *const X0 = d_X_, *const X20 = d_X2_, *const W0 = d_W_;
-    struct Restore {     // the members come back even if a HIP call throws while a lane is swapped in
-        Device &D; hipStream_t st; double *X, *X2, *W;
-        ~Restore() { D.stream = st; D.d_X_ = X; D.d_X2_ = X2; D.d_W_ = W; }
-    } restore{*this, main_stream, X0, X20, W0};
     HC(hipEventRecord(ev_[0], stream));
     int pass = 0;
     for (long long j0 = 0; j0 < nrhs; j0 += PW, pass++) {
-        const int nr = (int)std::min<long long>(PW, nrhs - j0);
-        const int ldx = nr;
         const int ln = two ? (pass & 1) : 0;
         collect(ln);                         // the lane's previous pass has finished: its buffers are free
-        stream = lanes[ln].st; d_X_ = lanes[ln].X; d_X2_ = lanes[ln].X2; d_W_ = lanes[ln].W;
-        hipEvent_t *ev = ev_lane_[ln];
-        HC(hipEventRecord(ev[0], stream));
-        // full solve: X = P b ; backward-only (F.UP \ z): z is taken in elimination order as is
-        if (ml) launch_batch_permute(stream, mode == 0 ? d_iperm_ : nullptr, (int)n, (int)ml->n_member, const_cast<double *>(dB) + j0 * ldin, ldin,
-                                     ml->sin, d_X_, nr, ldx, 0);
-        else launch_permute(stream, mode == 0 ? d_iperm_ : nullptr, (int)n, const_cast<double *>(dB) + j0 * ldin, ldin, d_X_, nr, ldx, 0);
-        HC(hipEventRecord(ev[1], stream));
-
-        if (mode == 0) forward(nr, ldx, 0, (int)levels_.size());
-        HC(hipEventRecord(ev[2], stream));
-        backward(nr, ldx, mode == 0, (int)levels_.size(), 0);
-        HC(hipEventRecord(ev[3], stream));
-        if (ml) launch_batch_permute(stream, d_iperm_, (int)n, (int)ml->n_member, dXo + j0 * ldout, ldout, ml->sout, d_X_, nr, ldx, 1);
-        else launch_permute(stream, d_iperm_, (int)n, dXo + j0 * ldout, ldout, d_X_, nr, ldx, 1);
-        HC(hipEventRecord(ev[4], stream));
+        sweep_pass(lanes[ln], ev_lane_[ln], dB + j0 * ldin, ldin, dXo + j0 * ldout, ldout, (int)std::min<long long>(PW, nrhs - j0), mode, ml);
         busy[ln] = true;
-        stream = main_stream; d_X_ = X0; d_X2_ = X20; d_W_ = W0;
     }
     if (two) {
         HC(hipEventRecord(ev_done1_, stream3));
@@ -1359,6 +1347,16 @@ double Device::logdet() {
     return *h_logdet_;
 }
 
+// a page-locked host buffer of results (h_qf_, h_bqf_) grown to `count` doubles, `floor` at least; a failed allocation leaves none
+static void grow_pinned(double *&buf, long long &cap, long long count, long long floor) {
+    if (count <= cap) return;
+    if (buf) HC(hipHostFree(buf));
+    buf = nullptr; cap = 0;
+    const long long fresh = std::max(count, floor);
+    HC(hipHostMalloc((void **)&buf, (size_t)fresh * sizeof(double), hipHostMallocDefault));
+    cap = fresh;
+}
+
 // pattern of Q and the partial-sum buffers of the quadratic-form kernels (grown geometrically)
 void Device::prepare_quadform(long long nvec) {
     const Symbolic &S = *S_;
@@ -1394,12 +1392,7 @@ void Device::refactorize_logpdf(const double *d_nz, const double *d_X, long long
     if (stream != own_stream_) throw std::invalid_argument("refactorize_logpdf: not on a caller's stream");
     if (nvec > 0) {
         prepare_quadform(nvec);
-        if (nvec > h_qf_cap_) {
-            if (h_qf_) HC(hipHostFree(h_qf_));
-            h_qf_ = nullptr; h_qf_cap_ = 0;
-            HC(hipHostMalloc((void **)&h_qf_, (size_t)std::max<long long>(nvec, 16) * sizeof(double), hipHostMallocDefault));
-            h_qf_cap_ = std::max<long long>(nvec, 16);
-        }
+        grow_pinned(h_qf_, h_qf_cap_, nvec, 16);
         HC(hipEventRecord(ev_ready_, stream));
         HC(hipStreamWaitEvent(stream2, ev_ready_, 0));
         launch_quadform(stream2, (int)S.n, d_in_colptr_, d_in_row_, d_nz, S.in_use, d_X, ldx, (int)nvec, d_mu, d_qf_part_, d_qf_out_);
@@ -1407,28 +1400,14 @@ void Device::refactorize_logpdf(const double *d_nz, const double *d_X, long long
         if (!ev_qf_) HC(hipEventCreateWithFlags(&ev_qf_, hipEventDisableTiming));
         HC(hipEventRecord(ev_qf_, stream2));
     }
-    nz_held_ = false;
-    nz_src_ = d_nz;
-    factor_serial_++;
-    HC(hipEventRecord(ev_[0], stream));
-    factor_levels(0, (int)levels_.size());
-    HC(hipEventRecord(ev_[1], stream));
-    HC(hipEventRecord(ev_fact_, stream));
-    fact_event_valid_ = true;
+    begin_factor(d_nz);
+    factor_levels(0, (int)levels_.size(), false);
+    enqueue_factor_tail();
     inverse_pending = true;
-    HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
-    factorized = true;
-    selinv_valid = false;
-    float tf = 0;
     enqueue_logdet(stream, false);
     if (nvec > 0) HC(hipStreamWaitEvent(stream, ev_qf_, 0));
     HC(hipStreamSynchronize(stream));
-    info_cached_ = true;
-    HC(hipGetLastError());
-    decide_inverse_cap();
-    HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
-    ms_factor = tf;
-    syrk_times_pending_ = true;
+    finish_factor();
     for (long long k = 0; k < nvec; k++) quad_out[k] = h_qf_[k];
     if (logdet_out) *logdet_out = *h_logdet_;
 }
@@ -1455,7 +1434,7 @@ void Device::quadform(const double *d_nz, const double *d_X, long long ldx, long
 void Device::selinv_begin() {
     const Symbolic &S = *S_;
     start_inverse_async();
-    wait_inverse();
+    wait_inverse(stream);
     if (!inverse_full_) {      // the sweeps only need inv_cap_-column inverses; the Takahashi step needs all of L11^-1
         invert_diag_blocks(stream, inv_cap_, 1 << 30);
         inverse_full_ = true;
@@ -1701,6 +1680,10 @@ void Device::batch_diag(double *logdet_out, long long *info_out) {
     if (bdiag_for_ != factor_serial_) enqueue_batch_diag(stream);
     HC(hipEventSynchronize(ev_bdiag_));
     HC(hipGetLastError());
+    read_batch_diag(logdet_out, info_out);
+}
+// h_bdiag_ (valid once ev_bdiag_ has passed): nbatch log dets, then nbatch info words; either output may be null
+void Device::read_batch_diag(double *logdet_out, long long *info_out) const {
     const long long *hi = reinterpret_cast<const long long *>(h_bdiag_ + nbatch_);
     for (int k = 0; k < nbatch_; k++) {
         if (logdet_out) logdet_out[k] = h_bdiag_[k];
@@ -1717,13 +1700,7 @@ void Device::prepare_batch_quadform(long long npairs) {
         d_bqf_out_ = dregrow(d_bqf_out_, (size_t)cap);
         bqf_cap_ = cap;
     }
-    if (npairs > h_bqf_cap_) {
-        if (h_bqf_) HC(hipHostFree(h_bqf_));
-        h_bqf_ = nullptr; h_bqf_cap_ = 0;
-        const long long cap = std::max<long long>(npairs, 64);
-        HC(hipHostMalloc((void **)&h_bqf_, (size_t)cap * sizeof(double), hipHostMallocDefault));
-        h_bqf_cap_ = cap;
-    }
+    grow_pinned(h_bqf_, h_bqf_cap_, npairs, 64);
 }
 
 void Device::enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,
@@ -1769,34 +1746,16 @@ void Device::batch_refactorize_logpdf(const double *d_nz, const double *d_X, lon
         if (!ev_qf_) HC(hipEventCreateWithFlags(&ev_qf_, hipEventDisableTiming));
         HC(hipEventRecord(ev_qf_, stream2));
     }
-    nz_held_ = false;
-    nz_src_ = d_nz;
-    factor_serial_++;
-    HC(hipEventRecord(ev_[0], stream));
-    factor_levels(0, (int)levels_.size());
-    HC(hipEventRecord(ev_[1], stream));
-    HC(hipEventRecord(ev_fact_, stream));
-    fact_event_valid_ = true;
+    begin_factor(d_nz);
+    factor_levels(0, (int)levels_.size(), false);
+    enqueue_factor_tail();
     inverse_pending = true;
-    HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
-    factorized = true;
-    selinv_valid = false;
     enqueue_batch_diag(stream);
     if (nvec > 0) HC(hipStreamWaitEvent(stream, ev_qf_, 0));
     HC(hipStreamSynchronize(stream));
-    info_cached_ = true;
-    HC(hipGetLastError());
-    decide_inverse_cap();
-    float tf = 0;
-    HC(hipEventElapsedTime(&tf, ev_[0], ev_[1]));
-    ms_factor = tf;
-    syrk_times_pending_ = true;
+    finish_factor();
     for (long long k = 0; k < nvec * nbatch_; k++) quad_out[k] = h_bqf_[k];
-    const long long *hi = reinterpret_cast<const long long *>(h_bdiag_ + nbatch_);
-    for (int k = 0; k < nbatch_; k++) {
-        if (logdet_out) logdet_out[k] = h_bdiag_[k];
-        if (info_out) info_out[k] = hi[k];
-    }
+    read_batch_diag(logdet_out, info_out);
 }
 
 }  // namespace gmrfx

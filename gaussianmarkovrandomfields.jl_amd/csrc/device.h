@@ -61,6 +61,9 @@ struct ConHost {
 
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
+// Where one sweep pass runs: a stream and the right-hand-side buffers it works in (X: the pass's columns in elimination order,
+// X2: y of the big fronts, W: the update vectors). The sweep drivers take it as a parameter; nothing selects a lane by state.
+struct SweepLane { hipStream_t st; double *X, *X2, *W; };
 class Device {
 public:
     Device() = default;
@@ -187,9 +190,24 @@ public:
 private:
     void upload(const Symbolic &S);
     void ensure_rhs_capacity(long long nrhs);
-    void factor_levels(int lo, int hi);
-    void forward(int nr, int ldx, int lo, int hi);
-    void backward(int nr, int ldx, bool y_in_x2, int hi, int lo);
+    // record_level_events: the pipelined call's "level is factored" events (ev_flevel_) behind every level
+    void factor_levels(int lo, int hi, bool record_level_events);
+    // follows_factor: the pipelined call's forward sweep, one level behind the factorisation (waits for the level events, builds the
+    // dense inverses level by level)
+    void forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor);
+    void backward(const SweepLane &ln, int nr, int ldx, bool y_in_x2, int hi, int lo);
+    // one pass of a solve on lane ln: transpose in, forward (mode 0), backward, transpose out; ev (nullable): the lane's five timing events
+    void sweep_pass(const SweepLane &ln, hipEvent_t *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
+                    const MemberLayout *ml);
+    // lane 0: the main stream and d_X_ / d_X2_ / d_W_; lane 1: the third stream and their twins (solves of more than 64 right-hand sides)
+    SweepLane lane(int k) const { return k == 0 ? SweepLane{stream, d_X_, d_X2_, d_W_} : SweepLane{stream3, d_Xb_, d_X2b_, d_Wb_}; }
+    // the three parts every numeric factorisation shares (device.cpp, above refactorize)
+    void begin_factor(const double *d_src);
+    void enqueue_factor_tail();
+    void finish_factor();
+    void newton_values(const double *h, bool on_device);
+    void ensure_io(long long need);
+    void read_batch_diag(double *logdet_out, long long *info_out) const;
     template <class T> T *dalloc(size_t count);
     // growable buffer: frees the previous allocation (after the streams have drained) and takes it off the books
     template <class T> T *dregrow(T *old, size_t count);
@@ -222,15 +240,15 @@ private:
     int wave_max_nr_ = 16;        // passes of up to this many right-hand sides use the wave tasks (0: never)
     const int *d_wave_order_ = nullptr;
     int wave_first_[kWaveClasses] = {0, 0}, wave_count_[kWaveClasses] = {0, 0};
-    void sweep_tasks(int phase, int nr, int ldx);
+    void sweep_tasks(const SweepLane &ln, int phase, int nr, int ldx, bool follows_factor);
 public:
     void set_external_stream(hipStream_t s, bool use, bool async);
     int level_times(int phase, double *out, int cap);
     void dist_front_phase(const double *d_nzval, int front, int what, int block);
 private:
-    void ensure_rdiag();
+    void ensure_rdiag(hipStream_t st);
     bool nzp_pending_ = false;                    // k_gather_values runs on the third stream and the main stream has not waited for it yet
-    void ensure_dtile();
+    void ensure_dtile(hipStream_t st);
     int fwd_front_min_ = 384;                     // the forward twin (k_fwd_front): levels with at least this many such fronts (measured at cfg 2, round 6, one workgroup per
                                                   // front against the three launches, us: level 5 (1472 fronts) 103 / 128, 6 (2271) 167 / 211, 7 (1034) 159 / 207, 8 (513) 103 / 131,
                                                   // 9 (256, 236 of them eligible) 103 + 58 / 113: a level needs about two workgroups per compute unit)
@@ -247,7 +265,7 @@ private:
     bool selinv_begun_ = false;   // sharded selected inversion: phase 0 has run since the last refactorisation (gmrfx_selinv_phase)
     std::vector<hipEvent_t> ev_level_[3];
     int level_slots_[3] = {0, 0, 0};
-    void level_event(int phase, int slot);
+    void level_event(hipStream_t st, int phase, int slot);
     bool level_mark_ = false;     // GMRFX_LEVEL_MARK=1: an empty marker kernel in front of every level (profiling aid, tools/sweep_levels.py)
     int *d_sub_first_ = nullptr, *d_sub_last_ = nullptr, *d_sel_levellist_ = nullptr;
     int nsub_cls_[3] = {0, 0, 0};
@@ -282,7 +300,6 @@ private:
     bool inverse_full_ = false;
     // pipelined factor + solve: per-level "level is factored" events, the dense-inverse stages per level, the highest level a
     // sweep task / small subtree reaches
-    bool fused_ = false, fused_fwd_ = false;
     std::vector<hipEvent_t> ev_flevel_;
     int bottom_top_level_ = 0, fused_gate_level_ = 0;
     int *d_inv_lvl_list_ = nullptr;
@@ -303,7 +320,7 @@ private:
     bool info_cached_ = false;
     void invert_diag_blocks(hipStream_t st, int b_from, int b_to);
     void start_inverse_async();
-    void wait_inverse();
+    void wait_inverse(hipStream_t st);
     int first_multiblock_level_ = 0;
     long long rhs_cap_ = 0, io_cap_ = 0, tmp_cap_ = 0;
     long long *d_yoff_ = nullptr;                 // selected inversion: per-front offsets of the Yh / Yt workspaces
@@ -311,9 +328,9 @@ private:
     std::vector<int> fc_levelptr_, fc_maxtrail_;  // ranges of d_fchild_ per level, max trailing rows per level
     void selinv_begin();
     void selinv_levels(int hi, int lo);
-    // Solves with more than 64 right-hand sides run their 64-column passes on TWO lanes (stream + buffers each):
+    // Solves with more than 64 right-hand sides run their 64-column passes on TWO lanes (SweepLane: stream + buffers each):
     // one pass is launch-latency bound (4.6 ms for 1 column, 5.9 for 64), two interleave on the idle CUs.
-    double *d_Xb_ = nullptr, *d_X2b_ = nullptr, *d_Wb_ = nullptr;   // lane 1 (lane 0 = d_X_ / d_X2_ / d_W_ on `stream`)
+    double *d_Xb_ = nullptr, *d_X2b_ = nullptr, *d_Wb_ = nullptr;   // lane 1 (lane 0 = d_X_ / d_X2_ / d_W_ on `stream`): lane()
     hipEvent_t ev_lane_[2][5] = {};
     hipEvent_t ev_ready_ = nullptr, ev_ready2_ = nullptr, ev_done1_ = nullptr;
     int *d_info_ = nullptr;

@@ -68,6 +68,84 @@ static int32_t need_device(gmrfx_handle *h, bool need_factor) {
     return GMRFX_OK;
 }
 
+// the pivot report of the factorisation just done: *info = 0, or 1 + the failing elimination step; an error when the handle checks
+static int32_t pivot_status(gmrfx_handle *h, int64_t *info) {
+    const long long fc = h->D->fail_col();
+    if (info) *info = fc < 0 ? 0 : fc + 1;
+    if (fc >= 0 && h->opts.check_posdef) {
+        h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
+        return GMRFX_ERR_NOT_POSDEF;
+    }
+    return GMRFX_OK;
+}
+
+// right-hand sides in, solutions out: column-major n x nrhs each (names: "B/X", "Z/X" -- how the message calls them)
+static void check_rhs(const gmrfx_handle *h, const void *B, int64_t ldb, const void *X, int64_t ldx, int64_t nrhs, const char *names) {
+    if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
+    if (nrhs > 0 && (!B || !X)) throw std::invalid_argument(std::string(names) + " is null");
+    if (nrhs > 0 && (ldb < h->S.n || ldx < h->S.n)) throw std::invalid_argument("leading dimension smaller than n");
+}
+
+// a device copy of a host block, freed on return
+namespace {
+struct DevBlock {
+    double *p = nullptr;
+    ~DevBlock() { if (p) (void)hipFree(p); }
+    void alloc(int64_t count) { hip_check(hipMalloc((void **)&p, (size_t)std::max<int64_t>(count, 1) * sizeof(double) + 16), "hipMalloc"); }
+    void up(const double *src, int64_t count) { hip_check(hipMemcpy(p, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy"); }
+    // n x nvec, leading dimension ld on the host, n on the device
+    void up(const double *src, int64_t ld, int64_t n, int64_t nvec) {
+        hip_check(hipMemcpy2D(p, (size_t)n * sizeof(double), src, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
+    }
+    void down(double *dst, int64_t ld, int64_t n, int64_t nvec) {
+        hip_check(hipMemcpy2D(dst, (size_t)ld * sizeof(double), p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
+    }
+};
+}  // namespace
+
+// create-time failures have no handle to carry the message: it goes to g_create_err
+static int32_t device_failure(const std::exception &e) {
+    g_create_err = e.what();
+    return std::string(e.what()).find("no HIP device") != std::string::npos ? GMRFX_ERR_NO_DEVICE : GMRFX_ERR_HIP;
+}
+// analysis = true: anything but a refused argument / a failed host allocation is a refused argument too (the analysis never touches
+// the device); false: it is a device failure
+template <class F> static int32_t create_guarded(bool analysis, F &&f) {
+    try {
+        return f();
+    } catch (const std::invalid_argument &e) {
+        g_create_err = e.what();
+        return GMRFX_ERR_INVALID_ARG;
+    } catch (const std::bad_alloc &) {
+        g_create_err = "out of host memory";
+        return GMRFX_ERR_ALLOC;
+    } catch (const std::exception &e) {
+        if (!analysis) return device_failure(e);
+        g_create_err = e.what();
+        return GMRFX_ERR_INVALID_ARG;
+    }
+}
+// the caller's options over the defaults (struct_size bytes of them); false: refused
+static bool read_opts(const gmrfx_opts *opts, gmrfx_opts &o) {
+    o = default_opts();
+    if (!opts) return true;
+    if (opts->struct_size <= 0) { g_create_err = "opts.struct_size not set"; return false; }
+    std::memcpy(&o, opts, std::min<size_t>((size_t)opts->struct_size, sizeof(gmrfx_opts)));
+    return true;
+}
+// the device state of an analysed handle (none for symbolic_only); every failure in here is a device failure
+static int32_t attach_device(gmrfx_handle *h, bool batched) {
+    if (h->opts.symbolic_only) return GMRFX_OK;
+    try {
+        h->D.reset(new Device());
+        h->D->init(h->S, h->opts.device);
+        if (batched) h->D->set_batch((int)h->nbatch, h->n_member, h->nnz_member);
+    } catch (const std::exception &e) {
+        return device_failure(e);
+    }
+    return GMRFX_OK;
+}
+
 // gmrfx_opts -> the analysis options (and the tuning / testing knobs of the environment)
 static void sym_options(const gmrfx_opts &o, SymOptions &so) {
     so.uplo = o.uplo;
@@ -99,37 +177,16 @@ extern "C" int32_t gmrfx_create(int64_t n, const int64_t *colptr, const int64_t 
     *out = nullptr;
     if (!colptr || !rowval) { g_create_err = "colptr/rowval is null"; return GMRFX_ERR_INVALID_ARG; }
     std::unique_ptr<gmrfx_handle> h(new gmrfx_handle());
-    h->opts = default_opts();
-    if (opts) {
-        size_t sz = std::min<size_t>((size_t)opts->struct_size, sizeof(gmrfx_opts));
-        if (opts->struct_size <= 0) { g_create_err = "opts.struct_size not set"; return GMRFX_ERR_INVALID_ARG; }
-        std::memcpy(&h->opts, opts, sz);
-    }
-    try {
-        SymOptions so;
-        sym_options(h->opts, so);
-        analyze(n, colptr, rowval, index_base, perm, so, h->S);
-        h->opts.coords = nullptr;  // caller-owned, not kept
-        h->n_member = h->S.n; h->nnz_member = h->S.nnz_in;
-    } catch (const std::invalid_argument &e) {
-        g_create_err = e.what();
-        return GMRFX_ERR_INVALID_ARG;
-    } catch (const std::bad_alloc &) {
-        g_create_err = "out of host memory";
-        return GMRFX_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        g_create_err = e.what();
-        return GMRFX_ERR_INVALID_ARG;
-    }
-    if (!h->opts.symbolic_only) {
-        try {
-            h->D.reset(new Device());
-            h->D->init(h->S, h->opts.device);
-        } catch (const std::exception &e) {
-            g_create_err = e.what();
-            return std::string(e.what()).find("no HIP device") != std::string::npos ? GMRFX_ERR_NO_DEVICE : GMRFX_ERR_HIP;
-        }
-    }
+    if (!read_opts(opts, h->opts)) return GMRFX_ERR_INVALID_ARG;
+    if (int32_t e = create_guarded(true, [&]() -> int32_t {
+            SymOptions so;
+            sym_options(h->opts, so);
+            analyze(n, colptr, rowval, index_base, perm, so, h->S);
+            h->opts.coords = nullptr;  // caller-owned, not kept
+            h->n_member = h->S.n; h->nnz_member = h->S.nnz_in;
+            return GMRFX_OK;
+        })) return e;
+    if (int32_t e = attach_device(h.get(), false)) return e;
     *out = h.release();
     return GMRFX_OK;
 }
@@ -164,13 +221,7 @@ static int32_t refactorize_impl(gmrfx_handle *h, const double *nz, int64_t *info
         if (int32_t e = need_device(h, false)) return e;
         if (!nz) throw std::invalid_argument("nzval is null");
         h->D->refactorize(nz, dev);
-        long long fc = h->D->fail_col();
-        if (info) *info = fc < 0 ? 0 : fc + 1;
-        if (fc >= 0 && h->opts.check_posdef) {
-            h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
-            return GMRFX_ERR_NOT_POSDEF;
-        }
-        return GMRFX_OK;
+        return pivot_status(h, info);
     });
 }
 extern "C" int32_t gmrfx_refactorize(gmrfx_handle *h, const double *nzval, int64_t *info) { return refactorize_impl(h, nzval, info, false); }
@@ -182,17 +233,9 @@ static int32_t refactorize_solve_impl(gmrfx_handle *h, const double *nz, const d
     return guarded(h, [&]() -> int32_t {
         if (int32_t e = need_device(h, false)) return e;
         if (!nz) throw std::invalid_argument("nzval is null");
-        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
-        if (nrhs > 0 && (!B || !X)) throw std::invalid_argument("B/X is null");
-        if (nrhs > 0 && (ldb < h->S.n || ldx < h->S.n)) throw std::invalid_argument("leading dimension smaller than n");
+        check_rhs(h, B, ldb, X, ldx, nrhs, "B/X");
         h->D->refactorize_solve(nz, dev, B, ldb, nrhs, X, ldx, dev);
-        long long fc = h->D->fail_col();
-        if (info) *info = fc < 0 ? 0 : fc + 1;
-        if (fc >= 0 && h->opts.check_posdef) {
-            h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
-            return GMRFX_ERR_NOT_POSDEF;
-        }
-        return GMRFX_OK;
+        return pivot_status(h, info);
     });
 }
 extern "C" int32_t gmrfx_refactorize_solve(gmrfx_handle *h, const double *nzval, const double *B, int64_t ldb, int64_t nrhs, double *X,
@@ -215,13 +258,7 @@ static int32_t refactorize_update_impl(gmrfx_handle *h, const double *hv, int64_
     return guarded(h, [&]() -> int32_t {
         if (int32_t e = need_device(h, false)) return e;
         h->D->refactorize_update(hv, dev);
-        long long fc = h->D->fail_col();
-        if (info) *info = fc < 0 ? 0 : fc + 1;
-        if (fc >= 0 && h->opts.check_posdef) {
-            h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
-            return GMRFX_ERR_NOT_POSDEF;
-        }
-        return GMRFX_OK;
+        return pivot_status(h, info);
     });
 }
 // One logpdf evaluation of the hyper-parameter loop in one call (Device::refactorize_logpdf): device pointers.
@@ -232,13 +269,7 @@ extern "C" int32_t gmrfx_refactorize_logpdf_dev(gmrfx_handle *h, const double *d
         if (!d_nzval) throw std::invalid_argument("nzval is null");
         if (nvec > 0 && (!d_X || !quad)) throw std::invalid_argument("X / quad is null");
         h->D->refactorize_logpdf(d_nzval, d_X, ldx, nvec, d_mu, quad, logdet);
-        long long fc = h->D->fail_col();
-        if (info) *info = fc < 0 ? 0 : fc + 1;
-        if (fc >= 0 && h->opts.check_posdef) {
-            h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
-            return GMRFX_ERR_NOT_POSDEF;
-        }
-        return GMRFX_OK;
+        return pivot_status(h, info);
     });
 }
 // One Newton iterate in one pipelined call (Device::refactorize_update_solve): Hessian values in, new mean's solve out.
@@ -246,17 +277,9 @@ static int32_t refactorize_update_solve_impl(gmrfx_handle *h, const double *hv, 
                                              int64_t *info, bool dev) {
     return guarded(h, [&]() -> int32_t {
         if (int32_t e = need_device(h, false)) return e;
-        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
-        if (nrhs > 0 && (!B || !X)) throw std::invalid_argument("B/X is null");
-        if (nrhs > 0 && (ldb < h->S.n || ldx < h->S.n)) throw std::invalid_argument("leading dimension smaller than n");
+        check_rhs(h, B, ldb, X, ldx, nrhs, "B/X");
         h->D->refactorize_update_solve(hv, dev, B, ldb, nrhs, X, ldx, dev);
-        long long fc = h->D->fail_col();
-        if (info) *info = fc < 0 ? 0 : fc + 1;
-        if (fc >= 0 && h->opts.check_posdef) {
-            h->err = "matrix is not positive definite (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
-            return GMRFX_ERR_NOT_POSDEF;
-        }
-        return GMRFX_OK;
+        return pivot_status(h, info);
     });
 }
 extern "C" int32_t gmrfx_refactorize_update_solve(gmrfx_handle *h, const double *hvals, const double *B, int64_t ldb, int64_t nrhs, double *X,
@@ -466,10 +489,8 @@ extern "C" int32_t gmrfx_refactorize_dev(gmrfx_handle *h, const double *d_nzval,
 static int32_t solve_impl(gmrfx_handle *h, const double *B, int64_t ldb, int64_t nrhs, double *X, int64_t ldx, bool dev, int mode) {
     return guarded(h, [&]() -> int32_t {
         if (int32_t e = need_device(h, true)) return e;
-        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
+        check_rhs(h, B, ldb, X, ldx, nrhs, "B/X");
         if (nrhs == 0) return GMRFX_OK;
-        if (!B || !X) throw std::invalid_argument("B/X is null");
-        if (ldb < h->S.n || ldx < h->S.n) throw std::invalid_argument("leading dimension smaller than n");
         h->D->solve(B, ldb, nrhs, X, ldx, dev, mode);
         return GMRFX_OK;
     });
@@ -619,6 +640,20 @@ static inline long long z_offset(const Symbolic &S, i64 i, i64 j) {
     return (long long)(S.panelptr[s] + (i64)(b - S.sfirst[s]) * S.ld[s] + (it - rows));
 }
 
+// z_offset of every entry of a caller's CSC pattern (checked by check_compressed_ptr), in the pattern's order
+static std::vector<long long> z_offsets_csc(const Symbolic &S, int64_t ncol, const int64_t *colptr, const int64_t *rowval, int32_t base) {
+    std::vector<long long> off((size_t)(colptr[ncol] - base));
+    parallel_ranges(ncol, [&](i64 lo, i64 hi) {
+        for (i64 j = lo; j < hi; j++)
+            for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; p++) {
+                i64 i = rowval[p] - base;
+                if (i < 0 || i >= S.n) throw std::invalid_argument("rowval out of range");
+                off[p] = z_offset(S, i, j);
+            }
+    });
+    return off;
+}
+
 extern "C" int32_t gmrfx_selinv_extract(gmrfx_handle *h, int64_t ncol, const int64_t *colptr, const int64_t *rowval,
                                         int32_t base, double *out) {
     return guarded(h, [&]() -> int32_t {
@@ -630,15 +665,7 @@ extern "C" int32_t gmrfx_selinv_extract(gmrfx_handle *h, int64_t ncol, const int
         check_compressed_ptr(colptr, ncol, base, "colptr");
         h->D->selinv_compute();
         const i64 nz = colptr[ncol] - base;
-        std::vector<long long> off((size_t)nz);
-        parallel_ranges(ncol, [&](i64 lo, i64 hi) {
-            for (i64 j = lo; j < hi; j++)
-                for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; p++) {
-                    i64 i = rowval[p] - base;
-                    if (i < 0 || i >= S.n) throw std::invalid_argument("rowval out of range");
-                    off[p] = z_offset(S, i, j);
-                }
-        });
+        const std::vector<long long> off = z_offsets_csc(S, ncol, colptr, rowval, base);
         h->D->gather_z(off.data(), nz, out);
         return GMRFX_OK;
     });
@@ -655,15 +682,7 @@ extern "C" int32_t gmrfx_selinv_dot(gmrfx_handle *h, int64_t ncol, const int64_t
         check_compressed_ptr(colptr, ncol, base, "colptr");
         h->D->selinv_compute();
         const i64 nz = colptr[ncol] - base;
-        std::vector<long long> off((size_t)nz);
-        parallel_ranges(ncol, [&](i64 lo, i64 hi) {
-            for (i64 j = lo; j < hi; j++)
-                for (i64 p = colptr[j] - base; p < colptr[j + 1] - base; p++) {
-                    i64 i = rowval[p] - base;
-                    if (i < 0 || i >= S.n) throw std::invalid_argument("rowval out of range");
-                    off[p] = z_offset(S, i, j);
-                }
-        });
+        const std::vector<long long> off = z_offsets_csc(S, ncol, colptr, rowval, base);
         // fixed chunks of 4096 entries are summed on the device, the chunk sums on the host in order
         const i64 CH = 4096, nseg = (nz + CH - 1) / CH;
         std::vector<long long> seg((size_t)nseg + 1);
@@ -776,20 +795,13 @@ static int32_t quadform_impl(gmrfx_handle *h, const double *nz, const double *X,
         if (dev) { h->D->quadform(nz, X, ldx, nvec, mu, out); return GMRFX_OK; }
         // host operands: stage them through plain device buffers (freed on return)
         const i64 n = h->S.n;
-        struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } bx, bm, bn;
+        DevBlock bx, bm, bn;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
-        hip_check(hipMalloc(&bx.p, (size_t)std::max<i64>(n * nvec, 1) * sizeof(double)), "hipMalloc");
-        hip_check(hipMemcpy2D(bx.p, (size_t)n * sizeof(double), X, (size_t)ldx * sizeof(double), (size_t)n * sizeof(double),
-                              (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
-        if (mu) {
-            hip_check(hipMalloc(&bm.p, (size_t)std::max<i64>(n, 1) * sizeof(double)), "hipMalloc");
-            hip_check(hipMemcpy(bm.p, mu, (size_t)n * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-        }
-        if (nz) {
-            hip_check(hipMalloc(&bn.p, (size_t)std::max<i64>(h->S.nnz_in, 1) * sizeof(double)), "hipMalloc");
-            hip_check(hipMemcpy(bn.p, nz, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-        }
-        h->D->quadform((const double *)bn.p, (const double *)bx.p, n, nvec, (const double *)bm.p, out);
+        bx.alloc(n * nvec);
+        bx.up(X, ldx, n, nvec);
+        if (mu) { bm.alloc(n); bm.up(mu, n); }
+        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
+        h->D->quadform(bn.p, bx.p, n, nvec, bm.p, out);
         return GMRFX_OK;
     });
 }
@@ -837,7 +849,7 @@ extern "C" int32_t gmrfx_kl_cholesky(int64_t n, const double *theta, int64_t ldt
                                      const int64_t *task_rows, const int64_t *task_colptr, const int64_t *task_cols,
                                      int32_t base, double reg, int32_t device, double *nzval, int64_t *info) {
     if (info) *info = 0;
-    try {
+    return create_guarded(false, [&]() -> int32_t {
         if (n <= 0 || !theta || ldt < n || !L_colptr || !nzval) throw std::invalid_argument("kl_cholesky: null argument / ldt < n");
         if (ntasks < 0 || (ntasks > 0 && (!task_rowptr || !task_rows || !task_colptr || !task_cols)))
             throw std::invalid_argument("kl_cholesky: null task arrays");
@@ -879,16 +891,7 @@ extern "C" int32_t gmrfx_kl_cholesky(int64_t n, const double *theta, int64_t ldt
             return GMRFX_ERR_NOT_POSDEF;
         }
         return GMRFX_OK;
-    } catch (const std::invalid_argument &e) {
-        g_create_err = e.what();
-        return GMRFX_ERR_INVALID_ARG;
-    } catch (const std::bad_alloc &) {
-        g_create_err = "out of host memory";
-        return GMRFX_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        g_create_err = e.what();
-        return std::string(e.what()).find("no HIP device") != std::string::npos ? GMRFX_ERR_NO_DEVICE : GMRFX_ERR_HIP;
-    }
+    });
 }
 
 extern "C" int32_t gmrfx_get_stats(const gmrfx_handle *h, gmrfx_stats *out, int32_t struct_size) {
@@ -1022,17 +1025,14 @@ extern "C" int32_t gmrfx_create_batched(int64_t n, const int64_t *colptr, const 
     if (nbatch < 1) { g_create_err = "nbatch must be >= 1"; return GMRFX_ERR_INVALID_ARG; }
     if (n <= 0) { g_create_err = "n must be positive"; return GMRFX_ERR_INVALID_ARG; }
     if (n > (int64_t)INT32_MAX / nbatch) { g_create_err = "nbatch * n exceeds INT32_MAX (32-bit node indices of the forest)"; return GMRFX_ERR_INVALID_ARG; }
-    gmrfx_opts o = default_opts();
-    if (opts) {
-        if (opts->struct_size <= 0) { g_create_err = "opts.struct_size not set"; return GMRFX_ERR_INVALID_ARG; }
-        std::memcpy(&o, opts, std::min<size_t>((size_t)opts->struct_size, sizeof(gmrfx_opts)));
-    }
+    gmrfx_opts o;
+    if (!read_opts(opts, o)) return GMRFX_ERR_INVALID_ARG;
     if (o.shard_world > 1 || o.shard_min_top > 0) { g_create_err = "batched handles cannot be sharded (shard_world > 1 / shard_min_top > 0)"; return GMRFX_ERR_INVALID_ARG; }
     const int64_t nnz = colptr[n] - index_base;
     if (nnz < 0 || nnz > INT64_MAX / nbatch) { g_create_err = "colptr[n] out of range"; return GMRFX_ERR_INVALID_ARG; }
     std::unique_ptr<gmrfx_handle> h(new gmrfx_handle());
     h->opts = o;
-    try {
+    if (int32_t e = create_guarded(true, [&]() -> int32_t {
         const auto t0 = std::chrono::steady_clock::now();
         SymOptions so;
         sym_options(h->opts, so);
@@ -1054,26 +1054,9 @@ extern "C" int32_t gmrfx_create_batched(int64_t n, const int64_t *colptr, const 
         h->S.ms_symbolic = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         h->opts.coords = nullptr;
         h->nbatch = nbatch; h->n_member = n; h->nnz_member = nnz;
-    } catch (const std::invalid_argument &e) {
-        g_create_err = e.what();
-        return GMRFX_ERR_INVALID_ARG;
-    } catch (const std::bad_alloc &) {
-        g_create_err = "out of host memory";
-        return GMRFX_ERR_ALLOC;
-    } catch (const std::exception &e) {
-        g_create_err = e.what();
-        return GMRFX_ERR_INVALID_ARG;
-    }
-    if (!h->opts.symbolic_only) {
-        try {
-            h->D.reset(new Device());
-            h->D->init(h->S, h->opts.device);
-            h->D->set_batch((int)nbatch, n, h->nnz_member);
-        } catch (const std::exception &e) {
-            g_create_err = e.what();
-            return std::string(e.what()).find("no HIP device") != std::string::npos ? GMRFX_ERR_NO_DEVICE : GMRFX_ERR_HIP;
-        }
-    }
+        return GMRFX_OK;
+    })) return e;
+    if (int32_t e = attach_device(h.get(), true)) return e;
     *out = h.release();
     return GMRFX_OK;
 }
@@ -1193,22 +1176,16 @@ static int32_t batch_quadform_impl(gmrfx_handle *h, const double *nz, const doub
         if (dev) { h->D->batch_quadform(nz, X, ldx, sx, nvec, mu, quad); return GMRFX_OK; }
         // host operands: staged through plain device buffers (freed on return), members packed (ld = n, stride = n nvec)
         const int64_t n = h->n_member, nb = h->nbatch;
-        struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } bx, bm, bn;
+        DevBlock bx, bm, bn;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         std::vector<double> xs((size_t)(n * nvec * nb));
         for (int64_t k = 0; k < nb; k++)
             for (int64_t v = 0; v < nvec; v++) std::memcpy(&xs[(size_t)((k * nvec + v) * n)], X + k * sx + v * ldx, (size_t)n * sizeof(double));
-        hip_check(hipMalloc(&bx.p, xs.size() * sizeof(double)), "hipMalloc");
-        hip_check(hipMemcpy(bx.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-        if (mu) {
-            hip_check(hipMalloc(&bm.p, (size_t)(n * nb) * sizeof(double)), "hipMalloc");
-            hip_check(hipMemcpy(bm.p, mu, (size_t)(n * nb) * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-        }
-        if (nz) {
-            hip_check(hipMalloc(&bn.p, (size_t)std::max<int64_t>(h->S.nnz_in, 1) * sizeof(double)), "hipMalloc");
-            hip_check(hipMemcpy(bn.p, nz, (size_t)h->S.nnz_in * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
-        }
-        h->D->batch_quadform((const double *)bn.p, (const double *)bx.p, n, n * nvec, nvec, (const double *)bm.p, quad);
+        bx.alloc((int64_t)xs.size());
+        bx.up(xs.data(), (int64_t)xs.size());
+        if (mu) { bm.alloc(n * nb); bm.up(mu, n * nb); }
+        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
+        h->D->batch_quadform(bn.p, bx.p, n, n * nvec, nvec, bm.p, quad);
         return GMRFX_OK;
     });
 }
@@ -1340,21 +1317,6 @@ extern "C" int32_t gmrfx_constraints_get(gmrfx_handle *h, double *A_tilde_T, int
     });
 }
 
-// a device copy of an n x nvec host block (ld = n), freed on return
-namespace {
-struct DevBlock {
-    double *p = nullptr;
-    ~DevBlock() { if (p) (void)hipFree(p); }
-    void alloc(int64_t count) { hip_check(hipMalloc((void **)&p, (size_t)std::max<int64_t>(count, 1) * sizeof(double) + 16), "hipMalloc"); }
-    void up(const double *src, int64_t ld, int64_t n, int64_t nvec) {
-        hip_check(hipMemcpy2D(p, (size_t)n * sizeof(double), src, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
-    }
-    void down(double *dst, int64_t ld, int64_t n, int64_t nvec) {
-        hip_check(hipMemcpy2D(dst, (size_t)ld * sizeof(double), p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
-    }
-};
-}  // namespace
-
 extern "C" int32_t gmrfx_constraints_mean(gmrfx_handle *h, const double *mu, double *mean_c, double *log_correction) {
     return guarded(h, [&]() -> int32_t {
         if (int32_t e = con_ready(h)) return e;
@@ -1419,9 +1381,7 @@ extern "C" int32_t gmrfx_constraints_var(gmrfx_handle *h, double *out) {
 
 static int32_t sample_impl(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t nrhs, const double *mu, double *X, int64_t ldx, bool dev) {
     return guarded(h, [&]() -> int32_t {
-        if (nrhs < 0) throw std::invalid_argument("nrhs < 0");
-        if (nrhs > 0 && (!Z || !X)) throw std::invalid_argument("Z/X is null");
-        if (nrhs > 0 && (ldz < h->S.n || ldx < h->S.n)) throw std::invalid_argument("leading dimension smaller than n");
+        check_rhs(h, Z, ldz, X, ldx, nrhs, "Z/X");
         if (int32_t e = con_ready(h)) return e;
         if (nrhs == 0) return GMRFX_OK;
         if (dev) {
