@@ -59,6 +59,8 @@ Device::~Device() {
     if (stream) { (void)hipStreamSynchronize(stream); }
     if (con_.ev0) (void)hipEventDestroy(con_.ev0);
     if (con_.ev1) (void)hipEventDestroy(con_.ev1);
+    if (bcon_.ev0) (void)hipEventDestroy(bcon_.ev0);
+    if (bcon_.ev1) (void)hipEventDestroy(bcon_.ev1);
     for (auto &p : allocs_) (void)hipFree(p.first);
     for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto &v : ev_level_) for (auto &e : v) (void)hipEventDestroy(e);

@@ -166,6 +166,25 @@ public:
     const std::vector<double> &con_linv() const { return con_.h_linv; }
     // max(diag Sigma - rowsum(B^2), 0) (selected inverse computed if absent); without constraints = selinv_diag
     void con_var(double *out_host);
+    // ---- the same for every member of a batched handle (gmrfx_batch_constraints_*): ONE A and e, everything derived per member ----
+    // Member k's At_k = Q_k^-1 A' and B_k = At_k L_ck^-T: n_member x m column-major blocks at + k n_member m; W_k (m x m, column-
+    // major) and L_ck^-1 (row-major) at + k m m. bcon_set builds the new state aside and throws std::bad_alloc, with nothing
+    // changed, when the two operand arrays do not fit. bcon_prepare (lazy, once per factorisation): memset + scatter of A' into all
+    // blocks, ONE member-strided forest solve of m columns, W_k by the chunked reduction, k_batch_con_chol (no download of W, no
+    // host loop), B_k; false = W_k is not positive definite for a member whose factorisation succeeded (bcon_cinfo: 0, 1 + the
+    // failing pivot, or -1 for a member whose factorisation failed -- its operands are NaN, nobody else's are touched).
+    void bcon_set(const ConHost &c);
+    int bcon_m() const { return bcon_.m; }
+    bool bcon_prepare();
+    const std::vector<double> &bcon_logdet_w() const { return bcon_.h_logdet; }
+    const std::vector<long long> &bcon_cinfo() const { return bcon_.h_cinfo; }
+    double bcon_ms() const { return bcon_.ms; }
+    void bcon_get(int member, double *At_host, long long ld, double *W_host);
+    // member k's n_member x nvec block at d_X + k sx (leading dimension ldx), d_mu: n_member x nbatch (nullable)
+    void bcon_correct(double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu);
+    // quad[k] = r_k' W_k^-1 r_k = |L_ck^-1 r_k|^2, r_k = A x_k - e, x_k = d_x + k n_member (d_x null: zero); host array of nbatch
+    void bcon_quad(const double *d_x, double *quad_host);
+    void bcon_var(double *out_host);       // n_member x nbatch
 
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
@@ -379,6 +398,22 @@ private:
         unsigned long long serial = 0;      // 0: nothing cached
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } con_;
+    struct BConDev {
+        int m = 0, maxchunks = 0;
+        long long nnz = 0, maxlen = 0, totchunks = 0, colcap = 0, piece = 0;
+        long long *rowptr = nullptr, *cinfo = nullptr;
+        int *col = nullptr, *choff = nullptr;
+        double *val = nullptr, *e = nullptr, *At = nullptr, *B = nullptr, *W = nullptr, *Linv = nullptr, *R = nullptr, *amu = nullptr, *part = nullptr,
+               *sig = nullptr, *stat = nullptr;      // stat: nbatch log det W, then nbatch |L_c^-1 r|^2
+        std::vector<double> h_logdet;
+        std::vector<long long> h_cinfo;
+        double ms = 0;
+        bool ok = false;
+        unsigned long long serial = 0;      // 0: nothing cached
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    } bcon_;
+    void bcon_free(BConDev &b);
+    void bcon_reserve_cols(long long want);
     void *con_alloc(size_t bytes);
     void con_release(void *p);
     void con_drop();

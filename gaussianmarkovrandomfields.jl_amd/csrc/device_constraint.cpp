@@ -5,6 +5,9 @@
 //   W  = A At       m x m, by the deterministic sparse-rows-times-dense reduction
 //   L_c, L_c^-1     host, plain C++ (m <= 64), L_c^-1 uploaded row-major
 //   B  = At L_c^-T  n x m, kept BESIDE At (2 x 8 n m bytes: 1 GB at n = 10^6, m = 64; the getter is a plain copy)
+// Batched handles (bcon_*, at the end of this file): one A and e, the same operands per member in member-strided blocks, and L_c,
+// L_c^-1 on the device (k_batch_con_chol) -- no download of W, no host loop over the members.
+#include <new>
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -51,7 +54,7 @@ void Device::con_drop() {
 void Device::con_set(const ConHost &c) {
     con_drop();
     if (c.m <= 0) return;
-    if (sharded() || batched()) throw std::invalid_argument("constraints need a plain (unsharded, unbatched) handle");
+    if (sharded() || nbatch_ > 1) throw std::invalid_argument("constraints need a plain (unsharded, unbatched) handle");
     const int m = c.m;
     const long long n = S_->n, nnz = c.rowptr[m];
     std::vector<int> choff((size_t)m + 1, 0);
@@ -210,6 +213,194 @@ void Device::con_var(double *out_host) {
     launch_gather_diag(stream, d_Z_, ds_.diagoff, ds_.perm, (int)n, con_.sig);
     launch_con_var(stream, con_.B, (int)n, con_.m, con_.sig);
     HC(hipMemcpyAsync(out_host, con_.sig, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+}
+
+// ---- batched handles: the constraint of every member (include/gmrfx.h: gmrfx_batch_constraints_*, gmrfx_batch_sample) -------------
+// Columns of X per piece of a correction (capacity of R: m x piece x B and of the chunk sums: totchunks x piece x B): the plain
+// handle's 1024 for one member, fewer for many -- 64 from B = 128 on, so that R stays at 4 MB for B = 128, m = 64. Columns are
+// independent of each other: the piece changes no bits.
+static long long bcon_piece(int nbatch) {
+    return std::min<long long>(kConColBatch, std::max<long long>(64, (8192 / std::max(nbatch, 1)) / 64 * 64));
+}
+
+void Device::bcon_free(BConDev &b) {
+    for (void *p : {(void *)b.rowptr, (void *)b.cinfo, (void *)b.col, (void *)b.choff, (void *)b.val, (void *)b.e, (void *)b.At, (void *)b.B, (void *)b.W,
+                    (void *)b.Linv, (void *)b.R, (void *)b.amu, (void *)b.part, (void *)b.sig, (void *)b.stat})
+        con_release(p);
+    const hipEvent_t e0 = b.ev0, e1 = b.ev1;
+    b = BConDev();
+    b.ev0 = e0; b.ev1 = e1;
+}
+
+void Device::bcon_set(const ConHost &c) {
+    HC(hipSetDevice(device));
+    if (c.m <= 0) {
+        HC(hipDeviceSynchronize());
+        bcon_free(bcon_);
+        return;
+    }
+    if (sharded() || !batched()) throw std::invalid_argument("batch constraints need an unsharded handle with its batch buffers");
+    if (nbatch_ > 65535) throw std::invalid_argument("batch constraints: more than 65535 members");
+    const int m = c.m, nb = nbatch_;
+    const long long n = nmember_, nnz = c.rowptr[m];
+    std::vector<int> choff((size_t)m + 1, 0);
+    long long maxlen = 0;
+    int maxchunks = 0;
+    for (int r = 0; r < m; r++) {
+        const long long len = c.rowptr[r + 1] - c.rowptr[r];
+        const int ch = (int)((len + kConChunk - 1) / kConChunk);
+        choff[r + 1] = choff[r] + ch;
+        maxlen = std::max(maxlen, len);
+        maxchunks = std::max(maxchunks, ch);
+    }
+    BConDev b;      // built aside: a failure leaves the handle's state as it was
+    try {
+        // the two big arrays first, and quietly: that they do not fit is an answer (GMRFX_ERR_ALLOC), not a failure of the device
+        for (double **big : {&b.At, &b.B}) {
+            void *p = nullptr;
+            const size_t bytes = (size_t)n * nb * m * sizeof(double) + 16;
+            if (hipMalloc(&p, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                throw std::bad_alloc();
+            }
+            allocs_.push_back({p, bytes});
+            bytes_total += (double)bytes;
+            *big = (double *)p;
+        }
+        b.rowptr = (long long *)con_alloc((size_t)(m + 1) * sizeof(long long));
+        b.col = (int *)con_alloc((size_t)nnz * sizeof(int));
+        b.val = (double *)con_alloc((size_t)nnz * sizeof(double));
+        b.e = (double *)con_alloc((size_t)m * sizeof(double));
+        b.choff = (int *)con_alloc((size_t)(m + 1) * sizeof(int));
+        b.W = (double *)con_alloc((size_t)m * m * nb * sizeof(double));
+        b.Linv = (double *)con_alloc((size_t)m * m * nb * sizeof(double));
+        b.amu = (double *)con_alloc((size_t)m * nb * sizeof(double));
+        b.sig = (double *)con_alloc((size_t)n * nb * sizeof(double));
+        b.stat = (double *)con_alloc(2 * (size_t)nb * sizeof(double));
+        b.cinfo = (long long *)con_alloc((size_t)nb * sizeof(long long));
+        HC(hipMemcpy(b.rowptr, c.rowptr.data(), (size_t)(m + 1) * sizeof(long long), hipMemcpyHostToDevice));
+        HC(hipMemcpy(b.col, c.col.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+        HC(hipMemcpy(b.val, c.val.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+        HC(hipMemcpy(b.e, c.e.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+        HC(hipMemcpy(b.choff, choff.data(), (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice));
+        if (!bcon_.ev0) { HC(hipEventCreate(&bcon_.ev0)); HC(hipEventCreate(&bcon_.ev1)); }
+    } catch (...) {
+        bcon_free(b);
+        throw;
+    }
+    b.m = m; b.nnz = nnz; b.maxlen = maxlen; b.maxchunks = maxchunks; b.totchunks = choff[m]; b.piece = bcon_piece(nb);
+    b.ev0 = bcon_.ev0; b.ev1 = bcon_.ev1;
+    HC(hipDeviceSynchronize());        // nothing in flight may still read the previous buffers
+    bcon_free(bcon_);
+    bcon_ = b;
+}
+
+void Device::bcon_reserve_cols(long long want) {
+    if (bcon_.colcap >= want) return;
+    void *R = con_alloc((size_t)bcon_.m * want * nbatch_ * sizeof(double));
+    void *part = nullptr;
+    try {
+        part = con_alloc((size_t)bcon_.totchunks * want * nbatch_ * sizeof(double));
+    } catch (...) {
+        con_release(R);
+        throw;
+    }
+    HC(hipDeviceSynchronize());
+    con_release(bcon_.R); con_release(bcon_.part);
+    bcon_.R = (double *)R; bcon_.part = (double *)part; bcon_.colcap = want;
+}
+
+bool Device::bcon_prepare() {
+    HC(hipSetDevice(device));
+    BConDev &b = bcon_;
+    const int m = b.m, nb = nbatch_;
+    if (m <= 0) return true;
+    if (b.serial == factor_serial_) return b.ok;
+    const long long n = nmember_;
+    b.serial = 0;
+    bcon_reserve_cols(64);       // W_k is an m-column product
+    if (bdiag_for_ != factor_serial_) enqueue_batch_diag(stream);       // the members' factorisation status, for k_batch_con_chol
+    HC(hipEventRecord(b.ev0, stream));
+    HC(hipMemsetAsync(b.At, 0, (size_t)n * nb * m * sizeof(double), stream));
+    launch_con_scatter(stream, b.rowptr, b.col, b.val, (int)n, m, b.maxlen, b.At, nb);
+    const MemberLayout ml{n, n * m, n * m};
+    solve(b.At, n, m, b.At, n, true, 0, &ml);         // ONE pass of the forest's sweeps for all members (m <= 64): in place
+    launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, b.At, n, m, b.part, nullptr, nullptr, b.W, nb, n * m);
+    launch_batch_con_chol(stream, b.W, m, nb, reinterpret_cast<const long long *>(d_bdiag_ + nbatch_), b.Linv, b.stat, b.cinfo);
+    launch_batch_con_void(stream, b.cinfo, b.At, n * m, b.W, m * m, nb);
+    launch_con_trsm(stream, b.At, b.Linv, (int)n, m, b.B, nb);
+    HC(hipEventRecord(b.ev1, stream));
+    b.h_logdet.assign((size_t)nb, 0.0);
+    b.h_cinfo.assign((size_t)nb, 0);
+    HC(hipMemcpyAsync(b.h_logdet.data(), b.stat, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipMemcpyAsync(b.h_cinfo.data(), b.cinfo, (size_t)nb * sizeof(long long), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    float ms = 0;
+    HC(hipEventElapsedTime(&ms, b.ev0, b.ev1));
+    b.ms = ms;
+    b.ok = true;
+    for (int k = 0; k < nb; k++) b.ok = b.ok && b.h_cinfo[(size_t)k] <= 0;
+    b.serial = factor_serial_;
+    return b.ok;
+}
+
+void Device::bcon_get(int member, double *At_host, long long ld, double *W_host) {
+    HC(hipSetDevice(device));
+    const int m = bcon_.m;
+    const long long n = nmember_;
+    if (m <= 0) return;
+    if (At_host) HC(hipMemcpy2D(At_host, (size_t)ld * sizeof(double), bcon_.At + (size_t)member * n * m, (size_t)n * sizeof(double),
+                                (size_t)n * sizeof(double), (size_t)m, hipMemcpyDeviceToHost));
+    if (W_host) HC(hipMemcpy(W_host, bcon_.W + (size_t)member * m * m, (size_t)m * m * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+void Device::bcon_correct(double *d_X, long long ldx, long long sx, long long nvec, const double *d_mu) {
+    HC(hipSetDevice(device));
+    BConDev &b = bcon_;
+    const int m = b.m, nb = nbatch_;
+    const long long n = nmember_;
+    if (nvec <= 0 || (m <= 0 && !d_mu)) return;
+    const long long piece = m > 0 ? b.piece : bcon_piece(nb);
+    if (m > 0) bcon_reserve_cols(std::min(piece, nvec));
+    // with a mean: A (X + mu) - e = A X + (A mu - e), the second term once
+    if (m > 0 && d_mu) launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_mu, n, 1, b.part, b.e, nullptr, b.amu, nb, n);
+    for (long long j0 = 0; j0 < nvec; j0 += piece) {
+        const int k = (int)std::min(piece, nvec - j0);
+        double *X = d_X + j0 * ldx;
+        if (m > 0)
+            launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, X, ldx, k, b.part, d_mu ? nullptr : b.e, d_mu ? b.amu : nullptr, b.R,
+                          nb, sx);
+        launch_con_apply(stream, b.B, b.Linv, b.R, d_mu, X, ldx, (int)n, m, k, nb, sx, n);
+    }
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+}
+
+void Device::bcon_quad(const double *d_x, double *quad_host) {
+    HC(hipSetDevice(device));
+    BConDev &b = bcon_;
+    const int m = b.m, nb = nbatch_;
+    const long long n = nmember_;
+    if (m <= 0) { std::fill(quad_host, quad_host + nb, 0.0); return; }
+    bcon_reserve_cols(1);
+    if (!d_x) HC(hipMemsetAsync(b.sig, 0, (size_t)n * sizeof(double), stream));       // a zero mean, shared by the members
+    launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_x ? d_x : b.sig, n, 1, b.part, b.e, nullptr, b.R, nb, d_x ? n : 0);
+    launch_batch_con_quad(stream, b.Linv, b.R, m, m, nb, b.stat + nb);
+    HC(hipMemcpyAsync(quad_host, b.stat + nb, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+}
+
+void Device::bcon_var(double *out_host) {
+    selinv_compute();
+    if (bcon_.m <= 0) { selinv_diag(out_host); return; }
+    const long long N = S_->n;
+    launch_gather_diag(stream, d_Z_, ds_.diagoff, ds_.perm, (int)N, bcon_.sig);
+    launch_con_var(stream, bcon_.B, (int)nmember_, bcon_.m, bcon_.sig, nbatch_);
+    HC(hipMemcpyAsync(out_host, bcon_.sig, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
 }

@@ -72,6 +72,9 @@ EXPORTS = [
     "gmrfx_batch_quadform", "gmrfx_batch_quadform_dev", "gmrfx_batch_refactorize_logpdf_dev",
     "gmrfx_constraints_set", "gmrfx_constraints_info", "gmrfx_constraints_get", "gmrfx_constraints_mean",
     "gmrfx_constraints_correct", "gmrfx_constraints_correct_dev", "gmrfx_constraints_var", "gmrfx_sample", "gmrfx_sample_dev",
+    "gmrfx_batch_constraints_set", "gmrfx_batch_constraints_info", "gmrfx_batch_constraints_get", "gmrfx_batch_constraints_mean",
+    "gmrfx_batch_constraints_correct", "gmrfx_batch_constraints_correct_dev", "gmrfx_batch_constraints_var", "gmrfx_batch_sample",
+    "gmrfx_batch_sample_dev", "gmrfx_batch_constrained_logpdf_dev",
 ]
 
 
@@ -186,6 +189,16 @@ def lib():
         L.gmrfx_constraints_var.argtypes = [vp, vp]
         L.gmrfx_sample.argtypes = [vp, vp, i64, i64, vp, vp, i64]
         L.gmrfx_sample_dev.argtypes = [vp, vp, i64, i64, vp, vp, i64]
+        L.gmrfx_batch_constraints_set.argtypes = [vp, i64, vp, vp, vp, i32, vp]
+        L.gmrfx_batch_constraints_info.argtypes = [vp, C.POINTER(i64), vp, C.POINTER(dbl), vp, C.POINTER(dbl)]
+        L.gmrfx_batch_constraints_get.argtypes = [vp, i64, vp, i64, vp]
+        L.gmrfx_batch_constraints_mean.argtypes = [vp, vp, vp, vp]
+        L.gmrfx_batch_constraints_correct.argtypes = [vp, vp, i64, i64, i64]
+        L.gmrfx_batch_constraints_correct_dev.argtypes = [vp, vp, i64, i64, i64]
+        L.gmrfx_batch_constraints_var.argtypes = [vp, vp]
+        L.gmrfx_batch_sample.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, i64]
+        L.gmrfx_batch_sample_dev.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, i64]
+        L.gmrfx_batch_constrained_logpdf_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

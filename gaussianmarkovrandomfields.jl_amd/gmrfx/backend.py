@@ -878,3 +878,121 @@ class MI355XBatchBackend:
         self._info = info
         check(code, self._h)
         return ld, quad, info.copy()
+
+    # -- one constraint A x = e for every member, computed per member on the device (include/gmrfx.h, gmrfx_batch_constraints_*) --
+    def set_constraints(self, A, e) -> None:
+        """ONE A (m <= 64 sparse rows over the member's n columns) and e for all members. What is derived (A~'_k = Q_k^-1 A',
+        W_k = A A~'_k, L_ck, B_k) is built lazily per member on the device, once per factorisation."""
+        A = sp.csr_matrix(A, dtype=np.float64)
+        e = np.ascontiguousarray(e, dtype=np.float64).reshape(-1)
+        if A.shape[1] != self.n:
+            raise ValueError(f"Constraint matrix size {A.shape} incompatible with member size {self.n}")
+        if A.shape[0] != e.shape[0]:
+            raise ValueError(f"Constraint matrix rows {A.shape[0]} != constraint vector length {e.shape[0]}")
+        self.set_constraints_csr(A.shape[0], A.indptr, A.indices, A.data, e)
+
+    def set_constraints_csr(self, m: int, rowptr, colind, values, e) -> None:
+        """The raw form: CSR arrays as given (0-based), checked by the library."""
+        rp = np.ascontiguousarray(rowptr, dtype=np.int64)
+        ci = np.ascontiguousarray(colind, dtype=np.int64)
+        va = np.ascontiguousarray(values, dtype=np.float64)
+        ev = np.ascontiguousarray(e, dtype=np.float64)
+        if rp.shape != (m + 1,) or ev.shape != (m,) or ci.shape != va.shape or (m > 0 and ci.shape[0] < rp[-1]):
+            raise ValueError("constraints: array lengths do not match m")
+        check(lib().gmrfx_batch_constraints_set(self._h, m, ptr(rp), ptr(ci), ptr(va), 0, ptr(ev)), self._h)
+
+    def clear_constraints(self) -> None:
+        check(lib().gmrfx_batch_constraints_set(self._h, 0, None, None, None, 0, None), self._h)
+
+    def constraint_info(self, check_posdef: bool = True) -> dict:
+        """m, log det(A A') and -- on a numeric handle, preparing the members if needed -- logdet_W (B,), cinfo (B,) (0, 1 + the
+        failing pivot of W_k, -1 = member k's factorisation failed) and the GPU time of the most recent preparation.
+        check_posdef = False returns the dictionary also when some W_k is not positive definite."""
+        m, lda, ms = C.c_int64(0), C.c_double(0.0), C.c_double(0.0)
+        if self.symbolic_only:
+            check(lib().gmrfx_batch_constraints_info(self._h, C.byref(m), None, C.byref(lda), None, None), self._h)
+            return {"m": m.value, "logdet_AAt": lda.value}
+        ldw = np.zeros(self.nbatch)
+        ci = np.zeros(self.nbatch, np.int64)
+        code = lib().gmrfx_batch_constraints_info(self._h, C.byref(m), ptr(ldw), C.byref(lda), ptr(ci), C.byref(ms))
+        if check_posdef or code != _lib.ERR_NOT_POSDEF:
+            check(code, self._h)
+        return {"m": m.value, "logdet_W": ldw, "logdet_AAt": lda.value, "cinfo": ci, "ms": ms.value}
+
+    def _con_m(self) -> int:
+        m = C.c_int64(0)
+        check(lib().gmrfx_batch_constraints_info(self._h, C.byref(m), None, None, None, None), self._h)
+        return m.value
+
+    def constraint_fields(self, member: int):
+        """(A_tilde_T, W) of one member: the n x m solve Q_k^-1 A' and W_k = A A~'_k."""
+        m = self._con_m()
+        At = np.empty((self.n, m), order="F")
+        W = np.empty((m, m), order="F")
+        check(lib().gmrfx_batch_constraints_get(self._h, int(member), ptr(At), self.n, ptr(W)), self._h)
+        return At, W
+
+    def constrained_mean(self, mu=None):
+        """(mean_c (n, B), log_constraint_correction (B,)) of workspace_gmrf.jl:43-51 per member; mu: (n,), (n, B) or None = 0."""
+        mu = self._mean(mu)
+        out = np.empty((self.n, self.nbatch), order="F")
+        lc = np.empty(self.nbatch)
+        check(lib().gmrfx_batch_constraints_mean(self._h, ptr(mu), ptr(out), ptr(lc)), self._h)
+        return out, lc
+
+    def constrained_var(self) -> np.ndarray:
+        """max(diag Sigma_k - rowsum(B_k^2), 0): (n, B); without a constraint = selinv_diag()."""
+        out = np.empty((self.n, self.nbatch), order="F")
+        check(lib().gmrfx_batch_constraints_var(self._h, ptr(out)), self._h)
+        return out
+
+    def constraint_correct(self, X) -> np.ndarray:
+        """x - A~'_k (L_ck \\ (A x - e)) on every column of every member: X (n, B) or (n, r, B). Returns a fresh array."""
+        Xf, r, s = self._members(X, "X")
+        Xf = np.array(Xf, order="F", copy=True)
+        check(lib().gmrfx_batch_constraints_correct(self._h, ptr(Xf), self.n, s, r), self._h)
+        return Xf
+
+    def constraint_correct_dev(self, d_X: int, ldx: int, sx: int, nvec: int) -> None:
+        check(lib().gmrfx_batch_constraints_correct_dev(self._h, d_X or None, ldx, sx, nvec), self._h)
+
+    def sample(self, Z, mean=None) -> np.ndarray:
+        """`_rand!` per member on given standard-normal draws: P' L_k^-T Z_k + mean_k, then the constraint correction."""
+        Zf, r, s = self._members(Z, "Z")
+        mu = self._mean(mean)
+        X = np.empty_like(Zf, order="F")
+        check(lib().gmrfx_batch_sample(self._h, ptr(Zf), self.n, s, r, ptr(mu), ptr(X), self.n, s), self._h)
+        return X
+
+    def sample_dev(self, d_Z: int, ldz: int, sz: int, nrhs: int, d_X: int, ldx: int, sx: int, d_mu: int = 0) -> None:
+        check(lib().gmrfx_batch_sample_dev(self._h, d_Z or None, ldz, sz, nrhs, d_mu or None, d_X or None, ldx, sx), self._h)
+
+    def constrained_logpdf_dev(self, d_nzval: int, d_X: int, ldx: int, sx: int, nvec: int, d_mu: int = 0, check_posdef: bool = True):
+        """gmrfx_batch_constrained_logpdf_dev: (logdet (B,), quad (nvec, B), log_correction (B,), info (B,), cinfo (B,)) in one call.
+        logpdf_k = -quad / 2 + logdet_k / 2 - n log(2 pi) / 2 + log_correction_k (workspace_gmrf.jl:288-305).
+        check_posdef = False returns the tuple also when a member or some W_k is not positive definite."""
+        quad = np.empty((max(nvec, 0), self.nbatch), order="F")
+        ld = np.empty(self.nbatch)
+        lc = np.empty(self.nbatch)
+        info = np.zeros(self.nbatch, np.int64)
+        ci = np.zeros(self.nbatch, np.int64)
+        code = lib().gmrfx_batch_constrained_logpdf_dev(self._h, d_nzval, d_X or None, ldx, sx, nvec, d_mu or None, quad.ctypes.data,
+                                                        ptr(ld), ptr(lc), ptr(info), ptr(ci))
+        self._info = info
+        if check_posdef or code != _lib.ERR_NOT_POSDEF:
+            check(code, self._h)
+        return ld, quad, lc, info.copy(), ci
+
+    def constrained_logpdf(self, NZ, X, mean=None):
+        """The host-array form of constrained_logpdf_dev (operands staged through torch device tensors)."""
+        import torch
+        nz = self._values(NZ)
+        Xf, nvec, s = self._members(X, "X")
+        mu = self._mean(mean)
+        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+        d_nz = torch.from_numpy(np.ascontiguousarray(nz.T)).to(dev)
+        d_x = torch.from_numpy(np.ascontiguousarray(Xf.reshape(self.n, -1, order="F").T)).to(dev)
+        d_mu = None if mu is None else torch.from_numpy(np.ascontiguousarray(mu.T)).to(dev)
+        out = self.constrained_logpdf_dev(d_nz.data_ptr(), d_x.data_ptr(), self.n, s, nvec, 0 if d_mu is None else d_mu.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out

@@ -584,6 +584,56 @@ function logpdf_terms(bb::MI355XBatch, NZ::Matrix{Float64}, Z::Matrix{Float64}; 
     return logdet(bb), quad, info(bb)
 end
 
+# ONE constraint A x = e for every member (gmrfx_batch_constraints_set: m <= 64 rows over the member's n columns). What is derived
+# from it -- A~'_k = Q_k^-1 A', W_k = A A~'_k, L_ck, B_k -- is built per member on the device, once per factorisation.
+function set_constraints!(bb::MI355XBatch, A::AbstractMatrix, e::AbstractVector)
+    At = sparse(transpose(sparse(A)))                 # CSC of A' = CSR of A
+    cp = Vector{Int}(SparseArrays.getcolptr(At)); rv = Vector{Int}(rowvals(At)); nz = Vector{Float64}(nonzeros(At))
+    ev = Vector{Float64}(e)
+    size(A, 2) == bb.n || throw(ArgumentError("Constraint matrix size $(size(A)) incompatible with member size $(bb.n)"))
+    size(A, 1) == length(ev) || throw(ArgumentError("Constraint matrix rows $(size(A, 1)) != constraint vector length $(length(ev))"))
+    GC.@preserve cp rv nz ev check(ccall((:gmrfx_batch_constraints_set, LIB), Int32,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}), bb.h.ptr, size(A, 1), cp, rv, nz, 1, ev), bb.h)
+    return nothing
+end
+function clear_constraints!(bb::MI355XBatch)
+    check(ccall((:gmrfx_batch_constraints_set, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}),
+        bb.h.ptr, 0, C_NULL, C_NULL, C_NULL, 1, C_NULL), bb.h)
+    return nothing
+end
+
+# logpdf_terms plus the members' log_constraint_correction (workspace_gmrf.jl:46-51, 288-305):
+# logpdf_k = -quad_k / 2 + logdet_k / 2 - n log(2 pi) / 2 + log_correction_k
+function constrained_logpdf_terms(bb::MI355XBatch, NZ::Matrix{Float64}, Z::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing)
+    ld, quad, inf = logpdf_terms(bb, NZ, Z; mean = mean)
+    lc = Vector{Float64}(undef, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve mean lc check(ccall((:gmrfx_batch_constraints_mean, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        bb.h.ptr, mu, C_NULL, lc), bb.h)
+    return ld, quad, lc, inf
+end
+
+# `_rand!` per member on given draws: X_k = P' L_k^-T Z_k + mean_k, then the constraint correction; Z: n x nbatch or n x r x nbatch
+function sample(bb::MI355XBatch, Z::Union{Matrix{Float64}, Array{Float64, 3}}, mean::Union{Nothing, Matrix{Float64}} = nothing)
+    (ndims(Z) == 2 && size(Z) == (bb.n, bb.nbatch)) || (ndims(Z) == 3 && size(Z, 1) == bb.n && size(Z, 3) == bb.nbatch) ||
+        throw(DimensionMismatch("expected n x nbatch or n x r x nbatch"))
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    r = ndims(Z) == 3 ? size(Z, 2) : 1
+    X = similar(Z)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve Z X mean check(ccall((:gmrfx_batch_sample, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64),
+        bb.h.ptr, Z, bb.n, bb.n * r, r, mu, X, bb.n, bb.n * r), bb.h)
+    return X
+end
+
+# max(diag Sigma_k - rowsum(B_k^2), 0) of every member: n x nbatch; without a constraint selinv_diag(bb)
+function constrained_var(bb::MI355XBatch)
+    out = Matrix{Float64}(undef, bb.n, bb.nbatch)
+    GC.@preserve out check(ccall((:gmrfx_batch_constraints_var, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, out), bb.h)
+    return out
+end
+
 # deepcopy(bb) (Newton loops copy their caches) reaches the owning Handle: a copy of a handle is a clone of the native one
 # (gmrfx_clone), never a second owner of the same pointer
 function Base.deepcopy_internal(h::Handle, stackdict::IdDict)

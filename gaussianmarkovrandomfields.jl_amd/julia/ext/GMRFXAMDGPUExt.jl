@@ -20,6 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
+import GMRFX: MI355XBatch, constrained_logpdf_terms
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -87,6 +88,22 @@ function logpdf_terms(b::MI355XBackend, d_nz::ROCVector{Float64}, X::ROCMatrix{F
     return quad, ld[]
 end
 
+
+# the batched, constrained evaluation with everything resident in HBM (gmrfx_batch_constrained_logpdf_dev): d_nz nnz x B, Z n x B,
+# mean n x B -> (logdet, quad, log_correction, info, cinfo), each of length B
+function constrained_logpdf_terms(bb::MI355XBatch, d_nz::ROCMatrix{Float64}, Z::ROCMatrix{Float64}; mean::Union{Nothing, ROCMatrix{Float64}} = nothing)
+    size(d_nz) == (bb.nnz, bb.nbatch) || throw(DimensionMismatch("d_nz must be nnz x nbatch"))
+    size(Z) == (bb.n, bb.nbatch) || throw(DimensionMismatch("Z must be n x nbatch"))
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    AMDGPU.synchronize()
+    quad = Vector{Float64}(undef, bb.nbatch); ld = similar(quad); lc = similar(quad)
+    cinfo = zeros(Int64, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : devptr(mean)
+    GC.@preserve d_nz Z mean quad ld lc cinfo check(ccall((:gmrfx_batch_constrained_logpdf_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}),
+        bb.h.ptr, devptr(d_nz), devptr(Z), bb.n, bb.n, 1, mu, quad, ld, lc, bb.info, cinfo), bb.h)
+    return ld, quad, lc, copy(bb.info), cinfo
+end
 
 # ---- one factorisation over several GPUs: the native RCCL driver (libgmrfx_rccl.so) with operands resident in HBM ----
 function refactorize!(sf::ShardedMI355X, d_nz::ROCVector{Float64})

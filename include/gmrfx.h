@@ -433,7 +433,7 @@ int32_t gmrfx_batch_refactorize_logpdf_dev(gmrfx_handle *h, const double *d_nzva
  * gmrfx_constraints_set: A as m sparse rows (CSR arrays = the CSC arrays of A', what `sparse(A')` holds), e: m values; duplicates within
  *   a row are summed; m = 0 removes the constraint. The handle keeps A (on the device with 32-bit columns), e and the host-computed
  *   log det(A A') (:51). GMRFX_ERR_INVALID_ARG with a message and NOTHING changed for: a column outside [0, n), a non-monotone rowptr,
- *   m > 64, an empty row, a batched handle (gmrfx_batch_size > 1), a sharded handle. Works on symbolic_only handles (validation;
+ *   m > 64, an empty row, a batched handle (gmrfx_batch_size > 1; see gmrfx_batch_constraints_set), a sharded handle. Works on symbolic_only handles (validation;
  *   numeric use there returns GMRFX_ERR_NO_DEVICE). gmrfx_clone carries A and e; the clone recomputes what is derived.
  * gmrfx_constraints_info: *m (0 without a constraint, the other outputs are then 0), *logdet_AAt, and -- these two trigger the
  *   preparation when they are asked for (non-null) -- *logdet_W = log det(A Q^-1 A') = logdet(L_c) (:50) and *ms = GPU time of the most
@@ -463,6 +463,64 @@ int32_t gmrfx_constraints_var(gmrfx_handle *h, double *out /* n */);
 int32_t gmrfx_sample(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t nrhs, const double *mu /* nullable */, double *X, int64_t ldx);
 int32_t gmrfx_sample_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t nrhs, const double *d_mu /* nullable */, double *d_X,
                          int64_t ldx);
+
+/* ---- the same constraint for every member of a batched handle ---------------------------------------------------------------------
+ * The intrinsic latent models of the hyper-parameter loop (Besag, RW1, RW2, BYM2) come with a sum-to-zero constraint, and its
+ * log-density term log_constraint_correction (src/workspace/workspace_gmrf.jl:46-51, 288-305) depends on Q through W = A Q^-1 A':
+ * it differs for every member. A batched handle therefore takes ONE A (m <= 64 sparse rows over the MEMBER's n columns) and ONE e,
+ * shared by all B members, and computes everything derived from them PER MEMBER on the device, once per factorisation: memset +
+ * scatter of A' into B blocks in one launch, ONE forest solve of m columns (the gmrfx_batch_solve_dev path), W_k = A A~'_k by the
+ * deterministic chunked reduction, then one workgroup per member for the Cholesky factor L_ck of W_k, its inverse, log det W_k and the
+ * status word (no download of W, no host loop over the members), and B_k = A~'_k L_ck^-T. Member k's A~'_k and B_k are n x m
+ * column-major blocks at k n m of two device arrays (2 x 8 n B m bytes). Cached per factorisation and dropped by every
+ * refactorisation. Same determinism as above: fixed summation orders, no atomics, bits independent of ldx, sx and alignment.
+ * A plain (unsharded) handle is a batch of one, as for the other gmrfx_batch_* calls. A handle holds at most ONE kind of constraint:
+ * gmrfx_batch_constraints_set while a plain constraint is set, or gmrfx_constraints_set while a batch constraint is set, is
+ * GMRFX_ERR_INVALID_ARG. gmrfx_constraints_set keeps refusing handles with more than one member.
+ *
+ * gmrfx_batch_constraints_set: CSR conventions and validation of gmrfx_constraints_set, columns in [0, n_member); duplicates are
+ *   summed; m = 0 clears. GMRFX_ERR_INVALID_ARG with a message and NOTHING changed for invalid input or a sharded handle;
+ *   GMRFX_ERR_ALLOC, nothing changed, when the two operand arrays do not fit. Works on symbolic_only handles. gmrfx_clone carries A
+ *   and e; the clone recomputes what is derived.
+ * gmrfx_batch_constraints_info: *m, *logdet_AAt, and -- these trigger the preparation when asked for -- logdet_W[k] = log det W_k,
+ *   cinfo[k] = 0, or 1 + j when pivot j of W_k fails (a pivot not above 16 m eps |W_jj|), or -1 when member k's factorisation itself
+ *   failed (member k's outputs are then NaN everywhere), *ms = GPU time of the most recent preparation. Any pointer may be NULL.
+ * gmrfx_batch_constraints_get: host copies of member `member`'s A~' (n x m, leading dimension ld) and W (m x m), either nullable.
+ * gmrfx_batch_constraints_mean: per member the two quantities of gmrfx_constraints_mean: mean_c (n x B) = mu_k - A~'_k W_k^-1 (A mu_k - e)
+ *   (mu: n x B, NULL = 0) and log_correction[k]; r_k' W_k^-1 r_k = |L_ck^-1 r_k|^2 is formed on the device. Host arrays, each nullable.
+ * gmrfx_batch_constraints_correct(_dev): in place X_k <- X_k - A~'_k W_k^-1 (A X_k - e) on the members' n x nvec blocks at X + k sx,
+ *   leading dimension ldx (layout of gmrfx_batch_solve). A no-op without a constraint.
+ * gmrfx_batch_sample(_dev): X_k = P' L_k^-T Z_k + mu_k (mu: n x B, nullable), then the correction. Without a constraint and with
+ *   mu = NULL the result has the bits of gmrfx_batch_backward_solve(_dev).
+ * gmrfx_batch_constraints_var: out (n x B) = max(Sigma_ii - sum_j B_ij^2, 0) per member; without a constraint gmrfx_selinv_diag,
+ *   bit for bit.
+ * gmrfx_batch_constrained_logpdf_dev: the constrained twin of gmrfx_batch_refactorize_logpdf_dev: refactorisation, the quadratic forms
+ *   beside it, per-member log det and info, the preparation above, and log_correction[k] with r_k = e - A mu_k. quad, logdet and info
+ *   have the bits of gmrfx_batch_refactorize_logpdf_dev, log_correction those of gmrfx_batch_constraints_mean after the same
+ *   refactorisation. log_correction (B), info (B) and cinfo (B) are host arrays, each nullable.
+ * Errors: GMRFX_ERR_NOT_FACTORIZED before the first factorisation, GMRFX_ERR_NO_DEVICE on symbolic_only handles.
+ *   GMRFX_ERR_NOT_POSDEF when W_k fails for a member whose factorisation succeeded (a rank-deficient A): cinfo is filled in either
+ *   way and the handle stays usable. A member whose factorisation failed is reported through cinfo only (and through info / the
+ *   handle's check_posdef by the factorising call); it never disturbs another member. */
+int32_t gmrfx_batch_constraints_set(gmrfx_handle *h, int64_t m, const int64_t *rowptr, const int64_t *colind, const double *values,
+                                    int32_t index_base, const double *e);
+int32_t gmrfx_batch_constraints_info(gmrfx_handle *h, int64_t *m, double *logdet_W /* nbatch */, double *logdet_AAt,
+                                     int64_t *cinfo /* nbatch */, double *ms);
+int32_t gmrfx_batch_constraints_get(gmrfx_handle *h, int64_t member, double *A_tilde_T /* n x m, nullable */, int64_t ld,
+                                    double *W /* m x m, nullable */);
+int32_t gmrfx_batch_constraints_mean(gmrfx_handle *h, const double *mu /* n x nbatch, nullable = 0 */, double *mean_c /* n x nbatch, nullable */,
+                                     double *log_correction /* nbatch, nullable */);
+int32_t gmrfx_batch_constraints_correct(gmrfx_handle *h, double *X, int64_t ldx, int64_t sx, int64_t nvec);
+int32_t gmrfx_batch_constraints_correct_dev(gmrfx_handle *h, double *d_X, int64_t ldx, int64_t sx, int64_t nvec);
+int32_t gmrfx_batch_constraints_var(gmrfx_handle *h, double *out /* n x nbatch */);
+int32_t gmrfx_batch_sample(gmrfx_handle *h, const double *Z, int64_t ldz, int64_t sz, int64_t nrhs, const double *mu /* n x nbatch, nullable */,
+                           double *X, int64_t ldx, int64_t sx);
+int32_t gmrfx_batch_sample_dev(gmrfx_handle *h, const double *d_Z, int64_t ldz, int64_t sz, int64_t nrhs,
+                               const double *d_mu /* n x nbatch, nullable */, double *d_X, int64_t ldx, int64_t sx);
+int32_t gmrfx_batch_constrained_logpdf_dev(gmrfx_handle *h, const double *d_nzval, const double *d_X, int64_t ldx, int64_t sx, int64_t nvec,
+                                           const double *d_mu, double *quad /* host, nvec x nbatch */, double *logdet /* host, nbatch */,
+                                           double *log_correction /* host, nbatch, nullable */, int64_t *info /* host, nbatch, nullable */,
+                                           int64_t *cinfo /* host, nbatch, nullable */);
 
 /* KL-optimal sparse approximate Cholesky factor, L L' ~ Theta^-1: a batch of small dense problems, one
  * workgroup each. A task = local rows R (task_rows[task_rowptr[t] .. task_rowptr[t+1]), in the caller's local order)
