@@ -61,6 +61,8 @@ Device::~Device() {
     if (con_.ev1) (void)hipEventDestroy(con_.ev1);
     if (bcon_.ev0) (void)hipEventDestroy(bcon_.ev0);
     if (bcon_.ev1) (void)hipEventDestroy(bcon_.ev1);
+    if (rb_.ev0) (void)hipEventDestroy(rb_.ev0);
+    if (rb_.ev1) (void)hipEventDestroy(rb_.ev1);
     for (auto &p : allocs_) (void)hipFree(p.first);
     for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
     for (auto &v : ev_level_) for (auto &e : v) (void)hipEventDestroy(e);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "device_plan.h"
+#include "rbmc_plan.h"
 
 namespace gmrfx { constexpr int kSyrkPipedMinCols = 128; }     // see DeviceFactor::syrk_piped_min_
 
@@ -185,6 +186,14 @@ public:
     // quad[k] = r_k' W_k^-1 r_k = |L_ck^-1 r_k|^2, r_k = A x_k - e, x_k = d_x + k n_member (d_x null: zero); host array of nbatch
     void bcon_quad(const double *d_x, double *quad_host);
     void bcon_var(double *out_host);       // n_member x nbatch
+
+    // ---- Rao-Blackwellised Monte Carlo marginal variances (device_rbmc.cpp, rbmc.hip; gmrfx_rbmc_var) --------------------------------
+    // plan = nullptr: RBMCStrategy, else BlockRBMCStrategy on that plan. Z: n x k column-major standard normals (host or device),
+    // processed in blocks of kRbmcW columns: backward sweep -> transpose -> estimator kernels, per-row (mean, M2) merged block by
+    // block; device memory O(n kRbmcW) for any k. d_nz = Q's values on the device (nullptr: the held values). out: n doubles.
+    void rbmc_var(const RbmcSym &sym, const RbmcPlan *plan, const double *d_nz, const double *Z, long long ldz, bool z_on_device, long long k,
+                  double *out, bool out_on_device);
+    double ms_rbmc = 0, ms_rbmc_bsolve = 0;      // GPU time of the most recent rbmc_var, and the backward sweeps' part of it
 
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
@@ -412,6 +421,18 @@ private:
         unsigned long long serial = 0;      // 0: nothing cached
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } bcon_;
+    struct RbmcState {
+        long long *rp = nullptr, *bptr = nullptr, *eptr = nullptr;
+        int *col = nullptr, *pos = nullptr, *dpos = nullptr, *rows = nullptr, *ns = nullptr, *loc = nullptr, *order[kRbmcClasses] = {};
+        unsigned char *owner = nullptr;
+        int cnt[kRbmcClasses] = {};
+        double *Xc = nullptr, *Xt = nullptr, *mean = nullptr, *m2 = nullptr, *base = nullptr, *out = nullptr, *scrM = nullptr, *scrR = nullptr;
+        int plan_enclosure = -2;
+        unsigned long long plan_serial = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    } rb_;
+    void rbmc_upload_sym(const RbmcSym &sym);
+    void rbmc_upload_plan(const RbmcPlan &plan);
     void bcon_free(BConDev &b);
     void bcon_reserve_cols(long long want);
     void *con_alloc(size_t bytes);

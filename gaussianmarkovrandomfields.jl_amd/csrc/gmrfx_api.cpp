@@ -33,6 +33,10 @@ struct gmrfx_handle {
     ConHost con;
     // the same for every member of a batch (gmrfx_batch_constraints_set): one A (n_member columns) and e; at most one of the two is set
     ConHost bcon;
+    // host analysis of the RBMC variance estimators (gmrfx_rbmc_plan / gmrfx_rbmc_var), built lazily: the symmetric row structure
+    // once, the block plan of the most recent enclosure_size
+    RbmcSym rsym;
+    RbmcPlan rplan;
 };
 
 static thread_local std::string g_create_err;
@@ -921,6 +925,7 @@ extern "C" int32_t gmrfx_get_stats(const gmrfx_handle *h, gmrfx_stats *out, int3
         st.ms_quadform = D.ms_quadform;
         st.inv_cap = D.inv_cap();
         st.ms_inv_decide = D.ms_inv_decide;
+        st.ms_rbmc = D.ms_rbmc;
         if (D.factorized) st.fail_col = const_cast<Device &>(D).fail_col();
     }
     std::memcpy(out, &st, std::min<size_t>((size_t)struct_size, sizeof(st)));
@@ -1627,4 +1632,63 @@ extern "C" int32_t gmrfx_batch_constrained_logpdf_dev(gmrfx_handle *h, const dou
         if (int32_t e = batch_status(h, inf)) return e;
         return rc;
     });
+}
+
+// ---- Rao-Blackwellised Monte Carlo marginal variances (include/gmrfx.h; csrc/rbmc_plan.cpp, Device::rbmc_var, csrc/rbmc.hip) --------
+static const RbmcPlan &rbmc_plan_for(gmrfx_handle *h, int32_t enclosure_size) {
+    if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+    if (h->rplan.enclosure != enclosure_size) rbmc_build_plan(h->rsym, h->S.n, enclosure_size, h->rplan);     // (unchanged when it throws)
+    return h->rplan;
+}
+
+extern "C" int32_t gmrfx_rbmc_plan(gmrfx_handle *h, int32_t enclosure_size, int32_t index_base, int64_t *counts, int64_t *block_ptr,
+                                   int64_t *rows, int64_t *n_interior, int64_t *owner) {
+    return guarded(h, [&]() -> int32_t {
+        if (!counts) throw std::invalid_argument("rbmc_plan: counts is null");
+        if (enclosure_size < 0) throw std::invalid_argument("rbmc_plan: enclosure_size < 0 (the plain estimator has no blocks)");
+        if (index_base != 0 && index_base != 1) throw std::invalid_argument("rbmc_plan: index_base must be 0 or 1");
+        if (h->S.shard_plan) throw std::invalid_argument("rbmc_plan: sharded handles are not supported");
+        const RbmcPlan &P = rbmc_plan_for(h, enclosure_size);
+        const i64 nb = P.nblocks(), tot = P.block_ptr[nb];
+        counts[0] = nb; counts[1] = tot; counts[2] = P.max_block;
+        if (block_ptr) for (i64 b = 0; b <= nb; b++) block_ptr[b] = P.block_ptr[b];
+        if (rows) for (i64 r = 0; r < tot; r++) rows[r] = (i64)P.rows[r] + index_base;
+        if (n_interior) for (i64 b = 0; b < nb; b++) n_interior[b] = P.n_interior[b];
+        if (owner) for (i64 r = 0; r < tot; r++) owner[r] = P.owner[r];
+        return GMRFX_OK;
+    });
+}
+
+static int32_t rbmc_var_impl(gmrfx_handle *h, const double *nz, const double *Z, int64_t ldz, int64_t nsamples, int32_t enclosure_size,
+                             double *out, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        if (!Z || !out) throw std::invalid_argument("rbmc_var: Z/out is null");
+        if (nsamples < 2) throw std::invalid_argument("rbmc_var: nsamples < 2 (the corrected sample variance needs two samples)");
+        if (ldz < h->S.n) throw std::invalid_argument("rbmc_var: ldz < n");
+        if (enclosure_size < -1) throw std::invalid_argument("rbmc_var: enclosure_size < -1");
+        if (h->S.shard_plan) throw std::invalid_argument("rbmc_var: sharded handles are not supported");
+        if (h->con.m > 0 || h->bcon.m > 0) throw std::invalid_argument("rbmc_var: the handle holds a constraint set; the constrained estimator is not implemented");
+        if (int32_t e = need_device(h, true)) return e;
+        const long long fc = h->D->fail_col();
+        if (fc >= 0) {
+            h->err = "rbmc_var: the last factorisation failed (non-positive pivot at elimination step " + std::to_string(fc + 1) + ")";
+            return GMRFX_ERR_NOT_POSDEF;
+        }
+        if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+        const RbmcPlan *plan = enclosure_size >= 0 ? &rbmc_plan_for(h, enclosure_size) : nullptr;
+        if (dev) { h->D->rbmc_var(h->rsym, plan, nz, Z, ldz, true, nsamples, out, true); return GMRFX_OK; }
+        DevBlock bn;
+        hip_check(hipSetDevice(h->D->device), "hipSetDevice");
+        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
+        h->D->rbmc_var(h->rsym, plan, bn.p, Z, ldz, false, nsamples, out, false);
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_rbmc_var(gmrfx_handle *h, const double *nzval, const double *Z, int64_t ldz, int64_t nsamples, int32_t enclosure_size,
+                                  double *out) {
+    return rbmc_var_impl(h, nzval, Z, ldz, nsamples, enclosure_size, out, false);
+}
+extern "C" int32_t gmrfx_rbmc_var_dev(gmrfx_handle *h, const double *d_nzval, const double *d_Z, int64_t ldz, int64_t nsamples,
+                                      int32_t enclosure_size, double *d_out) {
+    return rbmc_var_impl(h, d_nzval, d_Z, ldz, nsamples, enclosure_size, d_out, true);
 }

@@ -524,4 +524,23 @@ void launch_sel_diag(hipStream_t st, const DevSym &S, const int *list, int nacti
 void launch_sel_dense(hipStream_t st, const DevSym &S, const int *list, int nfronts, int phase, int max_c, int max_trail,
                       const double *L, double *Z, const double *ZB, double *Yt, double *Z21t, const long long *woff);
 
+// rbmc.hip -- Rao-Blackwellised Monte Carlo marginal variances (gmrfx_rbmc_var). Samples go through in blocks of kRbmcW columns:
+// ONE pass of the backward sweep (Device::pass_width), and one sample per lane of a wave in the estimator kernels.
+constexpr int kRbmcW = 64;
+// symmetric row structure of Q (RbmcSym) and, for the block estimator, the plan's tables (RbmcPlan) on the device
+struct RbmcDev {
+    const long long *rp; const int *col, *pos, *dpos;
+    const long long *bptr; const int *rows, *ns; const unsigned char *owner; const long long *eptr; const int *loc;
+};
+// blocks per launch of a size class: the classes that keep Q_BB (<= 512 rows) or R (<= 128, <= 512) in global scratch index it by workgroup
+inline int rbmc_class_chunk(int cls) { return cls == 3 ? 128 : (cls == 2 ? 1024 : 1 << 20); }
+// Xc (column-major n x w, ld n) -> Xt (row-major n x kRbmcW, zeros from column w on)
+void launch_rbmc_transpose(hipStream_t st, const double *Xc, long long n, int w, double *Xt);
+// one block of w samples after na earlier ones: the rows' (mean, M2) merged in place; last: out = base + M2 / (k - 1)
+void launch_rbmc_plain(hipStream_t st, const RbmcDev &P, long long n, const double *val, const double *Xt, long long na, int w, bool last,
+                       long long k, double *mean, double *m2, double *out);
+void launch_rbmc_blocks(hipStream_t st, const RbmcDev &P, int cls, const int *order, int cnt, const double *val, const double *Xt, long long na,
+                        int w, bool first, bool last, long long k, double *mean, double *m2, double *base, double *out, double *scrM,
+                        double *scrR);
+
 }  // namespace gmrfx

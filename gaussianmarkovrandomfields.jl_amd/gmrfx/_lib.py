@@ -32,7 +32,8 @@ class GmrfxStats(C.Structure):
         "ms_solve", "ms_solve_fwd", "ms_solve_bwd", "ms_solve_perm", "ms_backward_solve", "ms_logdet",
         "ms_selinv")] + [("last_nrhs", C.c_int64), ("fail_col", C.c_int64), ("ms_syrk", C.c_double),
                          ("syrk_flops", C.c_double), ("syrk_launches", C.c_int64),
-                         ("ms_quadform", C.c_double), ("inv_cap", C.c_int64), ("ms_inv_decide", C.c_double)]
+                         ("ms_quadform", C.c_double), ("inv_cap", C.c_int64), ("ms_inv_decide", C.c_double),
+                         ("ms_rbmc", C.c_double)]
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -75,6 +76,7 @@ EXPORTS = [
     "gmrfx_batch_constraints_set", "gmrfx_batch_constraints_info", "gmrfx_batch_constraints_get", "gmrfx_batch_constraints_mean",
     "gmrfx_batch_constraints_correct", "gmrfx_batch_constraints_correct_dev", "gmrfx_batch_constraints_var", "gmrfx_batch_sample",
     "gmrfx_batch_sample_dev", "gmrfx_batch_constrained_logpdf_dev",
+    "gmrfx_rbmc_var", "gmrfx_rbmc_var_dev", "gmrfx_rbmc_plan",
 ]
 
 
@@ -199,6 +201,9 @@ def lib():
         L.gmrfx_batch_sample.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, i64]
         L.gmrfx_batch_sample_dev.argtypes = [vp, vp, i64, i64, i64, vp, vp, i64, i64]
         L.gmrfx_batch_constrained_logpdf_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_rbmc_var.argtypes = [vp, vp, vp, i64, i64, i32, vp]
+        L.gmrfx_rbmc_var_dev.argtypes = [vp, vp, vp, i64, i64, i32, vp]
+        L.gmrfx_rbmc_plan.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

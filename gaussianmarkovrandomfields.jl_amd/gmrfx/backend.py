@@ -41,6 +41,34 @@ def _as_csc(Q) -> sp.csc_matrix:
     return Q
 
 
+# -- Rao-Blackwellised Monte Carlo marginal variances (gmrfx_rbmc_*): shared by the plain and the batched backend --------------
+def _rbmc_plan(h, enclosure_size: int, index_base: int = 0) -> dict:
+    """The blocks of BlockRBMCStrategy(enclosure_size) (host analysis; works on symbolic-only handles): block_ptr, rows (S first),
+    n_interior, owner (1 where the block writes the node), max_block."""
+    counts = np.zeros(3, np.int64)
+    check(lib().gmrfx_rbmc_plan(h, int(enclosure_size), int(index_base), ptr(counts), None, None, None, None), h)
+    nb, tot = int(counts[0]), int(counts[1])
+    out = {"block_ptr": np.empty(nb + 1, np.int64), "rows": np.empty(tot, np.int64), "n_interior": np.empty(nb, np.int64),
+           "owner": np.empty(tot, np.int64)}
+    check(lib().gmrfx_rbmc_plan(h, int(enclosure_size), int(index_base), ptr(counts), ptr(out["block_ptr"]), ptr(out["rows"]),
+                                ptr(out["n_interior"]), ptr(out["owner"])), h)
+    out["max_block"] = int(counts[2])
+    return out
+
+
+def _rbmc_var(h, n: int, nnz: int, Z, enclosure_size: int, nzval) -> np.ndarray:
+    Z = np.asarray(Z, dtype=np.float64)
+    if Z.ndim != 2 or Z.shape[0] != n:
+        raise ValueError(f"Z must have shape (n, nsamples) with n = {n}, got {Z.shape}")
+    Zf = np.asfortranarray(Z)
+    nz = None if nzval is None else np.ascontiguousarray(nzval, dtype=np.float64)
+    if nz is not None and nz.shape != (nnz,):
+        raise ValueError("nzval length does not match the pattern")
+    out = np.empty(n)
+    check(lib().gmrfx_rbmc_var(h, ptr(nz), ptr(Zf), n, Zf.shape[1], int(enclosure_size), ptr(out)), h)
+    return out
+
+
 class MI355XBackend:
     """`MI355XBackend(Symmetric(Q); ordering=nothing, coords=nothing)`.
 
@@ -671,6 +699,20 @@ class MI355XBackend:
             raise ValueError("sample_dev: null pointer, nrhs < 0 or leading dimension < n")
         check(lib().gmrfx_sample_dev(self._h, d_Z, ldz, nrhs, d_mu or None, d_X, ldx), self._h)
 
+    # -- Rao-Blackwellised Monte Carlo marginal variances (src/solvers/rbmc.jl) -----------------------------------------------
+    def rbmc_var(self, Z, enclosure_size: int = -1, nzval=None) -> np.ndarray:
+        """`var(d, RBMCStrategy(k))` (enclosure_size = -1) / `var(d, BlockRBMCStrategy(k; enclosure_size))` on the standard normals
+        Z (n, k) the caller drew. nzval: Q's values in the pattern's order; None = the values of the last refactorisation."""
+        return _rbmc_var(self._h, self.n, self._nnz, Z, enclosure_size, nzval)
+
+    def rbmc_var_dev(self, d_Z: int, ldz: int, nsamples: int, d_out: int, enclosure_size: int = -1, d_nzval: int = 0) -> None:
+        if not d_Z or not d_out:
+            raise ValueError("rbmc_var_dev: null pointer")
+        check(lib().gmrfx_rbmc_var_dev(self._h, d_nzval or None, d_Z, ldz, nsamples, int(enclosure_size), d_out), self._h)
+
+    def rbmc_plan(self, enclosure_size: int, index_base: int = 0) -> dict:
+        return _rbmc_plan(self._h, enclosure_size, index_base)
+
 
 class MI355XBatchBackend:
     """B precision matrices with ONE pattern, factored in one pass (gmrfx_create_batched, include/gmrfx.h): the hyper-parameter
@@ -996,3 +1038,20 @@ class MI355XBatchBackend:
         out = self.constrained_logpdf_dev(d_nz.data_ptr(), d_x.data_ptr(), self.n, s, nvec, 0 if d_mu is None else d_mu.data_ptr())
         torch.cuda.synchronize(dev)
         return out
+
+    # -- Rao-Blackwellised Monte Carlo marginal variances: the calls act on the forest diag(Q_1 .. Q_B) --------------------------
+    def rbmc_var(self, Z, enclosure_size: int = -1, nzval=None) -> np.ndarray:
+        """Z: (n B, k) standard normals in the forest's row order (member k's rows at k n); nzval (nnz, B) or None (held values).
+        Returns the (n, B) variances."""
+        nz = None if nzval is None else self._values(nzval).reshape(-1, order="F")
+        v = _rbmc_var(self._h, self.n * self.nbatch, self._nnz * self.nbatch, Z, enclosure_size, nz)
+        return v.reshape(self.n, self.nbatch, order="F")
+
+    def rbmc_var_dev(self, d_Z: int, ldz: int, nsamples: int, d_out: int, enclosure_size: int = -1, d_nzval: int = 0) -> None:
+        if not d_Z or not d_out:
+            raise ValueError("rbmc_var_dev: null pointer")
+        check(lib().gmrfx_rbmc_var_dev(self._h, d_nzval or None, d_Z, ldz, nsamples, int(enclosure_size), d_out), self._h)
+
+    def rbmc_plan(self, enclosure_size: int, index_base: int = 0) -> dict:
+        """Blocks over the forest's B n nodes (blocks never cross members)."""
+        return _rbmc_plan(self._h, enclosure_size, index_base)

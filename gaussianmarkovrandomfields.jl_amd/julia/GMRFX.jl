@@ -326,6 +326,18 @@ function constrained_var(b::MI355XBackend)
     GC.@preserve out check(ccall((:gmrfx_constraints_var, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h.ptr, out), b.h)
     return out
 end
+# Rao-Blackwellised Monte Carlo marginal variances on given standard-normal draws Z (n x k): `var(d, RBMCStrategy(k))`
+# (enclosure_size = -1) / `var(d, BlockRBMCStrategy(k; enclosure_size))`, src/solvers/rbmc.jl:71-87, :124-158 -- there k single-vector
+# rand! calls, a host SpMM and one CHOLMOD factorisation per block; here one call on the values of the last refactorisation.
+function rbmc_var(b::MI355XBackend, Z::Matrix{Float64}; enclosure_size::Integer = -1)
+    size(Z, 1) == b.n || throw(DimensionMismatch("Z must be n x k"))
+    out = Vector{Float64}(undef, b.n)
+    GC.@preserve Z out check(ccall((:gmrfx_rbmc_var, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}),
+        b.h.ptr, C_NULL, Z, stride(Z, 2), size(Z, 2), enclosure_size, out), b.h)
+    return out
+end
+function rbmc_var_dev! end      # ROCArray method: ext/GMRFXAMDGPUExt.jl
+
 # `_rand!` on given draws: X = P' L^-T Z + mean, then the constraint correction when the handle holds one
 function sample(b::MI355XBackend, Z::Matrix{Float64}, mean::Union{Nothing, Vector{Float64}} = nothing)
     X = similar(Z)
@@ -704,6 +716,17 @@ function Distributions._rand!(rng::AbstractRNG, d::MI355XGMRF, X::AbstractMatrix
     Z = randn!(rng, Matrix{Float64}(undef, size(X, 1), size(X, 2)))
     X .= G.backward_solve(d.linsolve_cache, Z) .+ d.mean
     return X
+end
+# seam-A methods of the two RBMC strategies (src/gmrf.jl:318-332 -> src/solvers/rbmc.jl:71-87, :124-158). `MI355XGMRF` is the plug-in's own
+# alias (its cache type carries `MI355XCholesky`), so, as for `_rand!` above, this is no piracy: every other GMRF keeps the reference's
+# generic host methods. The draws come from the strategy's rng, column by column, as the reference's k `rand!` calls would take them.
+function G.var(d::MI355XGMRF, s::G.RBMCStrategy)
+    Z = randn!(s.rng, Matrix{Float64}(undef, length(d.mean), s.n_samples))
+    return rbmc_var(_be(d.linsolve_cache), Z)
+end
+function G.var(d::MI355XGMRF, s::G.BlockRBMCStrategy)
+    Z = randn!(s.rng, Matrix{Float64}(undef, length(d.mean), s.n_samples))
+    return rbmc_var(_be(d.linsolve_cache), Z; enclosure_size = s.enclosure_size)
 end
 G._logdet_cov_impl(cache, ::MI355XCholesky) = -compute_logdet(_be(cache))       # note the sign (logdet.jl:30)
 G.prepare_for_linsolve(A::SparseMatrixCSC, ::MI355XCholesky) = Symmetric(A)

@@ -20,7 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
-import GMRFX: MI355XBatch, constrained_logpdf_terms
+import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -119,6 +119,16 @@ function solve!(X::ROCMatrix{Float64}, sf::ShardedMI355X, B::ROCMatrix{Float64};
     GC.@preserve B X check_rccl(ccall((:gmrfx_rccl_solve, LIB_RCCL), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Int32),
         sf.drv, devptr(B), stride(B, 2), size(B, 2), devptr(X), stride(X, 2), gather ? 1 : 0), sf)
     return X
+end
+
+# RBMC marginal variances with Z (n x k standard normals) and the result in HBM (src/solvers/rbmc.jl:71-87, :124-158); Q's values are
+# those of the last refactorisation
+function rbmc_var_dev!(out::ROCVector{Float64}, b::MI355XBackend, Z::ROCMatrix{Float64}; enclosure_size::Integer = -1)
+    size(Z, 1) == b.n && length(out) == b.n || throw(DimensionMismatch("Z must be n x k, out of length n"))
+    AMDGPU.synchronize()
+    GC.@preserve Z out check(ccall((:gmrfx_rbmc_var_dev, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}),
+        b.h.ptr, C_NULL, devptr(Z), stride(Z, 2), size(Z, 2), enclosure_size, devptr(out)), b.h)
+    return out
 end
 
 # X = P' L^-T Z over all ranks (samples: Z in elimination order, as CHOLMOD's F.UP \ z takes it)

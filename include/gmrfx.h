@@ -99,6 +99,7 @@ typedef struct gmrfx_stats {
      * found a front with pivot growth above 1e4), and the host wall time that one-time check took (0 before it ran) */
     int64_t inv_cap;
     double  ms_inv_decide;
+    double  ms_rbmc;               /* most recent gmrfx_rbmc_var(_dev): GPU time, backward sweeps included */
 } gmrfx_stats;
 
 /* Message for the most recent failed gmrfx_create on this thread. */
@@ -538,6 +539,45 @@ int32_t gmrfx_kl_cholesky(int64_t n, const double *theta, int64_t ldt, int32_t t
                           const int64_t *L_colptr, int64_t ntasks, const int64_t *task_rowptr, const int64_t *task_rows,
                           const int64_t *task_colptr, const int64_t *task_cols, int32_t index_base, double reg,
                           int32_t device, double *nzval, int64_t *info);
+
+/* ---- Rao-Blackwellised Monte Carlo marginal variances ---------------------------------------------------------------------------
+ * The reference's second way to marginal variances beside selected inversion, "in large-scale regimes where Takahashi recursions
+ * may be too expensive": `var(d, RBMCStrategy(k))` and `var(d, BlockRBMCStrategy(k; enclosure_size))`, src/solvers/rbmc.jl:71-87
+ * and :90-158, reached on seam A through src/gmrf.jl:318-332. There: k single-vector rand! calls, a host SpMM, and for the block
+ * form one CHOLMOD factorisation per block. Here: the k-column backward sweep in blocks of 64 samples, a symmetric SpMM fused with
+ * a per-row running variance, and one workgroup per block (gather Q_BB, Cholesky, substitutions, reduction over the samples).
+ * X = P' L^-T Z are the centred samples (`rand!` minus the mean, gmrf.jl:275-281); the caller supplies the standard normals Z
+ * (n x nsamples column-major, leading dimension ldz) -- there is no RNG in the library, as for gmrfx_sample. Variances over samples
+ * are corrected (divisor nsamples - 1, Julia's `var(...; dims = 2)`).
+ *   plain (enclosure_size = -1):  out_i = 1 / D_i + Var_s( (sum_{j != i} Q_ij X_js) / D_i ),  D = diag(Q)
+ *   block (enclosure_size >= 0):  `_build_disjoint_subsets` (:106-117) walks i = 1..n; an unvisited i opens a subset S = all stored
+ *     neighbours of i (row i of Q: i itself and explicit zeros included), visited or not -- the subsets OVERLAP, and
+ *     `var_estimate[interior] .=` (:151) lets the LAST subset that holds a node decide its value. B = S + enclosure_size
+ *     breadth-first rings (`_build_enclosure_idcs`, :93-104); out_i = (Q_BB^-1)_ii + Var_s( [Q_BB^-1 Q_{B,out} X_out]_i ), i in S.
+ *     (The two symamd calls, :140-144, reorder rows inside a block and do not change these values: not reproduced.)
+ * Q is Symmetric(Q) with the handle's uplo, as for gmrfx_quadform: neighbours and values come from the stored triangle that defines
+ * Q, mirrored; the other triangle is ignored even where it is stored. nzval: Q's CSC values (NULL = the values of the last
+ * refactorisation when the handle holds them, as gmrfx_quadform; a clone does not hold them).
+ * Device memory is O(64 n) for any nsamples. Every sum is formed in an order that depends on indices only, without atomics: results
+ * are bit-reproducible from run to run and do not depend on ldz or on the alignment of Z; the host and the _dev form agree bit for
+ * bit. A non-positive pivot in a block (rounding only: a principal block of a positive definite Q is positive definite) makes that
+ * block's outputs NaN. On a batched handle the calls act on the block-diagonal forest: Z and out have B n rows.
+ * LIMIT: a block of more than 512 rows is GMRFX_ERR_INVALID_ARG (the message names the block and its size); the limit of
+ * gmrfx_kl_cholesky. Also INVALID_ARG, with a message and nothing changed: nsamples < 2 (the reference would return NaN), ldz < n,
+ * enclosure_size < -1, a sharded handle, a handle with a constraint set (plain or batch: the constrained estimator is not
+ * implemented). GMRFX_ERR_NOT_FACTORIZED before the first factorisation, GMRFX_ERR_NOT_POSDEF when the last factorisation reported
+ * a failed pivot, GMRFX_ERR_NO_DEVICE for numeric use of a symbolic_only handle. gmrfx_stats.ms_rbmc: GPU time of the last call. */
+/* enclosure_size = -1: RBMCStrategy; >= 0: BlockRBMCStrategy with that enclosure. nzval: Q's CSC values
+ * (NULL = the values of the last refactorisation when the handle holds them, as gmrfx_quadform). */
+int32_t gmrfx_rbmc_var(gmrfx_handle *h, const double *nzval, const double *Z, int64_t ldz, int64_t nsamples,
+                       int32_t enclosure_size, double *out /* n, host */);
+int32_t gmrfx_rbmc_var_dev(gmrfx_handle *h, const double *d_nzval, const double *d_Z, int64_t ldz, int64_t nsamples,
+                           int32_t enclosure_size, double *d_out /* n, device */);
+/* Host analysis only (works on symbolic_only handles). Two-call protocol like gmrfx_symbolic_sweep_chunks:
+ * counts[0] blocks, [1] total rows, [2] largest block; block_ptr (blocks+1), rows (S first, index_base-based),
+ * n_interior (blocks), owner (total rows: 1 where this block writes the node, else 0; 0 for enclosure rows). */
+int32_t gmrfx_rbmc_plan(gmrfx_handle *h, int32_t enclosure_size, int32_t index_base, int64_t *counts,
+                        int64_t *block_ptr, int64_t *rows, int64_t *n_interior, int64_t *owner);
 
 #ifdef __cplusplus
 }

@@ -188,6 +188,22 @@ int main() {
         for (auto &x : th) x.join();
         device_plans(cp2, ri2, xy2.data(), 90 * 70, 1);
     }
+    // the RBMC block plan (csrc/rbmc_plan.cpp: the symmetric row structure, the subset walk, the threaded enclosures) on a symbolic-only
+    // handle, two-call protocol; every node is written by exactly one block
+    {
+        gmrfx_opts o; std::memset(&o, 0, sizeof(o)); o.struct_size = (int32_t)sizeof(o); o.symbolic_only = 1; o.device = -1;
+        gmrfx_handle *h = nullptr;
+        EXPECT(gmrfx_create(n, cp.data(), ri.data(), 0, nullptr, &o, &h) == GMRFX_OK && h != nullptr);
+        int64_t counts[3] = {0, 0, 0};
+        EXPECT(gmrfx_rbmc_plan(h, 2, 1, counts, nullptr, nullptr, nullptr, nullptr) == GMRFX_OK);
+        std::vector<int64_t> bp(counts[0] + 1), rows(counts[1]), ni(counts[0]), own(counts[1]), hits(n, 0);
+        EXPECT(gmrfx_rbmc_plan(h, 2, 1, counts, bp.data(), rows.data(), ni.data(), own.data()) == GMRFX_OK);
+        EXPECT(bp[counts[0]] == counts[1] && counts[2] <= 512);
+        for (int64_t r = 0; r < counts[1]; r++) { EXPECT(rows[r] >= 1 && rows[r] <= n); if (own[r]) hits[rows[r] - 1]++; }
+        for (int64_t i = 0; i < n; i++) EXPECT(hits[i] == 1);
+        EXPECT(gmrfx_rbmc_plan(h, -1, 0, counts, nullptr, nullptr, nullptr, nullptr) == GMRFX_ERR_INVALID_ARG);
+        gmrfx_destroy(h);
+    }
     // malformed input is rejected, not read out of bounds
     {
         gmrfx_opts o; std::memset(&o, 0, sizeof(o)); o.struct_size = (int32_t)sizeof(o); o.symbolic_only = 1; o.device = -1;
