@@ -12,7 +12,9 @@ Cases: the CASES of test_gpu_parity.py, a front wider than the inverse cap (defa
 whose levels hold thousands of fronts (sweep chunk programs, wave and workgroup tasks, and with GMRFX_FWD_FRONT=1 /
 GMRFX_BWD_FRONT=1 the one-workgroup sweep steps). Entry points: the plain refactorise, the pipelined refactorise+solve (host
 and device), the one-call logpdf, the Newton update (set_prior + refactorize_update[_solve]) and batched handles whose
-members carry different D_k; plus Q' = 4^k Q for k = +-20, +-150."""
+members carry different D_k; plus Q' = 4^k Q for k = +-20, +-150. The RBMC marginal variances (csrc/rbmc.hip), plain and block form:
+rbmc_var'(Z) = D^-2 rbmc_var(Z) -- given backward_solve' = D^-1 backward_solve (asserted above), every product of the estimators scales
+by a power of two, the pivots' sqrt included once both of a pivot's d_i factors are counted."""
 import math
 
 import numpy as np
@@ -21,6 +23,7 @@ import scipy.sparse as sp
 
 import gmrfx
 import intrinsic_models as im
+import rbmc_patterns
 from gmrfx import spde
 from test_gpu_parity import CASES as PARITY_CASES
 
@@ -292,3 +295,33 @@ def test_batched_members_with_their_own_scalings(nbatch):
         assert abs(p.compute_logdet() - lds[0]) <= 4 * np.spacing(abs(lds[0]))      # (reduced by another kernel: batch.hip)
         p.close()
     a.close(); b.close()
+
+
+def _rbmc_cases():
+    name, Q, kw = next(c for c in PARITY_CASES if c[0] == "matern64_coords")
+    yield name, sp.csc_matrix(Q), kw
+    yield "banded400_32", rbmc_patterns.banded(400, 32), {}
+
+
+@pytest.mark.parametrize("name,Q,kw", list(_rbmc_cases()), ids=["matern64_coords", "banded400_32"])
+def test_rbmc_variances_scale_exactly(name, Q, kw):
+    """Two handles, Q and D Q D, the same Z: the variances of the scaled handle are those of the plain one divided by d_i^2, bit for
+    bit, for the plain estimator and the block estimator (enclosure_size 0 and 2; k = 70: two sample blocks and a Chan merge).
+    D = diag(2^k_i) with k_i of this file's range, and D = 2^p I (Q' = 4^p Q, factor 4^-p) for p = +-20."""
+    Q = _canon(Q)
+    n = Q.shape[0]
+    Z = np.random.default_rng(12).standard_normal((n, 70))
+    be = gmrfx.MI355XBackend(Q, **kw)
+    want = {enc: be.rbmc_var(Z, enc) for enc in (-1, 0, 2)}
+    for enc, v in want.items():
+        assert np.isfinite(v).all() and (v > 0).all(), enc
+    scalings = [("diag", im.pow2_diag(n, np.random.default_rng(13)))] + [(f"uniform4^{p}", np.full(n, np.ldexp(1.0, p))) for p in (-20, 20)]
+    for tag, d in scalings:
+        bs = gmrfx.MI355XBackend(im.scaled(Q, d), **kw)
+        assert np.array_equal(bs.ordering_permutation(), be.ordering_permutation())
+        for enc, v in want.items():
+            got = bs.rbmc_var(Z, enc)
+            bad = np.flatnonzero(got != v / d / d)
+            assert bad.size == 0, f"{name}/{tag} enclosure_size={enc}: {bad.size} of {n} variances differ, first row {bad[:1]}"
+        bs.close()
+    be.close()

@@ -1,6 +1,7 @@
 """Host analysis of the Rao-Blackwellised Monte Carlo variance estimators (include/gmrfx.h: gmrfx_rbmc_plan; csrc/rbmc_plan.cpp) on
 symbolic_only handles, against the numpy restatement of src/solvers/rbmc.jl in tests/rbmc_ref.py: blocks (as sets, S first),
-n_interior and owner masks for enclosure_size 0, 1, 2; the used triangle only; index bases; a batched handle; argument errors."""
+n_interior and owner masks for enclosure_size 0, 1, 2; the used triangle only; index bases; a batched handle; argument errors; and
+the plans of tests/rbmc_patterns.py, pinned to the (ns, nb) pairs and per-class block counts that tests/test_gpu_rbmc_edges.py relies on."""
 import ctypes as C
 import os
 
@@ -9,6 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 import gmrfx
+import rbmc_patterns as rp
 import rbmc_ref
 from gmrfx import _lib, spde
 
@@ -63,6 +65,34 @@ def test_plan_equals_the_restatement(model, enclosure_size):
         assert (multi > 1).sum() == 405        # "disjoint" subsets overlap: most nodes lie in more than one
     if name == "matern21_s0" and enclosure_size == 0:
         assert max(len(S) + len(E) for S, E in ref) <= 32          # the <= 32-row class
+
+
+@pytest.mark.parametrize("name,enclosure_size", [(e.name, enc) for e in rp.EDGES for enc in sorted(e.plans)])
+def test_edge_patterns_keep_their_edges(name, enclosure_size):
+    """the library's plan equals the restatement's on every pattern of tests/rbmc_patterns.py, and holds the blocks the device
+    tests are there for: every size-class boundary, ns > 64, s0 > 0, and more blocks of a class than one launch takes"""
+    edge = rp.EDGE[name]
+    Q = edge.build()
+    plan = gmrfx.MI355XBackend(Q, symbolic_only=True).rbmc_plan(enclosure_size)
+    ref = rbmc_ref.check_plan(plan, rbmc_ref.SymQ(Q), enclosure_size)
+    sizes = rp.plan_sizes(plan)
+    assert sizes == rp.plan_sizes(ref)
+    rp.check_sizes(sizes, edge.plans[enclosure_size])
+    counts = rp.class_counts(sizes)
+    if (name, enclosure_size) == ("star200_hub_last", 1):
+        assert counts[3] == 200 > rp.CLASS_CHUNK[3] and Q.shape[0] == 201           # a second launch of the <= 512 class at b0 = 128
+        hub = 200                                                                   # held by all 200 subsets, owned by the last
+        bp, rows, ni, ow = plan["block_ptr"], plan["rows"], plan["n_interior"], plan["owner"]
+        held = [b for b in range(200) if hub in rows[bp[b]:bp[b] + ni[b]]]
+        owned = [b for b in range(200) if any(r == hub and o for r, o in zip(rows[bp[b]:bp[b] + ni[b]], ow[bp[b]:bp[b] + ni[b]]))]
+        assert held == list(range(200)) and owned == [199]
+    if name == "star_forest11x100":
+        assert counts[2] == 1100 > rp.CLASS_CHUNK[2] and Q.shape[0] == 1111         # a second launch of the <= 128 class at b0 = 1024
+    if name == "cliques":
+        assert Q.shape[0] == 1187 and plan["max_block"] == 512
+        assert [-(-s // 64) for s in (65, 128, 129, 512)] == [2, 2, 3, 8]           # passes of 64 unit vectors
+    if name == "banded1200_85":
+        assert (171, 511) in sizes and 511 - 171 == 340 and -(-171 // 64) == 3      # s0 = 340, three passes
 
 
 def test_structural_zeros_are_neighbours():
