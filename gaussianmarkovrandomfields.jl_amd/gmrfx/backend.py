@@ -484,6 +484,15 @@ class MI355XBackend:
         self.last_info = info.value
         return X[:, 0].copy() if vec else X
 
+    def refactorize_update_solve_dev(self, d_hvals: int, d_B: int, ldb: int, nrhs: int, d_X: int, ldx: int) -> int:
+        """Device-pointer form of refactorize_update_solve (gmrfx_refactorize_update_solve_dev): the Hessian values, B and X stay in HBM."""
+        info = C.c_int64(0)
+        check(lib().gmrfx_refactorize_update_solve_dev(self._h, d_hvals, d_B, ldb, nrhs, d_X, ldx, C.byref(info)), self._h)
+        self._selinv_cache = None
+        self._selinv_diag_cache = None
+        self.last_info = info.value
+        return info.value
+
     # -- sharded factorisation (include/gmrfx.h "sharded factorisation"; driver: gmrfx/shard.py) -------
     def refactorize_phase_dev(self, d_nzval_ptr: int, phase: int) -> None:
         check(lib().gmrfx_refactorize_phase(self._h, d_nzval_ptr, phase), self._h)

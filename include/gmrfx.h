@@ -262,6 +262,16 @@ int32_t gmrfx_logdet_partial(gmrfx_handle *h, double *out);
  * its slot, the slices tile the array" is checked on the CPU for sizes no test box holds. */
 int32_t gmrfx_host_io_plan(int64_t n, int64_t nrhs, int32_t download, int64_t *plan /* 6 */);
 
+/* ---- Layout of B, X and Z (every solve-family call: gmrfx_solve, gmrfx_backward_solve, gmrfx_refactorize_solve,
+ * gmrfx_refactorize_update_solve, gmrfx_quadform, gmrfx_refactorize_logpdf_dev and their _dev forms) ------------------------------
+ * A dense argument is a column-major n x nrhs WINDOW: element (i, j) at ptr[i + j ld], ld >= n (GMRFX_ERR_INVALID_ARG otherwise,
+ * and for a null array, whenever nrhs > 0; nrhs == 0 touches neither array). The window may sit anywhere inside a larger array -- a
+ * `@view` of a taller matrix: the base pointer and the column starts need the alignment of a double (8 bytes), nothing more. The
+ * rows n .. ld-1 between two columns and everything before and behind the window are never read into a result and never written;
+ * the input window is only read. Results do not depend on ld or on the alignment: a padded call returns the bits of the
+ * contiguous one (tests/test_gpu_layout.py).
+ * ALIASING: X may BE the input (X == B, or X == Z, the same pointer) when ldx == ldb: the solve then runs in place -- every pass of
+ * 64 columns reads its columns before it writes them. Any other overlap of the two windows is not allowed and not detected. */
 /* Q X = B. Replaces `F \ b` / `F \ B`: src/workspace/backend.jl:191-209. */
 int32_t gmrfx_solve(gmrfx_handle *h, const double *B, int64_t ldb, int64_t nrhs, double *X, int64_t ldx);
 int32_t gmrfx_solve_dev(gmrfx_handle *h, const double *d_B, int64_t ldb, int64_t nrhs, double *d_X, int64_t ldx);
