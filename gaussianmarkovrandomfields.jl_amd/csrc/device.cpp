@@ -32,67 +32,25 @@ template <class T> T *Device::dalloc(size_t count) {
     void *p = nullptr;
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T) + kPairSlackBytes;
     HC(hipMalloc(&p, bytes));
-    allocs_.push_back({p, bytes});
+    allocs_.push_back(p);
     bytes_total += (double)bytes;
     return (T *)p;
 }
 
 // Grows a buffer that may be replaced during the life of the handle: the NEW buffer is allocated first, so that a failed
-// allocation (exception) leaves the old pointer and its capacity valid; callers raise their *_cap_ only after the return.
-template <class T> T *Device::dregrow(T *old, size_t count) {
-    T *fresh = dalloc<T>(count);
-    if (old) {
-        HC(hipDeviceSynchronize());       // nothing in flight may still read the old buffer
-        for (size_t k = 0; k < allocs_.size(); k++)
-            if (allocs_[k].first == (void *)old) {
-                bytes_total -= (double)allocs_[k].second;
-                allocs_.erase(allocs_.begin() + (long)k);
-                break;
-            }
-        (void)hipFree(old);
-    }
-    return fresh;
+// allocation (exception) leaves the old one and its capacity valid; callers raise their *_cap_ only after the return. The old
+// one is released once nothing in flight can still read it.
+template <class T> static void regrow(DevBuf<T> &buf, size_t count, double *ledger) {
+    DevBuf<T> fresh;
+    fresh.alloc(count, ledger);
+    if (buf) HC(hipDeviceSynchronize());
+    buf = std::move(fresh);
 }
 
+// (the members release what they own, buffers and events before the streams: see the declarations)
 Device::~Device() {
-    for (size_t k = 0; k < rd_plans_.size(); k++) rowdiag_plan_free((long long)k);
     if (stream) { (void)hipStreamSynchronize(stream); }
-    if (con_.ev0) (void)hipEventDestroy(con_.ev0);
-    if (con_.ev1) (void)hipEventDestroy(con_.ev1);
-    if (bcon_.ev0) (void)hipEventDestroy(bcon_.ev0);
-    if (bcon_.ev1) (void)hipEventDestroy(bcon_.ev1);
-    if (rb_.ev0) (void)hipEventDestroy(rb_.ev0);
-    if (rb_.ev1) (void)hipEventDestroy(rb_.ev1);
-    for (auto &p : allocs_) (void)hipFree(p.first);
-    for (auto &e : ev_) if (e) (void)hipEventDestroy(e);
-    for (auto &v : ev_level_) for (auto &e : v) (void)hipEventDestroy(e);
-    for (auto &e : ev_flevel_) (void)hipEventDestroy(e);
-    for (auto &l : ev_lane_) for (auto &e : l) if (e) (void)hipEventDestroy(e);
-    if (h_info_) (void)hipHostFree(h_info_);
-    if (h_stage_) (void)hipHostFree(h_stage_);
-    if (h_nzstage_) (void)hipHostFree(h_nzstage_);
-    if (ev_up_) (void)hipEventDestroy(ev_up_);
-    if (ev_x_) (void)hipEventDestroy(ev_x_);
-    for (auto &e : ev_ring_) (void)hipEventDestroy(e);
-    if (stream_io_) (void)hipStreamDestroy(stream_io_);
-    if (h_logdet_) (void)hipHostFree(h_logdet_);
-    if (h_qf_) (void)hipHostFree(h_qf_);
-    if (ev_qf_) (void)hipEventDestroy(ev_qf_);
-    if (ev_logdet_) (void)hipEventDestroy(ev_logdet_);
-    if (h_bdiag_) (void)hipHostFree(h_bdiag_);
-    if (h_bqf_) (void)hipHostFree(h_bqf_);
-    if (ev_bdiag_) (void)hipEventDestroy(ev_bdiag_);
-    if (ev_ready_) (void)hipEventDestroy(ev_ready_);
-    if (ev_ready2_) (void)hipEventDestroy(ev_ready2_);
-    if (ev_done1_) (void)hipEventDestroy(ev_done1_);
-    if (stream3) (void)hipStreamDestroy(stream3);
-    for (auto &e : ev_syrk_) if (e) (void)hipEventDestroy(e);
-    if (ev_fact_) (void)hipEventDestroy(ev_fact_);
-    if (ev_nzp_) (void)hipEventDestroy(ev_nzp_);
-    if (ev_nzp0_) (void)hipEventDestroy(ev_nzp0_);
-    if (ev_inv_) (void)hipEventDestroy(ev_inv_);
-    if (stream2) (void)hipStreamDestroy(stream2);
-    if (own_stream_) (void)hipStreamDestroy(own_stream_);
+    for (void *p : allocs_) (void)hipFree(p);
 }
 
 // The caller's stream becomes the main stream (sharded drivers: torch's current stream, so that the library's kernels,
@@ -120,10 +78,10 @@ void Device::init(const Symbolic &S, int dev) {
         HC(hipDeviceGetStreamPriorityRange(&lo, &hi));
         // (Measured and settled in round 4, DESIGN.md section 3: no priorities, idle streams between the handle's streams, a CU mask on
         //  the side stream -- none of them helps; the three streams are created back to back: three distinct hardware queues.)
-        HC(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-        own_stream_ = stream;
-        HC(hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, lo));
-        HC(hipStreamCreateWithPriority(&stream3, hipStreamNonBlocking, hi));
+        own_stream_.create(hipStreamNonBlocking, hi);
+        stream = own_stream_;
+        stream2.create(hipStreamNonBlocking, lo);
+        stream3.create(hipStreamNonBlocking, hi);
     }
     // the environment's testing / A/B / profiling knobs
     if (const char *c = std::getenv("GMRFX_INV_CAP")) {      // testing knob: power of two >= 64
@@ -140,16 +98,16 @@ void Device::init(const Symbolic &S, int dev) {
     if (const char *e = std::getenv("GMRFX_FWD_FRONT")) fwd_front_min_ = std::atoi(e);    // ... and for the one-workgroup forward step
     if (const char *e = std::getenv("GMRFX_SYRK_XCD")) syrk_xcd_ = std::atoi(e) != 0;
     if (const char *e = std::getenv("GMRFX_SYRK_PIPED")) syrk_piped_min_ = std::atoi(e);
-    HC(hipEventCreateWithFlags(&ev_fact_, hipEventDisableTiming));
-    HC(hipEventCreateWithFlags(&ev_inv_, hipEventDisableTiming));
-    for (auto &ev : ev_) HC(hipEventCreate(&ev));
-    for (auto &l : ev_lane_) for (auto &ev : l) HC(hipEventCreate(&ev));
-    HC(hipHostMalloc((void **)&h_info_, 2 * sizeof(int), hipHostMallocDefault));
+    ev_fact_.create(hipEventDisableTiming);
+    ev_inv_.create(hipEventDisableTiming);
+    for (auto &ev : ev_) ev.create();
+    for (auto &l : ev_lane_) for (auto &ev : l) ev.create();
+    h_info_.alloc(2);
     h_info_[0] = INT_MAX;
     h_info_[1] = 0;
-    HC(hipEventCreateWithFlags(&ev_ready_, hipEventDisableTiming));
-    HC(hipEventCreateWithFlags(&ev_ready2_, hipEventDisableTiming));
-    HC(hipEventCreateWithFlags(&ev_done1_, hipEventDisableTiming));
+    ev_ready_.create(hipEventDisableTiming);
+    ev_ready2_.create(hipEventDisableTiming);
+    ev_done1_.create(hipEventDisableTiming);
     upload(S);
 }
 
@@ -182,8 +140,8 @@ void Device::upload(const Symbolic &S) {
     ds_.childptr = up(S.childptr); ds_.children = up(S.children); ds_.sparent = up(S.sparent);
     ds_.qptr = up(S.qptr); ds_.qsrc = up(P.qsrc); ds_.qdst = up(P.qdst); ds_.qcol = up(P.qcol); ds_.qcolptr = up(P.qcolptr);
     d_nzp_ = dalloc<double>((size_t)std::max<long long>(nq_, 1));
-    HC(hipEventCreateWithFlags(&ev_nzp_, hipEventDisableTiming));
-    HC(hipEventCreateWithFlags(&ev_nzp0_, hipEventDisableTiming));
+    ev_nzp_.create(hipEventDisableTiming);
+    ev_nzp0_.create(hipEventDisableTiming);
     ds_.wptr = up(S.wptr);
     ds_.edge = up(P.edge); ds_.etile = up(P.etile); ds_.erow = up(P.erow);
     ds_.diagoff = up(S.diagoff); ds_.perm = up(S.perm);
@@ -213,7 +171,7 @@ void Device::upload(const Symbolic &S) {
     for (const auto &off : P.inv_lvl_toff) d_inv_lvl_toff_.push_back(up(off));
     d_syrk_recs_ = up(P.syrk_recs); d_fwd_recs_ = up(P.fwd_recs); d_arec_ = up(P.arec);
     ev_syrk_.resize(2 * (size_t)S.nlevels);
-    for (auto &e : ev_syrk_) HC(hipEventCreate(&e));
+    for (auto &e : ev_syrk_) e.create();
 
     // INVARIANT (pair loads): the kernels that read operand rows in 16-byte pairs (sweep_front.hip, k_syrk_cb_rec, selinv.hip)
     // may read ONE double past a column's last row; for the last column of the last panel that is element l_size_ of the
@@ -256,7 +214,7 @@ void Device::clone_from(const Device &o, const Symbolic &S) {
 // at the full rate of the DMA engines, and what is overlapped is the host side: pageable memory is staged through a page-locked
 // buffer of the handle by several host threads (a single thread moves ~10 GB/s, the link 57), slice k's staging beside the DMA
 // of slice k-1, and on the way out slice k's copy to the caller's array beside the DMA of slice k+1. Page-locked caller memory
-// (hipHostMalloc / hipHostRegister, torch pin_memory) is handed to the DMA engine as it is.
+// (page-locked through HIP, torch pin_memory) is handed to the DMA engine as it is.
 // true for anything the DMA engines take as it is: page-locked host memory -- and device / managed memory handed to a host entry
 // point by mistake or convenience (the copy is then device-to-device; a host thread must never memcpy from it)
 static bool host_ptr_is_pinned(const void *p) {
@@ -320,14 +278,13 @@ static inline void host_io_slice(const HostIoPlan &p, long long k, long long n, 
 
 void Device::host_io_reserve(long long count) {
     if (!stream_io_) {
-        HC(hipStreamCreateWithFlags(&stream_io_, hipStreamNonBlocking));
-        HC(hipEventCreateWithFlags(&ev_up_, hipEventDisableTiming));
-        HC(hipEventCreateWithFlags(&ev_x_, hipEventDisableTiming));
+        stream_io_.create(hipStreamNonBlocking);
+        ev_up_.create(hipEventDisableTiming);
+        ev_x_.create(hipEventDisableTiming);
     }
-    if (count <= h_stage_cap_) return;
-    if (h_stage_) { HC(hipStreamSynchronize(stream_io_)); (void)hipHostFree(h_stage_); h_stage_ = nullptr; h_stage_cap_ = 0; }   // (only the copy stream ever touches it)
-    HC(hipHostMalloc((void **)&h_stage_, (size_t)count * sizeof(double), hipHostMallocDefault));
-    h_stage_cap_ = count;
+    if (count <= h_stage_.cap()) return;
+    if (h_stage_) HC(hipStreamSynchronize(stream_io_));       // (only the copy stream ever touches it)
+    h_stage_.alloc(count);
 }
 
 // Q's values from a host array to d_nz_, ahead of the factorisation (nothing else runs yet: plain DMA)
@@ -337,7 +294,7 @@ void Device::host_upload_values(const double *nzval) {
         HC(hipMemcpyAsync(d_nz_, nzval, (size_t)cnt * sizeof(double), hipMemcpyDefault, stream));
         return;
     }
-    if (!h_nzstage_) HC(hipHostMalloc((void **)&h_nzstage_, (size_t)std::max<long long>(cnt, 1) * sizeof(double), hipHostMallocDefault));
+    if (!h_nzstage_) h_nzstage_.alloc(cnt);
     HC(hipStreamSynchronize(stream));                 // (an earlier call's copy out of the staging buffer has finished long ago; cheap)
     parallel_memcpy(h_nzstage_, nzval, cnt);
     HC(hipMemcpyAsync(d_nz_, h_nzstage_, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -360,7 +317,7 @@ void Device::host_upload(const double *B, long long ldb, long long nrhs, double 
     const long long slot_doubles = pl.slot_doubles, nsl = pl.nsl;
     host_io_reserve(pl.reserve);
     const int T = (int)std::min<long long>(host_io_threads(), nsl);
-    while ((int)ev_ring_.size() < kIoRing) { hipEvent_t e; HC(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_ring_.push_back(e); }
+    while ((int)ev_ring_.size() < kIoRing) { Event e; e.create(hipEventDisableTiming); ev_ring_.push_back(std::move(e)); }
     std::vector<std::atomic<int>> posted((size_t)nsl);
     for (auto &a : posted) a.store(0);
     std::vector<std::thread> th;
@@ -374,7 +331,7 @@ void Device::host_upload(const double *B, long long ldb, long long nrhs, double 
                 long long j0, nc, r0, nr;
                 host_io_slice(pl, k, n, nrhs, j0, nc, r0, nr);
                 const int slot = (int)(k % kIoRing);
-                if ((slot + 1) * slot_doubles > h_stage_cap_ || nc * nr > slot_doubles) throw std::runtime_error("host_upload: slice leaves the staging ring");
+                if ((slot + 1) * slot_doubles > h_stage_.cap() || nc * nr > slot_doubles) throw std::runtime_error("host_upload: slice leaves the staging ring");
                 if (k >= kIoRing) {         // the slot's previous slice: its copy has been enqueued (posted), now wait until it has run
                     while (!posted[(size_t)(k - kIoRing)].load(std::memory_order_acquire)) { if (failed.load()) return; std::this_thread::yield(); }
                     HC(hipEventSynchronize(ev_ring_[slot]));
@@ -415,7 +372,7 @@ void Device::host_download(const double *d_src, long long nrhs, double *X, long 
     const HostIoPlan pl = host_io_plan(n, nrhs, kIoSliceBytes / 2);
     const long long slot_doubles = pl.slot_doubles, nsl = pl.nsl;
     host_io_reserve(pl.reserve);
-    while ((int)ev_ring_.size() < kIoRing) { hipEvent_t e; HC(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_ring_.push_back(e); }
+    while ((int)ev_ring_.size() < kIoRing) { Event e; e.create(hipEventDisableTiming); ev_ring_.push_back(std::move(e)); }
     std::vector<std::atomic<int>> done((size_t)nsl);
     for (auto &a : done) a.store(0);
     const int T = (int)std::min<long long>(std::min<long long>(host_io_threads(), kIoRing), nsl);
@@ -430,7 +387,7 @@ void Device::host_download(const double *d_src, long long nrhs, double *X, long 
                 long long j0, nc, r0, nr;
                 host_io_slice(pl, k, n, nrhs, j0, nc, r0, nr);
                 const int slot = (int)(k % kIoRing);
-                if ((slot + 1) * slot_doubles > h_stage_cap_ || nc * nr > slot_doubles) throw std::runtime_error("host_download: slice leaves the staging ring");
+                if ((slot + 1) * slot_doubles > h_stage_.cap() || nc * nr > slot_doubles) throw std::runtime_error("host_download: slice leaves the staging ring");
                 if (k >= kIoRing)
                     while (!done[(size_t)(k - kIoRing)].load(std::memory_order_acquire)) { if (failed.load()) return; std::this_thread::yield(); }
                 double *st = h_stage_ + slot * slot_doubles;
@@ -688,7 +645,7 @@ void Device::refactorize_solve(const double *nzval, bool nz_on_device, const dou
         ensure_io(n * nrhs);
         dB = d_io_; dXo = d_io_; ldin = n; ldout = n;
     }
-    while ((int)ev_flevel_.size() < nl + 1) { hipEvent_t e; HC(hipEventCreateWithFlags(&e, hipEventDisableTiming)); ev_flevel_.push_back(e); }
+    while ((int)ev_flevel_.size() < nl + 1) { Event e; e.create(hipEventDisableTiming); ev_flevel_.push_back(std::move(e)); }
     // host right-hand sides: in FRONT of the factorisation (see the measurements above host_upload): the transfers are serial --
     // B in, the pipelined step, X out -- never beside the factorisation
     if (!b_on_device) {
@@ -703,7 +660,7 @@ void Device::refactorize_solve(const double *nzval, bool nz_on_device, const dou
     // forms of the step give the same bits): forward sweep on the side stream, behind the level events
     const int PW = pass_width(nrhs);
     const int nr = (int)std::min<long long>(PW, nrhs), ldx = nr;
-    hipEvent_t *ev = ev_lane_[0];
+    const Event *ev = ev_lane_[0];
     // lane 0's buffers on the side stream for the forward half, on the main stream for the rest
     const SweepLane ln0 = lane(0), side{stream2, ln0.X, ln0.X2, ln0.W};
     HC(hipStreamWaitEvent(side.st, ev_ready_, 0));
@@ -896,8 +853,8 @@ void Device::set_prior(const double *prior_nzval, const long long *map, long lon
     HC(hipMemcpyAsync(d_prior_, prior_nzval, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, stream));
     if (cnt > hmap_cap_ || !d_hmap_ || !d_h_) {
         hmap_cap_ = 0;      // (if the second allocation throws, the next call regrows both)
-        d_hmap_ = dregrow(d_hmap_, (size_t)std::max<long long>(cnt, 1));
-        d_h_ = dregrow(d_h_, (size_t)std::max<long long>(cnt, 1));
+        regrow(d_hmap_, (size_t)cnt, &bytes_total);
+        regrow(d_h_, (size_t)cnt, &bytes_total);
         hmap_cap_ = cnt;
     }
     hmap_cnt_ = cnt;
@@ -973,7 +930,7 @@ void Device::ensure_rhs_capacity(long long nrhs) {
 void Device::ensure_io(long long need) {
     if (need <= io_cap_) return;
     const long long cap = std::max(need, 2 * io_cap_);
-    d_io_ = dregrow(d_io_, (size_t)cap);
+    regrow(d_io_, (size_t)cap, &bytes_total);
     io_cap_ = cap;
 }
 
@@ -1164,7 +1121,7 @@ void Device::backward(const SweepLane &ln, int nr, int ldx, bool y_in_x2, int hi
 // (slot numbering in level_times()); a profiling aid behind gmrfx_level_times, never on in production runs
 void Device::level_event(hipStream_t st, int phase, int slot) {
     auto &v = ev_level_[phase];
-    while ((int)v.size() <= slot) { hipEvent_t e; HC(hipEventCreate(&e)); v.push_back(e); }
+    while ((int)v.size() <= slot) { Event e; e.create(); v.push_back(std::move(e)); }
     HC(hipEventRecord(v[slot], st));
     level_slots_[phase] = std::max(level_slots_[phase], slot + 1);
 }
@@ -1234,7 +1191,7 @@ void Device::solve_phase(const double *d_B, long long ldb, long long nrhs, doubl
 
 // One pass of at most 64 columns on lane ln: dB (column-major, original ordering) -> ln.X (elimination order, row-major), the
 // sweeps, and back to dXo. mode 0: full solve, X = P b; 1: backward only (F.UP \ z), z is taken in elimination order as is.
-void Device::sweep_pass(const SweepLane &ln, hipEvent_t *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
+void Device::sweep_pass(const SweepLane &ln, const Event *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
                         const MemberLayout *ml) {
     const int n = (int)S_->n, ldx = nr, nl = (int)levels_.size();
     auto mark = [&](int k) { if (ev) HC(hipEventRecord(ev[k], ln.st)); };
@@ -1330,8 +1287,8 @@ void Device::solve(const double *B, long long ldb, long long nrhs, double *X, lo
 // is kept per factorisation; the pipelined factor + solve call enqueues it on the side stream beside the backward sweep.
 void Device::enqueue_logdet(hipStream_t st, bool timed) {
     if (!h_logdet_) {
-        HC(hipHostMalloc((void **)&h_logdet_, sizeof(double), hipHostMallocDefault));
-        HC(hipEventCreateWithFlags(&ev_logdet_, hipEventDisableTiming));
+        h_logdet_.alloc(1);
+        ev_logdet_.create(hipEventDisableTiming);
     }
     const int nparts = (int)std::min<long long>(1024, std::max<long long>(1, (S_->n + 255) / 256));
     if (timed) HC(hipEventRecord(ev_[0], st));
@@ -1351,16 +1308,6 @@ double Device::logdet() {
     return *h_logdet_;
 }
 
-// a page-locked host buffer of results (h_qf_, h_bqf_) grown to `count` doubles, `floor` at least; a failed allocation leaves none
-static void grow_pinned(double *&buf, long long &cap, long long count, long long floor) {
-    if (count <= cap) return;
-    if (buf) HC(hipHostFree(buf));
-    buf = nullptr; cap = 0;
-    const long long fresh = std::max(count, floor);
-    HC(hipHostMalloc((void **)&buf, (size_t)fresh * sizeof(double), hipHostMallocDefault));
-    cap = fresh;
-}
-
 // pattern of Q and the partial-sum buffers of the quadratic-form kernels (grown geometrically)
 void Device::prepare_quadform(long long nvec) {
     const Symbolic &S = *S_;
@@ -1375,8 +1322,8 @@ void Device::prepare_quadform(long long nvec) {
     if (nvec > qf_cap_) {
         const long long cap = std::max<long long>(nvec, 2 * qf_cap_);     // geometric growth, the old buffers are freed
         qf_cap_ = 0;        // (a failed second allocation must not leave the pair with different sizes behind one capacity)
-        d_qf_part_ = dregrow(d_qf_part_, (size_t)cap * nblk);
-        d_qf_out_ = dregrow(d_qf_out_, (size_t)cap);
+        regrow(d_qf_part_, (size_t)cap * nblk, &bytes_total);
+        regrow(d_qf_out_, (size_t)cap, &bytes_total);
         qf_cap_ = cap;
     }
 }
@@ -1396,12 +1343,12 @@ void Device::refactorize_logpdf(const double *d_nz, const double *d_X, long long
     if (stream != own_stream_) throw std::invalid_argument("refactorize_logpdf: not on a caller's stream");
     if (nvec > 0) {
         prepare_quadform(nvec);
-        grow_pinned(h_qf_, h_qf_cap_, nvec, 16);
+        h_qf_.grow(nvec, 16);
         HC(hipEventRecord(ev_ready_, stream));
         HC(hipStreamWaitEvent(stream2, ev_ready_, 0));
         launch_quadform(stream2, (int)S.n, d_in_colptr_, d_in_row_, d_nz, S.in_use, d_X, ldx, (int)nvec, d_mu, d_qf_part_, d_qf_out_);
         HC(hipMemcpyAsync(h_qf_, d_qf_out_, (size_t)nvec * sizeof(double), hipMemcpyDeviceToHost, stream2));
-        if (!ev_qf_) HC(hipEventCreateWithFlags(&ev_qf_, hipEventDisableTiming));
+        ev_qf_.ensure(hipEventDisableTiming);
         HC(hipEventRecord(ev_qf_, stream2));
     }
     begin_factor(d_nz);
@@ -1458,7 +1405,7 @@ void Device::selinv_begin() {
             }
             mx = std::max(mx, off);
         }
-        if (mx > tmp_cap_) { d_tmp_ = dregrow(d_tmp_, (size_t)mx); tmp_cap_ = mx; }
+        if (mx > tmp_cap_) { regrow(d_tmp_, (size_t)mx, &bytes_total); tmp_cap_ = mx; }
         d_yoff_ = dalloc<long long>(std::max<size_t>(yoff.size(), 1));
         HC(hipMemcpyAsync(d_yoff_, yoff.data(), yoff.size() * sizeof(long long), hipMemcpyHostToDevice, stream));
         HC(hipStreamSynchronize(stream));
@@ -1549,7 +1496,7 @@ void Device::selinv_phase(int what, int hi, int lo) {
 void Device::selinv_diag(double *out_host) {
     HC(hipSetDevice(device));
     const long long n = S_->n;
-    if (n > io_cap_) { d_io_ = dregrow(d_io_, (size_t)n); io_cap_ = n; }
+    if (n > io_cap_) { regrow(d_io_, (size_t)n, &bytes_total); io_cap_ = n; }
     launch_gather_diag(stream, d_Z_, ds_.diagoff, ds_.perm, (int)n, d_io_);
     HC(hipMemcpyAsync(out_host, d_io_, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
@@ -1558,16 +1505,14 @@ void Device::selinv_diag(double *out_host) {
 void Device::gather_z(const long long *offsets_host, long long cnt, double *out_host) {
     HC(hipSetDevice(device));
     if (cnt <= 0) return;
-    long long *d_off = nullptr;
-    double *d_out = nullptr;
-    HC(hipMalloc((void **)&d_off, (size_t)cnt * sizeof(long long)));
-    HC(hipMalloc((void **)&d_out, (size_t)cnt * sizeof(double)));
+    DevBuf<long long> d_off;
+    DevBuf<double> d_out;
+    d_off.alloc((size_t)cnt);
+    d_out.alloc((size_t)cnt);
     HC(hipMemcpyAsync(d_off, offsets_host, (size_t)cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
     launch_gather(stream, d_Z_, d_off, cnt, d_out);
     HC(hipMemcpyAsync(out_host, d_out, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
-    (void)hipFree(d_off);
-    (void)hipFree(d_out);
 }
 
 void Device::weighted_z_sums(const long long *segptr_host, long long nseg, const long long *off_host, const double *w_host,
@@ -1576,16 +1521,17 @@ void Device::weighted_z_sums(const long long *segptr_host, long long nseg, const
     if (nseg <= 0) return;
     if (nseg > 0x7fffffffLL) throw std::invalid_argument("too many segments");
     const long long cnt = segptr_host[nseg];
-    struct Buf { void *p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } bseg, boff, bw, bout;
-    HC(hipMalloc(&bseg.p, (size_t)(nseg + 1) * sizeof(long long)));
-    HC(hipMalloc(&boff.p, (size_t)std::max<long long>(cnt, 1) * sizeof(long long)));
-    HC(hipMalloc(&bw.p, (size_t)std::max<long long>(cnt, 1) * sizeof(double)));
-    HC(hipMalloc(&bout.p, (size_t)nseg * sizeof(double)));
-    HC(hipMemcpyAsync(bseg.p, segptr_host, (size_t)(nseg + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
-    HC(hipMemcpyAsync(boff.p, off_host, (size_t)cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
-    HC(hipMemcpyAsync(bw.p, w_host, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, stream));
-    launch_seg_wsum(stream, d_Z_, (const long long *)bseg.p, nseg, (const long long *)boff.p, (const double *)bw.p, (double *)bout.p);
-    HC(hipMemcpyAsync(out_host, bout.p, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, stream));
+    DevBuf<long long> bseg, boff;
+    DevBuf<double> bw, bout;
+    bseg.alloc((size_t)nseg + 1);
+    boff.alloc((size_t)cnt);
+    bw.alloc((size_t)cnt);
+    bout.alloc((size_t)nseg);
+    HC(hipMemcpyAsync(bseg, segptr_host, (size_t)(nseg + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+    HC(hipMemcpyAsync(boff, off_host, (size_t)cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
+    HC(hipMemcpyAsync(bw, w_host, (size_t)cnt * sizeof(double), hipMemcpyHostToDevice, stream));
+    launch_seg_wsum(stream, d_Z_, bseg, nseg, boff, bw, bout);
+    HC(hipMemcpyAsync(out_host, bout, (size_t)nseg * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
 }
 
@@ -1595,21 +1541,20 @@ long long Device::rowdiag_plan_create(const long long *segptr_host, long long ns
     if (nseg > 0x7fffffffLL) throw std::invalid_argument("too many rows");
     RowDiagPlan P;
     P.nseg = nseg; P.cnt = nseg > 0 ? segptr_host[nseg] : 0; P.nvals = nvals;
-    auto grab = [&](void **p, size_t bytes) { HC(hipMalloc(p, std::max<size_t>(bytes, 8))); };
-    grab((void **)&P.seg, (size_t)(nseg + 1) * sizeof(long long));
-    grab((void **)&P.off, (size_t)P.cnt * sizeof(long long));
-    grab((void **)&P.p, (size_t)P.cnt * sizeof(int));
-    grab((void **)&P.q, (size_t)P.cnt * sizeof(int));
-    grab((void **)&P.vals, (size_t)nvals * sizeof(double));
-    grab((void **)&P.out, (size_t)nseg * sizeof(double));
+    P.seg.alloc((size_t)nseg + 1);
+    P.off.alloc((size_t)P.cnt);
+    P.p.alloc((size_t)P.cnt);
+    P.q.alloc((size_t)P.cnt);
+    P.vals.alloc((size_t)nvals);
+    P.out.alloc((size_t)nseg);
     HC(hipMemcpyAsync(P.seg, segptr_host, (size_t)(nseg + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
     HC(hipMemcpyAsync(P.off, off_host, (size_t)P.cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
     HC(hipMemcpyAsync(P.p, p_host, (size_t)P.cnt * sizeof(int), hipMemcpyHostToDevice, stream));
     HC(hipMemcpyAsync(P.q, q_host, (size_t)P.cnt * sizeof(int), hipMemcpyHostToDevice, stream));
     HC(hipStreamSynchronize(stream));
     for (size_t k = 0; k < rd_plans_.size(); k++)
-        if (!rd_plans_[k].seg) { rd_plans_[k] = P; return (long long)k; }
-    rd_plans_.push_back(P);
+        if (!rd_plans_[k].seg) { rd_plans_[k] = std::move(P); return (long long)k; }
+    rd_plans_.push_back(std::move(P));
     return (long long)rd_plans_.size() - 1;
 }
 
@@ -1626,9 +1571,7 @@ void Device::rowdiag_plan_apply(long long id, const double *values_host, double 
 
 void Device::rowdiag_plan_free(long long id) {
     if (id < 0 || id >= (long long)rd_plans_.size() || !rd_plans_[id].seg) return;
-    RowDiagPlan &P = rd_plans_[id];
-    (void)hipFree(P.seg); (void)hipFree(P.off); (void)hipFree(P.p); (void)hipFree(P.q); (void)hipFree(P.vals); (void)hipFree(P.out);
-    P = RowDiagPlan{};
+    rd_plans_[id] = RowDiagPlan{};
 }
 
 void Device::dense_apply(const double *d_D, const double *d_T, double *d_R, long long n1, long long n2) {
@@ -1659,8 +1602,8 @@ void Device::set_batch(int nbatch, long long n_member, long long nnz_member) {
     d_bpsum_ = dalloc<double>((size_t)nbatch * batch_diag_parts((int)n_member));
     d_bpbad_ = dalloc<int>((size_t)nbatch * batch_diag_parts((int)n_member));
     d_bdiag_ = dalloc<double>(2 * (size_t)nbatch);
-    HC(hipHostMalloc((void **)&h_bdiag_, 2 * (size_t)nbatch * sizeof(double), hipHostMallocDefault));
-    HC(hipEventCreateWithFlags(&ev_bdiag_, hipEventDisableTiming));
+    h_bdiag_.alloc(2 * (long long)nbatch);
+    ev_bdiag_.create(hipEventDisableTiming);
     // the member's pattern = the forest's first n_member columns (rows unshifted)
     d_bin_colptr_ = dalloc<long long>((size_t)n_member + 1);
     d_bin_row_ = dalloc<int>((size_t)std::max<long long>(nnz_member, 1));
@@ -1700,11 +1643,11 @@ void Device::prepare_batch_quadform(long long npairs) {
     if (npairs > bqf_cap_) {
         const long long cap = std::max<long long>(npairs, 2 * bqf_cap_);
         bqf_cap_ = 0;
-        d_bqf_part_ = dregrow(d_bqf_part_, (size_t)(cap * nblk));
-        d_bqf_out_ = dregrow(d_bqf_out_, (size_t)cap);
+        regrow(d_bqf_part_, (size_t)(cap * nblk), &bytes_total);
+        regrow(d_bqf_out_, (size_t)cap, &bytes_total);
         bqf_cap_ = cap;
     }
-    grow_pinned(h_bqf_, h_bqf_cap_, npairs, 64);
+    h_bqf_.grow(npairs, 64);
 }
 
 void Device::enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,
@@ -1747,7 +1690,7 @@ void Device::batch_refactorize_logpdf(const double *d_nz, const double *d_X, lon
         HC(hipEventRecord(ev_ready_, stream));
         HC(hipStreamWaitEvent(stream2, ev_ready_, 0));
         enqueue_batch_quadform(stream2, d_nz, d_X, ldx, sx, nvec, d_mu);
-        if (!ev_qf_) HC(hipEventCreateWithFlags(&ev_qf_, hipEventDisableTiming));
+        ev_qf_.ensure(hipEventDisableTiming);
         HC(hipEventRecord(ev_qf_, stream2));
     }
     begin_factor(d_nz);

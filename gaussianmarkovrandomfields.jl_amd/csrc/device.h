@@ -8,6 +8,7 @@
 
 #include "device_plan.h"
 #include "rbmc_plan.h"
+#include "resource.h"
 
 namespace gmrfx { constexpr int kSyrkPipedMinCols = 128; }     // see DeviceFactor::syrk_piped_min_
 
@@ -65,6 +66,7 @@ struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoP
 // Where one sweep pass runs: a stream and the right-hand-side buffers it works in (X: the pass's columns in elimination order,
 // X2: y of the big fronts, W: the update vectors). The sweep drivers take it as a parameter; nothing selects a lane by state.
 struct SweepLane { hipStream_t st; double *X, *X2, *W; };
+constexpr size_t kTableMinBytes = 8;      // the constraint / RBMC tables' size rule: 8 bytes at least (+ the 16 of slack)
 class Device {
 public:
     Device() = default;
@@ -116,7 +118,7 @@ public:
                const MemberLayout *ml = nullptr);
     // ---- batched handles (gmrfx_create_batched): nbatch members of n_member nodes, the forest diag(Q_1 .. Q_B) -------------------
     void set_batch(int nbatch, long long n_member, long long nnz_member);
-    bool batched() const { return h_bdiag_ != nullptr; }
+    bool batched() const { return (bool)h_bdiag_; }
     // per-member log det / pivot status (1 + member-local column, 0 = fine) of the current factorisation, host arrays of nbatch
     void batch_diag(double *logdet_out, long long *info_out);
     // quad[k nvec + v] = (x_vk - mu_k)' Q_k (x_vk - mu_k), device operands: x_vk = d_X + k sx + v ldx, Q_k = d_nz + k nnz_member,
@@ -209,11 +211,10 @@ public:
     double bytes_total = 0;
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t own_stream_ = nullptr;   // the main stream this handle created (`stream` may be the caller's: set_external_stream)
+    Stream own_stream_;                  // the main stream this handle created (`stream` may be the caller's: set_external_stream)
     bool async_phases_ = false;          // sharded phase entry points return after enqueueing (no host synchronisation, no timings)
-    hipStream_t stream2 = nullptr;  // side stream: dense-inverse stages overlap the leaf levels of the forward sweep
-    hipStream_t stream3 = nullptr;  // second sweep lane (solves with more than 64 right-hand sides)
-    hipEvent_t ev_fact_ = nullptr, ev_inv_ = nullptr;
+    Stream stream2;                 // side stream: dense-inverse stages overlap the leaf levels of the forward sweep
+    Stream stream3;                 // second sweep lane (solves with more than 64 right-hand sides)
 
 private:
     void upload(const Symbolic &S);
@@ -225,7 +226,7 @@ private:
     void forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor);
     void backward(const SweepLane &ln, int nr, int ldx, bool y_in_x2, int hi, int lo);
     // one pass of a solve on lane ln: transpose in, forward (mode 0), backward, transpose out; ev (nullable): the lane's five timing events
-    void sweep_pass(const SweepLane &ln, hipEvent_t *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
+    void sweep_pass(const SweepLane &ln, const Event *ev, const double *dB, long long ldin, double *dXo, long long ldout, int nr, int mode,
                     const MemberLayout *ml);
     // lane 0: the main stream and d_X_ / d_X2_ / d_W_; lane 1: the third stream and their twins (solves of more than 64 right-hand sides)
     SweepLane lane(int k) const { return k == 0 ? SweepLane{stream, d_X_, d_X2_, d_W_} : SweepLane{stream3, d_Xb_, d_X2b_, d_Wb_}; }
@@ -236,10 +237,13 @@ private:
     void newton_values(const double *h, bool on_device);
     void ensure_io(long long need);
     void read_batch_diag(double *logdet_out, long long *info_out) const;
+    // Members are destroyed in reverse order of declaration: the streams (own_stream_, stream2, stream3 above, stream_io_ here) are
+    // declared before every buffer and event of the handle, so that those are released first and the streams last.
+    Stream stream_io_;                // copy stream of the pipelined call's host I/O
+    Event ev_fact_, ev_inv_;
+    // the arena of the tables that live as long as the handle (append-only, released by the destructor)
     template <class T> T *dalloc(size_t count);
-    // growable buffer: frees the previous allocation (after the streams have drained) and takes it off the books
-    template <class T> T *dregrow(T *old, size_t count);
-    std::vector<std::pair<void *, size_t>> allocs_;
+    std::vector<void *> allocs_;
 
     const Symbolic *S_ = nullptr;
     const SelRec *d_selrec_ = nullptr;    // one per supernode
@@ -256,7 +260,7 @@ private:
     FwdTile *d_fwd_recs_ = nullptr;     // one record per 32-row tile of every big front's update vector (sweep levels)
     double *d_nzp_ = nullptr;           // Q's values in assembly order (nzp[q] = nzval[qsrc[q]]): gathered once per factorisation, one dependent load less per panel column
     long long nq_ = 0;
-    hipEvent_t ev_nzp_ = nullptr, ev_nzp0_ = nullptr;
+    Event ev_nzp_, ev_nzp0_;
     AsmRec *d_arec_ = nullptr;          // one per position of the level lists (Symbolic::levellist order)
     SyrkTile *d_syrk_recs_ = nullptr;   // one record per contribution-block tile, level by level, in hand-out order
     int syrk_piped_min_ = kSyrkPipedMinCols;      // GMRFX_SYRK_PIPED=N: levels whose widest front has >= N columns take the software-pipelined
@@ -291,7 +295,7 @@ private:
     std::vector<int> sel_max_cols_, sel_max_trail_;   // per level, over the big fronts of the selected-inversion list
     int *d_dist_list_ = nullptr;  // the distributed fronts (Symbolic::dist_fronts) as a device list for the assembly / SYRK kernels
     bool selinv_begun_ = false;   // sharded selected inversion: phase 0 has run since the last refactorisation (gmrfx_selinv_phase)
-    std::vector<hipEvent_t> ev_level_[3];
+    std::vector<Event> ev_level_[3];
     int level_slots_[3] = {0, 0, 0};
     void level_event(hipStream_t st, int phase, int slot);
     bool level_mark_ = false;     // GMRFX_LEVEL_MARK=1: an empty marker kernel in front of every level (profiling aid, tools/sweep_levels.py)
@@ -299,10 +303,12 @@ private:
     int nsub_cls_[3] = {0, 0, 0};
     double *d_L_ = nullptr, *d_Z_ = nullptr, *d_cb_ = nullptr, *d_nz_ = nullptr;
     const double *nz_src_ = nullptr;
-    double *d_prior_ = nullptr, *d_h_ = nullptr;
-    long long *d_hmap_ = nullptr;
+    double *d_prior_ = nullptr;
+    DevBuf<double> d_h_;
+    DevBuf<long long> d_hmap_;
     long long hmap_cnt_ = 0, hmap_cap_ = 0;   // values of the refactorisation in flight (d_nz_ or the caller's device buffer)
-    double *d_X_ = nullptr, *d_X2_ = nullptr, *d_W_ = nullptr, *d_io_ = nullptr, *d_tmp_ = nullptr, *d_part_ = nullptr;
+    double *d_X_ = nullptr, *d_X2_ = nullptr, *d_W_ = nullptr, *d_part_ = nullptr;
+    DevBuf<double> d_io_, d_tmp_;
     // dense-inverse stages (inverse.hip)
     int *d_invlist_ = nullptr;
     std::vector<int> inv_nact_;            // per stage: fronts with more than 64<<stage columns
@@ -328,7 +334,7 @@ private:
     bool inverse_full_ = false;
     // pipelined factor + solve: per-level "level is factored" events, the dense-inverse stages per level, the highest level a
     // sweep task / small subtree reaches
-    std::vector<hipEvent_t> ev_flevel_;
+    std::vector<Event> ev_flevel_;
     int bottom_top_level_ = 0, fused_gate_level_ = 0;
     int *d_inv_lvl_list_ = nullptr;
     std::vector<int> inv_lvl_first_, inv_lvl_maxc_;
@@ -336,14 +342,13 @@ private:
     std::vector<long long *> d_inv_lvl_toff_;                  // per stage: offsets into d_invT_, aligned with d_inv_lvl_list_
     void invert_level(hipStream_t st, int lev);
     bool fact_event_valid_ = false;   // ev_fact_ was recorded at the end of the last factorisation
-    int *h_info_ = nullptr;           // pinned: the pivot report of the last factorisation
-    double *h_qf_ = nullptr;          // pinned: quadratic forms of refactorize_logpdf
-    long long h_qf_cap_ = 0;
-    hipEvent_t ev_qf_ = nullptr;
+    PinnedBuf<int> h_info_;           // the pivot report of the last factorisation
+    PinnedBuf<double> h_qf_;          // quadratic forms of refactorize_logpdf
+    Event ev_qf_;
     void prepare_quadform(long long nvec);
-    double *h_logdet_ = nullptr;      // pinned: log det of factorisation logdet_for_ (valid once ev_logdet_ has passed)
+    PinnedBuf<double> h_logdet_;      // log det of factorisation logdet_for_ (valid once ev_logdet_ has passed)
     unsigned long long logdet_for_ = 0;
-    hipEvent_t ev_logdet_ = nullptr;
+    Event ev_logdet_;
     void enqueue_logdet(hipStream_t st, bool timed);
     bool info_cached_ = false;
     void invert_diag_blocks(hipStream_t st, int b_from, int b_to);
@@ -359,84 +364,89 @@ private:
     // Solves with more than 64 right-hand sides run their 64-column passes on TWO lanes (SweepLane: stream + buffers each):
     // one pass is launch-latency bound (4.6 ms for 1 column, 5.9 for 64), two interleave on the idle CUs.
     double *d_Xb_ = nullptr, *d_X2b_ = nullptr, *d_Wb_ = nullptr;   // lane 1 (lane 0 = d_X_ / d_X2_ / d_W_ on `stream`): lane()
-    hipEvent_t ev_lane_[2][5] = {};
-    hipEvent_t ev_ready_ = nullptr, ev_ready2_ = nullptr, ev_done1_ = nullptr;
+    Event ev_lane_[2][5];
+    Event ev_ready_, ev_ready2_, ev_done1_;
     int *d_info_ = nullptr;
-    // host I/O of the pipelined factor + solve call: copy stream, page-locked staging buffer, events
-    hipStream_t stream_io_ = nullptr;
-    double *h_stage_ = nullptr, *h_nzstage_ = nullptr;
-    long long h_stage_cap_ = 0;
+    // host I/O of the pipelined factor + solve call (copy stream: stream_io_): page-locked staging buffers, events
+    PinnedBuf<double> h_stage_, h_nzstage_;
     void host_upload_values(const double *nzval);
-    hipEvent_t ev_up_ = nullptr, ev_x_ = nullptr;
-    std::vector<hipEvent_t> ev_ring_;             // one per slot of the page-locked staging ring (host_upload / host_download)
+    Event ev_up_, ev_x_;
+    std::vector<Event> ev_ring_;                  // one per slot of the page-locked staging ring (host_upload / host_download)
     void host_io_reserve(long long count);
     void host_upload(const double *B, long long ldb, long long nrhs, double *d_dst);
     void host_download(const double *d_src, long long nrhs, double *X, long long ldx, hipStream_t after);
-    struct RowDiagPlan { long long nseg = 0, cnt = 0, nvals = 0; long long *seg = nullptr, *off = nullptr; int *p = nullptr, *q = nullptr; double *vals = nullptr, *out = nullptr; };
+    struct RowDiagPlan { long long nseg = 0, cnt = 0, nvals = 0; DevBuf<long long> seg, off; DevBuf<int> p, q; DevBuf<double> vals, out; };     // (not on the handle's books)
     std::vector<RowDiagPlan> rd_plans_;
     // caller's CSC pattern, uploaded on the first quadform call
     long long *d_in_colptr_ = nullptr;
     int *d_in_row_ = nullptr;
-    double *d_qf_part_ = nullptr, *d_qf_out_ = nullptr;
+    DevBuf<double> d_qf_part_, d_qf_out_;
     long long qf_cap_ = 0;
     bool nz_held_ = false;    // d_nz_ holds the values of the factorisation
-    hipEvent_t ev_[8] = {};
-    std::vector<hipEvent_t> ev_syrk_;   // begin/end event of every k_syrk_cb launch
+    Event ev_[8];
+    std::vector<Event> ev_syrk_;        // begin/end event of every k_syrk_cb launch
     long long l_size_ = 0, sum_trail_ = 0;
     // batched handles (set_batch): members, member size / values; device partials + results of batch_diag / batch_quadform, pinned copies
     int nbatch_ = 1;
     long long nmember_ = 0, nnz_member_ = 0;
-    double *d_bpsum_ = nullptr, *d_bdiag_ = nullptr, *h_bdiag_ = nullptr;    // d_bdiag_ / h_bdiag_: nbatch log dets, then nbatch info words
+    double *d_bpsum_ = nullptr, *d_bdiag_ = nullptr;
+    PinnedBuf<double> h_bdiag_;                   // d_bdiag_ / h_bdiag_: nbatch log dets, then nbatch info words
     int *d_bpbad_ = nullptr;
     unsigned long long bdiag_for_ = 0;            // h_bdiag_ belongs to factorisation number bdiag_for_
-    hipEvent_t ev_bdiag_ = nullptr;
+    Event ev_bdiag_;
     long long *d_bin_colptr_ = nullptr;           // the MEMBER's pattern (the forest's first n_member columns)
     int *d_bin_row_ = nullptr;
-    double *d_bqf_part_ = nullptr, *d_bqf_out_ = nullptr, *h_bqf_ = nullptr;
-    long long bqf_cap_ = 0, h_bqf_cap_ = 0;
+    DevBuf<double> d_bqf_part_, d_bqf_out_;
+    PinnedBuf<double> h_bqf_;
+    long long bqf_cap_ = 0;
     void enqueue_batch_diag(hipStream_t st);
-    // constraint state: A (CSR) and e on the device, chunk offsets of the reduction, the cached operands of factorisation con_.serial
-    struct ConDev {
+    // what con_set / bcon_set keep of A itself: the CSR rows and e on the device, the chunk offsets of the reduction and its buffers
+    // (R: m x colcap, part: totchunks x colcap, per member)
+    struct ConRows {
         int m = 0, maxchunks = 0;
         long long nnz = 0, maxlen = 0, totchunks = 0, colcap = 0;
-        long long *rowptr = nullptr;
-        int *col = nullptr, *choff = nullptr;
-        double *val = nullptr, *e = nullptr, *At = nullptr, *B = nullptr, *Linv = nullptr, *R = nullptr, *amu = nullptr, *part = nullptr, *sig = nullptr;
+        DevBuf<long long> rowptr;
+        DevBuf<int> col, choff;
+        DevBuf<double> val, e, R, part;
+    };
+    ConRows con_rows_upload(const ConHost &c);
+    void con_reserve_cols(ConRows &a, long long cols, int members);
+    // constraint state: A, the cached operands of factorisation serial. The events outlive the state: a new A replaces the state only.
+    struct ConDev : ConRows {
+        DevBuf<double> At, B, Linv, amu, sig;
         std::vector<double> h_w, h_linv;
         double logdet_w = 0, ms = 0;
         unsigned long long serial = 0;      // 0: nothing cached
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } con_;
-    struct BConDev {
-        int m = 0, maxchunks = 0;
-        long long nnz = 0, maxlen = 0, totchunks = 0, colcap = 0, piece = 0;
-        long long *rowptr = nullptr, *cinfo = nullptr;
-        int *col = nullptr, *choff = nullptr;
-        double *val = nullptr, *e = nullptr, *At = nullptr, *B = nullptr, *W = nullptr, *Linv = nullptr, *R = nullptr, *amu = nullptr, *part = nullptr,
-               *sig = nullptr, *stat = nullptr;      // stat: nbatch log det W, then nbatch |L_c^-1 r|^2
+    struct BConDev : ConRows {
+        long long piece = 0;
+        DevBuf<long long> cinfo;
+        DevBuf<double> At, B, W, Linv, amu, sig, stat;      // stat: nbatch log det W, then nbatch |L_c^-1 r|^2
         std::vector<double> h_logdet;
         std::vector<long long> h_cinfo;
         double ms = 0;
         bool ok = false;
         unsigned long long serial = 0;      // 0: nothing cached
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
     } bcon_;
-    struct RbmcState {
-        long long *rp = nullptr, *bptr = nullptr, *eptr = nullptr;
-        int *col = nullptr, *pos = nullptr, *dpos = nullptr, *rows = nullptr, *ns = nullptr, *loc = nullptr, *order[kRbmcClasses] = {};
-        unsigned char *owner = nullptr;
+    Event con_ev_[2], bcon_ev_[2], rb_ev_[2];     // begin / end of the timed part of con_*, bcon_*, rbmc_var
+    // RBMC state: the symmetric row structure of Q and the work arrays (uploaded once), the tables of the current block plan
+    struct RbmcSymDev {
+        DevBuf<long long> rp;
+        DevBuf<int> col, pos, dpos;
+        DevBuf<double> Xc, Xt, mean, m2, base, out;
+    };
+    struct RbmcPlanDev {
+        DevBuf<long long> bptr, eptr;
+        DevBuf<int> rows, ns, loc, order[kRbmcClasses];
+        DevBuf<unsigned char> owner;
         int cnt[kRbmcClasses] = {};
-        double *Xc = nullptr, *Xt = nullptr, *mean = nullptr, *m2 = nullptr, *base = nullptr, *out = nullptr, *scrM = nullptr, *scrR = nullptr;
-        int plan_enclosure = -2;
-        unsigned long long plan_serial = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    } rb_;
+        DevBuf<double> scrM, scrR;
+        int enclosure = -2;
+        unsigned long long serial = 0;
+    };
+    struct RbmcState { RbmcSymDev sym; RbmcPlanDev plan; } rb_;
     void rbmc_upload_sym(const RbmcSym &sym);
     void rbmc_upload_plan(const RbmcPlan &plan);
-    void bcon_free(BConDev &b);
-    void bcon_reserve_cols(long long want);
-    void *con_alloc(size_t bytes);
-    void con_release(void *p);
     void con_drop();
     void prepare_batch_quadform(long long npairs);
     void enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,

@@ -20,35 +20,37 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-void *Device::con_alloc(size_t bytes) {
-    void *p = nullptr;
-    bytes = std::max<size_t>(bytes, 8) + 16;       // 16 bytes of slack, as dalloc
-    HC(hipMalloc(&p, bytes));
-    allocs_.push_back({p, bytes});
-    bytes_total += (double)bytes;
-    return p;
-}
-
-void Device::con_release(void *p) {
-    if (!p) return;
-    for (size_t k = 0; k < allocs_.size(); k++)
-        if (allocs_[k].first == p) {
-            bytes_total -= (double)allocs_[k].second;
-            allocs_.erase(allocs_.begin() + (long)k);
-            break;
-        }
-    (void)hipFree(p);
+// A's rows, e and the chunk offsets of the reduction on the device (c.m > 0)
+Device::ConRows Device::con_rows_upload(const ConHost &c) {
+    ConRows a;
+    const int m = c.m;
+    const long long nnz = c.rowptr[m];
+    std::vector<int> choff((size_t)m + 1, 0);
+    for (int r = 0; r < m; r++) {
+        const long long len = c.rowptr[r + 1] - c.rowptr[r];
+        const int ch = (int)((len + kConChunk - 1) / kConChunk);
+        choff[r + 1] = choff[r] + ch;
+        a.maxlen = std::max(a.maxlen, len);
+        a.maxchunks = std::max(a.maxchunks, ch);
+    }
+    a.rowptr.alloc((size_t)m + 1, &bytes_total, kTableMinBytes);
+    a.col.alloc((size_t)nnz, &bytes_total, kTableMinBytes);
+    a.val.alloc((size_t)nnz, &bytes_total, kTableMinBytes);
+    a.e.alloc((size_t)m, &bytes_total, kTableMinBytes);
+    a.choff.alloc((size_t)m + 1, &bytes_total, kTableMinBytes);
+    HC(hipMemcpy(a.rowptr, c.rowptr.data(), (size_t)(m + 1) * sizeof(long long), hipMemcpyHostToDevice));
+    HC(hipMemcpy(a.col, c.col.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
+    HC(hipMemcpy(a.val, c.val.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
+    HC(hipMemcpy(a.e, c.e.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
+    HC(hipMemcpy(a.choff, choff.data(), (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice));
+    a.m = m; a.nnz = nnz; a.totchunks = choff[m];
+    return a;
 }
 
 void Device::con_drop() {
     HC(hipSetDevice(device));
     HC(hipDeviceSynchronize());        // nothing in flight may still read the buffers
-    for (void *p : {(void *)con_.rowptr, (void *)con_.col, (void *)con_.choff, (void *)con_.val, (void *)con_.e, (void *)con_.At, (void *)con_.B,
-                    (void *)con_.Linv, (void *)con_.R, (void *)con_.amu, (void *)con_.part, (void *)con_.sig})
-        con_release(p);
-    const hipEvent_t e0 = con_.ev0, e1 = con_.ev1;
     con_ = ConDev();
-    con_.ev0 = e0; con_.ev1 = e1;
 }
 
 void Device::con_set(const ConHost &c) {
@@ -56,43 +58,31 @@ void Device::con_set(const ConHost &c) {
     if (c.m <= 0) return;
     if (sharded() || nbatch_ > 1) throw std::invalid_argument("constraints need a plain (unsharded, unbatched) handle");
     const int m = c.m;
-    const long long n = S_->n, nnz = c.rowptr[m];
-    std::vector<int> choff((size_t)m + 1, 0);
-    long long maxlen = 0;
-    int maxchunks = 0;
-    for (int r = 0; r < m; r++) {
-        const long long len = c.rowptr[r + 1] - c.rowptr[r];
-        const int ch = (int)((len + kConChunk - 1) / kConChunk);
-        choff[r + 1] = choff[r] + ch;
-        maxlen = std::max(maxlen, len);
-        maxchunks = std::max(maxchunks, ch);
-    }
-    try {
-        con_.rowptr = (long long *)con_alloc((size_t)(m + 1) * sizeof(long long));
-        con_.col = (int *)con_alloc((size_t)nnz * sizeof(int));
-        con_.val = (double *)con_alloc((size_t)nnz * sizeof(double));
-        con_.e = (double *)con_alloc((size_t)m * sizeof(double));
-        con_.choff = (int *)con_alloc((size_t)(m + 1) * sizeof(int));
-        con_.At = (double *)con_alloc((size_t)n * m * sizeof(double));
-        con_.B = (double *)con_alloc((size_t)n * m * sizeof(double));
-        con_.Linv = (double *)con_alloc((size_t)m * m * sizeof(double));
-        con_.amu = (double *)con_alloc((size_t)m * sizeof(double));
-        con_.sig = (double *)con_alloc((size_t)n * sizeof(double));
-        HC(hipMemcpy(con_.rowptr, c.rowptr.data(), (size_t)(m + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        HC(hipMemcpy(con_.col, c.col.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-        HC(hipMemcpy(con_.val, c.val.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-        HC(hipMemcpy(con_.e, c.e.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-        HC(hipMemcpy(con_.choff, choff.data(), (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice));
-        if (!con_.ev0) { HC(hipEventCreate(&con_.ev0)); HC(hipEventCreate(&con_.ev1)); }
-    } catch (...) {
-        con_drop();
-        throw;
-    }
-    con_.m = m; con_.nnz = nnz; con_.maxlen = maxlen; con_.maxchunks = maxchunks; con_.totchunks = choff[m];
+    const long long n = S_->n;
+    ConDev d;        // a failure half-way leaves the handle without constraints
+    static_cast<ConRows &>(d) = con_rows_upload(c);
+    d.At.alloc((size_t)n * m, &bytes_total, kTableMinBytes);
+    d.B.alloc((size_t)n * m, &bytes_total, kTableMinBytes);
+    d.Linv.alloc((size_t)m * m, &bytes_total, kTableMinBytes);
+    d.amu.alloc((size_t)m, &bytes_total, kTableMinBytes);
+    d.sig.alloc((size_t)n, &bytes_total, kTableMinBytes);
+    for (Event &e : con_ev_) e.ensure();
+    con_ = std::move(d);
 }
 
 // column capacity of the reduction's buffers (R: m x cols, part: totchunks x cols); wider blocks go through in pieces
 static constexpr long long kConColBatch = 1024;
+
+// the reduction's buffers for `cols` columns: the new pair first (released again if either does not fit), the old pair goes
+// once nothing in flight can still read it
+void Device::con_reserve_cols(ConRows &a, long long cols, int members) {
+    if (a.colcap >= cols) return;
+    DevBuf<double> R, part;
+    R.alloc((size_t)a.m * cols * members, &bytes_total, kTableMinBytes);
+    part.alloc((size_t)a.totchunks * cols * members, &bytes_total, kTableMinBytes);
+    HC(hipDeviceSynchronize());
+    a.R = std::move(R); a.part = std::move(part); a.colcap = cols;
+}
 
 bool Device::con_prepare() {
     HC(hipSetDevice(device));
@@ -100,14 +90,8 @@ bool Device::con_prepare() {
     if (m <= 0 || con_.serial == factor_serial_) return true;
     const long long n = S_->n;
     con_.serial = 0;
-    if (con_.colcap < m) {       // W is an m-column product
-        const long long cap = 64;
-        void *R = con_alloc((size_t)m * cap * sizeof(double)), *part = con_alloc((size_t)con_.totchunks * cap * sizeof(double));
-        HC(hipDeviceSynchronize());
-        con_release(con_.R); con_release(con_.part);
-        con_.R = (double *)R; con_.part = (double *)part; con_.colcap = cap;
-    }
-    HC(hipEventRecord(con_.ev0, stream));
+    if (con_.colcap < m) con_reserve_cols(con_, 64, 1);       // W is an m-column product
+    HC(hipEventRecord(con_ev_[0], stream));
     HC(hipMemsetAsync(con_.At, 0, (size_t)n * m * sizeof(double), stream));
     launch_con_scatter(stream, con_.rowptr, con_.col, con_.val, (int)n, m, con_.maxlen, con_.At);
     solve(con_.At, n, m, con_.At, n, true, 0);          // one pass of the sweeps (m <= 64): in place
@@ -142,11 +126,11 @@ bool Device::con_prepare() {
     }
     HC(hipMemcpyAsync(con_.Linv, Li.data(), (size_t)m * m * sizeof(double), hipMemcpyHostToDevice, stream));
     launch_con_trsm(stream, con_.At, con_.Linv, (int)n, m, con_.B);
-    HC(hipEventRecord(con_.ev1, stream));
+    HC(hipEventRecord(con_ev_[1], stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
     float ms = 0;
-    HC(hipEventElapsedTime(&ms, con_.ev0, con_.ev1));
+    HC(hipEventElapsedTime(&ms, con_ev_[0], con_ev_[1]));
     con_.ms = ms;
     con_.h_w = W; con_.h_linv = Li; con_.logdet_w = ld;
     con_.serial = factor_serial_;
@@ -176,28 +160,22 @@ void Device::con_correct(double *d_X, long long ldx, long long nvec, const doubl
         HC(hipGetLastError());
         return;
     }
-    const long long want = std::min(kConColBatch, nvec);
-    if (con_.colcap < want) {
-        void *R = con_alloc((size_t)m * want * sizeof(double)), *part = con_alloc((size_t)con_.totchunks * want * sizeof(double));
-        HC(hipDeviceSynchronize());
-        con_release(con_.R); con_release(con_.part);
-        con_.R = (double *)R; con_.part = (double *)part; con_.colcap = want;
-    }
-    HC(hipEventRecord(con_.ev0, stream));
+    con_reserve_cols(con_, std::min(kConColBatch, nvec), 1);
+    HC(hipEventRecord(con_ev_[0], stream));
     // with a mean: A (X + mu) - e = A X + (A mu - e), the second term once
     if (d_mu) launch_con_ax(stream, con_.rowptr, con_.col, con_.val, con_.choff, con_.maxchunks, m, d_mu, n, 1, con_.part, con_.e, nullptr, con_.amu);
     for (long long j0 = 0; j0 < nvec; j0 += kConColBatch) {
         const int k = (int)std::min(kConColBatch, nvec - j0);
         double *X = d_X + j0 * ldx;
-        launch_con_ax(stream, con_.rowptr, con_.col, con_.val, con_.choff, con_.maxchunks, m, X, ldx, k, con_.part, d_mu ? nullptr : con_.e,
-                      d_mu ? con_.amu : nullptr, con_.R);
+        launch_con_ax(stream, con_.rowptr, con_.col, con_.val, con_.choff, con_.maxchunks, m, X, ldx, k, con_.part, d_mu ? nullptr : con_.e.get(),
+                      d_mu ? con_.amu.get() : nullptr, con_.R);
         launch_con_apply(stream, con_.B, con_.Linv, con_.R, d_mu, X, ldx, (int)n, m, k);
     }
-    HC(hipEventRecord(con_.ev1, stream));
+    HC(hipEventRecord(con_ev_[1], stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
     float ms = 0;
-    HC(hipEventElapsedTime(&ms, con_.ev0, con_.ev1));
+    HC(hipEventElapsedTime(&ms, con_ev_[0], con_ev_[1]));
     ms_con_correct = ms;
 }
 
@@ -225,91 +203,31 @@ static long long bcon_piece(int nbatch) {
     return std::min<long long>(kConColBatch, std::max<long long>(64, (8192 / std::max(nbatch, 1)) / 64 * 64));
 }
 
-void Device::bcon_free(BConDev &b) {
-    for (void *p : {(void *)b.rowptr, (void *)b.cinfo, (void *)b.col, (void *)b.choff, (void *)b.val, (void *)b.e, (void *)b.At, (void *)b.B, (void *)b.W,
-                    (void *)b.Linv, (void *)b.R, (void *)b.amu, (void *)b.part, (void *)b.sig, (void *)b.stat})
-        con_release(p);
-    const hipEvent_t e0 = b.ev0, e1 = b.ev1;
-    b = BConDev();
-    b.ev0 = e0; b.ev1 = e1;
-}
-
 void Device::bcon_set(const ConHost &c) {
     HC(hipSetDevice(device));
     if (c.m <= 0) {
         HC(hipDeviceSynchronize());
-        bcon_free(bcon_);
+        bcon_ = BConDev();
         return;
     }
     if (sharded() || !batched()) throw std::invalid_argument("batch constraints need an unsharded handle with its batch buffers");
     if (nbatch_ > 65535) throw std::invalid_argument("batch constraints: more than 65535 members");
     const int m = c.m, nb = nbatch_;
-    const long long n = nmember_, nnz = c.rowptr[m];
-    std::vector<int> choff((size_t)m + 1, 0);
-    long long maxlen = 0;
-    int maxchunks = 0;
-    for (int r = 0; r < m; r++) {
-        const long long len = c.rowptr[r + 1] - c.rowptr[r];
-        const int ch = (int)((len + kConChunk - 1) / kConChunk);
-        choff[r + 1] = choff[r] + ch;
-        maxlen = std::max(maxlen, len);
-        maxchunks = std::max(maxchunks, ch);
-    }
+    const long long n = nmember_;
     BConDev b;      // built aside: a failure leaves the handle's state as it was
-    try {
-        // the two big arrays first, and quietly: that they do not fit is an answer (GMRFX_ERR_ALLOC), not a failure of the device
-        for (double **big : {&b.At, &b.B}) {
-            void *p = nullptr;
-            const size_t bytes = (size_t)n * nb * m * sizeof(double) + 16;
-            if (hipMalloc(&p, bytes) != hipSuccess) {
-                (void)hipGetLastError();
-                throw std::bad_alloc();
-            }
-            allocs_.push_back({p, bytes});
-            bytes_total += (double)bytes;
-            *big = (double *)p;
-        }
-        b.rowptr = (long long *)con_alloc((size_t)(m + 1) * sizeof(long long));
-        b.col = (int *)con_alloc((size_t)nnz * sizeof(int));
-        b.val = (double *)con_alloc((size_t)nnz * sizeof(double));
-        b.e = (double *)con_alloc((size_t)m * sizeof(double));
-        b.choff = (int *)con_alloc((size_t)(m + 1) * sizeof(int));
-        b.W = (double *)con_alloc((size_t)m * m * nb * sizeof(double));
-        b.Linv = (double *)con_alloc((size_t)m * m * nb * sizeof(double));
-        b.amu = (double *)con_alloc((size_t)m * nb * sizeof(double));
-        b.sig = (double *)con_alloc((size_t)n * nb * sizeof(double));
-        b.stat = (double *)con_alloc(2 * (size_t)nb * sizeof(double));
-        b.cinfo = (long long *)con_alloc((size_t)nb * sizeof(long long));
-        HC(hipMemcpy(b.rowptr, c.rowptr.data(), (size_t)(m + 1) * sizeof(long long), hipMemcpyHostToDevice));
-        HC(hipMemcpy(b.col, c.col.data(), (size_t)nnz * sizeof(int), hipMemcpyHostToDevice));
-        HC(hipMemcpy(b.val, c.val.data(), (size_t)nnz * sizeof(double), hipMemcpyHostToDevice));
-        HC(hipMemcpy(b.e, c.e.data(), (size_t)m * sizeof(double), hipMemcpyHostToDevice));
-        HC(hipMemcpy(b.choff, choff.data(), (size_t)(m + 1) * sizeof(int), hipMemcpyHostToDevice));
-        if (!bcon_.ev0) { HC(hipEventCreate(&bcon_.ev0)); HC(hipEventCreate(&bcon_.ev1)); }
-    } catch (...) {
-        bcon_free(b);
-        throw;
-    }
-    b.m = m; b.nnz = nnz; b.maxlen = maxlen; b.maxchunks = maxchunks; b.totchunks = choff[m]; b.piece = bcon_piece(nb);
-    b.ev0 = bcon_.ev0; b.ev1 = bcon_.ev1;
+    // the two big arrays first, and quietly: that they do not fit is an answer (GMRFX_ERR_ALLOC), not a failure of the device
+    if (!b.At.try_alloc((size_t)n * nb * m, &bytes_total) || !b.B.try_alloc((size_t)n * nb * m, &bytes_total)) throw std::bad_alloc();
+    static_cast<ConRows &>(b) = con_rows_upload(c);
+    b.W.alloc((size_t)m * m * nb, &bytes_total, kTableMinBytes);
+    b.Linv.alloc((size_t)m * m * nb, &bytes_total, kTableMinBytes);
+    b.amu.alloc((size_t)m * nb, &bytes_total, kTableMinBytes);
+    b.sig.alloc((size_t)n * nb, &bytes_total, kTableMinBytes);
+    b.stat.alloc(2 * (size_t)nb, &bytes_total, kTableMinBytes);
+    b.cinfo.alloc((size_t)nb, &bytes_total, kTableMinBytes);
+    for (Event &e : bcon_ev_) e.ensure();
+    b.piece = bcon_piece(nb);
     HC(hipDeviceSynchronize());        // nothing in flight may still read the previous buffers
-    bcon_free(bcon_);
-    bcon_ = b;
-}
-
-void Device::bcon_reserve_cols(long long want) {
-    if (bcon_.colcap >= want) return;
-    void *R = con_alloc((size_t)bcon_.m * want * nbatch_ * sizeof(double));
-    void *part = nullptr;
-    try {
-        part = con_alloc((size_t)bcon_.totchunks * want * nbatch_ * sizeof(double));
-    } catch (...) {
-        con_release(R);
-        throw;
-    }
-    HC(hipDeviceSynchronize());
-    con_release(bcon_.R); con_release(bcon_.part);
-    bcon_.R = (double *)R; bcon_.part = (double *)part; bcon_.colcap = want;
+    bcon_ = std::move(b);
 }
 
 bool Device::bcon_prepare() {
@@ -320,9 +238,9 @@ bool Device::bcon_prepare() {
     if (b.serial == factor_serial_) return b.ok;
     const long long n = nmember_;
     b.serial = 0;
-    bcon_reserve_cols(64);       // W_k is an m-column product
+    con_reserve_cols(bcon_, 64, nbatch_);       // W_k is an m-column product
     if (bdiag_for_ != factor_serial_) enqueue_batch_diag(stream);       // the members' factorisation status, for k_batch_con_chol
-    HC(hipEventRecord(b.ev0, stream));
+    HC(hipEventRecord(bcon_ev_[0], stream));
     HC(hipMemsetAsync(b.At, 0, (size_t)n * nb * m * sizeof(double), stream));
     launch_con_scatter(stream, b.rowptr, b.col, b.val, (int)n, m, b.maxlen, b.At, nb);
     const MemberLayout ml{n, n * m, n * m};
@@ -331,7 +249,7 @@ bool Device::bcon_prepare() {
     launch_batch_con_chol(stream, b.W, m, nb, reinterpret_cast<const long long *>(d_bdiag_ + nbatch_), b.Linv, b.stat, b.cinfo);
     launch_batch_con_void(stream, b.cinfo, b.At, n * m, b.W, m * m, nb);
     launch_con_trsm(stream, b.At, b.Linv, (int)n, m, b.B, nb);
-    HC(hipEventRecord(b.ev1, stream));
+    HC(hipEventRecord(bcon_ev_[1], stream));
     b.h_logdet.assign((size_t)nb, 0.0);
     b.h_cinfo.assign((size_t)nb, 0);
     HC(hipMemcpyAsync(b.h_logdet.data(), b.stat, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -339,7 +257,7 @@ bool Device::bcon_prepare() {
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
     float ms = 0;
-    HC(hipEventElapsedTime(&ms, b.ev0, b.ev1));
+    HC(hipEventElapsedTime(&ms, bcon_ev_[0], bcon_ev_[1]));
     b.ms = ms;
     b.ok = true;
     for (int k = 0; k < nb; k++) b.ok = b.ok && b.h_cinfo[(size_t)k] <= 0;
@@ -364,14 +282,14 @@ void Device::bcon_correct(double *d_X, long long ldx, long long sx, long long nv
     const long long n = nmember_;
     if (nvec <= 0 || (m <= 0 && !d_mu)) return;
     const long long piece = m > 0 ? b.piece : bcon_piece(nb);
-    if (m > 0) bcon_reserve_cols(std::min(piece, nvec));
+    if (m > 0) con_reserve_cols(bcon_, std::min(piece, nvec), nbatch_);
     // with a mean: A (X + mu) - e = A X + (A mu - e), the second term once
     if (m > 0 && d_mu) launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_mu, n, 1, b.part, b.e, nullptr, b.amu, nb, n);
     for (long long j0 = 0; j0 < nvec; j0 += piece) {
         const int k = (int)std::min(piece, nvec - j0);
         double *X = d_X + j0 * ldx;
         if (m > 0)
-            launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, X, ldx, k, b.part, d_mu ? nullptr : b.e, d_mu ? b.amu : nullptr, b.R,
+            launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, X, ldx, k, b.part, d_mu ? nullptr : b.e.get(), d_mu ? b.amu.get() : nullptr, b.R,
                           nb, sx);
         launch_con_apply(stream, b.B, b.Linv, b.R, d_mu, X, ldx, (int)n, m, k, nb, sx, n);
     }
@@ -385,7 +303,7 @@ void Device::bcon_quad(const double *d_x, double *quad_host) {
     const int m = b.m, nb = nbatch_;
     const long long n = nmember_;
     if (m <= 0) { std::fill(quad_host, quad_host + nb, 0.0); return; }
-    bcon_reserve_cols(1);
+    con_reserve_cols(bcon_, 1, nbatch_);
     if (!d_x) HC(hipMemsetAsync(b.sig, 0, (size_t)n * sizeof(double), stream));       // a zero mean, shared by the members
     launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_x ? d_x : b.sig, n, 1, b.part, b.e, nullptr, b.R, nb, d_x ? n : 0);
     launch_batch_con_quad(stream, b.Linv, b.R, m, m, nb, b.stat + nb);

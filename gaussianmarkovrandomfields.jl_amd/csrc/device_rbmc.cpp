@@ -16,57 +16,55 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-template <class T, class U> static T *rb_up(void *dst, const std::vector<U> &src) {
+// dst = a device copy of src (converted to T), on the handle's books
+template <class T, class U> static void rb_up(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) {
     std::vector<T> tmp(src.begin(), src.end());
+    dst.alloc(tmp.size(), ledger, kTableMinBytes);
     if (!tmp.empty()) HC(hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
-    return (T *)dst;
 }
 
 void Device::rbmc_upload_sym(const RbmcSym &sym) {
-    if (rb_.rp) return;
-    const long long n = S_->n;
+    if (rb_.sym.rp) return;
+    const size_t n = (size_t)S_->n;
     if (S_->nnz_in > INT_MAX || (long long)sym.col.size() > (1ll << 40)) throw std::invalid_argument("rbmc: Q has too many stored entries for 32-bit positions");
-    long long *rp = (long long *)con_alloc((size_t)(n + 1) * sizeof(long long));
-    rb_.col = rb_up<int>(con_alloc(sym.col.size() * sizeof(int)), sym.col);
-    rb_.pos = rb_up<int>(con_alloc(sym.pos.size() * sizeof(int)), sym.pos);
-    rb_.dpos = rb_up<int>(con_alloc((size_t)n * sizeof(int)), sym.diag);
-    rb_.Xc = (double *)con_alloc((size_t)n * kRbmcW * sizeof(double));
-    rb_.Xt = (double *)con_alloc((size_t)n * kRbmcW * sizeof(double));
-    rb_.mean = (double *)con_alloc((size_t)n * sizeof(double));
-    rb_.m2 = (double *)con_alloc((size_t)n * sizeof(double));
-    rb_.base = (double *)con_alloc((size_t)n * sizeof(double));
-    rb_.out = (double *)con_alloc((size_t)n * sizeof(double));
-    if (!rb_.ev0) HC(hipEventCreate(&rb_.ev0));
-    if (!rb_.ev1) HC(hipEventCreate(&rb_.ev1));
-    rb_.rp = rb_up<long long>(rp, sym.rowptr);       // set last: marks the upload complete
+    RbmcSymDev d;        // built aside: an upload that fails half-way leaves nothing behind
+    rb_up(d.rp, sym.rowptr, &bytes_total);      // n + 1
+    rb_up(d.col, sym.col, &bytes_total);
+    rb_up(d.pos, sym.pos, &bytes_total);
+    rb_up(d.dpos, sym.diag, &bytes_total);      // n
+    d.Xc.alloc(n * kRbmcW, &bytes_total, kTableMinBytes);
+    d.Xt.alloc(n * kRbmcW, &bytes_total, kTableMinBytes);
+    d.mean.alloc(n, &bytes_total, kTableMinBytes);
+    d.m2.alloc(n, &bytes_total, kTableMinBytes);
+    d.base.alloc(n, &bytes_total, kTableMinBytes);
+    d.out.alloc(n, &bytes_total, kTableMinBytes);
+    for (Event &e : rb_ev_) e.ensure();
+    rb_.sym = std::move(d);
 }
 
 void Device::rbmc_upload_plan(const RbmcPlan &plan) {
-    if (rb_.plan_serial == plan.serial && rb_.plan_enclosure == plan.enclosure) return;
+    if (rb_.plan.serial == plan.serial && rb_.plan.enclosure == plan.enclosure) return;
     HC(hipDeviceSynchronize());        // nothing in flight may still read the old tables
-    for (void *p : {(void *)rb_.bptr, (void *)rb_.eptr, (void *)rb_.rows, (void *)rb_.ns, (void *)rb_.loc, (void *)rb_.owner, (void *)rb_.scrM,
-                    (void *)rb_.scrR, (void *)rb_.order[0], (void *)rb_.order[1], (void *)rb_.order[2], (void *)rb_.order[3]})
-        con_release(p);
-    rb_.bptr = rb_.eptr = nullptr; rb_.rows = rb_.ns = rb_.loc = nullptr; rb_.owner = nullptr; rb_.scrM = rb_.scrR = nullptr;
-    for (int c = 0; c < kRbmcClasses; c++) { rb_.order[c] = nullptr; rb_.cnt[c] = 0; }
-    rb_.plan_enclosure = -2; rb_.plan_serial = 0;
+    rb_.plan = RbmcPlanDev();
     if (plan.loc.size() > (size_t)1 << 40) throw std::invalid_argument("rbmc: plan too large");
-    rb_.bptr = rb_up<long long>(con_alloc(plan.block_ptr.size() * sizeof(long long)), plan.block_ptr);
-    rb_.eptr = rb_up<long long>(con_alloc(plan.eptr.size() * sizeof(long long)), plan.eptr);
-    rb_.rows = rb_up<int>(con_alloc(plan.rows.size() * sizeof(int)), plan.rows);
-    rb_.ns = rb_up<int>(con_alloc(plan.n_interior.size() * sizeof(int)), plan.n_interior);
-    rb_.loc = rb_up<int>(con_alloc(plan.loc.size() * sizeof(int)), plan.loc);
-    rb_.owner = rb_up<unsigned char>(con_alloc(plan.owner.size()), plan.owner);
+    RbmcPlanDev d;
+    rb_up(d.bptr, plan.block_ptr, &bytes_total);
+    rb_up(d.eptr, plan.eptr, &bytes_total);
+    rb_up(d.rows, plan.rows, &bytes_total);
+    rb_up(d.ns, plan.n_interior, &bytes_total);
+    rb_up(d.loc, plan.loc, &bytes_total);
+    rb_up(d.owner, plan.owner, &bytes_total);
     for (int c = 0; c < kRbmcClasses; c++) {
-        rb_.cnt[c] = (int)plan.order[c].size();
-        if (rb_.cnt[c]) rb_.order[c] = rb_up<int>(con_alloc(plan.order[c].size() * sizeof(int)), plan.order[c]);
+        d.cnt[c] = (int)plan.order[c].size();
+        if (d.cnt[c]) rb_up(d.order[c], plan.order[c], &bytes_total);
     }
     // global scratch of the two large classes, by workgroup of a launch: Q_BB (512 x 512) and R (rows x kRbmcW)
-    const size_t wg3 = (size_t)std::min(rb_.cnt[3], rbmc_class_chunk(3)), wg2 = (size_t)std::min(rb_.cnt[2], rbmc_class_chunk(2));
-    if (wg3) rb_.scrM = (double *)con_alloc(wg3 * kRbmcMaxBlock * kRbmcMaxBlock * sizeof(double));
+    const size_t wg3 = (size_t)std::min(d.cnt[3], rbmc_class_chunk(3)), wg2 = (size_t)std::min(d.cnt[2], rbmc_class_chunk(2));
+    if (wg3) d.scrM.alloc(wg3 * kRbmcMaxBlock * kRbmcMaxBlock, &bytes_total, kTableMinBytes);
     const size_t rdoubles = std::max(wg3 * kRbmcMaxBlock * kRbmcW, wg2 * 128 * kRbmcW);
-    if (rdoubles) rb_.scrR = (double *)con_alloc(rdoubles * sizeof(double));
-    rb_.plan_enclosure = plan.enclosure; rb_.plan_serial = plan.serial;
+    if (rdoubles) d.scrR.alloc(rdoubles, &bytes_total, kTableMinBytes);
+    d.enclosure = plan.enclosure; d.serial = plan.serial;
+    rb_.plan = std::move(d);
 }
 
 void Device::rbmc_var(const RbmcSym &sym, const RbmcPlan *plan, const double *d_nz, const double *Z, long long ldz, bool z_on_device, long long k,
@@ -82,35 +80,37 @@ void Device::rbmc_var(const RbmcSym &sym, const RbmcPlan *plan, const double *d_
     }
     rbmc_upload_sym(sym);
     if (plan) rbmc_upload_plan(*plan);
-    const RbmcDev P{rb_.rp, rb_.col, rb_.pos, rb_.dpos, rb_.bptr, rb_.rows, rb_.ns, rb_.owner, rb_.eptr, rb_.loc};
-    double *d_out = out_on_device ? out : rb_.out;
+    const RbmcSymDev &sy = rb_.sym;
+    const RbmcPlanDev &pl = rb_.plan;
+    const RbmcDev P{sy.rp, sy.col, sy.pos, sy.dpos, pl.bptr, pl.rows, pl.ns, pl.owner, pl.eptr, pl.loc};
+    double *d_out = out_on_device ? out : sy.out;
     double bs = 0;
-    HC(hipEventRecord(rb_.ev0, stream));
+    HC(hipEventRecord(rb_ev_[0], stream));
     for (long long j0 = 0; j0 < k; j0 += kRbmcW) {
         const int w = (int)std::min<long long>(kRbmcW, k - j0);
         const bool first = j0 == 0, last = j0 + w == k;
-        if (z_on_device) solve(Z + j0 * ldz, ldz, w, rb_.Xc, n, true, 1);
+        if (z_on_device) solve(Z + j0 * ldz, ldz, w, sy.Xc, n, true, 1);
         else {
-            HC(hipMemcpy2DAsync(rb_.Xc, (size_t)n * sizeof(double), Z + j0 * ldz, (size_t)ldz * sizeof(double), (size_t)n * sizeof(double), (size_t)w,
+            HC(hipMemcpy2DAsync(sy.Xc, (size_t)n * sizeof(double), Z + j0 * ldz, (size_t)ldz * sizeof(double), (size_t)n * sizeof(double), (size_t)w,
                                 hipMemcpyHostToDevice, stream));
-            solve(rb_.Xc, n, w, rb_.Xc, n, true, 1);
+            solve(sy.Xc, n, w, sy.Xc, n, true, 1);
         }
         bs += ms_bsolve;
-        launch_rbmc_transpose(stream, rb_.Xc, n, w, rb_.Xt);
-        if (!plan) launch_rbmc_plain(stream, P, n, d_nz, rb_.Xt, j0, w, last, k, rb_.mean, rb_.m2, d_out);
+        launch_rbmc_transpose(stream, sy.Xc, n, w, sy.Xt);
+        if (!plan) launch_rbmc_plain(stream, P, n, d_nz, sy.Xt, j0, w, last, k, sy.mean, sy.m2, d_out);
         else
             for (int c = 0; c < kRbmcClasses; c++)
-                if (rb_.cnt[c])
-                    launch_rbmc_blocks(stream, P, c, rb_.order[c], rb_.cnt[c], d_nz, rb_.Xt, j0, w, first, last, k, rb_.mean, rb_.m2, rb_.base, d_out,
-                                       rb_.scrM, rb_.scrR);
+                if (pl.cnt[c])
+                    launch_rbmc_blocks(stream, P, c, pl.order[c], pl.cnt[c], d_nz, sy.Xt, j0, w, first, last, k, sy.mean, sy.m2, sy.base, d_out,
+                                       pl.scrM, pl.scrR);
         HC(hipGetLastError());
     }
-    HC(hipEventRecord(rb_.ev1, stream));
-    if (!out_on_device) HC(hipMemcpyAsync(out, rb_.out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipEventRecord(rb_ev_[1], stream));
+    if (!out_on_device) HC(hipMemcpyAsync(out, sy.out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
     float ms = 0;
-    HC(hipEventElapsedTime(&ms, rb_.ev0, rb_.ev1));
+    HC(hipEventElapsedTime(&ms, rb_ev_[0], rb_ev_[1]));
     ms_rbmc = ms; ms_rbmc_bsolve = bs;
 }
 

@@ -93,21 +93,19 @@ static void check_rhs(const gmrfx_handle *h, const void *B, int64_t ldb, const v
 }
 
 // a device copy of a host block, freed on return
-namespace {
-struct DevBlock {
-    double *p = nullptr;
-    ~DevBlock() { if (p) (void)hipFree(p); }
-    void alloc(int64_t count) { hip_check(hipMalloc((void **)&p, (size_t)std::max<int64_t>(count, 1) * sizeof(double) + 16), "hipMalloc"); }
-    void up(const double *src, int64_t count) { hip_check(hipMemcpy(p, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy"); }
-    // n x nvec, leading dimension ld on the host, n on the device
-    void up(const double *src, int64_t ld, int64_t n, int64_t nvec) {
-        hip_check(hipMemcpy2D(p, (size_t)n * sizeof(double), src, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
-    }
-    void down(double *dst, int64_t ld, int64_t n, int64_t nvec) {
-        hip_check(hipMemcpy2D(dst, (size_t)ld * sizeof(double), p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
-    }
-};
-}  // namespace
+using DevBlock = DevBuf<double>;
+static void block_up(DevBlock &b, const double *src, int64_t count) {
+    b.alloc((size_t)count);
+    hip_check(hipMemcpy(b, src, (size_t)count * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy");
+}
+// n x nvec, leading dimension ld on the host, n on the device
+static void block_up(DevBlock &b, const double *src, int64_t ld, int64_t n, int64_t nvec) {
+    b.alloc((size_t)(n * nvec));
+    hip_check(hipMemcpy2D(b, (size_t)n * sizeof(double), src, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
+}
+static void block_down(const DevBlock &b, double *dst, int64_t ld, int64_t n, int64_t nvec) {
+    hip_check(hipMemcpy2D(dst, (size_t)ld * sizeof(double), b, (size_t)n * sizeof(double), (size_t)n * sizeof(double), (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
+}
 
 // create-time failures have no handle to carry the message: it goes to g_create_err
 static int32_t device_failure(const std::exception &e) {
@@ -805,11 +803,10 @@ static int32_t quadform_impl(gmrfx_handle *h, const double *nz, const double *X,
         const i64 n = h->S.n;
         DevBlock bx, bm, bn;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
-        bx.alloc(n * nvec);
-        bx.up(X, ldx, n, nvec);
-        if (mu) { bm.alloc(n); bm.up(mu, n); }
-        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
-        h->D->quadform(bn.p, bx.p, n, nvec, bm.p, out);
+        block_up(bx, X, ldx, n, nvec);
+        if (mu) block_up(bm, mu, n);
+        if (nz) block_up(bn, nz, h->S.nnz_in);
+        h->D->quadform(bn, bx, n, nvec, bm, out);
         return GMRFX_OK;
     });
 }
@@ -1190,11 +1187,10 @@ static int32_t batch_quadform_impl(gmrfx_handle *h, const double *nz, const doub
         std::vector<double> xs((size_t)(n * nvec * nb));
         for (int64_t k = 0; k < nb; k++)
             for (int64_t v = 0; v < nvec; v++) std::memcpy(&xs[(size_t)((k * nvec + v) * n)], X + k * sx + v * ldx, (size_t)n * sizeof(double));
-        bx.alloc((int64_t)xs.size());
-        bx.up(xs.data(), (int64_t)xs.size());
-        if (mu) { bm.alloc(n * nb); bm.up(mu, n * nb); }
-        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
-        h->D->batch_quadform(bn.p, bx.p, n, n * nvec, nvec, bm.p, quad);
+        block_up(bx, xs.data(), (int64_t)xs.size());
+        if (mu) block_up(bm, mu, n * nb);
+        if (nz) block_up(bn, nz, h->S.nnz_in);
+        h->D->batch_quadform(bn, bx, n, n * nvec, nvec, bm, quad);
         return GMRFX_OK;
     });
 }
@@ -1339,11 +1335,13 @@ extern "C" int32_t gmrfx_constraints_mean(gmrfx_handle *h, const double *mu, dou
         const int m = h->con.m;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x;
-        x.alloc(n);
-        if (mu) x.up(mu, n, n, 1);
-        else hip_check(hipMemsetAsync(x.p, 0, (size_t)n * sizeof(double), h->D->stream), "hipMemsetAsync");      // ordered before the kernels
-        h->D->con_correct(x.p, n, 1, nullptr);
-        if (mean_c) x.down(mean_c, n, n, 1);
+        if (mu) block_up(x, mu, n, n, 1);
+        else {
+            x.alloc((size_t)n);
+            hip_check(hipMemsetAsync(x, 0, (size_t)n * sizeof(double), h->D->stream), "hipMemsetAsync");      // ordered before the kernels
+        }
+        h->D->con_correct(x, n, 1, nullptr);
+        if (mean_c) block_down(x, mean_c, n, n, 1);
         if (log_correction) {
             *log_correction = 0.0;
             if (m > 0) {
@@ -1375,10 +1373,9 @@ static int32_t constraints_correct_impl(gmrfx_handle *h, double *X, int64_t ldx,
         const int64_t n = h->S.n;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x;
-        x.alloc(n * nvec);
-        x.up(X, ldx, n, nvec);
-        h->D->con_correct(x.p, n, nvec, nullptr);
-        x.down(X, ldx, n, nvec);
+        block_up(x, X, ldx, n, nvec);
+        h->D->con_correct(x, n, nvec, nullptr);
+        block_down(x, X, ldx, n, nvec);
         return GMRFX_OK;
     });
 }
@@ -1408,12 +1405,11 @@ static int32_t sample_impl(gmrfx_handle *h, const double *Z, int64_t ldz, int64_
         const int64_t n = h->S.n;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x, dm;
-        x.alloc(n * nrhs);
-        x.up(Z, ldz, n, nrhs);
-        if (mu) { dm.alloc(n); dm.up(mu, n, n, 1); }
-        h->D->solve(x.p, n, nrhs, x.p, n, true, 1);
-        h->D->con_correct(x.p, n, nrhs, dm.p);
-        x.down(X, ldx, n, nrhs);
+        block_up(x, Z, ldz, n, nrhs);
+        if (mu) block_up(dm, mu, n, n, 1);
+        h->D->solve(x, n, nrhs, x, n, true, 1);
+        h->D->con_correct(x, n, nrhs, dm);
+        block_down(x, X, ldx, n, nrhs);
         return GMRFX_OK;
     });
 }
@@ -1503,17 +1499,19 @@ extern "C" int32_t gmrfx_batch_constraints_mean(gmrfx_handle *h, const double *m
         const int64_t n = h->n_member, nb = h->nbatch;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x;
-        x.alloc(n * nb);
-        if (mu) x.up(mu, n * nb);
-        else hip_check(hipMemsetAsync(x.p, 0, (size_t)(n * nb) * sizeof(double), h->D->stream), "hipMemsetAsync");       // ordered before the kernels
+        if (mu) block_up(x, mu, n * nb);
+        else {
+            x.alloc((size_t)(n * nb));
+            hip_check(hipMemsetAsync(x, 0, (size_t)(n * nb) * sizeof(double), h->D->stream), "hipMemsetAsync");       // ordered before the kernels
+        }
         if (log_correction) {
             std::vector<double> quad((size_t)nb, 0.0);
-            h->D->bcon_quad(x.p, quad.data());
+            h->D->bcon_quad(x, quad.data());
             batch_log_correction(h, quad, log_correction);
         }
         if (mean_c) {
-            h->D->bcon_correct(x.p, n, n, 1, nullptr);
-            x.down(mean_c, n, n, nb);
+            h->D->bcon_correct(x, n, n, 1, nullptr);
+            block_down(x, mean_c, n, n, nb);
         }
         return GMRFX_OK;
     });
@@ -1528,15 +1526,15 @@ static void check_member_block(const gmrfx_handle *h, const void *X, int64_t ldx
 // host blocks of the members <-> one packed device array (ld = n, member stride n nvec)
 static void members_up(const gmrfx_handle *h, DevBlock &d, const double *X, int64_t ldx, int64_t sx, int64_t nvec) {
     const int64_t n = h->n_member;
-    d.alloc(n * nvec * h->nbatch);
+    d.alloc((size_t)(n * nvec * h->nbatch));
     for (int64_t k = 0; k < h->nbatch; k++)
-        hip_check(hipMemcpy2D(d.p + k * n * nvec, (size_t)n * sizeof(double), X + k * sx, (size_t)ldx * sizeof(double), (size_t)n * sizeof(double),
+        hip_check(hipMemcpy2D(d.get() + k * n * nvec, (size_t)n * sizeof(double), X + k * sx, (size_t)ldx * sizeof(double), (size_t)n * sizeof(double),
                               (size_t)nvec, hipMemcpyHostToDevice), "hipMemcpy2D");
 }
 static void members_down(const gmrfx_handle *h, const DevBlock &d, double *X, int64_t ldx, int64_t sx, int64_t nvec) {
     const int64_t n = h->n_member;
     for (int64_t k = 0; k < h->nbatch; k++)
-        hip_check(hipMemcpy2D(X + k * sx, (size_t)ldx * sizeof(double), d.p + k * n * nvec, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
+        hip_check(hipMemcpy2D(X + k * sx, (size_t)ldx * sizeof(double), d.get() + k * n * nvec, (size_t)n * sizeof(double), (size_t)n * sizeof(double),
                               (size_t)nvec, hipMemcpyDeviceToHost), "hipMemcpy2D");
 }
 
@@ -1549,7 +1547,7 @@ static int32_t batch_constraints_correct_impl(gmrfx_handle *h, double *X, int64_
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x;
         members_up(h, x, X, ldx, sx, nvec);
-        h->D->bcon_correct(x.p, h->n_member, h->n_member * nvec, nvec, nullptr);
+        h->D->bcon_correct(x, h->n_member, h->n_member * nvec, nvec, nullptr);
         members_down(h, x, X, ldx, sx, nvec);
         return GMRFX_OK;
     });
@@ -1588,10 +1586,10 @@ static int32_t batch_sample_impl(gmrfx_handle *h, const double *Z, int64_t ldz, 
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
         DevBlock x, dm;
         members_up(h, x, Z, ldz, sz, nrhs);
-        if (mu) { dm.alloc(n * h->nbatch); dm.up(mu, n * h->nbatch); }
+        if (mu) block_up(dm, mu, n * h->nbatch);
         const Device::MemberLayout ml{n, n * nrhs, n * nrhs};
-        h->D->solve(x.p, n, nrhs, x.p, n, true, 1, &ml);
-        h->D->bcon_correct(x.p, n, n * nrhs, nrhs, dm.p);
+        h->D->solve(x, n, nrhs, x, n, true, 1, &ml);
+        h->D->bcon_correct(x, n, n * nrhs, nrhs, dm);
         members_down(h, x, X, ldx, sx, nrhs);
         return GMRFX_OK;
     });
@@ -1679,8 +1677,8 @@ static int32_t rbmc_var_impl(gmrfx_handle *h, const double *nz, const double *Z,
         if (dev) { h->D->rbmc_var(h->rsym, plan, nz, Z, ldz, true, nsamples, out, true); return GMRFX_OK; }
         DevBlock bn;
         hip_check(hipSetDevice(h->D->device), "hipSetDevice");
-        if (nz) { bn.alloc(h->S.nnz_in); bn.up(nz, h->S.nnz_in); }
-        h->D->rbmc_var(h->rsym, plan, bn.p, Z, ldz, false, nsamples, out, false);
+        if (nz) block_up(bn, nz, h->S.nnz_in);
+        h->D->rbmc_var(h->rsym, plan, bn, Z, ldz, false, nsamples, out, false);
         return GMRFX_OK;
     });
 }

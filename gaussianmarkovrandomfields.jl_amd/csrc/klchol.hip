@@ -127,12 +127,6 @@ __global__ __launch_bounds__(256) void k_kl_chol_big(const KlTask *__restrict__ 
                          nzval, info, t);
 }
 
-struct DBuf {
-    void *p = nullptr;
-    ~DBuf() { if (p) (void)hipFree(p); }
-    template <class T> T *alloc(size_t cnt) { hip_check(hipMalloc(&p, std::max<size_t>(cnt, 1) * sizeof(T)), "hipMalloc"); return (T *)p; }
-};
-
 template <int NMAX> void launch_class(hipStream_t st, int cnt, const KlTask *d_tasks, const int *d_order, const int *d_rows,
                                       const int *d_cols, const double *d_theta, long long ldt, double reg,
                                       const long long *d_colptr, double *d_nz, int *d_info) {
@@ -160,28 +154,30 @@ long long kl_cholesky_run(int device, long long n, const double *theta, long lon
         if (N > KL_BIG) throw std::invalid_argument("kl_cholesky: a local system has more than 512 rows (pattern too dense)");
         order[N <= 32 ? 0 : (N <= 64 ? 1 : (N <= 128 ? 2 : 3))].push_back(t);
     }
-    hipStream_t st;
-    hip_check(hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreate");
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{st};
-    DBuf btheta, btasks, border, brows, bcols, bcolptr, bnz, binfo, bscr;
+    Stream st;       // (declared first: released after the buffers)
+    st.create(hipStreamNonBlocking);
+    DevBuf<double> btheta, d_nz, d_scr;
+    DevBuf<KlTask> d_tasks;
+    DevBuf<int> d_rows, d_cols, d_info, d_order;
+    DevBuf<long long> d_colptr;
     const double *d_theta = theta;
     if (!theta_on_device) {
-        double *p = btheta.alloc<double>((size_t)n * n);
-        hip_check(hipMemcpy2DAsync(p, (size_t)n * sizeof(double), theta, (size_t)ldt * sizeof(double), (size_t)n * sizeof(double),
+        btheta.alloc((size_t)n * n);
+        hip_check(hipMemcpy2DAsync(btheta, (size_t)n * sizeof(double), theta, (size_t)ldt * sizeof(double), (size_t)n * sizeof(double),
                                    (size_t)n, hipMemcpyHostToDevice, st), "hipMemcpy2D");
-        d_theta = p;
+        d_theta = btheta;
         ldt = n;
     }
-    KlTask *d_tasks = btasks.alloc<KlTask>(ntasks);
-    int *d_rows = brows.alloc<int>(rows.size());
-    int *d_cols = bcols.alloc<int>(cols.size());
-    long long *d_colptr = bcolptr.alloc<long long>((size_t)n + 1);
-    double *d_nz = bnz.alloc<double>((size_t)nnzL);
-    int *d_info = binfo.alloc<int>(1);
+    d_tasks.alloc(ntasks);
+    d_rows.alloc(rows.size());
+    d_cols.alloc(cols.size());
+    d_colptr.alloc((size_t)n + 1);
+    d_nz.alloc((size_t)nnzL);
+    d_info.alloc(1);
     std::vector<int> all_order;
     int off[5] = {0, 0, 0, 0, 0};
     for (int k = 0; k < 4; k++) { off[k + 1] = off[k] + (int)order[k].size(); all_order.insert(all_order.end(), order[k].begin(), order[k].end()); }
-    int *d_order = border.alloc<int>(all_order.size());
+    d_order.alloc(all_order.size());
     const int big = 0x7fffffff;
     hip_check(hipMemcpyAsync(d_tasks, tasks.data(), (size_t)ntasks * sizeof(KlTask), hipMemcpyHostToDevice, st), "copy tasks");
     hip_check(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, st), "copy rows");
@@ -195,7 +191,7 @@ long long kl_cholesky_run(int device, long long n, const double *theta, long lon
     launch_class<128>(st, (int)order[2].size(), d_tasks, d_order + off[2], d_rows, d_cols, d_theta, ldt, reg, d_colptr, d_nz, d_info);
     if (!order[3].empty()) {
         const int chunk = 256;   // 256 x 2 MB of scratch
-        double *d_scr = bscr.alloc<double>((size_t)chunk * KL_BIG * KL_BIG);
+        d_scr.alloc((size_t)chunk * KL_BIG * KL_BIG);
         for (int b = 0; b < (int)order[3].size(); b += chunk) {
             const int cnt = std::min(chunk, (int)order[3].size() - b);
             hipLaunchKernelGGL(k_kl_chol_big, dim3(cnt), dim3(256), 0, st, d_tasks, d_order + off[3] + b, d_rows, d_cols, d_theta,
