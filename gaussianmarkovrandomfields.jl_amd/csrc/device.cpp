@@ -83,21 +83,8 @@ void Device::init(const Symbolic &S, int dev) {
         stream2.create(hipStreamNonBlocking, lo);
         stream3.create(hipStreamNonBlocking, hi);
     }
-    // the environment's testing / A/B / profiling knobs
-    if (const char *c = std::getenv("GMRFX_INV_CAP")) {      // testing knob: power of two >= 64
-        int v = std::atoi(c), p2 = NB;
-        while (p2 < v) p2 *= 2;
-        inv_cap_ = p2;
-    }
-    if (const char *e = std::getenv("GMRFX_TASK_MODE")) {       // A/B knob: "wg" / "wave" force one form for every width
-        const std::string m(e);
-        wave_max_nr_ = m == "wg" ? 0 : m == "wave" ? 64 : wave_max_nr_;
-    }
-    if (const char *e = std::getenv("GMRFX_LEVEL_MARK")) level_mark_ = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GMRFX_BWD_FRONT")) bwd_front_min_ = std::atoi(e);    // fronts a level needs for the one-workgroup backward step (0: never)
-    if (const char *e = std::getenv("GMRFX_FWD_FRONT")) fwd_front_min_ = std::atoi(e);    // ... and for the one-workgroup forward step
-    if (const char *e = std::getenv("GMRFX_SYRK_XCD")) syrk_xcd_ = std::atoi(e) != 0;
-    if (const char *e = std::getenv("GMRFX_SYRK_PIPED")) syrk_piped_min_ = std::atoi(e);
+    env_ = read_env_knobs();
+    inv_cap_ = env_.inv_cap;
     ev_fact_.create(hipEventDisableTiming);
     ev_inv_.create(hipEventDisableTiming);
     for (auto &ev : ev_) ev.create();
@@ -113,7 +100,7 @@ void Device::init(const Symbolic &S, int dev) {
 
 void Device::upload(const Symbolic &S) {
     S_ = &S;
-    const DevicePlan P = build_device_plan(S, PlanOptions{syrk_xcd_});
+    const DevicePlan P = build_device_plan(S, PlanOptions{env_.syrk_xcd});
     // a device copy of a host vector (the analysis' int64_t offsets become the kernels' long long: the same bytes). The copies
     // read the host vectors until the synchronisation at the end, while P and S still hold them.
     auto up = [&](const auto &host) {
@@ -410,8 +397,131 @@ void Device::host_download(const double *d_src, long long nrhs, double *X, long 
 
 static const int kClsRows[4] = {48, 64, 96, 128};
 static const int OBK = 4;   // 64-column blocks per outer (256-column) block of the panel factorisation
-static inline int level_max_trail(const LevelInfo &L) { return L.active.back(); }
-static inline int level_nblk(const LevelInfo &L) { return (int)L.active.size() - 2; }
+static const FrontArg kNoFront{0, 0, 0, 0, 0, 0, 0};
+
+// The small fronts of a level (fused one-workgroup kernels) and its big fronts (assembly -> panel chain -> SYRK)
+// only depend on the levels below, not on each other: when a level has both, the small ones run on the second
+// stream next to the big-front pipeline, and the level ends when both have.
+// A level with small fronts only still has up to four size classes = four launches with a tail each: the widest
+// non-empty class stays on the main stream, the others go to the second one.
+bool Device::factor_small_fronts(const LevelInfo &L) {
+    const int nf = L.nbig();
+    int ncls_used = 0, widest = -1;
+    for (int k = 0; k < 4; k++) if (L.ncls[k] > 0) { ncls_used++; widest = k; }
+    const bool split_small = L.nsmall > 0 && (nf > 0 || ncls_used > 1);
+    if (split_small) {
+        HC(hipEventRecord(ev_ready_, stream));
+        HC(hipStreamWaitEvent(stream3, ev_ready_, 0));
+    }
+    for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++) {
+        hipStream_t st_small = !split_small ? stream : (nf > 0 || k != widest) ? stream3 : stream;
+        launch_factor_small(st_small, ds_, d_levellist_ + L.first + off, L.ncls[k], kClsRows[k], nz_src_, d_L_, d_cb_, d_info_);
+    }
+    return split_small;
+}
+
+// One panel chain of a level: its stream and its fronts -- the level's width-sorted list of big fronts, or (two chains) the
+// fronts at its even / odd positions, sorted as well.
+struct Device::PanelChain {
+    hipStream_t st;
+    const FrontView *views;   // geometry records of the chain's fronts
+    int half;                 // -1: the whole list, 0 / 1: its even / odd positions
+    // geometry of the widest front of the chain: when it is the only one still active, the panel kernels get it in
+    // their arguments (kernels.h, FrontArg)
+    FrontArg f1;
+    // of the first a fronts of the level's list, those on this chain
+    int of(int a) const { return half < 0 ? a : half == 0 ? (a + 1) / 2 : a / 2; }
+    // the chain's fronts with a 64-column block b: the first count(L, b) of views
+    int count(const LevelInfo &L, int b) const { return of(L.wider_than(b * NB)); }
+    const FrontArg &arg(int active) const { return active == 1 ? f1 : kNoFront; }
+};
+
+// Block b of a chain: potrf64 of the diagonal blocks -> trsm of the rows below -> the updates of the two-level blocking.
+void Device::panel_block(const PanelChain &ch, const LevelInfo &L, int b) {
+    const int n = ch.count(L, b), kb = b * NB;
+    if (n <= 0) return;
+    hipStream_t st = ch.st;
+    const FrontView *hl = ch.views;
+    if (b == 0 && n > 1) {
+        // first block of a level with many fronts: one launch per width class (the list is sorted by decreasing width;
+        // the even / odd halves of two chains are sorted as well), each in the workgroup shape that fits it
+        const int cut[5] = {0, ch.of(L.wider[0]), ch.of(L.wider[1]), ch.of(L.wider[2]), n};
+        const int wcls[4] = {64, 48, 32, 16};
+        for (int q = 0; q < 4; q++)
+            if (cut[q + 1] > cut[q])
+                launch_potrf64(st, ds_, hl + cut[q], cut[q + 1] - cut[q], kb, d_L_, d_info_, kNoFront, std::min(wcls[q], L.max_cols));
+    } else
+        launch_potrf64(st, ds_, hl, n, kb, d_L_, d_info_, ch.arg(n), std::min(NB, L.max_cols - kb));
+    {
+        // first block of a level with many fronts: the fronts at most 32 columns wide (the tail of the sorted list) go to
+        // the narrow-block kernel (same arithmetic on half the registers: more resident waves)
+        constexpr int narrow_min = 256;
+        const int cut32 = b == 0 ? ch.of(L.wider[1]) : n;
+        const int nnarrow = n - cut32;
+        if (b == 0 && narrow_min > 0 && nnarrow >= narrow_min) {
+            if (cut32 > 0) launch_trsm(st, ds_, hl, cut32, kb, 0, L.max_rows - kb - 1, d_L_, nullptr, nullptr, kNoFront);
+            launch_trsm_narrow(st, hl + cut32, nnarrow, kb, L.max_rows - kb - 1, d_L_);
+        } else
+            launch_trsm(st, ds_, hl, n, kb, 0, L.max_rows - kb - 1, d_L_, nullptr, nullptr, ch.arg(n));
+    }
+    // two-level blocking: K = 64 updates only inside the current 256-column block, the
+    // rest of the panel once per block with K = 256
+    const int J1 = (b / OBK + 1) * OBK;   // first 64-block of the next 256-column block
+    const int nnext = ch.count(L, b + 1), nouter = ch.count(L, J1);     // (0 behind the widest front's last block)
+    if (b + 1 < J1 && nnext > 0)
+        launch_gemm_nt(st, ds_, hl, nnext, kb, NB, kb + NB, J1 * NB, L.max_rows - kb - NB,
+                       std::min(J1 * NB, L.max_cols) - kb - NB, d_L_, ch.arg(nnext));
+    if (b + 1 == J1 && nouter > 0)
+        launch_gemm_nt(st, ds_, hl, nouter, (J1 - OBK) * NB, OBK * NB, J1 * NB, INT_MAX,
+                       L.max_rows - J1 * NB, L.max_cols - J1 * NB, d_L_, ch.arg(nouter));
+}
+
+// The panel factorisation of a level is a chain of small dependent launches per 64-column block (potrf64 on ONE
+// workgroup per front -> trsm -> gemm): while the diagonal blocks factor, the chip idles. Levels with several
+// wide fronts run TWO independent chains -- the fronts at even / odd positions of the width-sorted list -- on two
+// streams, so one half's trsm / gemm fills the chip while the other half sits in potrf64. Same arithmetic per
+// front: bit-identical factor.
+// (Measured and dropped -- DESIGN.md section 3: a look-ahead diagonal chain with the bulk one step behind on a second stream,
+//  a persistent kernel per 256-column outer block, a pair chain, a rolling SYRK: the chain is bounded by the 64 x 64
+//  factorisation and by single-CU tile rates, not by its dispatches.)
+bool Device::factor_panel_chains(const LevelInfo &L) {
+    const int nf = L.nbig(), nblk = L.nblk(), base = L.first + L.nsmall;
+    const bool two = nf >= 2 && nblk >= 4 && !sharded();
+    if (two) {
+        HC(hipEventRecord(ev_ready2_, stream));               // (after the assembly of this level's panels)
+        HC(hipStreamWaitEvent(stream3, ev_ready2_, 0));
+    }
+    auto front_at = [&](int pos) {       // position pos of the level's list of big fronts (kNoFront: the list is shorter)
+        if (pos >= nf) return kNoFront;
+        const i32 s = S_->levellist[base + pos];
+        return FrontArg{1, (int)s, S_->ncols(s), S_->nrows(s), (int)S_->ld[s], (int)S_->sfirst[s], (long long)S_->panelptr[s]};
+    };
+    const PanelChain ch[2] = {{stream, two ? d_frec2_ + base : d_frec_ + base, two ? 0 : -1, front_at(0)},
+                              {stream3, d_frec2_ + base + (nf + 1) / 2, 1, front_at(1)}};
+    // (the two chains are enqueued block by block in turn, not one after the other: the host stays ahead of both)
+    for (int b = 0; b < nblk; b++)
+        for (int h = 0; h < (two ? 2 : 1); h++) panel_block(ch[h], L, b);
+    if (two) {
+        HC(hipEventRecord(ev_done1_, stream3));
+        HC(hipStreamWaitEvent(stream, ev_done1_, 0));
+    }
+    return two;
+}
+
+// The contribution blocks of a level's big fronts (children gathered + L21 L21'), between the level's pair of timing events.
+void Device::factor_contribution_blocks(const LevelInfo &L, int slot) {
+    const int *list = d_levellist_ + L.first + L.nsmall;
+    const int nf = L.nbig();
+    HC(hipEventRecord(ev_syrk_[2 * slot], stream));
+    // levels of HUGE fronts (3-D problems): the children's extend-add alone, then the product on 128 x 128 staged tiles
+    const bool huge = env_.syrk_xcd && !sharded() && L.max_trail >= 4096 && L.max_cols >= 1024;
+    // levels of wide fronts (the product dominates the tile): the software-pipelined product loop (kernels.hip, k_syrk_cb_rec<true>;
+    // same sums in the same order: a level's choice does not show in the bits)
+    if (env_.syrk_xcd) launch_syrk_cb_recs(stream, ds_, d_syrk_recs_ + L.syrk_off, L.syrk_split, L.syrk_per, d_L_, d_cb_, huge ? 1 : 0, L.max_cols >= env_.syrk_piped_min);
+    else launch_syrk_cb(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_);
+    if (huge) launch_syrk_big(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_);
+    HC(hipEventRecord(ev_syrk_[2 * slot + 1], stream));
+}
 
 void Device::factor_levels(int lo, int hi, bool record_level_events) {
     if (lo == 0) {
@@ -437,108 +547,14 @@ void Device::factor_levels(int lo, int hi, bool record_level_events) {
     }
     int nsy = (int)syrk_launches;
     for (int lev = lo; lev < hi; lev++) {
-        auto &L = levels_[lev];
-        if (level_mark_) { launch_level_mark(stream, 3, lev); level_event(stream, 0, lev); }
-        const int *list = d_levellist_ + L.first + L.nsmall;
-        const int nf = L.count - L.nsmall;
-        // The small fronts of a level (fused one-workgroup kernels) and its big fronts (assembly -> panel chain -> SYRK)
-        // only depend on the levels below, not on each other: when a level has both, the small ones run on the second
-        // stream next to the big-front pipeline, and the level ends when both have.
-        // A level with small fronts only still has up to four size classes = four launches with a tail each: the widest
-        // non-empty class stays on the main stream, the others go to the second one.
-        int ncls_used = 0, widest = -1;
-        for (int k = 0; k < 4; k++) if (L.ncls[k] > 0) { ncls_used++; widest = k; }
-        const bool split_small = L.nsmall > 0 && (nf > 0 || ncls_used > 1);
-        if (split_small) {
-            HC(hipEventRecord(ev_ready_, stream));
-            HC(hipStreamWaitEvent(stream3, ev_ready_, 0));
-        }
-        for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++) {
-            hipStream_t st_small = !split_small ? stream : (nf > 0 || k != widest) ? stream3 : stream;
-            launch_factor_small(st_small, ds_, d_levellist_ + L.first + off, L.ncls[k], kClsRows[k], nz_src_, d_L_, d_cb_, d_info_);
-        }
+        const LevelInfo &L = levels_[lev];
+        if (env_.level_mark) { launch_level_mark(stream, 3, lev); level_event(stream, 0, lev); }
+        const int nf = L.nbig();
+        const bool split_small = factor_small_fronts(L);
         if (nf > 0 && nzp_pending_) { HC(hipStreamWaitEvent(stream, ev_nzp_, 0)); nzp_pending_ = false; }
-        launch_assemble(stream, ds_, list, d_arec_ + L.first + L.nsmall, d_nzp_, nf, L.max_cols, L.max_rows, nz_src_, d_L_, d_cb_);
-        const int nblk = level_nblk(L);
-        // The panel factorisation of a level is a chain of small dependent launches per 64-column block (potrf64 on ONE
-        // workgroup per front -> trsm -> gemm): while the diagonal blocks factor, the chip idles. Levels with several
-        // wide fronts run TWO independent chains -- the fronts at even / odd positions of the width-sorted list -- on two
-        // streams, so one half's trsm / gemm fills the chip while the other half sits in potrf64. Same arithmetic per
-        // front: bit-identical factor.
-        // (Measured and dropped -- DESIGN.md section 3: a look-ahead diagonal chain with the bulk one step behind on a second stream,
-        //  a persistent kernel per 256-column outer block, a pair chain, a rolling SYRK: the chain is bounded by the 64 x 64
-        //  factorisation and by single-CU tile rates, not by its dispatches.)
-        const bool two = nf >= 2 && nblk >= 4 && !sharded();
-        const int nhalf = two ? 2 : 1;
-        if (two) {
-            HC(hipEventRecord(ev_ready2_, stream));               // (after the assembly of this level's panels)
-            HC(hipStreamWaitEvent(stream3, ev_ready2_, 0));
-        }
-        // (the two chains are enqueued block by block in turn, not one after the other: the host stays ahead of both)
-        for (int it = 0; it < nblk * nhalf; it++) {
-                const int b = it / nhalf, hf = it % nhalf;
-                hipStream_t st = hf == 0 ? stream : stream3;
-                const FrontView *hl = two ? d_frec2_ + L.first + L.nsmall + (hf == 0 ? 0 : (nf + 1) / 2) : d_frec_ + L.first + L.nsmall;
-                auto act = [&](int bb) { const int a = L.active[bb]; return two ? (hf == 0 ? (a + 1) / 2 : a / 2) : a; };
-                if (act(b) <= 0) continue;
-                // geometry of the widest front of the (half-)list (fronts are sorted by decreasing width): when it is
-                // the only one still active, the panel kernels get it in their arguments (kernels.h, FrontArg)
-                FrontArg f1{0, 0, 0, 0, 0, 0, 0}, f0{0, 0, 0, 0, 0, 0, 0};
-                if (nf > hf) {
-                    const i32 s1 = S_->levellist[L.first + L.nsmall + hf];
-                    f1 = FrontArg{1, (int)s1, S_->ncols(s1), S_->nrows(s1), (int)S_->ld[s1], (int)S_->sfirst[s1], (long long)S_->panelptr[s1]};
-                }
-                const int kb = b * NB;
-                if (b == 0 && act(0) > 1) {
-                    // first block of a level with many fronts: one launch per width class (the list is sorted by decreasing width;
-                    // the even / odd halves of two chains are sorted as well), each in the workgroup shape that fits it
-                    auto half = [&](int a) { return two ? (hf == 0 ? (a + 1) / 2 : a / 2) : a; };
-                    const int cut[5] = {0, half(L.wider[0]), half(L.wider[1]), half(L.wider[2]), act(0)};
-                    const int wcls[4] = {64, 48, 32, 16};
-                    for (int q = 0; q < 4; q++)
-                        if (cut[q + 1] > cut[q])
-                            launch_potrf64(st, ds_, hl + cut[q], cut[q + 1] - cut[q], kb, d_L_, d_info_, f0, std::min(wcls[q], L.max_cols));
-                } else
-                    launch_potrf64(st, ds_, hl, act(b), kb, d_L_, d_info_, act(b) == 1 ? f1 : f0, std::min(NB, L.max_cols - kb));
-                {
-                    // first block of a level with many fronts: the fronts at most 32 columns wide (the tail of the sorted list) go to
-                    // the narrow-block kernel (same arithmetic on half the registers: more resident waves)
-                    constexpr int narrow_min = 256;
-                    auto half = [&](int a) { return two ? (hf == 0 ? (a + 1) / 2 : a / 2) : a; };
-                    const int cut32 = b == 0 ? half(L.wider[1]) : act(b);
-                    const int nnarrow = act(b) - cut32;
-                    if (b == 0 && narrow_min > 0 && nnarrow >= narrow_min) {
-                        if (cut32 > 0) launch_trsm(st, ds_, hl, cut32, kb, 0, L.max_rows - kb - 1, d_L_, nullptr, nullptr, f0);
-                        launch_trsm_narrow(st, hl + cut32, nnarrow, kb, L.max_rows - kb - 1, d_L_);
-                    } else
-                        launch_trsm(st, ds_, hl, act(b), kb, 0, L.max_rows - kb - 1, d_L_, nullptr, nullptr, act(b) == 1 ? f1 : f0);
-                }
-                // two-level blocking: K = 64 updates only inside the current 256-column block, the
-                // rest of the panel once per block with K = 256
-                const int J1 = (b / OBK + 1) * OBK;   // first 64-block of the next 256-column block
-                if (b + 1 < nblk && b + 1 < J1 && act(b + 1) > 0)
-                    launch_gemm_nt(st, ds_, hl, act(b + 1), kb, NB, kb + NB, J1 * NB, L.max_rows - kb - NB,
-                                   std::min(J1 * NB, L.max_cols) - kb - NB, d_L_, act(b + 1) == 1 ? f1 : f0);
-                if (b + 1 == J1 && J1 < nblk && act(J1) > 0)
-                    launch_gemm_nt(st, ds_, hl, act(J1), (J1 - OBK) * NB, OBK * NB, J1 * NB, INT_MAX,
-                                   L.max_rows - J1 * NB, L.max_cols - J1 * NB, d_L_, act(J1) == 1 ? f1 : f0);
-            }
-        if (two) {
-            HC(hipEventRecord(ev_done1_, stream3));
-            HC(hipStreamWaitEvent(stream, ev_done1_, 0));
-        }
-        if (nf > 0 && level_max_trail(L) > 0) {
-            HC(hipEventRecord(ev_syrk_[2 * nsy], stream));
-            // levels of HUGE fronts (3-D problems): the children's extend-add alone, then the product on 128 x 128 staged tiles
-            const bool huge = syrk_xcd_ && !sharded() && level_max_trail(L) >= 4096 && L.max_cols >= 1024;
-            // levels of wide fronts (the product dominates the tile): the software-pipelined product loop (kernels.hip, k_syrk_cb_rec<true>;
-            // same sums in the same order: a level's choice does not show in the bits)
-            if (syrk_xcd_) launch_syrk_cb_recs(stream, ds_, d_syrk_recs_ + L.syrk_off, L.syrk_split, L.syrk_per, d_L_, d_cb_, huge ? 1 : 0, L.max_cols >= syrk_piped_min_);
-            else launch_syrk_cb(stream, ds_, list, nf, level_max_trail(L), d_L_, d_cb_);
-            if (huge) launch_syrk_big(stream, ds_, list, nf, level_max_trail(L), d_L_, d_cb_);
-            HC(hipEventRecord(ev_syrk_[2 * nsy + 1], stream));
-            nsy++;
-        }
+        launch_assemble(stream, ds_, d_levellist_ + L.first + L.nsmall, d_arec_ + L.first + L.nsmall, d_nzp_, nf, L.max_cols, L.max_rows, nz_src_, d_L_, d_cb_);
+        const bool two = factor_panel_chains(L);
+        if (nf > 0 && L.max_trail > 0) factor_contribution_blocks(L, nsy++);
         if (split_small && !two) {        // (with two chains the join before the SYRK already covered the small fronts)
             HC(hipEventRecord(ev_done1_, stream3));
             HC(hipStreamWaitEvent(stream, ev_done1_, 0));
@@ -547,7 +563,7 @@ void Device::factor_levels(int lo, int hi, bool record_level_events) {
     }
     syrk_launches = nsy;
     if (lo == 0 && nzp_pending_) { HC(hipStreamWaitEvent(stream, ev_nzp_, 0)); nzp_pending_ = false; }     // (see above)
-    if (level_mark_) level_event(stream, 0, hi);
+    if (env_.level_mark) level_event(stream, 0, hi);
 }
 
 // The dense inverses are only needed by the sweeps and the selected inversion of the big
@@ -656,8 +672,8 @@ void Device::refactorize_solve(const double *nzval, bool nz_on_device, const dou
     HC(hipEventRecord(ev_ready_, stream));                 // the side stream starts behind the uploads / whatever precedes this call
     factor_levels(0, nl, true);
     enqueue_factor_tail();
-    // ---- first pass (pass_width(): up to 64 columns, 16 for 17 .. 32 right-hand sides -- the widths solve() uses, so that the two
-    // forms of the step give the same bits): forward sweep on the side stream, behind the level events
+    // ---- first pass (pass_width(): up to 64 columns -- the width solve() uses, so that the two forms of the step give the
+    // same bits): forward sweep on the side stream, behind the level events
     const int PW = pass_width(nrhs);
     const int nr = (int)std::min<long long>(PW, nrhs), ldx = nr;
     const Event *ev = ev_lane_[0];
@@ -934,13 +950,13 @@ void Device::ensure_io(long long need) {
     io_cap_ = cap;
 }
 
-// The bottom subtrees. Up to wave_max_nr_ (16) right-hand sides: one wave per (task, 16 columns), sweep_wave.hip, biggest LDS
+// The bottom subtrees. Up to env_.wave_max_nr (16) right-hand sides: one wave per (task, 16 columns), sweep_wave.hip, biggest LDS
 // class first; wider passes: the chunk form, four waves per (task, 16 columns), sweep_chunk.hip. Measured at cfg 2, round 5
 // (tools/nrhs_sweep.py, ms per solve, wave form / chunk form): 1 RHS 2.88 / 3.22, 16: 3.00 / 3.36, 32: 3.71 / 3.47, 64: - / 3.90 at the
 // time of the choice; with the narrow level kernels and the local vector as wide as the pass: 1 RHS 1.65, 16: 2.28.
 // GMRFX_TASK_MODE = wg / wave forces one form.
 void Device::sweep_tasks(const SweepLane &ln, int phase, int nr, int ldx, bool follows_factor) {
-    if (nr > wave_max_nr_) {
+    if (nr > env_.wave_max_nr) {
         // pipelined call: the forward task kernel runs beside the top of the factorisation -- TWO resident workgroups per CU
         // instead of four (16 KB of unused dynamic LDS on top of its 40 KB), so that the panel chain's kernels find LDS
         // (measured at cfg 2, round 5: pad 0 / 8 / 16 / 42 KB -> step 12.59 / 12.61 / 12.38 / 12.91 ms)
@@ -965,7 +981,7 @@ void Device::sweep_tasks(const SweepLane &ln, int phase, int nr, int ldx, bool f
 // 1 / L_jj (+ the zero word masked operand elements are read from), once per factorisation, on stream st:
 // solve() calls this on the main stream BEFORE its lanes fork, so that a second lane never reads it half-written
 void Device::ensure_rdiag(hipStream_t st) {
-    if (wave_max_nr_ <= 0 || nswt_ <= 0) return;
+    if (env_.wave_max_nr <= 0 || nswt_ <= 0) return;
     if (!d_rdiag_) { d_rdiag_ = dalloc<double>((size_t)S_->n + 2); rdiag_for_ = 0; }
     if (rdiag_for_ == factor_serial_) return;
     launch_rdiag(st, d_L_, ds_.diagoff, (int)S_->n, d_rdiag_);
@@ -981,13 +997,19 @@ void Device::ensure_dtile(hipStream_t st) {
     dtile_for_ = factor_serial_;
 }
 
+SweepKnobs Device::sweep_knobs() const {
+    return SweepKnobs{inv_cap_, env_.fwd_front_min, env_.bwd_front_min, env_.syrk_xcd, narrow_pass_max(), narrow_pass_max_bwd(),
+                      bwd_front_max_cols(), launch_wave_split_cols(), launch_wave_split_rows()};
+}
+
 void Device::forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor) {
-    if (level_mark_ && lo == 0) { launch_level_mark(ln.st, 1, -1); level_event(ln.st, 1, 0); }
+    const SweepKnobs knobs = sweep_knobs();
+    if (env_.level_mark && lo == 0) { launch_level_mark(ln.st, 1, -1); level_event(ln.st, 1, 0); }
     // pipelined factor + solve (refactorize_solve): the bottom waits for the highest level a task / subtree reaches, every level
     // above for its own "factored" event; the dense inverses are built level by level instead of all at once
     if (follows_factor) {
         HC(hipStreamWaitEvent(ln.st, ev_flevel_[fused_gate_level_], 0));
-        if (nr <= wave_max_nr_ && nswt_ > 0) rdiag_for_ = 0;      // 1 / L_jj of the task fronts: their diagonals are final now, the rest is never read
+        if (nr <= env_.wave_max_nr && nswt_ > 0) rdiag_for_ = 0;      // 1 / L_jj of the task fronts: their diagonals are final now, the rest is never read
         dtile_for_ = 0;                                            // (the same for the chunks' inverse diagonal blocks)
     }
     if (lo == 0) sweep_tasks(ln, 1, nr, ldx, follows_factor);
@@ -996,8 +1018,8 @@ void Device::forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool 
             launch_subtree(ln.st, ds_, 1, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
                            nullptr, ln.X, ln.W, nr, ldx);
     for (int lev = lo; lev < hi; lev++) {
-        auto &L = swlevels_[lev];
-        if (level_mark_) { launch_level_mark(ln.st, 1, lev); level_event(ln.st, 1, 1 + lev); }
+        const LevelInfo &L = swlevels_[lev];
+        if (env_.level_mark) { launch_level_mark(ln.st, 1, lev); level_event(ln.st, 1, 1 + lev); }
         if (follows_factor) {
             if (lev > fused_gate_level_) HC(hipStreamWaitEvent(ln.st, ev_flevel_[lev], 0));
             invert_level(ln.st, lev);
@@ -1005,116 +1027,74 @@ void Device::forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool 
         for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++)
             launch_fwd_small(ln.st, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, ln.X, ln.W, nr, ldx);
         const int *list = d_sw_levellist_ + L.first + L.nsmall;
-        int nf = L.count - L.nsmall;
+        const FwdLevelPlan p = plan_forward_level(L, nr, knobs);
         // fronts of at most 128 columns (the tail of the list: sorted by decreasing width): the WHOLE step -- own rows assembled,
         // y = L11^-1 b, W = children - L21 y -- as one workgroup and one launch (k_fwd_front, sweep_front.hip), on levels with enough
         // of them to fill the chip and for passes wider than the narrow kernels take; wider fronts keep the three launches below
-        int cmin_front = 0;
-        if (fwd_front_min_ > 0 && nr > narrow_pass_max()) {
-            const size_t kq = (size_t)std::min(bwd_front_max_cols(), inv_cap_) / NB;       // (a front needs its WHOLE inverse for this)
-            const int nwide = kq + 1 < L.active.size() ? L.active[kq] : 0;
-            if (nf - nwide >= fwd_front_min_) {
-                launch_fwd_front(ln.st, ds_, list + nwide, nf - nwide, d_L_, ln.X, ln.X2, ln.W, nr, ldx);
-                nf = nwide;
-                cmin_front = (int)kq * NB;       // the record-driven update below skips the fronts taken here (its records cover the level)
-                if (nf == 0) continue;
-            }
+        if (p.ntail > 0) {
+            launch_fwd_front(ln.st, ds_, list + p.nf, p.ntail, d_L_, ln.X, ln.X2, ln.W, nr, ldx);
+            if (p.nf == 0) continue;
         }
-        launch_fwd_assemble(ln.st, ds_, list, nf, L.max_cols, ln.X, ln.W, nr, ldx);   // own rows only
+        launch_fwd_assemble(ln.st, ds_, list, p.nf, L.max_cols, ln.X, ln.W, nr, ldx);   // own rows only
         // y = L11^-1 b as one triangular product per front (dense inverse, inverse.hip), then the
         // trailing update W -= L21 y with K = all columns of the front
         // y of the big fronts stays in X2 (no copy back): the update below and the backward sweep read it there
         // fronts wider than inv_cap_: block by block (y_j = X_jj b_j, then the own rows below -= L[.., block j] y_j)
-        const int nbk = std::max(1, (L.max_cols + inv_cap_ - 1) / inv_cap_);
-        for (int j = 0; j < nbk; j++) {
-            // (nf: k_fwd_front may have taken the narrow tail of the list above -- block 0's count is "every big front" otherwise)
-            const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-            launch_xmul(ln.st, ds_, list, na, L.max_cols, 0, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
-            if (j + 1 < nbk) launch_fwd_own_update(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X2, ln.X, nr, ldx, j, inv_cap_);
+        for (int j = 0; j < p.nbk; j++) {
+            launch_xmul(ln.st, ds_, list, p.xmul_fronts(j), L.max_cols, 0, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
+            if (j + 1 < p.nbk) launch_fwd_own_update(ln.st, ds_, list, p.own_fronts(j), L.max_cols, d_L_, ln.X2, ln.X, nr, ldx, j, inv_cap_);
         }
-        // levels with many tiles: record-driven, per-XCD runs; the handful-of-fronts levels keep the 16-row latency variant
-        // Passes of at most 16 right-hand sides: the fronts up to kFwdWaveCols columns wide go one WAVE per 32-row tile (no LDS, no
-        // barrier: k_fwd_update_wave), chosen per FRONT so that a front's sums do not depend on the list it comes in
-        constexpr int kFwdWaveCols = 1024;      // (measured at cfg 2, 1 RHS, forward ms, with four waves sharing the K range of a front wider than 128
-                                                //  columns: 256: 0.933, 512: 0.841, 1024: 0.832, 2048: 0.836)
-        const int cwave = syrk_xcd_ && nr <= narrow_pass_max() ? kFwdWaveCols : 0;
-        const int cmin = std::max(cwave, cmin_front);          // fronts up to this width are not the split-K kernels' (wave kernel / k_fwd_front)
-        const int nwider = (size_t)(kFwdWaveCols / NB + 1) < L.active.size() ? L.active[kFwdWaveCols / NB] : 0;      // fronts wider than that
-        if (cwave > 0 && nwider < nf) launch_fwd_update_wave(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, cwave,
-                                                              L.max_cols > launch_wave_split_cols());
-        if (L.max_cols > cmin) {
-            if (syrk_xcd_ && (long long)((level_max_trail(L) + 31) / 32) * nf > 128)
-                launch_fwd_update_recs(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, cmin);
-            else
-                launch_fwd_update(ln.st, ds_, list, nf, level_max_trail(L), d_L_, ln.X2, ln.W, nr, ldx, cmin);
-        }
+        // W -= L21 y: the wave kernel for the fronts up to p.cmin columns wide (narrow passes), the split-K kernels for the wider ones
+        if (p.wave) launch_fwd_update_wave(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, p.cmin, p.wave_split_k);
+        if (p.update == FwdLevelPlan::kRecords)
+            launch_fwd_update_recs(ln.st, ds_, d_fwd_recs_ + L.fwd_off, L.fwd_split, L.fwd_per, d_L_, ln.X2, ln.W, nr, ldx, p.cmin);
+        else if (p.update == FwdLevelPlan::kGrid)
+            launch_fwd_update(ln.st, ds_, list, p.nf, L.max_trail, d_L_, ln.X2, ln.W, nr, ldx, p.cmin);
     }
-    if (level_mark_) level_event(ln.st, 1, 1 + hi);
+    if (env_.level_mark) level_event(ln.st, 1, 1 + hi);
 }
 
 // y_in_x2: the forward sweep left y of the big fronts in X2 (full solve). The backward sweep then turns it
 // into t = y - L21' x in place there and writes x = L11^-T t straight into X -- no copies. A backward-only
 // solve (F.UP \ z) gets z in X: classic path with one copy per level.
 void Device::backward(const SweepLane &ln, int nr, int ldx, bool y_in_x2, int hi, int lo) {
+    const SweepKnobs knobs = sweep_knobs();
+    // t lives where y was left (Xt), x = L11^-T t goes to the other buffer (Xx): X2 -> X after a forward sweep, X -> X2 in place
+    double *const Xt = y_in_x2 ? ln.X2 : ln.X, *const Xx = y_in_x2 ? ln.X : ln.X2;
     wait_inverse(ln.st);   // (a no-op event wait once the forward sweep has passed it)
     for (int l = hi - 1; l >= lo; l--) {
-        auto &L = swlevels_[l];
-        if (level_mark_) { launch_level_mark(ln.st, 2, l); level_event(ln.st, 2, (int)levels_.size() - 1 - l); }
+        const LevelInfo &L = swlevels_[l];
+        if (env_.level_mark) { launch_level_mark(ln.st, 2, l); level_event(ln.st, 2, (int)levels_.size() - 1 - l); }
         const int *list = d_sw_levellist_ + L.first + L.nsmall;
-        int nf = L.count - L.nsmall;
         for (int k = 0, off = 0; k < 4; off += L.ncls[k], k++)
             launch_bwd_small(ln.st, ds_, d_sw_levellist_ + L.first + off, L.ncls[k], kClsRows[k], d_L_, ln.X, nr, ldx);
+        const BwdLevelPlan p = plan_backward_level(L, nr, knobs);
         // fronts of at most 128 columns (the tail of the list: sorted by decreasing width): the whole step as one workgroup and
         // one launch (sweep_front.hip); in place when y sits in X (own rows are read and written by their front alone)
         // Only on levels with enough such fronts to fill the chip: a workgroup walks its front's trailing rows batch after batch,
         // and a level of a hundred fronts with 700 trailing rows each is faster as many small workgroups (the two launches).
-        // Passes of at most 16 right-hand sides: t = y - L21' x one WAVE per 16 own columns for the fronts with at most kBwdWaveRows
-        // trailing rows (k_bwd_wave), the split-K kernels for the others, x = L11^-T t as everywhere
-        constexpr int kBwdWaveRows = 4096;      // (every front of a 2-D problem; measured at cfg 2, 1 RHS, backward ms, with four waves sharing the K range of a front of more than 256
-                                                //  rows: 768: 0.848, 1100: 0.824, 1600: 0.814, every front: 0.792; one wave per tile only: 768 was the optimum, 1.177)
-        const bool narrow = nr <= narrow_pass_max_bwd();
-        if (bwd_front_min_ > 0 && !narrow) {
-            // (a front needs its WHOLE inverse for this: at most min(128, inv_cap_) columns)
-            const size_t kq = (size_t)std::min(bwd_front_max_cols(), inv_cap_) / NB;
-            const int nwide = kq + 1 < L.active.size() ? L.active[kq] : 0;   // fronts with more than kq NB columns (the last entry of `active` is the stash of level_max_trail)
-            if (nf - nwide >= bwd_front_min_) {
-                launch_bwd_front(ln.st, ds_, list + nwide, nf - nwide, d_L_, ln.X, y_in_x2 ? ln.X2 : ln.X, ln.X, nr, ldx);
-                nf = nwide;
-                if (nf == 0) continue;
-            }
+        if (p.ntail > 0) {
+            launch_bwd_front(ln.st, ds_, list + p.nf, p.ntail, d_L_, ln.X, Xt, ln.X, nr, ldx);
+            if (p.nf == 0) continue;
         }
-        const int nbk = std::max(1, (L.max_cols + inv_cap_ - 1) / inv_cap_);
-        double *const Xt = y_in_x2 ? ln.X2 : ln.X;
-        const int mmin = narrow ? kBwdWaveRows : 0;
-        if (narrow && level_max_trail(L) > 0 && L.min_trail <= kBwdWaveRows) launch_bwd_wave(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, Xt, nr, ldx, kBwdWaveRows,
-                                                                                                  level_max_trail(L) > launch_wave_split_rows());
-        if (y_in_x2) {
-            if (level_max_trail(L) > mmin) launch_bwd_gemm(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, ln.X2, nr, ldx, -1, 1 << 30, mmin);
-            // fronts wider than inv_cap_: from the last block up, t_j -= L[own rows below, block j]' x, x_j = X_jj' t_j
-            for (int j = nbk - 1; j >= 0; j--) {
-                // (nf: k_bwd_front may have taken the narrow tail of the list above -- block 0's count is "every big front" otherwise)
-                const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-                if (j + 1 < nbk) launch_bwd_gemm(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
-                launch_xmul(ln.st, ds_, list, na, L.max_cols, 1, d_L_, ln.X2, ln.X, nr, ldx, j, inv_cap_);
-            }
-        } else {
-            if (level_max_trail(L) > mmin) launch_bwd_gemm(ln.st, ds_, list, nf, L.max_cols, d_L_, ln.X, ln.X, nr, ldx, -1, 1 << 30, mmin);
-            for (int j = nbk - 1; j >= 0; j--) {
-                const int na = nbk == 1 ? nf : std::min(nf, L.active[std::min<size_t>((size_t)j * inv_cap_ / NB, L.active.size() - 2)]);
-                if (j + 1 < nbk) launch_bwd_gemm(ln.st, ds_, list, std::min(nf, L.active[(size_t)(j + 1) * inv_cap_ / NB]), L.max_cols, d_L_, ln.X, ln.X, nr, ldx, j, inv_cap_);
-                launch_xmul(ln.st, ds_, list, na, L.max_cols, 1, d_L_, ln.X, ln.X2, nr, ldx, j, inv_cap_);
-                // x_j has to be back in X before the block above reads it
-                launch_copy_own(ln.st, ds_, list, na, L.max_cols, ln.X2, ln.X, nr, ldx, j, inv_cap_);
-            }
+        // t = y - L21' x: the wave kernel for the fronts with at most p.mmin trailing rows (narrow passes), the split-K kernels for the others
+        if (p.wave) launch_bwd_wave(ln.st, ds_, list, p.nf, L.max_cols, d_L_, ln.X, Xt, nr, ldx, p.mmin, p.wave_split_k);
+        if (p.gemm) launch_bwd_gemm(ln.st, ds_, list, p.nf, L.max_cols, d_L_, ln.X, Xt, nr, ldx, -1, 1 << 30, p.mmin);
+        // fronts wider than inv_cap_: from the last block up, t_j -= L[own rows below, block j]' x, x_j = X_jj' t_j
+        for (int j = p.nbk - 1; j >= 0; j--) {
+            if (j + 1 < p.nbk) launch_bwd_gemm(ln.st, ds_, list, p.own_fronts(j), L.max_cols, d_L_, ln.X, Xt, nr, ldx, j, inv_cap_);
+            launch_xmul(ln.st, ds_, list, p.xmul_fronts(j), L.max_cols, 1, d_L_, Xt, Xx, nr, ldx, j, inv_cap_);
+            // in place: x_j has to be back in X before the block above reads it
+            if (!y_in_x2) launch_copy_own(ln.st, ds_, list, p.xmul_fronts(j), L.max_cols, ln.X2, ln.X, nr, ldx, j, inv_cap_);
         }
     }
-    if (level_mark_ && lo == 0) { launch_level_mark(ln.st, 2, -1); level_event(ln.st, 2, (int)levels_.size()); }
+    if (env_.level_mark && lo == 0) { launch_level_mark(ln.st, 2, -1); level_event(ln.st, 2, (int)levels_.size()); }
     if (lo == 0)
         for (int k = 0, off = 0; k < 3; off += nsub_cls_[k], k++)
             launch_subtree(ln.st, ds_, 2, d_sub_first_ + off, d_sub_last_ + off, nsub_cls_[k], kClsRows[k], nullptr, d_L_, nullptr,
                            nullptr, ln.X, nullptr, nr, ldx);
     if (lo == 0) sweep_tasks(ln, 2, nr, ldx, false);
-    if (level_mark_ && lo == 0) level_event(ln.st, 2, (int)levels_.size() + 1);
+    if (env_.level_mark && lo == 0) level_event(ln.st, 2, (int)levels_.size() + 1);
 }
 
 // GMRFX_LEVEL_MARK=1: HIP events at the level boundaries of the most recent factorisation / forward / backward sweep
@@ -1129,7 +1109,7 @@ void Device::level_event(hipStream_t st, int phase, int slot) {
 int Device::level_times(int phase, double *out, int cap) {
     HC(hipSetDevice(device));
     const int nl = (int)levels_.size();
-    if (!level_mark_ || phase < 0 || phase > 2 || level_slots_[phase] < (phase == 0 ? nl + 1 : nl + 2)) return 0;
+    if (!env_.level_mark || phase < 0 || phase > 2 || level_slots_[phase] < (phase == 0 ? nl + 1 : nl + 2)) return 0;
     HC(hipDeviceSynchronize());
     auto &v = ev_level_[phase];
     auto dt = [&](int a, int b) { float ms = 0; HC(hipEventElapsedTime(&ms, v[a], v[b])); return (double)ms; };
@@ -1418,7 +1398,6 @@ void Device::selinv_levels(int hi, int lo) {
     DevSym dsz = ds_;            // the selected inversion has its own slot layout in the contribution-block arena
     dsz.cbptr = d_zbptr_;
     for (int l = hi - 1; l >= lo; l--) {
-        auto &L = levels_[l];
         // all fronts of the level (subtree members included): small first, then big
         const int sfirst = (int)S.sel_levelptr[l], scount = (int)(S.sel_levelptr[l + 1] - S.sel_levelptr[l]);
         const int snsmall = S.sel_level_nsmall[l];
@@ -1428,8 +1407,7 @@ void Device::selinv_levels(int hi, int lo) {
         // Yt lives at d_tmp_ + yoff[s], Z21t right behind it (offset (r-c)*c): pass both bases.
         // (geometry over the level's fronts of the SELECTED-INVERSION list: the factor's level list of a sharded handle
         //  leaves out the distributed root, which the owner still inverts)
-        (void)L;
-        if (level_mark_) launch_level_mark(stream, 4, l);      // (profiling aid: tools/cfg3_profile.py cuts the trace into levels)
+        if (env_.level_mark) launch_level_mark(stream, 4, l);      // (profiling aid: tools/cfg3_profile.py cuts the trace into levels)
         launch_sel_gather(stream, d_selrec_, dsz, list, nf, sel_max_trail_[l], d_Z_, d_cb_);
         for (int phase = 0; phase < 3; phase++)
             launch_sel_dense(stream, dsz, list, nf, phase, sel_max_cols_[l], sel_max_trail_[l], d_L_, d_Z_, d_cb_, d_tmp_,

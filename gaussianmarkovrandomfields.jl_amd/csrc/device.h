@@ -10,8 +10,6 @@
 #include "rbmc_plan.h"
 #include "resource.h"
 
-namespace gmrfx { constexpr int kSyrkPipedMinCols = 128; }     // see DeviceFactor::syrk_piped_min_
-
 namespace gmrfx {
 
 // Pointers to the symbolic structure in HBM; passed to kernels by value.
@@ -221,6 +219,13 @@ private:
     void ensure_rhs_capacity(long long nrhs);
     // record_level_events: the pipelined call's "level is factored" events (ev_flevel_) behind every level
     void factor_levels(int lo, int hi, bool record_level_events);
+    // the three parts of a level (device.cpp, above factor_levels); factor_small_fronts returns whether the third stream took part
+    struct PanelChain;
+    bool factor_small_fronts(const LevelInfo &L);
+    bool factor_panel_chains(const LevelInfo &L);       // returns whether there were two chains (joined behind the last block)
+    void panel_block(const PanelChain &ch, const LevelInfo &L, int b);
+    void factor_contribution_blocks(const LevelInfo &L, int slot);
+    SweepKnobs sweep_knobs() const;
     // follows_factor: the pipelined call's forward sweep, one level behind the factorisation (waits for the level events, builds the
     // dense inverses level by level)
     void forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor);
@@ -263,13 +268,10 @@ private:
     Event ev_nzp_, ev_nzp0_;
     AsmRec *d_arec_ = nullptr;          // one per position of the level lists (Symbolic::levellist order)
     SyrkTile *d_syrk_recs_ = nullptr;   // one record per contribution-block tile, level by level, in hand-out order
-    int syrk_piped_min_ = kSyrkPipedMinCols;      // GMRFX_SYRK_PIPED=N: levels whose widest front has >= N columns take the software-pipelined
-                                                  // product loop of k_syrk_cb_rec (0: every level; a huge N: none) -- same bits either way
-    bool syrk_xcd_ = true;          // GMRFX_SYRK_XCD=0: k_syrk_cb on a plain 3-D grid (front, tile row, tile column) instead
+    EnvKnobs env_;                  // the environment's knobs (device_plan.h), read by init
     FrontView *d_frec_ = nullptr, *d_frec2_ = nullptr, *d_sel_frec_ = nullptr;   // geometry records parallel to the level lists
     int *d_levellist2_ = nullptr;   // per level: the big fronts re-ordered [even positions..., odd positions...] (two-stream panel chains)
     // wave tasks (sweep_wave.hip): task ids by LDS class (kWaveRows, device_plan.h)
-    int wave_max_nr_ = 16;        // passes of up to this many right-hand sides use the wave tasks (0: never)
     const int *d_wave_order_ = nullptr;
     int wave_first_[kWaveClasses] = {0, 0}, wave_count_[kWaveClasses] = {0, 0};
     void sweep_tasks(const SweepLane &ln, int phase, int nr, int ldx, bool follows_factor);
@@ -281,10 +283,6 @@ private:
     void ensure_rdiag(hipStream_t st);
     bool nzp_pending_ = false;                    // k_gather_values runs on the third stream and the main stream has not waited for it yet
     void ensure_dtile(hipStream_t st);
-    int fwd_front_min_ = 384;                     // the forward twin (k_fwd_front): levels with at least this many such fronts (measured at cfg 2, round 6, one workgroup per
-                                                  // front against the three launches, us: level 5 (1472 fronts) 103 / 128, 6 (2271) 167 / 211, 7 (1034) 159 / 207, 8 (513) 103 / 131,
-                                                  // 9 (256, 236 of them eligible) 103 + 58 / 113: a level needs about two workgroups per compute unit)
-    int bwd_front_min_ = 192;                     // backward step of fronts <= 128 columns wide as one workgroup (sweep_front.hip) on levels with at least this many of them (0: never)
     Symbolic::SwChunk *d_swc_fwd_ = nullptr, *d_swc_bwd_ = nullptr;   // chunk records of the sweep tasks (forward order / backward slot programs)
     int *d_swc_listf_ = nullptr, *d_swc_listb_ = nullptr;               // their target rows as LDS byte offsets, in the lane order of the two kernels
     double *d_dtile_ = nullptr;                   // inverse diagonal blocks of the chunks, packed (k_pack_diag): 256 doubles per chunk
@@ -298,7 +296,6 @@ private:
     std::vector<Event> ev_level_[3];
     int level_slots_[3] = {0, 0, 0};
     void level_event(hipStream_t st, int phase, int slot);
-    bool level_mark_ = false;     // GMRFX_LEVEL_MARK=1: an empty marker kernel in front of every level (profiling aid, tools/sweep_levels.py)
     int *d_sub_first_ = nullptr, *d_sub_last_ = nullptr, *d_sel_levellist_ = nullptr;
     int nsub_cls_[3] = {0, 0, 0};
     double *d_L_ = nullptr, *d_Z_ = nullptr, *d_cb_ = nullptr, *d_nz_ = nullptr;
@@ -318,7 +315,7 @@ private:
     // Recursive doubling of the diagonal-block inverses stops at inv_cap_ columns (a full inverse of a c-column
     // front costs O(c^3): most of a 3-D solve); wider fronts substitute block by block in the sweeps. The selected
     // inversion needs the full inverses and runs the remaining stages on demand (B from inv_cap_ up).
-    int inv_cap_ = 2048;     // measured: cfg 2 flat between 1024 and 4096 (6.18 vs 6.26 ms), 3-D 100^3 solve 44 vs 54 ms
+    int inv_cap_ = EnvKnobs{}.inv_cap;     // 2048, measured: cfg 2 flat between 1024 and 4096 (6.18 vs 6.26 ms), 3-D 100^3 solve 44 vs 54 ms
     // An explicit inverse of an ill-conditioned L11 is not backward stable (inverse.hip, "Conditioning"): the handle's first
     // successful factorisation measures the pivot growth max_j sqrt(A11_jj) / L_jj of every front wider than NB, and above
     // kInvGrowthMax the cap drops to NB for the rest of the handle's life. One cap per handle, decided before any sweep runs

@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cstdlib>
 #include <stdexcept>
 #include <string>
 
@@ -55,14 +56,65 @@ static std::vector<LevelInfo> level_infos(const Symbolic &S, const std::vector<i
             for (int k = L.nsmall; k < L.count && S.ncols(llist[L.first + k]) > w; k++) cnt++;
             return cnt;
         };
-        int nblk = (L.max_cols + NB - 1) / NB;
-        L.active.assign(nblk + 1, 0);
-        for (int b = 0; b <= nblk; b++) L.active[b] = wider_than(b * NB);
+        std::vector<int> blk((size_t)L.nblk());
+        for (int b = 0; b < L.nblk(); b++) blk[b] = wider_than(b * NB);
+        L.set_block_counts(std::move(blk));
         for (int q = 0; q < 3; q++) L.wider[q] = wider_than(48 - 16 * q);
+        L.max_trail = max_trail;
         L.min_trail = min_trail == INT_MAX ? 0 : min_trail;
-        L.active.push_back(max_trail);  // stash: last element = max trailing rows of the level
     }
     return LV;
+}
+
+EnvKnobs read_env_knobs() {
+    EnvKnobs k;
+    if (const char *e = std::getenv("GMRFX_INV_CAP")) {
+        const int v = std::atoi(e);
+        k.inv_cap = NB;
+        while (k.inv_cap < v) k.inv_cap *= 2;
+    }
+    if (const char *e = std::getenv("GMRFX_TASK_MODE")) {       // A/B knob: "wg" / "wave" force one form for every width
+        const std::string m(e);
+        k.wave_max_nr = m == "wg" ? 0 : m == "wave" ? 64 : k.wave_max_nr;
+    }
+    if (const char *e = std::getenv("GMRFX_LEVEL_MARK")) k.level_mark = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GMRFX_BWD_FRONT")) k.bwd_front_min = std::atoi(e);
+    if (const char *e = std::getenv("GMRFX_FWD_FRONT")) k.fwd_front_min = std::atoi(e);
+    if (const char *e = std::getenv("GMRFX_SYRK_XCD")) k.syrk_xcd = std::atoi(e) != 0;
+    if (const char *e = std::getenv("GMRFX_SYRK_PIPED")) k.syrk_piped_min = std::atoi(e);
+    return k;
+}
+
+// The fronts of at most min(front_max_cols, inv_cap) columns (a front needs its WHOLE inverse for the one-workgroup step) are the
+// tail of the list; the front kernel takes them on levels with at least front_min of them (enough to fill the chip), when allowed.
+static LevelBlocks split_level(const LevelInfo &L, bool front_kernel, int front_min, const SweepKnobs &k) {
+    LevelBlocks b{&L, k.inv_cap, 0, L.nbig(), std::max(1, (L.max_cols + k.inv_cap - 1) / k.inv_cap)};
+    const int nwide = L.wider_than(std::min(k.front_max_cols, k.inv_cap) / NB * NB);
+    if (front_kernel && front_min > 0 && b.nf - nwide >= front_min) { b.ntail = b.nf - nwide; b.nf = nwide; }
+    return b;
+}
+
+FwdLevelPlan plan_forward_level(const LevelInfo &L, int nr, const SweepKnobs &k) {
+    const bool narrow = nr <= k.narrow_pass_max;      // (the front kernel is for passes wider than the narrow kernels take)
+    FwdLevelPlan p{split_level(L, !narrow, k.fwd_front_min, k), 0, false, false, FwdLevelPlan::kNone};
+    // the record-driven update skips the fronts the front kernel took by their width (its records cover the level)
+    p.cmin = narrow ? (k.tile_records ? kFwdWaveCols : 0) : p.ntail > 0 ? std::min(k.front_max_cols, k.inv_cap) / NB * NB : 0;
+    p.wave = narrow && k.tile_records && L.wider_than(kFwdWaveCols) < p.nf;
+    p.wave_split_k = L.max_cols > k.wave_split_cols;
+    // levels with many tiles: record-driven, per-XCD runs; the handful-of-fronts levels keep the 16-row latency variant
+    if (p.nf > 0 && L.max_cols > p.cmin)
+        p.update = k.tile_records && (long long)((L.max_trail + 31) / 32) * p.nf > 128 ? FwdLevelPlan::kRecords : FwdLevelPlan::kGrid;
+    return p;
+}
+
+BwdLevelPlan plan_backward_level(const LevelInfo &L, int nr, const SweepKnobs &k) {
+    const bool narrow = nr <= k.narrow_pass_max_bwd;
+    BwdLevelPlan p{split_level(L, !narrow, k.bwd_front_min, k), 0, false, false, false};
+    p.mmin = narrow ? kBwdWaveRows : 0;
+    p.wave = narrow && L.max_trail > 0 && L.min_trail <= kBwdWaveRows;
+    p.wave_split_k = L.max_trail > k.wave_split_rows;
+    p.gemm = L.max_trail > p.mmin;
+    return p;
 }
 
 // Dense-inverse stage B: T-buffer offsets of the fronts wider than B, a list sorted by decreasing width; *total = doubles.

@@ -1,6 +1,8 @@
 // device_plan.h -- the host images of the tables the kernels read and the level schedule the drivers keep, built from the
 // symbolic analysis on the host (device_plan.cpp, no HIP); Device::upload copies the tables to the device as they are.
 #pragma once
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "symbolic.h"
@@ -109,8 +111,8 @@ struct LevelInfo {
     int ncls[4];      // of which r <= 48 / 64 / 96 / 128 (in this order)
     int max_rows;     // over big fronts
     int max_cols;     // over big fronts (they are sorted by decreasing column count)
+    int max_trail = 0; // most trailing rows of a big front
     int min_trail = 0; // fewest trailing rows of a big front with any (0: none has)
-    std::vector<int> active;  // active[k] = number of big fronts with ncols > k*NB
     int wider[3] = {0, 0, 0}; // big fronts with more than 48 / 32 / 16 columns (first 64-column block: the diagonal-block kernel's shapes)
     // contribution-block SYRK: the level's 64 x 64 tiles in the order they are handed out, cut into one run per XCD
     long long syrk_off = 0;   // offset of the level's tiles in Device::d_syrk_recs_
@@ -120,7 +122,82 @@ struct LevelInfo {
     long long fwd_off = 0;
     SyrkSplit fwd_split{};
     int fwd_per = 0;
+
+    int nbig() const { return count - nsmall; }             // big fronts: positions nsmall .. count - 1 of the level's list
+    int nblk() const { return (max_cols + NB - 1) / NB; }   // 64-column blocks of the widest big front
+    // Big fronts with more than `cols` columns, cols a multiple of NB: they are the first wider_than(cols) of the width-sorted
+    // list of big fronts. 0 from max_cols on, however large cols is.
+    int wider_than(int cols) const { const size_t k = (size_t)cols / NB; return k < wider_blk_.size() ? wider_blk_[k] : 0; }
+    void set_block_counts(std::vector<int> counts) { wider_blk_ = std::move(counts); }   // (level_infos: one per block of nblk())
+private:
+    std::vector<int> wider_blk_;   // [k] = big fronts with more than k NB columns, k < nblk()
 };
+
+constexpr int kSyrkPipedMinCols = 128;     // see EnvKnobs::syrk_piped_min (kernels.h: the measurement)
+// The environment's testing / A/B / profiling knobs, read once per handle (Device::init; a clone reads them again).
+struct EnvKnobs {
+    int inv_cap = 2048;          // GMRFX_INV_CAP: testing knob, rounded up to a power of two >= 64 (the default: Device::inv_cap_)
+    int wave_max_nr = 16;        // GMRFX_TASK_MODE = wg / wave: 0 / 64. Passes of up to this many right-hand sides use the wave tasks (0: never)
+    bool level_mark = false;     // GMRFX_LEVEL_MARK=1: an empty marker kernel in front of every level (profiling aid, tools/sweep_levels.py)
+    int fwd_front_min = 384;     // GMRFX_FWD_FRONT. The forward twin (k_fwd_front): levels with at least this many such fronts (measured at cfg 2, round 6, one workgroup per
+                                 // front against the three launches, us: level 5 (1472 fronts) 103 / 128, 6 (2271) 167 / 211, 7 (1034) 159 / 207, 8 (513) 103 / 131,
+                                 // 9 (256, 236 of them eligible) 103 + 58 / 113: a level needs about two workgroups per compute unit)
+    int bwd_front_min = 192;     // GMRFX_BWD_FRONT. Backward step of fronts <= 128 columns wide as one workgroup (sweep_front.hip) on levels with at least this many of them (0: never)
+    bool syrk_xcd = true;        // GMRFX_SYRK_XCD=0: k_syrk_cb on a plain 3-D grid (front, tile row, tile column) instead, and no tile records at all
+    int syrk_piped_min = kSyrkPipedMinCols;    // GMRFX_SYRK_PIPED=N: levels whose widest front has >= N columns take the software-pipelined
+                                 // product loop of k_syrk_cb_rec (0: every level; a huge N: none) -- same bits either way
+};
+EnvKnobs read_env_knobs();
+
+// ---- the sweeps' per-level decisions: which fronts of a level's width-sorted list of big fronts go to which launch -----------------
+// Plain functions of values (no device, no HIP): Device::forward / backward read the plan and launch; tools/sanitize_host.cpp
+// walks every level of its plans through them.
+// Passes of at most narrow_pass_max right-hand sides, forward: the fronts up to kFwdWaveCols columns wide go one WAVE per 32-row tile
+// (no LDS, no barrier: k_fwd_update_wave), chosen per FRONT so that a front's sums do not depend on the list it comes in
+constexpr int kFwdWaveCols = 1024;      // (measured at cfg 2, 1 RHS, forward ms, with four waves sharing the K range of a front wider than 128
+                                        //  columns: 256: 0.933, 512: 0.841, 1024: 0.832, 2048: 0.836)
+// Passes of at most narrow_pass_max_bwd right-hand sides, backward: t = y - L21' x one WAVE per 16 own columns for the fronts with at
+// most kBwdWaveRows trailing rows (k_bwd_wave), the split-K kernels for the others, x = L11^-T t as everywhere
+constexpr int kBwdWaveRows = 4096;      // (every front of a 2-D problem; measured at cfg 2, 1 RHS, backward ms, with four waves sharing the K range of a front of more than 256
+                                        //  rows: 768: 0.848, 1100: 0.824, 1600: 0.814, every front: 0.792; one wave per tile only: 768 was the optimum, 1.177)
+
+// What the decisions read besides the level: the handle's knobs and the limits of the launch side (kernels.h; Device::sweep_knobs)
+struct SweepKnobs {
+    int inv_cap;                     // Device::inv_cap_: wider fronts substitute block by block
+    int fwd_front_min, bwd_front_min;   // EnvKnobs
+    bool tile_records;               // EnvKnobs::syrk_xcd: the forward update's tile records exist
+    int narrow_pass_max, narrow_pass_max_bwd;   // widest pass of the narrow level kernels
+    int front_max_cols;              // bwd_front_max_cols(): widest front of the one-workgroup front kernels
+    int wave_split_cols, wave_split_rows;       // launch_wave_split_cols() / _rows()
+};
+
+// How a level's big fronts are split between the one-workgroup front kernel and the blocked substitution. The list is sorted by
+// decreasing width: [0, nf) is the head, [nf, nf + ntail) the tail.
+struct LevelBlocks {
+    const LevelInfo *L;
+    int inv_cap;
+    int ntail;    // the narrow tail, every front at most min(front_max_cols, inv_cap) columns wide: its WHOLE step is k_fwd_front's / k_bwd_front's (0: not used)
+    int nf;       // the head: everything below runs on these fronts only
+    int nbk;      // blocks of inv_cap columns of the widest front (1: every front multiplies by its whole inverse)
+    // launch_xmul of block j: the head fronts wider than j inv_cap (block 0: the whole head -- never the tail, which is finished)
+    int xmul_fronts(int j) const { return std::min(nf, L->wider_than(j * inv_cap)); }
+    // own-rows update of block j (launch_fwd_own_update / launch_bwd_gemm, j + 1 < nbk): the head fronts that have a block j + 1
+    int own_fronts(int j) const { return std::min(nf, L->wider_than((j + 1) * inv_cap)); }
+};
+struct FwdLevelPlan : LevelBlocks {
+    int cmin;             // head fronts up to this width are not the split-K update's: kFwdWaveCols with the wave kernel, the tail's width bound with k_fwd_front
+    bool wave;            // launch_fwd_update_wave runs (cmax = cmin): some head front is at most kFwdWaveCols wide
+    bool wave_split_k;
+    enum Update { kNone, kRecords, kGrid } update;   // W -= L21 y of the head fronts wider than cmin: none left / record-driven / plain grid
+};
+struct BwdLevelPlan : LevelBlocks {
+    int mmin;             // head fronts with at most this many trailing rows are not the split-K product's (kBwdWaveRows with the wave kernel)
+    bool wave;            // launch_bwd_wave runs (mmax = mmin)
+    bool wave_split_k;
+    bool gemm;            // launch_bwd_gemm over all blocks runs: some head front has more than mmin trailing rows
+};
+FwdLevelPlan plan_forward_level(const LevelInfo &L, int nr, const SweepKnobs &k);
+BwdLevelPlan plan_backward_level(const LevelInfo &L, int nr, const SweepKnobs &k);
 
 // What changes the tables besides the analysis.
 struct PlanOptions {

@@ -146,6 +146,69 @@ static void check_runs(const std::vector<gmrfx::LevelInfo> &LV, bool fwd, size_t
     EXPECT(any || end == 0);
 }
 
+// The level schedule the drivers read (device_plan.h): LevelInfo's counts against a brute-force walk over the level's list of big
+// fronts, and the sweeps' step plans (plan_forward_level / plan_backward_level) for every pass width, inverse cap, front-kernel
+// minimum and both values of the records flag: every big front is finished exactly once -- by the one-workgroup front kernel or
+// by the blocks of the substitution, never both (the list arithmetic that once ran the blocked loop over the finished tail).
+static int levels_with_wide_head_and_tail = 0;
+static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx::LevelInfo> &LV, const std::vector<gmrfx::i32> &llist) {
+    using namespace gmrfx;
+    const EnvKnobs env;
+    for (const LevelInfo &L : LV) {
+        std::vector<int> cols, trail;
+        for (int k = L.nsmall; k < L.count; k++) {
+            const i32 s = llist[(size_t)L.first + k];
+            cols.push_back(S.ncols(s)); trail.push_back(S.nrows(s) - S.ncols(s));
+        }
+        const int nbig = (int)cols.size();
+        EXPECT(nbig == L.nbig());
+        auto wider = [&](int c, int upto) { int cnt = 0; for (int i = 0; i < upto; i++) cnt += cols[i] > c; return cnt; };
+        int max_cols = 0, max_trail = 0, min_trail = 0;
+        for (int i = 0; i < nbig; i++) {
+            EXPECT(i == 0 || cols[i] <= cols[i - 1]);          // sorted by decreasing width
+            max_cols = std::max(max_cols, cols[i]); max_trail = std::max(max_trail, trail[i]);
+            if (trail[i] > 0) min_trail = min_trail ? std::min(min_trail, trail[i]) : trail[i];
+        }
+        EXPECT(L.max_cols == max_cols && L.max_trail == max_trail && L.min_trail == min_trail && L.nblk() == (max_cols + NB - 1) / NB);
+        for (int c = 0; c <= max_cols + 2 * NB; c += NB) { EXPECT(L.wider_than(c) == wider(c, nbig)); EXPECT(c < max_cols || L.wider_than(c) == 0); }
+        EXPECT(L.wider_than(INT32_MAX / NB * NB) == 0);
+        bool counted = false;
+        for (int nr : {1, 16, 17, 32, 33, 64})
+            for (int cap : {64, 128, 2048})
+                for (int fm = 0; fm < 3; fm++)
+                    for (bool rec : {true, false}) {
+                        // (the limits as the launch side has them today; the properties hold for any)
+                        const SweepKnobs kn{cap, fm < 2 ? fm : env.fwd_front_min, fm < 2 ? fm : env.bwd_front_min, rec, 32, 16, 128, 128, 256};
+                        const FwdLevelPlan f = plan_forward_level(L, nr, kn);
+                        const BwdLevelPlan b = plan_backward_level(L, nr, kn);
+                        for (const LevelBlocks *p : {(const LevelBlocks *)&f, (const LevelBlocks *)&b}) {
+                            EXPECT(p->nf >= 0 && p->ntail >= 0 && p->nf + p->ntail == nbig);
+                            EXPECT(p->nbk == std::max(1, (max_cols + cap - 1) / cap));
+                            for (int j = 0; j < p->nbk; j++) {
+                                EXPECT(p->xmul_fronts(j) == wider(j * cap, p->nf));                 // block j: the head fronts wider than j cap
+                                if (j + 1 < p->nbk) EXPECT(p->own_fronts(j) == wider((j + 1) * cap, p->nf));
+                            }
+                            for (int i = 0; i < nbig; i++) {
+                                int blocks = 0;
+                                for (int j = 0; j < p->nbk; j++) blocks += i < p->xmul_fronts(j);
+                                // the tail is the front kernel's alone, a head front gets each of its blocks once
+                                if (i >= p->nf) EXPECT(blocks == 0 && cols[i] <= std::min(128, cap));
+                                else EXPECT(blocks == (cols[i] + cap - 1) / cap);
+                            }
+                            if (p->ntail > 0 && wider(cap, p->nf) > 0 && !counted) { levels_with_wide_head_and_tail++; counted = true; }
+                        }
+                        EXPECT(nr > 32 || f.ntail == 0);      // narrow passes never take the front kernels
+                        EXPECT(nr > 16 || b.ntail == 0);
+                        for (int i = 0; i < f.nf; i++)      // a front's update W -= L21 y: exactly one form, by its width
+                            EXPECT((f.wave && cols[i] <= f.cmin) + (f.update != FwdLevelPlan::kNone && cols[i] > f.cmin) == 1);
+                        EXPECT(f.update != FwdLevelPlan::kRecords || rec);
+                        EXPECT(!f.wave || (rec && f.cmin == kFwdWaveCols));
+                        for (int i = 0; i < b.nf; i++)      // ... and t = y - L21' x, by its trailing rows
+                            if (trail[i] > 0) EXPECT((b.wave && trail[i] <= b.mmin) + (b.gemm && trail[i] > b.mmin) == 1);
+                    }
+    }
+}
+
 // the device tables of every rank of a (sharded, world > 1) analysis, with and without the tile records (GMRFX_SYRK_XCD=0)
 static void device_plans(const std::vector<int64_t> &cp, const std::vector<int64_t> &ri, const double *coords, int64_t n, int world) {
     for (int rank = 0; rank < world; rank++) {
@@ -159,6 +222,8 @@ static void device_plans(const std::vector<int64_t> &cp, const std::vector<int64
             check_runs(P.levels, false, P.syrk_recs.size(), xcd);
             check_runs(P.swlevels, true, P.fwd_recs.size(), xcd);
             EXPECT(P.edge.size() == S.children.size() && (int)P.levels.size() == S.nlevels);
+            check_level_plans(S, P.levels, S.levellist);
+            check_level_plans(S, P.swlevels, S.sw_levellist);
             EXPECT(S.shard_plan ? P.owncol.size() == (size_t)n && P.fc_levelptr.back() == (int)P.fchild.size() : P.owncol.empty());
         }
     }
@@ -215,6 +280,9 @@ int main() {
         std::vector<int64_t> p(n, 0);
         EXPECT(gmrfx_create(n, cp.data(), ri.data(), 0, p.data(), &o, &h) != GMRFX_OK && h == nullptr);
     }
+    // (levels with a front wider than the inverse cap in the head AND a tail for the front kernel: what the check above is for)
+    std::printf("levels with a wide head and a front-kernel tail: %d\n", levels_with_wide_head_and_tail);
+    EXPECT(levels_with_wide_head_and_tail > 0);
     std::printf("sanitize_host: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
 }
