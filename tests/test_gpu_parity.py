@@ -875,12 +875,24 @@ def _kl_problem(n, rho_len, seed):
     return X, K, klchol.radius_pattern(X, rho_len)
 
 
+def _kl_classes(sizes):
+    # tasks of <= 32, 33..64, 65..128 and more than 128 rows: the kernels k_kl_chol<32|64|128> and k_kl_chol_big
+    s = np.asarray(sizes)
+    return [int((s <= 32).sum()), int(((s > 32) & (s <= 64)).sum()), int(((s > 64) & (s <= 128)).sum()), int((s > 128).sum())]
+
+
+# (n, rho_len) -> tasks per size class; (400, 2.0) has more big tasks than one launch of 256 takes
+_KL_CLASSES = {(4, 2.0): [4, 0, 0, 0], (60, 0.25): [60, 0, 0, 0], (300, 0.12): [300, 0, 0, 0], (300, 0.3): [159, 112, 29, 0],
+               (500, 0.5): [74, 69, 136, 221], (400, 2.0): [32, 32, 64, 272]}
+
+
 @pytest.mark.parametrize("n,rho_len", [(4, 2.0), (60, 0.25), (300, 0.12), (300, 0.3), (500, 0.5), (400, 2.0)])
 def test_kl_cholesky_columns_match_oracle(n, rho_len):
     # local systems of up to 32 / 64 / 128 rows (LDS classes) and beyond (global-scratch class; (400, 2.0) is the
     # complete pattern: 400-row systems and L L' = (K + 1e-6 I)^-1 exactly)
     from gmrfx import klchol
     X, K, P = _kl_problem(n, rho_len, seed=n)
+    assert _kl_classes(np.diff(P.indptr)) == _KL_CLASSES[(n, rho_len)]
     L = klchol.sparse_approximate_cholesky_inplace(K, P)
     Lo = orc.kl_cholesky_inplace(K, P)
     assert (L.indices == Lo.indices).all() and (L.indptr == Lo.indptr).all()
@@ -928,6 +940,7 @@ def test_kl_cholesky_supernodal_matches_oracle():
         rows.update(members)
         col_idx.append(sorted(members)); row_idx.append(sorted(rows, reverse=True))
     assert max(map(len, col_idx)) > 1
+    assert _kl_classes([len(r) for r in row_idx]) == [68, 7, 0, 0] and max(map(len, col_idx)) == 8    # (more than 4 member columns)
     L = klchol.sparse_approximate_cholesky_supernodal(K, col_idx, row_idx)
     Lo = orc.kl_cholesky_supernodal(K, col_idx, row_idx)
     assert (L.indices == Lo.indices).all() and (L.indptr == Lo.indptr).all()
