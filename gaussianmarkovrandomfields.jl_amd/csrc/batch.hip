@@ -10,7 +10,7 @@
 
 #include <climits>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 
@@ -97,7 +97,7 @@ void launch_batch_diag(hipStream_t st, const double *L, const long long *diagoff
 // Right-hand-side permutation with a member stride: forest row I = k nm + i (member k, member row i) of column j lives at
 // A[k s + j ld + i] on the caller's side, at X[iperm[I] ldx + j] on the solver's side (row-major, elimination order; iperm == nullptr:
 // identity -- the backward-only solve takes Z in elimination order, and the forest's elimination order is the members' one after
-// the other). dir 0: gather A -> X, dir 1: scatter X -> A. The same two shapes as k_permute_narrow / k_permute (kernels.hip): a
+// the other). dir 0: gather A -> X, dir 1: scatter X -> A. The same two shapes as k_permute_narrow / k_permute (sweep_level.hip): a
 // thread per forest row for passes of <= 8 columns (caller side coalesced along i, every element read once), a 64 x 64 LDS
 // transpose for wider passes. Within a member consecutive rows are consecutive addresses; a run of 64 rows that crosses a member
 // boundary splits into two coalesced pieces.

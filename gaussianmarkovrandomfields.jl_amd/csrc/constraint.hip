@@ -24,7 +24,7 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

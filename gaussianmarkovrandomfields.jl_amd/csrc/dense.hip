@@ -2,12 +2,12 @@
 // (SeparableModel, /root/reference/src/latent_models/separable.jl:122-172) is solved / sampled as a sweep over the large factor
 // followed by the SMALL factor applied as a dense n1 x n1 operator (Q_1^-1, or A_1 = P_1' L_1^-T for samples) to the row-major
 // n1 x n2 result:  R = D T.  This is a genuine dense contraction (n1 = 512, n2 = 250 000 at BASELINE cfg 5: 1.3e11 flops), so
-// it runs on the FP64 MFMA with the library's own 32 x 32 wave products (kernels.h) -- no vendor GEMM.
+// it runs on the FP64 MFMA with the library's own 32 x 32 wave products (kernel_common.h) -- no vendor GEMM.
 //   k_dense_apply   R[i1, i2] = sum_k D[i1, k] T[k, i2]      (all row-major; T and R are n1 x n2, D is n1 x n1)
 //   k_transpose     dst[j, i] = src[i, j]                    (row-major rows x cols -> cols x rows; two large factors)
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

@@ -515,7 +515,7 @@ void Device::factor_contribution_blocks(const LevelInfo &L, int slot) {
     HC(hipEventRecord(ev_syrk_[2 * slot], stream));
     // levels of HUGE fronts (3-D problems): the children's extend-add alone, then the product on 128 x 128 staged tiles
     const bool huge = env_.syrk_xcd && !sharded() && L.max_trail >= 4096 && L.max_cols >= 1024;
-    // levels of wide fronts (the product dominates the tile): the software-pipelined product loop (kernels.hip, k_syrk_cb_rec<true>;
+    // levels of wide fronts (the product dominates the tile): the software-pipelined product loop (factor_kernels.hip, k_syrk_cb_rec<true>;
     // same sums in the same order: a level's choice does not show in the bits)
     if (env_.syrk_xcd) launch_syrk_cb_recs(stream, ds_, d_syrk_recs_ + L.syrk_off, L.syrk_split, L.syrk_per, d_L_, d_cb_, huge ? 1 : 0, L.max_cols >= env_.syrk_piped_min);
     else launch_syrk_cb(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_);
@@ -998,8 +998,8 @@ void Device::ensure_dtile(hipStream_t st) {
 }
 
 SweepKnobs Device::sweep_knobs() const {
-    return SweepKnobs{inv_cap_, env_.fwd_front_min, env_.bwd_front_min, env_.syrk_xcd, narrow_pass_max(), narrow_pass_max_bwd(),
-                      bwd_front_max_cols(), launch_wave_split_cols(), launch_wave_split_rows()};
+    return SweepKnobs{inv_cap_, env_.fwd_front_min, env_.bwd_front_min, env_.syrk_xcd, kNarrowPassMax, kNarrowPassMaxBwd,
+                      kFrontMaxCols, kWaveSplitCols, kWaveSplitRows};
 }
 
 void Device::forward(const SweepLane &ln, int nr, int ldx, int lo, int hi, bool follows_factor) {

@@ -104,7 +104,7 @@ public:
     // the same bits for the same nrhs. 64 throughout. (Round 6, measured and dropped: 17 .. 32 right-hand sides as TWO 16-column
     // passes side by side on the two lanes -- 17 / 24 / 32 columns 3.01 / 3.35 / 3.71 ms against 3.40 / 3.4 / 3.44 as one pass: two
     // latency-bound passes do not overlap on this runtime (twice the launches through one command processor), the second lane only
-    // pays from 65 columns on. What such passes get instead: the narrow level kernels on two right-hand-side tiles, narrow_pass_max().)
+    // pays from 65 columns on. What such passes get instead: the narrow level kernels on two right-hand-side tiles, kNarrowPassMax.)
     static int pass_width(long long) { return 64; }
     double *cb_arena() { return d_cb_; }
     double *factor_panels() { return d_L_; }

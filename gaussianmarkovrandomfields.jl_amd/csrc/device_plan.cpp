@@ -9,7 +9,7 @@
 
 namespace gmrfx {
 
-// one 32-byte geometry record per position of a level list (kernels.h, front_view)
+// one 32-byte geometry record per position of a level list (kernel_common.h, front_view)
 static std::vector<FrontView> front_views(const Symbolic &S, const std::vector<i32> &lst) {
     std::vector<FrontView> v(lst.size());
     for (size_t k = 0; k < lst.size(); k++) {
@@ -103,7 +103,7 @@ FwdLevelPlan plan_forward_level(const LevelInfo &L, int nr, const SweepKnobs &k)
     p.wave_split_k = L.max_cols > k.wave_split_cols;
     // levels with many tiles: record-driven, per-XCD runs; the handful-of-fronts levels keep the 16-row latency variant
     if (p.nf > 0 && L.max_cols > p.cmin)
-        p.update = k.tile_records && (long long)((L.max_trail + 31) / 32) * p.nf > 128 ? FwdLevelPlan::kRecords : FwdLevelPlan::kGrid;
+        p.update = k.tile_records && (long long)cdiv(L.max_trail, 32) * p.nf > kFwdUpdate16MaxTiles ? FwdLevelPlan::kRecords : FwdLevelPlan::kGrid;
     return p;
 }
 
@@ -115,6 +115,66 @@ BwdLevelPlan plan_backward_level(const LevelInfo &L, int nr, const SweepKnobs &k
     p.wave_split_k = L.max_trail > k.wave_split_rows;
     p.gemm = L.max_trail > p.mmin;
     return p;
+}
+
+// ---- launch choices (device_plan.h) ---------------------------------------------------------------------------------------------------
+Launch choose_assemble_hbm(int nfronts, int max_cols) {
+    if (nfronts <= 0) return {};
+    if ((long long)cdiv(max_cols, ASM_CW) * nfronts <= kAsmHbmWgMaxGroups) return {kAssembleHbmWg, odd(max_cols), (unsigned)nfronts, 1, 256};
+    return {kAssembleHbmWave, odd(cdiv(max_cols, ASM_CW)), (unsigned)nfronts, 1, 256};
+}
+Launch choose_assemble(int nfronts, int max_cols, int max_rows) {
+    if (nfronts <= 0) return {};
+    const int ldmax = asm_ldmax(max_rows);
+    const size_t col = (size_t)ldmax * sizeof(double);
+    if (ldmax <= kAsmLdsWaveMaxRows) return {kAssembleLdsWave, odd(cdiv(max_cols, ASM_CW)), (unsigned)nfronts, 1, 256, 4 * col};
+    if (ldmax <= kAsmLdsWgMaxRows) return {kAssembleLdsWg, odd(max_cols), (unsigned)nfronts, 1, 256, col, col > 65536};
+    return choose_assemble_hbm(nfronts, max_cols);
+}
+Launch choose_trsm(int nactive, int max_rows_below) {
+    if (nactive <= 0 || max_rows_below <= 0) return {};
+    const bool split = (long long)cdiv(max_rows_below, 64) * nactive <= kTrsmSplitMaxTiles;
+    return {split ? kTrsmSplit : kTrsmWhole, odd(cdiv(max_rows_below, split ? 16 : 128)), (unsigned)nactive, 1, 256};
+}
+Launch choose_gemm_nt(int nactive, int K, int maxM, int maxN) {
+    if (nactive <= 0 || maxM <= 0 || maxN <= 0) return {};
+    if (K % kGemmBigKStep == 0 && K >= kGemmBigMinK && maxM >= kGemmBigMinM && maxN >= kGemmBigMinN)
+        return {kGemmNtBig, odd(cdiv(maxM, 128)), odd(cdiv(maxN, 128)), (unsigned)nactive, 512};
+    if ((long long)cdiv(maxM, 64) * cdiv(maxN, 64) * nactive <= kGemmSmallTileMax)
+        return {kGemmNt32, odd(cdiv(maxM, 32)), odd(cdiv(maxN, 32)), (unsigned)nactive, 256};
+    return {kGemmNt64, odd(cdiv(maxM, 64)), odd(cdiv(maxN, 64)), (unsigned)nactive, 256};
+}
+Launch choose_fwd_update(int nfronts, int max_trail) {
+    if (nfronts <= 0 || max_trail <= 0) return {};
+    if ((long long)cdiv(max_trail, 32) * nfronts <= kFwdUpdate16MaxTiles) return {kFwdUpdate16, odd(cdiv(max_trail, 16)), (unsigned)nfronts, 1, 256};
+    return {kFwdUpdate32, odd(cdiv(max_trail, 32)), (unsigned)nfronts, 1, 256};
+}
+Launch choose_fwd_update_wave(int per_xcd, int nr, bool split_k) {
+    if (per_xcd <= 0) return {};
+    return {split_k ? kWaveSplitK : kWaveWhole, 8 * (unsigned)per_xcd, (unsigned)cdiv(nr, 16), 1, split_k ? 256u : 64u};
+}
+Launch choose_fwd_own_update(int nfronts, int max_cols, int blk, int cap) {
+    const int rows_below = max_cols - (blk + 1) * cap;      // own rows below the block in the widest front
+    if (nfronts <= 0 || rows_below <= 0) return {};
+    return {kFwdOwnUpdate, odd(cdiv(rows_below, 32)), (unsigned)nfronts, 1, 256};
+}
+Launch choose_bwd_gemm(int nfronts, int max_cols, int blk, int cap) {
+    if (nfronts <= 0 || max_cols <= 0) return {};
+    if (blk >= 0) max_cols = std::min(max_cols - blk * cap, cap);
+    if (max_cols <= 0) return {};
+    const long long wg32 = (long long)cdiv(max_cols, 32) * nfronts;
+    if (wg32 > kBwdGemm8Max) return {kBwdGemm32x4, odd(cdiv(max_cols, 32)), (unsigned)nfronts, 1, 256};
+    if (wg32 >= kBwdGemmWide8Min) return {kBwdGemm32x8, odd(cdiv(max_cols, 32)), (unsigned)nfronts, 1, 512};
+    return {kBwdGemm16x8, odd(cdiv(max_cols, 16)), (unsigned)nfronts, 1, 512};
+}
+Launch choose_bwd_wave(int nfronts, int max_cols, int nr, bool split_k) {
+    if (nfronts <= 0 || max_cols <= 0) return {};
+    return {split_k ? kWaveSplitK : kWaveWhole, odd(cdiv(max_cols, 16)), (unsigned)nfronts, (unsigned)cdiv(nr, 16), split_k ? 256u : 64u};
+}
+Launch choose_permute(int n, int nr) {
+    if (n <= 0) return {};
+    if (nr <= kPermuteNarrowMaxNr) return {kPermuteNarrow, (unsigned)cdiv(n, 256), 1, 1, 256};
+    return {kPermuteTiles, (unsigned)cdiv(n, 64), 1, 1, 256};
 }
 
 // Dense-inverse stage B: T-buffer offsets of the fronts wider than B, a list sorted by decreasing width; *total = doubles.
@@ -366,7 +426,7 @@ DevicePlan build_device_plan(const Symbolic &S, const PlanOptions &o) {
 
     // Contribution-block tiles of every level in hand-out order: front by front (the level list's order), inside a
     // front by 8 x 8-tile squares of the lower triangle (row-major inside a square), then cut into 8 runs of equal
-    // estimated cost -- one per XCD. One self-contained record per tile (kernels.hip, k_syrk_cb_rec).
+    // estimated cost -- one per XCD. One self-contained record per tile (factor_kernels.hip, k_syrk_cb_rec).
     std::vector<double> cost;
     constexpr int SQ = 8;
     for (i32 l = 0; l < S.nlevels; l++) {

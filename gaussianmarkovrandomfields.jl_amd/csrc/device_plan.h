@@ -152,23 +152,23 @@ EnvKnobs read_env_knobs();
 // ---- the sweeps' per-level decisions: which fronts of a level's width-sorted list of big fronts go to which launch -----------------
 // Plain functions of values (no device, no HIP): Device::forward / backward read the plan and launch; tools/sanitize_host.cpp
 // walks every level of its plans through them.
-// Passes of at most narrow_pass_max right-hand sides, forward: the fronts up to kFwdWaveCols columns wide go one WAVE per 32-row tile
+// Passes of at most kNarrowPassMax right-hand sides, forward: the fronts up to kFwdWaveCols columns wide go one WAVE per 32-row tile
 // (no LDS, no barrier: k_fwd_update_wave), chosen per FRONT so that a front's sums do not depend on the list it comes in
 constexpr int kFwdWaveCols = 1024;      // (measured at cfg 2, 1 RHS, forward ms, with four waves sharing the K range of a front wider than 128
                                         //  columns: 256: 0.933, 512: 0.841, 1024: 0.832, 2048: 0.836)
-// Passes of at most narrow_pass_max_bwd right-hand sides, backward: t = y - L21' x one WAVE per 16 own columns for the fronts with at
+// Passes of at most kNarrowPassMaxBwd right-hand sides, backward: t = y - L21' x one WAVE per 16 own columns for the fronts with at
 // most kBwdWaveRows trailing rows (k_bwd_wave), the split-K kernels for the others, x = L11^-T t as everywhere
 constexpr int kBwdWaveRows = 4096;      // (every front of a 2-D problem; measured at cfg 2, 1 RHS, backward ms, with four waves sharing the K range of a front of more than 256
                                         //  rows: 768: 0.848, 1100: 0.824, 1600: 0.814, every front: 0.792; one wave per tile only: 768 was the optimum, 1.177)
 
-// What the decisions read besides the level: the handle's knobs and the limits of the launch side (kernels.h; Device::sweep_knobs)
+// What the decisions read besides the level: the handle's knobs and the limits of the launch side (the constants below; Device::sweep_knobs)
 struct SweepKnobs {
     int inv_cap;                     // Device::inv_cap_: wider fronts substitute block by block
     int fwd_front_min, bwd_front_min;   // EnvKnobs
     bool tile_records;               // EnvKnobs::syrk_xcd: the forward update's tile records exist
-    int narrow_pass_max, narrow_pass_max_bwd;   // widest pass of the narrow level kernels
-    int front_max_cols;              // bwd_front_max_cols(): widest front of the one-workgroup front kernels
-    int wave_split_cols, wave_split_rows;       // launch_wave_split_cols() / _rows()
+    int narrow_pass_max, narrow_pass_max_bwd;   // kNarrowPassMax / kNarrowPassMaxBwd: widest pass of the narrow level kernels
+    int front_max_cols;              // kFrontMaxCols: widest front of the one-workgroup front kernels
+    int wave_split_cols, wave_split_rows;       // kWaveSplitCols / kWaveSplitRows
 };
 
 // How a level's big fronts are split between the one-workgroup front kernel and the blocked substitution. The list is sorted by
@@ -198,6 +198,82 @@ struct BwdLevelPlan : LevelBlocks {
 };
 FwdLevelPlan plan_forward_level(const LevelInfo &L, int nr, const SweepKnobs &k);
 BwdLevelPlan plan_backward_level(const LevelInfo &L, int nr, const SweepKnobs &k);
+
+// ---- the launch wrappers' choices: which variant of a kernel a launch gets, and its geometry -----------------------------------------
+// Plain functions of values as well: a wrapper (kernels.h) returns on kNoLaunch, switches on the variant and launches with this grid,
+// block and dynamic LDS; tools/sanitize_host.cpp pins every threshold and walks every level of its plans through them.
+constexpr int ASM_CW = 4;    // front columns owned by one assembly workgroup
+constexpr int FWD_RB = 32;    // front rows owned by one forward-assembly workgroup
+// Columns through LDS, written once: a wave per column while four columns of a workgroup fit in 40 KB, a workgroup per column
+// for the tall columns of the top of the tree (up to 128 KB). Measured at cfg 2 (factorisation): HBM assembly above 1280 rows
+// 9.33 ms; wave-per-column up to 2048 rows 9.10; + workgroup-per-column above: 9.03; wave-per-column up to 1280, workgroup-per-column
+// above: 8.96.
+constexpr int kAsmLdsWaveMaxRows = 1280, kAsmLdsWgMaxRows = 16384;
+constexpr int kAsmHbmWgMaxGroups = 2200;     // HBM form: one WORKGROUP per column up to this many four-column groups (levels with a few tall fronts)
+constexpr int kTrsmSplitMaxTiles = 128;      // k_trsm<MODE, 1> (16 rows per workgroup instead of 128) up to this many 64-row tiles
+// k_gemm_nt_big is only used where a launch has thousands of such tiles: K a multiple of 16, at least 4096 rows below the block
+constexpr int kGemmBigKStep = 16, kGemmBigMinK = 256, kGemmBigMinM = 4096, kGemmBigMinN = 512;
+// Levels with a handful of fronts are latency bound: 32x32 workgroup tiles there (four times
+// the workgroups, a quarter of the MFMA chain per wave).
+constexpr int kGemmSmallTileMax = 256;       // ... up to this many 64x64 tiles
+constexpr int kFwdUpdate16MaxTiles = 128;    // k_fwd_update_longk<1> (16-row tiles) up to this many 32-row tiles: the handful-of-fronts levels
+// the 8-wave variants up to ~3 workgroups per CU (measured: 512-1024 beats 128 and 2048). Every workgroup of a front gathers ALL
+// of the front's trailing rows of x: 32 own columns per workgroup instead of 16 halves those re-reads (levels 10-13 of cfg 2
+// moved 2.5-3 x their algorithmic bytes) on levels that still fill the chip with them (measured at cfg 2, 32 / 16 columns per
+// workgroup: level 10 (768 workgroups of 32) 72 / 83 us, 11 (576) 79 / 88; 12 (352) 79 / 73, 13: 85 / 75, 14: 66 / 55, 15: 62 / 47)
+constexpr int kBwdGemmWide8Min = 384, kBwdGemm8Max = 768;      // workgroups of 32 own columns: <1, 8> below, <2, 8> inside, <2, 4> above
+constexpr int kPermuteNarrowMaxNr = 8;       // k_permute_narrow: passes of at most 8 right-hand sides
+// Passes of up to 32 right-hand sides take the narrow FORWARD kernels (k_fwd_update_wave, k_xmul_narrow) on two right-hand-side tiles
+// (round 6; measured at cfg 2, tools/nrhs_sweep.py: 17 / 24 / 32 columns 3.22 / 3.29 / 3.35 -> 2.98 / 3.05 / 3.09 ms; the same on three
+// or four tiles loses: 48 columns 3.54 -> 3.85 ms). The BACKWARD kernels of such passes stay the 64-column ones -- k_bwd_front /
+// k_bwd_gemm_longk beat k_bwd_wave on two tiles (backward 1.39 vs 1.42-1.47 ms) --, and so do the bottom tasks (chunk form on two column
+// slices: 2.98 ms at 17 columns against 3.37 with one wave per task and tile).
+// widest pass (right-hand sides) that takes the narrow level kernels -- one wave / one right-hand-side tile per workgroup, grid z (y
+// for k_fwd_update_wave) = ceil(nr / 16) tiles: k_fwd_update_wave, k_bwd_wave, k_xmul_narrow
+constexpr int kNarrowPassMax = 32, kNarrowPassMaxBwd = 16;
+// k_fwd_update_wave<4> / k_bwd_wave<4>: four waves share the K range of a front wider than this / with more trailing rows than this
+constexpr int kWaveSplitCols = 128, kWaveSplitRows = 256;
+constexpr int kFrontMaxCols = 128;           // columns of a front the one-workgroup front kernels take (sweep_front.hip)
+
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// Workgroups are handed to the 8 XCDs round-robin by linear id (x fastest). Rectangular grids whose
+// x extent (or x*y extent) is a multiple of 8 put tile (bi, bj) of EVERY front on the same XCD --
+// with triangular / ragged tile sets that leaves some XCDs idle and others with twice the work
+// (measured: the 4x4-tile level of k_syrk_cb ran 1.9x longer than the 3x3 and 6x6 levels around
+// it). Odd extents make consecutive fronts rotate through all XCDs; the extra workgroups exit at
+// once through the kernels' own range checks.
+inline unsigned odd(int v) { return (unsigned)(v | 1); }
+inline int asm_ldmax(int max_rows) { return (max_rows + 1) & ~1; }       // Symbolic rounds ld up to even
+
+enum KernelVariant {
+    kNoLaunch,                                                            // an empty launch: the wrapper returns
+    kAssembleLdsWave, kAssembleLdsWg, kAssembleHbmWg, kAssembleHbmWave,   // k_assemble_lds<0> / <1>, k_assemble<1> / <0>
+    kTrsmSplit, kTrsmWhole,                                               // k_trsm<MODE, 1> / <MODE, 0>
+    kGemmNtBig, kGemmNt32, kGemmNt64,                                     // k_gemm_nt_big, k_gemm_nt<1> / <2>
+    kFwdUpdate16, kFwdUpdate32,                                           // k_fwd_update_longk<1> / <2>
+    kBwdGemm16x8, kBwdGemm32x8, kBwdGemm32x4,                             // k_bwd_gemm_longk<1, 8> / <2, 8> / <2, 4>
+    kPermuteNarrow, kPermuteTiles,                                        // k_permute_narrow, k_permute
+    kWaveWhole, kWaveSplitK,                                              // k_fwd_update_wave / k_bwd_wave <1> / <4>
+    kFwdOwnUpdate,
+    kVariantCount
+};
+struct Launch {
+    KernelVariant variant = kNoLaunch;
+    unsigned gx = 0, gy = 1, gz = 1, block = 0;
+    size_t lds = 0;             // dynamic LDS bytes
+    bool raised_lds = false;    // lds is more than the 64 KB a kernel may ask for as it is: the wrapper raises the kernel's limit first
+};
+// (launch_assemble falls back to the HBM choice when the limit cannot be raised)
+Launch choose_assemble(int nfronts, int max_cols, int max_rows);
+Launch choose_assemble_hbm(int nfronts, int max_cols);
+Launch choose_trsm(int nactive, int max_rows_below);
+Launch choose_gemm_nt(int nactive, int K, int maxM, int maxN);
+Launch choose_fwd_update(int nfronts, int max_trail);
+Launch choose_fwd_update_wave(int per_xcd, int nr, bool split_k);
+Launch choose_fwd_own_update(int nfronts, int max_cols, int blk, int cap);    // own rows below block blk of `cap` columns
+Launch choose_bwd_gemm(int nfronts, int max_cols, int blk, int cap);          // blk >= 0: the own columns of that block only
+Launch choose_bwd_wave(int nfronts, int max_cols, int nr, bool split_k);
+Launch choose_permute(int n, int nr);
 
 // What changes the tables besides the analysis.
 struct PlanOptions {

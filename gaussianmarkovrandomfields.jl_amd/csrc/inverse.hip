@@ -29,7 +29,7 @@
 
 #include <algorithm>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_inv_stage(DevSym S, const int *__restri
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
-    // operand rows in pairs (kernels.h, wave_gemm_32x32_pm / _rr / _kr): tile a of the rows is i0 + 2 lm + a on the operand
+    // operand rows in pairs (kernel_common.h, wave_gemm_32x32_pm / _rr / _kr): tile a of the rows is i0 + 2 lm + a on the operand
     // side and i0 + 2 (lk + 4 rr) + a in the accumulators, tile b of the columns is j0 + 2 lm + b
     const int nlast = (nC - 1) & ~1;
     if (phase == 1) {
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(256) void k_inv_stage(DevSym S, const int *__restri
 //   trans = 1: Y[k] = sum_{q >= k} X[q][k] b[q]        (backward)
 // b = rows first..first+c of Xin (row-major, ldx), result goes to the same rows of Xout (it cannot
 // be written in place: other workgroups still need b). One wave = 16 rows x up to 64 RHS.
-template <int NW>   // waves per workgroup splitting K; 8 for launches with about one workgroup per CU (kernels.h)
+template <int NW>   // waves per workgroup splitting K; 8 for launches with about one workgroup per CU (kernel_common.h)
 __global__ __launch_bounds__(64 * NW) void k_xmul(DevSym S, const int *__restrict__ list, int trans,
                                               const double *__restrict__ L, const double *__restrict__ Xin,
                                               double *__restrict__ Xout, int nr, int ldx, int blk, int cap) {
@@ -251,7 +251,6 @@ __global__ __launch_bounds__(256) void k_copy_own(DevSym S, const int *__restric
     }
 }
 
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 void launch_inv_stage(hipStream_t st, const DevSym &S, const int *list, int nactive, int B, int max_c, int phase,
                       double *L, double *T, const long long *toff) {
@@ -316,7 +315,7 @@ void launch_xmul(hipStream_t st, const DevSym &S, const int *list, int nfronts, 
     if (nfronts <= 0 || max_c <= 0) return;
     max_c = std::min(max_c - blk * cap, cap);      // width of block `blk` of the widest front
     if (max_c <= 0) return;
-    if (nr <= (trans ? narrow_pass_max_bwd() : narrow_pass_max())) {          // one right-hand-side tile per workgroup, ceil(nr / 16) tiles in grid z
+    if (nr <= (trans ? kNarrowPassMaxBwd : kNarrowPassMax)) {          // one right-hand-side tile per workgroup, ceil(nr / 16) tiles in grid z
         const unsigned jt = (unsigned)cdiv(nr, 16);
         if ((long long)cdiv(max_c, 16) * nfronts <= 256)
             hipLaunchKernelGGL(k_xmul_narrow<8>, dim3((unsigned)(cdiv(max_c, 16) | 1), nfronts, jt), dim3(512), 0, st, S, list, trans, L, Xin, Xout, nr, ldx, blk, cap);

@@ -25,7 +25,7 @@
 #include <vector>
 
 #include "device.h"
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

@@ -8,7 +8,7 @@
 // here for one dense diagonal block of a supernode.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "kernel_common.h"
 #include "potrf64_blocked.h"
 
 namespace gmrfx {

@@ -26,7 +26,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 namespace pb {

@@ -13,7 +13,7 @@
 // result is reproducible from run to run.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

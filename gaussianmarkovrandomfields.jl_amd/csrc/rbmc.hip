@@ -21,7 +21,7 @@
 
 #include <cmath>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

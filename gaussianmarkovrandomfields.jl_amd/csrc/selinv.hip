@@ -15,7 +15,7 @@
 
 #include <cstdlib>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(64 * WT * WT) void k_sel_dense(DevSym S, const int 
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++) acc[a][b] = (d4){0.0, 0.0, 0.0, 0.0};
-    // Operand rows in PAIRS throughout (kernels.h, wave_gemm_32x32_pm / _rr / _rk): tile a of the "m" index is
+    // Operand rows in PAIRS throughout (kernel_common.h, wave_gemm_32x32_pm / _rr / _rk): tile a of the "m" index is
     // m0 + 2 lm + a on the operand side and m0 + 2 (lk + 4 rr) + a in the accumulators, tile b of the "n" index is
     // n0 + 2 lm + b -- 16-byte loads and stores, half the vector memory instructions. Lanes past the last row re-read
     // the last pair; their results are never stored.
@@ -444,7 +444,6 @@ __global__ __launch_bounds__(512) void k_sel_z21_big(DevSym S, const int *__rest
         }
 }
 
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 void launch_sel_gather(hipStream_t st, const SelRec *recs, const DevSym &S, const int *list, int nfronts, int max_trail,
                        const double *Z, double *ZB) {

@@ -9,14 +9,14 @@
 //   inverse threads 128.. carry the block forward substitution  L X = I  along: rows of the
 //           current panel of X = L11^-1 become final (W), rows below get M -= L[i,p] W.  M / X
 //           live in the strict UPPER triangle of F's c x c block, transposed -- exactly where the
-//           HBM panel stores (L11^-1)' for the solve kernels (see k_potrf in kernels.hip)
+//           HBM panel stores (L11^-1)' for the solve kernels (see k_potrf in potrf64.hip)
 //   update  F[i,k] -= sum_q P[q][i] P[q][k] on 16x16 tiles with v_mfma_f64_16x16x4_f64, tiles
 //           read-modify-written in LDS (leading dimension = 2 mod 32 doubles: conflict-free)
 #include <hip/hip_runtime.h>
 
 #include <climits>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

@@ -38,7 +38,7 @@
 
 #include <cstdlib>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

@@ -28,18 +28,16 @@
 //  range -- those levels are latency-bound per front, not traffic-bound. Removed.)
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 
 typedef gmrfx_d4 d4;
 typedef gmrfx_d2u d2u;
 
-constexpr int BF_MAXC = 128;          // columns of a front this kernel takes
+constexpr int BF_MAXC = kFrontMaxCols;   // columns of a front this kernel takes (device_plan.h: the sweeps' level plans read it)
 constexpr int BF_SS = 80;             // doubles per staged row (64 + 16: see above)
 constexpr int BF_TS = 72;             // doubles per row of t (phase 2 reads consecutive rows: a 64-byte skew is enough)
-
-int bwd_front_max_cols() { return BF_MAXC; }
 
 // NTL: right-hand-side tiles per wave (4, 2, 1: see above); wave w owns column tile w / (4 / NTL), tiles t0 .. t0 + NTL - 1
 template <int NTL> __device__ __forceinline__ void bwd_front_body(double *sh, const DevSym &S, const int s, const double *__restrict__ L,

@@ -29,7 +29,7 @@
 
 #include <cstdlib>
 
-#include "kernels.h"
+#include "kernel_common.h"
 
 namespace gmrfx {
 

@@ -1165,7 +1165,7 @@ def test_one_workgroup_backward_step_beside_blocked_substitution(cap, monkeypatc
 @pytest.mark.parametrize("name", ["matern64_coords", "cfg1_alpha3_65x65", "matern3d_10", "rand400"])
 def test_tile_records_and_plain_grid_give_the_same_bits(name, monkeypatch):
     """The record-driven kernels (contribution-block SYRK and forward update: one self-contained record per tile, handed
-    out in per-XCD runs, csrc/kernels.hip k_syrk_cb_rec / k_fwd_update_rec; the default) against the plain-grid forms
+    out in per-XCD runs, csrc/factor_kernels.hip k_syrk_cb_rec / csrc/sweep_level.hip k_fwd_update_rec; the default) against the plain-grid forms
     they replaced (GMRFX_SYRK_XCD=0): the SAME factor bit for bit (same sums in the same order), the same solve bits,
     and the factor against the oracle entry by entry."""
     Q, kw = next((sp.csc_matrix(q), k) for n, q, k in CASES if n == name)
@@ -1467,7 +1467,7 @@ def test_dense_fronts_of_every_width_through_the_diagonal_block_kernel(n, monkey
 
 
 def test_one_dense_front_wide_enough_for_the_staged_panel_update():
-    """Round 5 (csrc/kernels.hip, k_gemm_nt_big): fronts with at least 4096 rows below a 256-column outer block take the K = 256
+    """Round 5 (csrc/factor_kernels.hip, k_gemm_nt_big): fronts with at least 4096 rows below a 256-column outer block take the K = 256
     panel update on 128 x 128 LDS-staged tiles (the top fronts of 3-D problems: cfg 4). A dense SPD matrix of 4700 unknowns is ONE
     front of that kind (its first outer blocks qualify, the rest fall back to the direct-operand tiles): solve and log-determinant
     against LAPACK."""
@@ -1487,7 +1487,7 @@ def test_one_dense_front_wide_enough_for_the_staged_panel_update():
 
 
 def test_two_huge_fronts_take_the_two_pass_contribution_product():
-    """Round 5 (csrc/kernels.hip, k_syrk_big): on a level whose fronts have >= 1024 columns and >= 4096 rows below them the
+    """Round 5 (csrc/factor_kernels.hip, k_syrk_big): on a level whose fronts have >= 1024 columns and >= 4096 rows below them the
     contribution block is built in two passes -- the children's extend-add alone (k_syrk_cb_rec, noprod), then CB -= L21 L21' on
     128 x 128 LDS-staged tiles. Two dense 1024-column blocks that only meet through a dense 4100-column block (4100: a ragged
     last tile) are two such fronts under the natural ordering; solve and log-determinant against LAPACK."""

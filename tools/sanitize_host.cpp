@@ -146,12 +146,135 @@ static void check_runs(const std::vector<gmrfx::LevelInfo> &LV, bool fwd, size_t
     EXPECT(any || end == 0);
 }
 
+// The launch choices (device_plan.h, choose_*): what every launch must satisfy, and how many launches reached each variant.
+static long long variant_hits[gmrfx::kVariantCount];
+static const char *const variant_names[gmrfx::kVariantCount] = {
+    "no launch", "k_assemble_lds<0>", "k_assemble_lds<1>", "k_assemble<1>", "k_assemble<0>", "k_trsm<.,1>", "k_trsm<.,0>", "k_gemm_nt_big",
+    "k_gemm_nt<1>", "k_gemm_nt<2>", "k_fwd_update_longk<1>", "k_fwd_update_longk<2>", "k_bwd_gemm_longk<1,8>", "k_bwd_gemm_longk<2,8>",
+    "k_bwd_gemm_longk<2,4>", "k_permute_narrow", "k_permute", "wave kernel <1>", "wave kernel <4>", "k_fwd_own_update"};
+// rows / columns a workgroup of the variant owns along grid x (gemm_nt: and y)
+static int variant_tile(gmrfx::KernelVariant v) {
+    using namespace gmrfx;
+    switch (v) {
+    case kAssembleLdsWave: case kAssembleHbmWave: return ASM_CW;
+    case kAssembleLdsWg: case kAssembleHbmWg: case kWaveSplitK: case kWaveWhole: return 1;     // (wave kernels: per call site)
+    case kTrsmSplit: case kFwdUpdate16: case kBwdGemm16x8: return 16;
+    case kGemmNt32: case kFwdUpdate32: case kBwdGemm32x8: case kBwdGemm32x4: case kFwdOwnUpdate: return 32;
+    case kGemmNt64: case kPermuteTiles: return 64;
+    case kTrsmWhole: case kGemmNtBig: return 128;
+    case kPermuteNarrow: return 256;
+    default: return 0;
+    }
+}
+// empty: the launch has nothing to do (no variant may be chosen, and one must be otherwise); ox / oy: the odd() rule governs grid x / y;
+// ex / ey / ez: the extents the grid has to cover with tx / ty / tz rows, columns or right-hand sides per workgroup (0: the variant's own tile)
+static void check_launch(const gmrfx::Launch &c, bool empty, bool ox, bool oy, long long ex, int tx = 0, long long ey = 1, int ty = 1,
+                         long long ez = 1, int tz = 1) {
+    variant_hits[c.variant]++;
+    EXPECT((c.variant == gmrfx::kNoLaunch) == empty);
+    if (c.variant == gmrfx::kNoLaunch) return;
+    if (!tx) tx = variant_tile(c.variant);
+    if (!ty) ty = variant_tile(c.variant);
+    EXPECT(c.gx >= 1 && c.gy >= 1 && c.gz >= 1 && c.gy <= 65535 && c.gz <= 65535 && (c.block == 64 || c.block == 256 || c.block == 512));
+    EXPECT((long long)c.gx * tx >= ex && (long long)c.gy * ty >= ey && (long long)c.gz * tz >= ez);
+    EXPECT((!ox || c.gx % 2 == 1) && (!oy || c.gy % 2 == 1));
+    EXPECT(c.lds <= (c.raised_lds ? 131072u : 65536u) && (!c.raised_lds || c.lds > 65536u));
+}
+
+// Both sides of every threshold of the choice functions, against the variant and geometry the wrappers used to pick inline.
+static void check_launch_edges() {
+    using namespace gmrfx;
+    auto is = [](const Launch &c, KernelVariant v, unsigned gx, unsigned gy, unsigned gz, unsigned block, size_t lds = 0, bool raised = false) {
+        return c.variant == v && c.gx == gx && c.gy == gy && c.gz == gz && c.block == block && c.lds == lds && c.raised_lds == raised;
+    };
+    // gemm_nt: the 128 x 128 tile needs K % 16 == 0, K >= 256, M >= 4096, N >= 512; then 32 x 32 tiles up to 256 tiles of 64 x 64
+    EXPECT(is(choose_gemm_nt(3, 256, 4096, 512), kGemmNtBig, 33, 5, 3, 512));
+    EXPECT(choose_gemm_nt(3, 240, 4096, 512).variant == kGemmNt64 && choose_gemm_nt(3, 264, 4096, 512).variant == kGemmNt64);
+    EXPECT(choose_gemm_nt(3, 256, 4095, 512).variant == kGemmNt64 && choose_gemm_nt(3, 256, 4096, 511).variant == kGemmNt64);
+    EXPECT(is(choose_gemm_nt(1, 64, 1024, 1024), kGemmNt32, 33, 33, 1, 256));           // 16 x 16 tiles = 256
+    EXPECT(is(choose_gemm_nt(1, 64, 64 * 257, 64), kGemmNt64, 257, 1, 1, 256));         // 257
+    EXPECT(is(choose_gemm_nt(4, 64, 512, 512), kGemmNt32, 17, 17, 4, 256) && choose_gemm_nt(4, 64, 513, 512).variant == kGemmNt64);
+    EXPECT(choose_gemm_nt(0, 64, 64, 64).variant == kNoLaunch && choose_gemm_nt(1, 64, 0, 64).variant == kNoLaunch &&
+           choose_gemm_nt(1, 64, 64, 0).variant == kNoLaunch);
+    // trsm: 64-row tiles x fronts
+    EXPECT(is(choose_trsm(1, 64 * 128), kTrsmSplit, 513, 1, 1, 256) && is(choose_trsm(1, 64 * 128 + 1), kTrsmWhole, 65, 1, 1, 256));
+    EXPECT(is(choose_trsm(64, 128), kTrsmSplit, 9, 64, 1, 256) && is(choose_trsm(64, 129), kTrsmWhole, 3, 64, 1, 256));
+    EXPECT(choose_trsm(0, 5).variant == kNoLaunch && choose_trsm(5, 0).variant == kNoLaunch);
+    // fwd_update: 32-row tiles x fronts
+    EXPECT(is(choose_fwd_update(1, 32 * 128), kFwdUpdate16, 257, 1, 1, 256) && is(choose_fwd_update(1, 32 * 128 + 1), kFwdUpdate32, 129, 1, 1, 256));
+    EXPECT(is(choose_fwd_update(128, 32), kFwdUpdate16, 3, 128, 1, 256) && is(choose_fwd_update(129, 32), kFwdUpdate32, 1, 129, 1, 256));
+    EXPECT(choose_fwd_update(0, 5).variant == kNoLaunch && choose_fwd_update(5, 0).variant == kNoLaunch);
+    // bwd_gemm: workgroups of 32 own columns
+    EXPECT(is(choose_bwd_gemm(1, 32 * 383, -1, 1 << 30), kBwdGemm16x8, 767, 1, 1, 512));
+    EXPECT(is(choose_bwd_gemm(1, 32 * 384, -1, 1 << 30), kBwdGemm32x8, 385, 1, 1, 512));
+    EXPECT(is(choose_bwd_gemm(768, 32, -1, 1 << 30), kBwdGemm32x8, 1, 768, 1, 512));
+    EXPECT(is(choose_bwd_gemm(769, 32, -1, 1 << 30), kBwdGemm32x4, 1, 769, 1, 256));
+    // ... of the block alone: block 1 of 64 columns is whole, block 2 of a 129-column front has one column, of a 128-column front none
+    EXPECT(is(choose_bwd_gemm(4, 129, 1, 64), kBwdGemm16x8, 5, 4, 1, 512) && is(choose_bwd_gemm(4, 129, 2, 64), kBwdGemm16x8, 1, 4, 1, 512));
+    EXPECT(choose_bwd_gemm(4, 128, 2, 64).variant == kNoLaunch && choose_bwd_gemm(4, 128, 3, 64).variant == kNoLaunch);
+    EXPECT(choose_bwd_gemm(0, 128, -1, 1 << 30).variant == kNoLaunch && choose_bwd_gemm(4, 0, -1, 1 << 30).variant == kNoLaunch);
+    // fwd_own_update: the own rows below block blk
+    EXPECT(is(choose_fwd_own_update(4, 129, 1, 64), kFwdOwnUpdate, 1, 4, 1, 256) && choose_fwd_own_update(4, 128, 1, 64).variant == kNoLaunch);
+    EXPECT(is(choose_fwd_own_update(4, 4096, 0, 2048), kFwdOwnUpdate, 65, 4, 1, 256) && choose_fwd_own_update(0, 4096, 0, 2048).variant == kNoLaunch);
+    // assemble: by the rows of the tallest column, rounded up to even first
+    EXPECT(is(choose_assemble(7, 100, 1280), kAssembleLdsWave, 25, 7, 1, 256, 4 * 1280 * 8));
+    EXPECT(is(choose_assemble(7, 100, 1279), kAssembleLdsWave, 25, 7, 1, 256, 4 * 1280 * 8));
+    EXPECT(is(choose_assemble(7, 100, 1281), kAssembleLdsWg, 101, 7, 1, 256, 1282 * 8) && is(choose_assemble(7, 100, 1282), kAssembleLdsWg, 101, 7, 1, 256, 1282 * 8));
+    EXPECT(is(choose_assemble(7, 100, 8192), kAssembleLdsWg, 101, 7, 1, 256, 65536));
+    EXPECT(is(choose_assemble(7, 100, 8193), kAssembleLdsWg, 101, 7, 1, 256, 8194 * 8, true) && is(choose_assemble(7, 100, 8194), kAssembleLdsWg, 101, 7, 1, 256, 8194 * 8, true));
+    EXPECT(is(choose_assemble(7, 100, 16384), kAssembleLdsWg, 101, 7, 1, 256, 131072, true));
+    EXPECT(is(choose_assemble(7, 100, 16385), kAssembleHbmWg, 101, 7, 1, 256) && is(choose_assemble(7, 100, 16386), kAssembleHbmWg, 101, 7, 1, 256));
+    EXPECT(is(choose_assemble_hbm(1, 8800), kAssembleHbmWg, 8801, 1, 1, 256) && is(choose_assemble_hbm(1, 8801), kAssembleHbmWave, 2201, 1, 1, 256));
+    EXPECT(is(choose_assemble_hbm(2200, 4), kAssembleHbmWg, 5, 2200, 1, 256) && is(choose_assemble_hbm(2201, 4), kAssembleHbmWave, 1, 2201, 1, 256));
+    EXPECT(choose_assemble(0, 100, 100).variant == kNoLaunch && choose_assemble_hbm(0, 100).variant == kNoLaunch);
+    // permute and the wave kernels
+    EXPECT(is(choose_permute(1000, 8), kPermuteNarrow, 4, 1, 1, 256) && is(choose_permute(1000, 9), kPermuteTiles, 16, 1, 1, 256));
+    EXPECT(is(choose_fwd_update_wave(5, 17, false), kWaveWhole, 40, 2, 1, 64) && is(choose_fwd_update_wave(5, 16, true), kWaveSplitK, 40, 1, 1, 256));
+    EXPECT(is(choose_bwd_wave(3, 100, 16, false), kWaveWhole, 7, 3, 1, 64) && is(choose_bwd_wave(3, 100, 1, true), kWaveSplitK, 7, 3, 1, 256));
+    EXPECT(choose_fwd_update_wave(0, 1, true).variant == kNoLaunch && choose_bwd_wave(0, 100, 1, true).variant == kNoLaunch &&
+           choose_bwd_wave(3, 0, 1, true).variant == kNoLaunch);
+    EXPECT(cdiv(0, 4) == 0 && cdiv(1, 4) == 1 && cdiv(4, 4) == 1 && cdiv(5, 4) == 2 && odd(0) == 1 && odd(7) == 7 && odd(8) == 9);
+}
+
+// The launches of a factorisation level as Device::factor_levels / panel_block issue them (the panel chain whole, and as the even / odd
+// halves of two chains on levels that run two), through the choice functions.
+static void check_factor_launches(const std::vector<gmrfx::LevelInfo> &LV) {
+    using namespace gmrfx;
+    constexpr int OBK = 4, narrow_min = 256;     // (device.cpp: 64-column blocks per outer block; fronts for the narrow-block trsm)
+    for (const LevelInfo &L : LV) {
+        const int nf = L.nbig();
+        check_launch(choose_assemble(nf, L.max_cols, L.max_rows), nf <= 0, true, false, L.max_cols);
+        check_launch(choose_assemble_hbm(nf, L.max_cols), nf <= 0, true, false, L.max_cols);        // (the fallback)
+        const bool two = nf >= 2 && L.nblk() >= 4;
+        for (int half = two ? 0 : -1; half < (two ? 2 : 0); half++) {
+            auto of = [&](int a) { return half < 0 ? a : half == 0 ? (a + 1) / 2 : a / 2; };
+            for (int b = 0; b < L.nblk(); b++) {
+                const int n = of(L.wider_than(b * NB)), kb = b * NB, below = L.max_rows - kb - 1;
+                if (n <= 0) continue;
+                const int cut32 = b == 0 ? of(L.wider[1]) : n;
+                const int ntrsm = b == 0 && n - cut32 >= narrow_min ? cut32 : n;
+                check_launch(choose_trsm(ntrsm, below), ntrsm <= 0 || below <= 0, true, false, below);
+                const int J1 = (b / OBK + 1) * OBK, nnext = of(L.wider_than((b + 1) * NB)), nouter = of(L.wider_than(J1 * NB));
+                if (b + 1 < J1 && nnext > 0) {
+                    const int M = L.max_rows - kb - NB, N = std::min(J1 * NB, L.max_cols) - kb - NB;
+                    check_launch(choose_gemm_nt(nnext, NB, M, N), M <= 0 || N <= 0, true, true, M, 0, N, 0);
+                }
+                if (b + 1 == J1 && nouter > 0) {
+                    const int M = L.max_rows - J1 * NB, N = L.max_cols - J1 * NB;
+                    check_launch(choose_gemm_nt(nouter, OBK * NB, M, N), M <= 0 || N <= 0, true, true, M, 0, N, 0);
+                }
+            }
+        }
+    }
+}
+
 // The level schedule the drivers read (device_plan.h): LevelInfo's counts against a brute-force walk over the level's list of big
 // fronts, and the sweeps' step plans (plan_forward_level / plan_backward_level) for every pass width, inverse cap, front-kernel
 // minimum and both values of the records flag: every big front is finished exactly once -- by the one-workgroup front kernel or
-// by the blocks of the substitution, never both (the list arithmetic that once ran the blocked loop over the finished tail).
+// by the blocks of the substitution, never both (the list arithmetic that once ran the blocked loop over the finished tail). sweep: these are the levels the sweeps walk --
+// the launches Device::forward / backward issue from a plan go through the choice functions.
 static int levels_with_wide_head_and_tail = 0;
-static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx::LevelInfo> &LV, const std::vector<gmrfx::i32> &llist) {
+static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx::LevelInfo> &LV, const std::vector<gmrfx::i32> &llist, bool sweep) {
     using namespace gmrfx;
     const EnvKnobs env;
     for (const LevelInfo &L : LV) {
@@ -178,7 +301,8 @@ static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx:
                 for (int fm = 0; fm < 3; fm++)
                     for (bool rec : {true, false}) {
                         // (the limits as the launch side has them today; the properties hold for any)
-                        const SweepKnobs kn{cap, fm < 2 ? fm : env.fwd_front_min, fm < 2 ? fm : env.bwd_front_min, rec, 32, 16, 128, 128, 256};
+                        const SweepKnobs kn{cap, fm < 2 ? fm : env.fwd_front_min, fm < 2 ? fm : env.bwd_front_min, rec, kNarrowPassMax, kNarrowPassMaxBwd,
+                                            kFrontMaxCols, kWaveSplitCols, kWaveSplitRows};
                         const FwdLevelPlan f = plan_forward_level(L, nr, kn);
                         const BwdLevelPlan b = plan_backward_level(L, nr, kn);
                         for (const LevelBlocks *p : {(const LevelBlocks *)&f, (const LevelBlocks *)&b}) {
@@ -205,6 +329,23 @@ static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx:
                         EXPECT(!f.wave || (rec && f.cmin == kFwdWaveCols));
                         for (int i = 0; i < b.nf; i++)      // ... and t = y - L21' x, by its trailing rows
                             if (trail[i] > 0) EXPECT((b.wave && trail[i] <= b.mmin) + (b.gemm && trail[i] > b.mmin) == 1);
+                        if (!sweep) continue;
+                        if (f.ntail == 0 || f.nf > 0) {
+                            for (int j = 0; j + 1 < f.nbk; j++) {
+                                const int below = L.max_cols - (j + 1) * cap;
+                                check_launch(choose_fwd_own_update(f.own_fronts(j), L.max_cols, j, cap), f.own_fronts(j) <= 0 || below <= 0, true, false, below);
+                            }
+                            if (f.wave) check_launch(choose_fwd_update_wave(L.fwd_per, nr, f.wave_split_k), L.fwd_per <= 0, false, false, L.fwd_split.start[8], 1, nr, 16);
+                            if (f.update == FwdLevelPlan::kGrid) check_launch(choose_fwd_update(f.nf, L.max_trail), f.nf <= 0 || L.max_trail <= 0, true, false, L.max_trail);
+                        }
+                        if (b.ntail == 0 || b.nf > 0) {
+                            if (b.wave) check_launch(choose_bwd_wave(b.nf, L.max_cols, nr, b.wave_split_k), b.nf <= 0 || L.max_cols <= 0, true, false, L.max_cols, 16, b.nf, 1, nr, 16);
+                            if (b.gemm) check_launch(choose_bwd_gemm(b.nf, L.max_cols, -1, 1 << 30), b.nf <= 0 || L.max_cols <= 0, true, false, L.max_cols);
+                            for (int j = 0; j + 1 < b.nbk; j++) {
+                                const int own = std::min(L.max_cols - j * cap, cap);
+                                check_launch(choose_bwd_gemm(b.own_fronts(j), L.max_cols, j, cap), b.own_fronts(j) <= 0 || own <= 0, true, false, own);
+                            }
+                        }
                     }
     }
 }
@@ -222,8 +363,10 @@ static void device_plans(const std::vector<int64_t> &cp, const std::vector<int64
             check_runs(P.levels, false, P.syrk_recs.size(), xcd);
             check_runs(P.swlevels, true, P.fwd_recs.size(), xcd);
             EXPECT(P.edge.size() == S.children.size() && (int)P.levels.size() == S.nlevels);
-            check_level_plans(S, P.levels, S.levellist);
-            check_level_plans(S, P.swlevels, S.sw_levellist);
+            check_level_plans(S, P.levels, S.levellist, false);
+            check_level_plans(S, P.swlevels, S.sw_levellist, true);
+            check_factor_launches(P.levels);
+            for (int nr : {1, 8, 9, 64}) check_launch(gmrfx::choose_permute((int)n, nr), false, false, false, n);
             EXPECT(S.shard_plan ? P.owncol.size() == (size_t)n && P.fc_levelptr.back() == (int)P.fchild.size() : P.owncol.empty());
         }
     }
@@ -241,6 +384,7 @@ int main() {
     sharded_handles(cp, ri, xy.data(), n, 2);
     sharded_handles(cp, ri, xy.data(), n, 4);
     sharded_handles(cp, ri, xy.data(), n, 8);      // the width the driver scales to
+    check_launch_edges();
     device_plans(cp, ri, xy.data(), n, 1);
     device_plans(cp, ri, xy.data(), n, 2);         // owner columns, foreign parents, other ranks' children
     // distinct handles are used concurrently from different host threads (WorkspacePool contract)
@@ -282,6 +426,8 @@ int main() {
     }
     // (levels with a front wider than the inverse cap in the head AND a tail for the front kernel: what the check above is for)
     std::printf("levels with a wide head and a front-kernel tail: %d\n", levels_with_wide_head_and_tail);
+    // (a report: the plans here are small, no variant's count is a condition)
+    for (int v = 0; v < gmrfx::kVariantCount; v++) std::printf("launches of the plans' levels choosing %s: %lld\n", variant_names[v], variant_hits[v]);
     EXPECT(levels_with_wide_head_and_tail > 0);
     std::printf("sanitize_host: %s\n", fails ? "FAILED" : "ok");
     return fails ? 1 : 0;
