@@ -94,6 +94,14 @@ int batch_quadform_blocks(int nm);
 void launch_batch_quadform(hipStream_t st, int nm, const long long *colptr, const int *row, const double *val, long long nnz, int use_lower,
                            const double *X, long long ldx, long long sx, int nvec, int nbatch, const double *mu, double *part, double *out);
 
+// klchol.hip -- KL (Vecchia-type) sparse approximate Cholesky (gmrfx_kl_cholesky): one task = the rows of a local system (nrows
+// entries of rows[] from rows_off) and the columns of L it yields (ncols entries of cols[] from cols_off). The host driver: all
+// index arrays 0-based, theta n x n column-major (host or device); returns -1, or the first task whose local matrix is not positive definite.
+struct KlTask { long long rows_off, cols_off; int nrows, ncols; };
+long long kl_cholesky_run(int device, long long n, const double *theta, long long ldt, bool theta_on_device, const std::vector<KlTask> &tasks,
+                          const std::vector<int> &rows, const std::vector<int> &cols, const long long *Lcolptr, long long nnzL, double reg,
+                          double *nzval_out);
+
 // dense.hip -- the dense-operator leg of the Kronecker path: R = D T (row-major, D n1 x n1, T / R n1 x n2) and a transpose
 void launch_dense_apply(hipStream_t st, const double *D, const double *T, double *R, int n1, long long n2);
 void launch_transpose(hipStream_t st, const double *src, double *dst, long long rows, long long cols);

@@ -29,12 +29,6 @@
 
 namespace gmrfx {
 
-struct KlTask {
-    long long rows_off;   // into rows[]
-    long long cols_off;   // into cols[]
-    int nrows, ncols;
-};
-
 namespace {
 
 // M: lower triangle of the n x n local matrix (leading dimension ldm), in LDS or in global scratch.

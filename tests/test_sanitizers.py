@@ -1,5 +1,5 @@
 """CPU-only sanitizer job for the host C++ of the product: AddressSanitizer + UBSan and
-ThreadSanitizer builds of csrc/{symbolic,ordering,device_plan,device,gmrfx_api}.cpp, driven through the C ABI by
+ThreadSanitizer builds of csrc/{symbolic,ordering,device_plan,device,api_*}.cpp, driven through the C ABI by
 tools/sanitize_host.cpp (threaded nested dissection, threaded scatter map, concurrent handles, malformed input), which also
 builds the device tables (build_device_plan) of plain and sharded analyses.
 No GPU is involved (GPU sanitizers are not available on the pool)."""

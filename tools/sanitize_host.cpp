@@ -1,5 +1,5 @@
 // sanitize_host.cpp -- CPU-only sanitizer job for the host C++ of libgmrfx: the symbolic phase
-// (ordering.cpp, symbolic.cpp) spawns threads, gmrfx_api.cpp parses caller arrays, device_plan.cpp builds the device
+// (ordering.cpp, symbolic.cpp) spawns threads, the C ABI (api_*.cpp) parses caller arrays, device_plan.cpp builds the device
 // tables with index arithmetic over the analysis (called directly: it needs no device). Built twice by
 // `make -C gaussianmarkovrandomfields.jl_amd sanitize` (AddressSanitizer + UBSan, ThreadSanitizer) from the SAME
 // sources as the product, driven through the C ABI with symbolic_only handles (no GPU is touched; the HIP kernel
