@@ -195,6 +195,18 @@ public:
                   double *out, bool out_on_device);
     double ms_rbmc = 0, ms_rbmc_bsolve = 0;      // GPU time of the most recent rbmc_var, and the backward sweeps' part of it
 
+    // ---- log-density gradients on Q's own pattern (device_grad.cpp, grad.hip; gmrfx_logpdf_grad, gmrfx_pattern_dot) -----------------
+    // Members: the handle's batch (a handle without batch buffers is one member of S.n nodes). Device operands: nz = Q's values
+    // (nnz per member; nullptr: the held values; only read for mubar), z at + k sz, mu n per member (nullable), Qbar nnz per member and
+    // mubar n per member (either nullable: not computed); ybar: host, one per member. With a constraint set (con_* or bcon_*, A = its
+    // host rows) the outputs are the gradient of logpdf + log_correction. Ensures the selected inverse (Qbar) and the constraint
+    // preparation, enqueues the kernels on the main stream and synchronises once. info_host[k] (nullable): 0, -1 when member k's
+    // factorisation failed, 1 + the failing pivot when its W did -- such a member's outputs are NaN, nobody else's are touched.
+    struct GradIO { const double *d_nz, *d_z; long long sz; const double *d_mu; const double *ybar_host; double *d_Qbar, *d_mubar; };
+    void logpdf_grad(const RbmcSym &sym, const ConHost *A, const GradIO &io, long long *info_host);
+    // out[k p + c] = sum_e w_e G[k nnz + e] J[k sj + c ldj + e], w_e the weights of the quadratic form; out: host, p per member
+    void pattern_dot(const double *d_G, const double *d_J, long long ldj, long long sj, long long p, double *out_host);
+
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
     double ms_factor = 0, ms_solve = 0, ms_fwd = 0, ms_bwd = 0, ms_perm = 0, ms_bsolve = 0, ms_logdet = 0, ms_selinv = 0;
@@ -426,10 +438,14 @@ private:
         unsigned long long serial = 0;      // 0: nothing cached
     } bcon_;
     Event con_ev_[2], bcon_ev_[2], rb_ev_[2];     // begin / end of the timed part of con_*, bcon_*, rbmc_var
-    // RBMC state: the symmetric row structure of Q and the work arrays (uploaded once), the tables of the current block plan
-    struct RbmcSymDev {
+    // the symmetric row structure of Q (RbmcSym) on the device, uploaded once per handle: shared by rbmc_var and logpdf_grad
+    struct SymRowsDev {
         DevBuf<long long> rp;
         DevBuf<int> col, pos, dpos;
+    } sym_rows_;
+    void sym_rows_upload(const RbmcSym &sym);
+    // RBMC state: the work arrays (allocated once), the tables of the current block plan
+    struct RbmcSymDev {
         DevBuf<double> Xc, Xt, mean, m2, base, out;
     };
     struct RbmcPlanDev {
@@ -444,6 +460,21 @@ private:
     struct RbmcState { RbmcSymDev sym; RbmcPlanDev plan; } rb_;
     void rbmc_upload_sym(const RbmcSym &sym);
     void rbmc_upload_plan(const RbmcPlan &plan);
+    // gradient state. Tables of the handle's life: zoff (offset of every stored entry of Q in the selected-inverse panels; all members),
+    // wgt (the member's quadratic-form weights, one byte per entry). Bt = B' per member, of factorisation bt_serial and the constraint
+    // set then, and acol* (A by columns): con_set / bcon_set drop both. Work arrays, allocated once: r, u (n per member), tw (2 x 64), R (64),
+    // zero (a zero mean), ybar and the bad words, the contraction's partial sums and results.
+    struct GradDev {
+        DevBuf<long long> zoff, acolptr, bad;
+        DevBuf<unsigned char> wgt;
+        DevBuf<int> arow;
+        DevBuf<double> aval, Bt, r, u, tw, R, ybar, zero, dpart, dout;
+        long long dot_cap = 0, out_cap = 0;
+        unsigned long long bt_serial = 0;       // 0: nothing cached
+    } grad_;
+    void grad_tables();
+    void grad_drop_constraint() { grad_.acolptr.reset(); grad_.arow.reset(); grad_.aval.reset(); grad_.Bt.reset(); grad_.bt_serial = 0; }   // (behind a synchronisation)
+    void grad_constraint_tables(const ConHost &A, int m, const double *d_B, int nb, long long n);
     void con_drop();
     void prepare_batch_quadform(long long npairs);
     void enqueue_batch_quadform(hipStream_t st, const double *d_nz, const double *d_X, long long ldx, long long sx, long long nvec,

@@ -51,6 +51,7 @@ void Device::con_drop() {
     HC(hipSetDevice(device));
     HC(hipDeviceSynchronize());        // nothing in flight may still read the buffers
     con_ = ConDev();
+    grad_drop_constraint();
 }
 
 void Device::con_set(const ConHost &c) {
@@ -208,6 +209,7 @@ void Device::bcon_set(const ConHost &c) {
     if (c.m <= 0) {
         HC(hipDeviceSynchronize());
         bcon_ = BConDev();
+        grad_drop_constraint();
         return;
     }
     if (sharded() || !batched()) throw std::invalid_argument("batch constraints need an unsharded handle with its batch buffers");
@@ -228,6 +230,7 @@ void Device::bcon_set(const ConHost &c) {
     b.piece = bcon_piece(nb);
     HC(hipDeviceSynchronize());        // nothing in flight may still read the previous buffers
     bcon_ = std::move(b);
+    grad_drop_constraint();
 }
 
 bool Device::bcon_prepare() {

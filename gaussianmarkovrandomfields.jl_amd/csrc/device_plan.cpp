@@ -177,6 +177,19 @@ Launch choose_permute(int n, int nr) {
     return {kPermuteTiles, (unsigned)cdiv(n, 64), 1, 1, 256};
 }
 
+Launch choose_grad_pattern(int n, int nbatch) {
+    if (n <= 0 || nbatch <= 0) return {};
+    return {kGradPattern, (unsigned)cdiv(n, kGradCols), (unsigned)nbatch, 1, 256};
+}
+Launch choose_grad_mubar(int n, int nbatch) {
+    if (n <= 0 || nbatch <= 0) return {};
+    return {kGradMubar, (unsigned)cdiv(n, kGradRows), (unsigned)nbatch, 1, 256};
+}
+Launch choose_grad_dot(long long nnz, int p, int nbatch) {
+    if (nnz <= 0 || p <= 0 || nbatch <= 0) return {};
+    return {kGradDot, (unsigned)((nnz + kGradDotChunk - 1) / kGradDotChunk), (unsigned)p, (unsigned)nbatch, 256};
+}
+
 // Dense-inverse stage B: T-buffer offsets of the fronts wider than B, a list sorted by decreasing width; *total = doubles.
 static std::vector<long long> stage_offsets(const Symbolic &S, const std::vector<int> &fronts, int B, long long *total) {
     std::vector<long long> off;

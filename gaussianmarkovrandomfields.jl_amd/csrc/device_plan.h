@@ -255,6 +255,7 @@ enum KernelVariant {
     kPermuteNarrow, kPermuteTiles,                                        // k_permute_narrow, k_permute
     kWaveWhole, kWaveSplitK,                                              // k_fwd_update_wave / k_bwd_wave <1> / <4>
     kFwdOwnUpdate,
+    kGradPattern, kGradMubar, kGradDot,                                   // k_grad_pattern, k_grad_mubar, k_grad_dot_part (grad.hip)
     kVariantCount
 };
 struct Launch {
@@ -274,6 +275,15 @@ Launch choose_fwd_own_update(int nfronts, int max_cols, int blk, int cap);    //
 Launch choose_bwd_gemm(int nfronts, int max_cols, int blk, int cap);          // blk >= 0: the own columns of that block only
 Launch choose_bwd_wave(int nfronts, int max_cols, int nr, bool split_k);
 Launch choose_permute(int n, int nr);
+// grad.hip -- log-density gradients on Q's pattern. A lane group of kGradLanes lanes walks one column (pattern kernel) or one row of
+// symmetric Q (mean kernel) in passes of kGradLanes entries; a workgroup of 256 threads is 16 such groups. The pattern kernel gives a
+// group kGradColsPerGroup columns, so a workgroup owns kGradCols consecutive columns. The contraction sums fixed chunks of
+// kGradDotChunk stored entries per workgroup (the sums' order depends on it). Members of a batch ride in grid y (z: the contraction).
+constexpr int kGradLanes = 16, kGradColsPerGroup = 4, kGradCols = 16 * kGradColsPerGroup, kGradRows = 16;
+constexpr int kGradDotChunk = 4096;
+Launch choose_grad_pattern(int n, int nbatch);
+Launch choose_grad_mubar(int n, int nbatch);
+Launch choose_grad_dot(long long nnz, int p, int nbatch);
 
 // What changes the tables besides the analysis.
 struct PlanOptions {

@@ -23,15 +23,22 @@ template <class T, class U> static void rb_up(DevBuf<T> &dst, const std::vector<
     if (!tmp.empty()) HC(hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
 }
 
-void Device::rbmc_upload_sym(const RbmcSym &sym) {
-    if (rb_.sym.rp) return;
-    const size_t n = (size_t)S_->n;
+void Device::sym_rows_upload(const RbmcSym &sym) {
+    if (sym_rows_.rp) return;
     if (S_->nnz_in > INT_MAX || (long long)sym.col.size() > (1ll << 40)) throw std::invalid_argument("rbmc: Q has too many stored entries for 32-bit positions");
-    RbmcSymDev d;        // built aside: an upload that fails half-way leaves nothing behind
+    SymRowsDev d;        // built aside: an upload that fails half-way leaves nothing behind
     rb_up(d.rp, sym.rowptr, &bytes_total);      // n + 1
     rb_up(d.col, sym.col, &bytes_total);
     rb_up(d.pos, sym.pos, &bytes_total);
     rb_up(d.dpos, sym.diag, &bytes_total);      // n
+    sym_rows_ = std::move(d);
+}
+
+void Device::rbmc_upload_sym(const RbmcSym &sym) {
+    sym_rows_upload(sym);
+    if (rb_.sym.Xc) return;
+    const size_t n = (size_t)S_->n;
+    RbmcSymDev d;
     d.Xc.alloc(n * kRbmcW, &bytes_total, kTableMinBytes);
     d.Xt.alloc(n * kRbmcW, &bytes_total, kTableMinBytes);
     d.mean.alloc(n, &bytes_total, kTableMinBytes);
@@ -82,7 +89,7 @@ void Device::rbmc_var(const RbmcSym &sym, const RbmcPlan *plan, const double *d_
     if (plan) rbmc_upload_plan(*plan);
     const RbmcSymDev &sy = rb_.sym;
     const RbmcPlanDev &pl = rb_.plan;
-    const RbmcDev P{sy.rp, sy.col, sy.pos, sy.dpos, pl.bptr, pl.rows, pl.ns, pl.owner, pl.eptr, pl.loc};
+    const RbmcDev P{sym_rows_.rp, sym_rows_.col, sym_rows_.pos, sym_rows_.dpos, pl.bptr, pl.rows, pl.ns, pl.owner, pl.eptr, pl.loc};
     double *d_out = out_on_device ? out : sy.out;
     double bs = 0;
     HC(hipEventRecord(rb_ev_[0], stream));

@@ -193,4 +193,39 @@ void launch_rbmc_blocks(hipStream_t st, const RbmcDev &P, int cls, const int *or
                         int w, bool first, bool last, long long k, double *mean, double *m2, double *base, double *out, double *scrM,
                         double *scrR);
 
+// grad.hip -- log-density gradients on the pattern of Q (gmrfx_logpdf_grad, gmrfx_pattern_dot). nb members (a plain handle is one):
+// member k's values / offsets / Qbar at + k nnz, vectors at + k n, Bt at + k n m, tw at + k 2m, ybar[k], bad[k] (nullable; nonzero: NaN)
+struct GradPattern {
+    int n, m;                    // m = 0: no constraint (Bt, u unused)
+    long long nnz;
+    const long long *colptr;     // the member's pattern
+    const int *row;
+    const long long *zoff;       // offset of every stored entry in the selected-inverse panels
+    const double *Z, *r, *ybar, *Bt, *u;
+    const long long *bad;
+    double *Qbar;
+};
+struct GradMean {
+    int n, m;
+    long long nnz;
+    const long long *rp;         // Symmetric(Q) by rows (RbmcSym): row pointers, columns, positions in the caller's values
+    const int *col, *pos;
+    const double *val, *r, *ybar;
+    const long long *acolptr;    // A by columns (nullable: no constraint)
+    const int *arow;
+    const double *aval, *tw;
+    const long long *bad;
+    double *mubar;
+};
+void launch_grad_residual(hipStream_t st, int n, int nb, const double *z, long long sz, const double *mu, double *r);
+void launch_grad_bt(hipStream_t st, int n, int m, int nb, const double *B, double *Bt);
+// tw: per member t = L_c^-1 (e - A mu), then w = L_c^-T t, from R = A mu - e
+void launch_grad_tw(hipStream_t st, int m, int nb, const double *Linv, const double *R, double *tw);
+void launch_grad_u(hipStream_t st, int n, int m, int nb, const double *B, const double *tw, double *u);
+void launch_grad_pattern(hipStream_t st, const GradPattern &a, int nb);
+void launch_grad_mubar(hipStream_t st, const GradMean &a, int nb);
+// out[k p + c] = sum_e wgt[e] G[k nnz + e] J[k sj + c ldj + e]; part: nb p choose_grad_dot(nnz, p, nb).gx doubles
+void launch_grad_dot(hipStream_t st, long long nnz, const unsigned char *wgt, const double *G, const double *J, long long ldj, long long sj, int p,
+                     int nb, double *part, double *out);
+
 }  // namespace gmrfx

@@ -77,6 +77,8 @@ EXPORTS = [
     "gmrfx_batch_constraints_correct", "gmrfx_batch_constraints_correct_dev", "gmrfx_batch_constraints_var", "gmrfx_batch_sample",
     "gmrfx_batch_sample_dev", "gmrfx_batch_constrained_logpdf_dev",
     "gmrfx_rbmc_var", "gmrfx_rbmc_var_dev", "gmrfx_rbmc_plan",
+    "gmrfx_pattern_nnz", "gmrfx_logpdf_grad", "gmrfx_logpdf_grad_dev", "gmrfx_pattern_dot", "gmrfx_pattern_dot_dev",
+    "gmrfx_batch_logpdf_grad", "gmrfx_batch_logpdf_grad_dev", "gmrfx_batch_pattern_dot", "gmrfx_batch_pattern_dot_dev",
 ]
 
 
@@ -204,6 +206,15 @@ def lib():
         L.gmrfx_rbmc_var.argtypes = [vp, vp, vp, i64, i64, i32, vp]
         L.gmrfx_rbmc_var_dev.argtypes = [vp, vp, vp, i64, i64, i32, vp]
         L.gmrfx_rbmc_plan.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+        L.gmrfx_pattern_nnz.argtypes = [vp, C.POINTER(i64)]
+        L.gmrfx_logpdf_grad.argtypes = [vp, vp, vp, vp, dbl, vp, vp]
+        L.gmrfx_logpdf_grad_dev.argtypes = [vp, vp, vp, vp, dbl, vp, vp]
+        L.gmrfx_pattern_dot.argtypes = [vp, vp, vp, i64, i64, vp]
+        L.gmrfx_pattern_dot_dev.argtypes = [vp, vp, vp, i64, i64, vp]
+        L.gmrfx_batch_logpdf_grad.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_logpdf_grad_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_pattern_dot.argtypes = [vp, vp, vp, i64, i64, i64, vp]
+        L.gmrfx_batch_pattern_dot_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

@@ -722,6 +722,49 @@ class MI355XBackend:
     def rbmc_plan(self, enclosure_size: int, index_base: int = 0) -> dict:
         return _rbmc_plan(self._h, enclosure_size, index_base)
 
+    # -- log-density gradients on Q's own pattern (src/autodiff/logpdf.jl, src/workspace/autodiff.jl) ---------------------------
+    def logpdf_grad(self, z, mean=None, ybar: float = 1.0, nzval=None):
+        """The pullback of logpdf (+ log_correction with a constraint set) at cotangent ybar: (Qbar, mubar) with Qbar a csc matrix on
+        Q's own pattern and mubar (n,); zbar = -mubar. nzval: Q's values in the pattern's order; None = the values of the last
+        refactorisation."""
+        zz = np.ascontiguousarray(z, dtype=np.float64)
+        mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        if zz.shape != (self.n,) or (mu is not None and mu.shape != (self.n,)):
+            raise ValueError("dimension mismatch")
+        nz = None if nzval is None else np.ascontiguousarray(nzval, dtype=np.float64)
+        if nz is not None and nz.shape != (self._nnz,):
+            raise ValueError("nzval length does not match the pattern")
+        qbar, mubar = np.empty(self._nnz), np.empty(self.n)
+        check(lib().gmrfx_logpdf_grad(self._h, ptr(nz), ptr(zz), ptr(mu), float(ybar), ptr(qbar), ptr(mubar)), self._h)
+        return sp.csc_matrix((qbar, self._rowval.copy(), self._colptr.copy()), shape=(self.n, self.n)), mubar
+
+    def logpdf_grad_dev(self, d_z: int, d_Qbar: int = 0, d_mubar: int = 0, d_mu: int = 0, ybar: float = 1.0, d_nzval: int = 0) -> None:
+        """Device pointers: z (n), Qbar (nnz) and mubar (n) outputs (0 = not computed, not both), mu (n, 0 = zero mean), Q's values."""
+        if not d_z or (not d_Qbar and not d_mubar):
+            raise ValueError("logpdf_grad_dev: null pointer")
+        check(lib().gmrfx_logpdf_grad_dev(self._h, d_nzval or None, d_z, d_mu or None, float(ybar), d_Qbar or None, d_mubar or None), self._h)
+
+    def pattern_dot(self, G, J) -> np.ndarray:
+        """out[k] = sum_e w_e G[e] J[e, k] over the stored entries of Q (w_e: the Symmetric(Q) weights of sqmahal): dlogpdf/dtheta_k
+        from G = Qbar's values (nnz,) or a csc matrix on Q's pattern, and the Jacobian J (nnz, p) of Q's values."""
+        g = np.ascontiguousarray(G.data if sp.issparse(G) else G, dtype=np.float64)
+        Jf = np.asarray(J, dtype=np.float64)
+        if g.shape != (self._nnz,) or Jf.shape[0] != self._nnz or Jf.ndim > 2:
+            raise ValueError("G must have nnz values and J nnz rows")
+        Jf = np.asfortranarray(Jf.reshape(self._nnz, -1))
+        if Jf.shape[1] < 1:
+            raise ValueError("J must have at least one column")
+        out = np.empty(Jf.shape[1])
+        check(lib().gmrfx_pattern_dot(self._h, ptr(g), ptr(Jf), max(self._nnz, 1), Jf.shape[1], ptr(out)), self._h)
+        return out
+
+    def pattern_dot_dev(self, d_G: int, d_J: int, ldj: int, p: int) -> np.ndarray:
+        if not d_G or not d_J or p < 1 or ldj < self._nnz:
+            raise ValueError("pattern_dot_dev: null pointer, p < 1 or ldj < nnz")
+        out = np.empty(p)
+        check(lib().gmrfx_pattern_dot_dev(self._h, d_G, d_J, ldj, p, ptr(out)), self._h)
+        return out
+
 
 class MI355XBatchBackend:
     """B precision matrices with ONE pattern, factored in one pass (gmrfx_create_batched, include/gmrfx.h): the hyper-parameter
@@ -1064,3 +1107,52 @@ class MI355XBatchBackend:
     def rbmc_plan(self, enclosure_size: int, index_base: int = 0) -> dict:
         """Blocks over the forest's B n nodes (blocks never cross members)."""
         return _rbmc_plan(self._h, enclosure_size, index_base)
+
+    # -- log-density gradients on Q's own pattern, per member ---------------------------------------------------------------------
+    def logpdf_grad(self, z, mean=None, ybar=1.0, nzval=None):
+        """Per member: (Qbar (nnz, B) in the pattern's order, mubar (n, B), info (B,)). z (n, B); mean (n,) or (n, B); ybar a scalar
+        or (B,); nzval (nnz, B), None = the held values. info[k]: 0, -1 (factorisation failed) or 1 + the failing pivot of W_k; such
+        a member's columns are NaN."""
+        Z = np.asarray(z, dtype=np.float64)
+        if Z.shape != (self.n, self.nbatch):
+            raise ValueError(f"z must have shape (n, nbatch) = ({self.n}, {self.nbatch}), got {Z.shape}")
+        Zf = np.asfortranarray(Z)
+        mu = self._mean(mean)
+        nz = None if nzval is None else self._values(nzval)
+        yb = np.ascontiguousarray(np.broadcast_to(np.asarray(ybar, dtype=np.float64), (self.nbatch,)))
+        qbar = np.empty((self._nnz, self.nbatch), order="F")
+        mubar = np.empty((self.n, self.nbatch), order="F")
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_logpdf_grad(self._h, ptr(nz), ptr(Zf), self.n, ptr(mu), ptr(yb), ptr(qbar), ptr(mubar), ptr(info)), self._h)
+        return qbar, mubar, info
+
+    def logpdf_grad_dev(self, d_z: int, sz: int, ybar, d_Qbar: int = 0, d_mubar: int = 0, d_mu: int = 0, d_nzval: int = 0) -> np.ndarray:
+        """Device pointers (member k's z at + k sz, Qbar at + k nnz, mu / mubar at + k n); ybar a scalar or (B,); returns info (B,)."""
+        if not d_z or (not d_Qbar and not d_mubar) or (self.nbatch > 1 and sz < self.n):
+            raise ValueError("logpdf_grad_dev: null pointer or member stride < n")
+        yb = np.ascontiguousarray(np.broadcast_to(np.asarray(ybar, dtype=np.float64), (self.nbatch,)))
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_logpdf_grad_dev(self._h, d_nzval or None, d_z, sz, d_mu or None, ptr(yb), d_Qbar or None, d_mubar or None,
+                                                ptr(info)), self._h)
+        return info
+
+    def pattern_dot(self, G, J) -> np.ndarray:
+        """out[k, b] = sum_e w_e G[e, b] J[e, k, b]: G (nnz, B), J (nnz, p, B) or (nnz, B) (p = 1); returns (p, B)."""
+        g = self._values(G)
+        Jf = np.asarray(J, dtype=np.float64)
+        if Jf.ndim == 2:
+            Jf = Jf[:, None, :]
+        if Jf.ndim != 3 or Jf.shape[0] != self._nnz or Jf.shape[2] != self.nbatch or Jf.shape[1] < 1:
+            raise ValueError(f"J must have shape (nnz, p, nbatch) with nnz = {self._nnz}, nbatch = {self.nbatch}, got {Jf.shape}")
+        Jf = np.asfortranarray(Jf)
+        p = Jf.shape[1]
+        out = np.empty((p, self.nbatch), order="F")
+        check(lib().gmrfx_batch_pattern_dot(self._h, ptr(g), ptr(Jf), max(self._nnz, 1), self._nnz * p, p, out.ctypes.data), self._h)
+        return out
+
+    def pattern_dot_dev(self, d_G: int, d_J: int, ldj: int, sj: int, p: int) -> np.ndarray:
+        if not d_G or not d_J or p < 1 or ldj < self._nnz or (self.nbatch > 1 and sj < ldj * p):
+            raise ValueError("pattern_dot_dev: null pointer, p < 1, ldj < nnz or member stride < ldj * p")
+        out = np.empty((p, self.nbatch), order="F")
+        check(lib().gmrfx_batch_pattern_dot_dev(self._h, d_G, d_J, ldj, sj, p, out.ctypes.data), self._h)
+        return out

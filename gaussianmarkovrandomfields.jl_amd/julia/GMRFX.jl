@@ -338,6 +338,36 @@ function rbmc_var(b::MI355XBackend, Z::Matrix{Float64}; enclosure_size::Integer 
 end
 function rbmc_var_dev! end      # ROCArray method: ext/GMRFXAMDGPUExt.jl
 
+# The arithmetic of the logpdf / logdetcov pullbacks (src/autodiff/logpdf.jl:63-90, src/workspace/autodiff.jl:14-50) on the device and
+# on Q's own pattern: (Qbar as a SparseMatrixCSC on the pattern of `Q`, mubar); zbar = -mubar. With a constraint set on the handle the
+# two constraint terms of autodiff.jl:24-37 are included. `Q` only lends its pattern (the one the handle was created with); the values
+# are those of the last refactorisation.
+function logpdf_grad(b::MI355XBackend, Q::SparseMatrixCSC{Float64, Int}, z::Vector{Float64}; mean::Union{Nothing, Vector{Float64}} = nothing,
+                     ybar::Real = 1.0)
+    length(z) == b.n && size(Q) == (b.n, b.n) || throw(DimensionMismatch("z must have n entries, Q be n x n"))
+    hn = Ref{Int64}(0)
+    check(ccall((:gmrfx_pattern_nnz, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), b.h.ptr, hn), b.h)
+    nnz(Q) == hn[] || throw(DimensionMismatch("Q has $(nnz(Q)) stored entries, the handle's pattern $(hn[]): Q must be the matrix the handle was created with"))
+    mean === nothing || length(mean) == b.n || throw(DimensionMismatch("mean must have n entries"))
+    qbar = Vector{Float64}(undef, nnz(Q)); mubar = Vector{Float64}(undef, b.n)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve z mean qbar mubar check(ccall((:gmrfx_logpdf_grad, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, C_NULL, z, mu, Float64(ybar), qbar, mubar), b.h)
+    return SparseMatrixCSC(b.n, b.n, copy(Q.colptr), copy(Q.rowval), qbar), mubar
+end
+# out[k] = sum_e w_e G[e] J[e, k] over the stored entries (w_e: the Symmetric(Q) weights of the quadratic form): dlogpdf/dtheta_k from
+# G = nonzeros(Qbar) and the Jacobian J (nnz x p) of Q's stored values
+function pattern_dot(b::MI355XBackend, G::Vector{Float64}, J::Matrix{Float64})
+    size(J, 1) == length(G) || throw(DimensionMismatch("J must have one row per stored entry"))
+    out = Vector{Float64}(undef, size(J, 2))
+    GC.@preserve G J out check(ccall((:gmrfx_pattern_dot, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}),
+        b.h.ptr, G, J, max(stride(J, 2), 1), size(J, 2), out), b.h)
+    return out
+end
+function logpdf_grad_dev! end   # ROCArray methods: ext/GMRFXAMDGPUExt.jl
+function pattern_dot_dev end
+
 # `_rand!` on given draws: X = P' L^-T Z + mean, then the constraint correction when the handle holds one
 function sample(b::MI355XBackend, Z::Matrix{Float64}, mean::Union{Nothing, Vector{Float64}} = nothing)
     X = similar(Z)
@@ -637,6 +667,31 @@ function sample(bb::MI355XBatch, Z::Union{Matrix{Float64}, Array{Float64, 3}}, m
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Int64),
         bb.h.ptr, Z, bb.n, bb.n * r, r, mu, X, bb.n, bb.n * r), bb.h)
     return X
+end
+
+# The gradient of every member's logpdf (+ log_correction) on the members' pattern: Z, mean n x nbatch, ybar a number or one per member
+# -> (Qbar nnz x nbatch, mubar n x nbatch, info); info[k] != 0 (-1: factorisation failed, > 0: W_k failed): member k's columns are NaN
+function logpdf_grad(bb::MI355XBatch, Z::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing, ybar = 1.0)
+    size(Z) == (bb.n, bb.nbatch) || throw(DimensionMismatch("Z must be n x nbatch"))
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    yb = ybar isa Real ? fill(Float64(ybar), bb.nbatch) : Vector{Float64}(ybar)
+    length(yb) == bb.nbatch || throw(DimensionMismatch("ybar must have one entry per member"))
+    qbar = Matrix{Float64}(undef, bb.nnz, bb.nbatch); mubar = Matrix{Float64}(undef, bb.n, bb.nbatch)
+    inf = zeros(Int64, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve Z mean yb qbar mubar inf check(ccall((:gmrfx_batch_logpdf_grad, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, C_NULL, Z, bb.n, mu, yb, qbar, mubar, inf), bb.h)
+    return qbar, mubar, inf
+end
+# out[k, b] = sum_e w_e G[e, b] J[e, k, b]: G nnz x nbatch, J nnz x p x nbatch -> p x nbatch
+function pattern_dot(bb::MI355XBatch, G::Matrix{Float64}, J::Array{Float64, 3})
+    size(G) == (bb.nnz, bb.nbatch) && size(J, 1) == bb.nnz && size(J, 3) == bb.nbatch || throw(DimensionMismatch("G nnz x nbatch, J nnz x p x nbatch"))
+    p = size(J, 2)
+    out = Matrix{Float64}(undef, p, bb.nbatch)
+    GC.@preserve G J out check(ccall((:gmrfx_batch_pattern_dot, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}),
+        bb.h.ptr, G, J, max(bb.nnz, 1), bb.nnz * p, p, out), bb.h)
+    return out
 end
 
 # max(diag Sigma_k - rowsum(B_k^2), 0) of every member: n x nbatch; without a constraint selinv_diag(bb)

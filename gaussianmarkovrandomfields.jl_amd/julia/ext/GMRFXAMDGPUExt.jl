@@ -20,7 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
-import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!
+import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -128,6 +128,52 @@ function rbmc_var_dev!(out::ROCVector{Float64}, b::MI355XBackend, Z::ROCMatrix{F
     AMDGPU.synchronize()
     GC.@preserve Z out check(ccall((:gmrfx_rbmc_var_dev, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int32, Ptr{Float64}),
         b.h.ptr, C_NULL, devptr(Z), stride(Z, 2), size(Z, 2), enclosure_size, devptr(out)), b.h)
+    return out
+end
+
+# The gradient of logpdf (+ log_correction) with everything resident in HBM (gmrfx_logpdf_grad_dev): Qbar (nnz, in the pattern's order)
+# and mubar (n) are written in place; Q's values are those of the last refactorisation unless d_nz is given
+function logpdf_grad_dev!(Qbar::ROCVector{Float64}, mubar::ROCVector{Float64}, b::MI355XBackend, z::ROCVector{Float64};
+                          mean::Union{Nothing, ROCVector{Float64}} = nothing, ybar::Real = 1.0, d_nz::Union{Nothing, ROCVector{Float64}} = nothing)
+    length(z) == b.n && length(mubar) == b.n || throw(DimensionMismatch("z and mubar must have n entries"))
+    AMDGPU.synchronize()
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : devptr(mean)
+    nz = d_nz === nothing ? Ptr{Float64}(C_NULL) : devptr(d_nz)
+    GC.@preserve Qbar mubar z mean d_nz check(ccall((:gmrfx_logpdf_grad_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, nz, devptr(z), mu, Float64(ybar), devptr(Qbar), devptr(mubar)), b.h)
+    return Qbar, mubar
+end
+# the members of a batch: Qbar nnz x B, mubar / Z / mean n x B; returns info
+function logpdf_grad_dev!(Qbar::ROCMatrix{Float64}, mubar::ROCMatrix{Float64}, bb::MI355XBatch, Z::ROCMatrix{Float64}, ybar::Vector{Float64};
+                          mean::Union{Nothing, ROCMatrix{Float64}} = nothing, d_nz::Union{Nothing, ROCMatrix{Float64}} = nothing)
+    size(Z) == (bb.n, bb.nbatch) && size(mubar) == (bb.n, bb.nbatch) && size(Qbar) == (bb.nnz, bb.nbatch) && length(ybar) == bb.nbatch ||
+        throw(DimensionMismatch("Z / mubar n x nbatch, Qbar nnz x nbatch, ybar of length nbatch"))
+    AMDGPU.synchronize()
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : devptr(mean)
+    nz = d_nz === nothing ? Ptr{Float64}(C_NULL) : devptr(d_nz)
+    inf = zeros(Int64, bb.nbatch)
+    GC.@preserve Qbar mubar Z mean d_nz ybar inf check(ccall((:gmrfx_batch_logpdf_grad_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, nz, devptr(Z), stride(Z, 2), mu, ybar, devptr(Qbar), devptr(mubar), inf), bb.h)
+    return inf
+end
+# dlogpdf/dtheta from Qbar's values and the Jacobian of Q's values, both in HBM: p numbers come back
+function pattern_dot_dev(b::MI355XBackend, G::ROCVector{Float64}, J::ROCMatrix{Float64})
+    size(J, 1) == length(G) || throw(DimensionMismatch("J must have one row per stored entry"))
+    AMDGPU.synchronize()
+    out = Vector{Float64}(undef, size(J, 2))
+    GC.@preserve G J out check(ccall((:gmrfx_pattern_dot_dev, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Ptr{Float64}),
+        b.h.ptr, devptr(G), devptr(J), max(stride(J, 2), 1), size(J, 2), out), b.h)
+    return out
+end
+function pattern_dot_dev(bb::MI355XBatch, G::ROCMatrix{Float64}, J::ROCArray{Float64, 3})
+    size(G) == (bb.nnz, bb.nbatch) && size(J, 1) == bb.nnz && size(J, 3) == bb.nbatch || throw(DimensionMismatch("G nnz x nbatch, J nnz x p x nbatch"))
+    AMDGPU.synchronize()
+    p = size(J, 2)
+    out = Matrix{Float64}(undef, p, bb.nbatch)
+    GC.@preserve G J out check(ccall((:gmrfx_batch_pattern_dot_dev, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Ptr{Float64}),
+        bb.h.ptr, devptr(G), devptr(J), max(bb.nnz, 1), bb.nnz * p, p, out), bb.h)
     return out
 end
 

@@ -589,6 +589,50 @@ int32_t gmrfx_rbmc_var_dev(gmrfx_handle *h, const double *d_nzval, const double 
 int32_t gmrfx_rbmc_plan(gmrfx_handle *h, int32_t enclosure_size, int32_t index_base, int64_t *counts,
                         int64_t *block_ptr, int64_t *rows, int64_t *n_interior, int64_t *owner);
 
+/* ---- Log-density gradients on Q's own pattern -------------------------------------------------------------------------------------
+ * The array arithmetic of the reference's logpdf / logdetcov pullbacks (src/autodiff/logpdf.jl:63-90, src/autodiff/logdetcov.jl:14-18,
+ * src/autodiff/precision_gradient.jl, src/workspace/autodiff.jl:14-50), formed on the device and only on the stored entries of Q --
+ * the cotangent is contracted with a dQ/dtheta that lives there:
+ *   Qbar[e] = c (Sigma_ij - r_i r_j) - c (sum_k B_ik B_jk - u_i u_j)     e = (i, j) a stored entry,  c = ybar / 2,  r = z - mu
+ *   mubar   = ybar Q r - ybar A' W^-1 (e - A mu)                          (zbar = -mubar)
+ * Sigma = Q^-1 (the selected inverse: computed if absent, cached per factorisation), and with a constraint A x = e set
+ * (gmrfx_constraints_set or gmrfx_batch_constraints_set; the second terms exist only then) B = Q^-1 A' L_c^-T, L_c L_c' = W = A Q^-1 A',
+ * u = B L_c^-1 (e - A mu): the outputs are then the gradient of logpdf + log_correction (gmrfx_constraints_mean), src/workspace/
+ * autodiff.jl:24-37. An entry gets its value whichever triangle it lies in (opts.uplo does not matter for Qbar); the first term is
+ * computed as c * (Sigma_ij - r_i * r_j), in that association. mubar uses Symmetric(Q) as gmrfx_quadform does: the triangle not in use
+ * is never read. nzval: Q's CSC values, only read for mubar (NULL = the values of the last refactorisation when the handle holds them,
+ * as gmrfx_quadform; INVALID_ARG when it holds none). mu NULL = zero mean. Qbar (nnz, in the pattern's order) and mubar (n) are each
+ * nullable (not computed), not both.
+ * gmrfx_pattern_dot: out[k] = sum_e w_e G[e] J[e + k ldj], k < p -- dlogpdf/dtheta_k from G = Qbar and the Jacobian J of Q's stored
+ * values (nnz x p column-major, ldj >= nnz); w_e are the weights of gmrfx_quadform: 1 on the diagonal, 2 off the diagonal in the
+ * triangle that defines Q and 0 in the other one. Only p numbers cross PCIe. Needs no factorisation.
+ * Batch forms: member k's values / Qbar at + k nnz, mu / mubar at + k n, z at + k sz, J at + k sj; ybar, info and out (p x nbatch) are
+ * host arrays. A plain handle is a batch of one. A member whose factorisation or whose W_k failed gets NaN in its own outputs and
+ * info[k] = -1 resp. 1 + the failing pivot of W_k (as gmrfx_batch_constraints_info); nobody else's outputs are disturbed. With
+ * info = NULL such a member makes the call return GMRFX_ERR_NOT_POSDEF, as a failed factorisation or W does for the plain forms.
+ * No atomics: every sum is formed in an order that depends on indices only; results are bit-reproducible, independent of sz and of the
+ * alignment of the operands, the host and the _dev forms agree bit for bit, and member k of a batch equals a plain handle on Q_k.
+ * Errors: GMRFX_ERR_INVALID_ARG with a message for sharded handles, the plain forms on a batched handle, p < 1, ldj < nnz, member
+ * strides that overlap, null required pointers; GMRFX_ERR_NOT_FACTORIZED before the first factorisation (gradient forms);
+ * GMRFX_ERR_NO_DEVICE for symbolic_only handles. LIMITS: one z per call, m <= 64 constraint rows, p <= 65535. */
+int32_t gmrfx_pattern_nnz(const gmrfx_handle *h, int64_t *nnz /* stored entries of the (member's) pattern: the length of Qbar / G */);
+int32_t gmrfx_logpdf_grad(gmrfx_handle *h, const double *nzval /* nullable */, const double *z, const double *mu /* nullable */, double ybar,
+                          double *Qbar /* nnz, nullable */, double *mubar /* n, nullable */);
+int32_t gmrfx_logpdf_grad_dev(gmrfx_handle *h, const double *d_nzval, const double *d_z, const double *d_mu, double ybar, double *d_Qbar,
+                              double *d_mubar);
+int32_t gmrfx_pattern_dot(gmrfx_handle *h, const double *G /* nnz */, const double *J, int64_t ldj, int64_t p, double *out /* host, p */);
+int32_t gmrfx_pattern_dot_dev(gmrfx_handle *h, const double *d_G, const double *d_J, int64_t ldj, int64_t p, double *out /* host, p */);
+int32_t gmrfx_batch_logpdf_grad(gmrfx_handle *h, const double *nzval /* nnz x nbatch, nullable */, const double *z, int64_t sz,
+                                const double *mu /* n x nbatch, nullable */, const double *ybar /* host, nbatch */,
+                                double *Qbar /* nnz x nbatch, nullable */, double *mubar /* n x nbatch, nullable */,
+                                int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_logpdf_grad_dev(gmrfx_handle *h, const double *d_nzval, const double *d_z, int64_t sz, const double *d_mu,
+                                    const double *ybar /* host, nbatch */, double *d_Qbar, double *d_mubar, int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_pattern_dot(gmrfx_handle *h, const double *G /* nnz x nbatch */, const double *J, int64_t ldj, int64_t sj, int64_t p,
+                                double *out /* host, p x nbatch */);
+int32_t gmrfx_batch_pattern_dot_dev(gmrfx_handle *h, const double *d_G, const double *d_J, int64_t ldj, int64_t sj, int64_t p,
+                                    double *out /* host, p x nbatch */);
+
 #ifdef __cplusplus
 }
 #endif

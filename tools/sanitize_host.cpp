@@ -151,7 +151,8 @@ static long long variant_hits[gmrfx::kVariantCount];
 static const char *const variant_names[gmrfx::kVariantCount] = {
     "no launch", "k_assemble_lds<0>", "k_assemble_lds<1>", "k_assemble<1>", "k_assemble<0>", "k_trsm<.,1>", "k_trsm<.,0>", "k_gemm_nt_big",
     "k_gemm_nt<1>", "k_gemm_nt<2>", "k_fwd_update_longk<1>", "k_fwd_update_longk<2>", "k_bwd_gemm_longk<1,8>", "k_bwd_gemm_longk<2,8>",
-    "k_bwd_gemm_longk<2,4>", "k_permute_narrow", "k_permute", "wave kernel <1>", "wave kernel <4>", "k_fwd_own_update"};
+    "k_bwd_gemm_longk<2,4>", "k_permute_narrow", "k_permute", "wave kernel <1>", "wave kernel <4>", "k_fwd_own_update",
+    "k_grad_pattern", "k_grad_mubar", "k_grad_dot_part"};
 // rows / columns a workgroup of the variant owns along grid x (gemm_nt: and y)
 static int variant_tile(gmrfx::KernelVariant v) {
     using namespace gmrfx;
@@ -229,6 +230,10 @@ static void check_launch_edges() {
     EXPECT(choose_assemble(0, 100, 100).variant == kNoLaunch && choose_assemble_hbm(0, 100).variant == kNoLaunch);
     // permute and the wave kernels
     EXPECT(is(choose_permute(1000, 8), kPermuteNarrow, 4, 1, 1, 256) && is(choose_permute(1000, 9), kPermuteTiles, 16, 1, 1, 256));
+    // gradients on Q's pattern: 64 columns / 16 rows per workgroup, chunks of 4096 entries; members in grid y (z: the contraction)
+    EXPECT(is(choose_grad_pattern(64, 3), kGradPattern, 1, 3, 1, 256) && is(choose_grad_pattern(65, 1), kGradPattern, 2, 1, 1, 256) && choose_grad_pattern(0, 1).variant == kNoLaunch);
+    EXPECT(is(choose_grad_mubar(16, 2), kGradMubar, 1, 2, 1, 256) && is(choose_grad_mubar(17, 1), kGradMubar, 2, 1, 1, 256) && choose_grad_mubar(5, 0).variant == kNoLaunch);
+    EXPECT(is(choose_grad_dot(4096, 5, 2), kGradDot, 1, 5, 2, 256) && is(choose_grad_dot(4097, 1, 1), kGradDot, 2, 1, 1, 256) && choose_grad_dot(0, 1, 1).variant == kNoLaunch);
     EXPECT(is(choose_fwd_update_wave(5, 17, false), kWaveWhole, 40, 2, 1, 64) && is(choose_fwd_update_wave(5, 16, true), kWaveSplitK, 40, 1, 1, 256));
     EXPECT(is(choose_bwd_wave(3, 100, 16, false), kWaveWhole, 7, 3, 1, 64) && is(choose_bwd_wave(3, 100, 1, true), kWaveSplitK, 7, 3, 1, 256));
     EXPECT(choose_fwd_update_wave(0, 1, true).variant == kNoLaunch && choose_bwd_wave(0, 100, 1, true).variant == kNoLaunch &&
