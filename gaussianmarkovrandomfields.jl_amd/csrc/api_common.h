@@ -31,6 +31,8 @@ struct gmrfx_handle {
     ConHost con;
     // the same for every member of a batch (gmrfx_batch_constraints_set): one A (n_member columns) and e; at most one of the two is set
     ConHost bcon;
+    // the observation likelihood of Fisher scoring (gmrfx_obs_set): host copy, also on symbolic_only handles; obs.nobs = 0: none
+    ObsHost obs;
     // host analysis of the RBMC variance estimators (gmrfx_rbmc_plan / gmrfx_rbmc_var), built lazily: the symmetric row structure
     // once, the block plan of the most recent enclosure_size
     RbmcSym rsym;

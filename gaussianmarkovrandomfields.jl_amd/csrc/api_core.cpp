@@ -73,6 +73,8 @@ extern "C" int32_t gmrfx_clone(const gmrfx_handle *h, gmrfx_handle **out) {
         if (c->D && c->con.m > 0) c->D->con_set(c->con);
         c->bcon = h->bcon;
         if (c->D && c->bcon.m > 0) c->D->bcon_set(c->bcon);
+        c->obs = h->obs;        // the likelihood travels too (the prior's values do not: the clone calls gmrfx_set_prior itself)
+        if (c->D && c->obs.nobs > 0) c->D->obs_set(c->obs);
     } catch (const std::exception &e) {
         g_create_err = e.what();
         return GMRFX_ERR_HIP;

@@ -59,6 +59,19 @@ struct ConHost {
     double logdet_AAt = 0;
 };
 
+// The observation likelihood a plain handle keeps (gmrfx_obs_set), host copy, also on symbolic_only handles; nobs = 0: none.
+// Families (canonical or log link, reference canonical_implementations.jl:146-327): 0 Normal / identity (param sigma), 1 Poisson / log
+// (aux = log exposure), 2 Bernoulli / logit, 3 Binomial / logit (aux = trials), 4 NegativeBinomial / log (aux = log exposure, param r),
+// 5 Gamma / log (param phi). idx: the observed nodes, 0-based, in the caller's order; y and aux (empty: none) go with them.
+struct ObsHost {
+    int family = 0;
+    long long nobs = 0;
+    std::vector<long long> idx;
+    std::vector<double> y, aux;
+    double param = 0, loglik_const = 0;      // the sum of the terms of loglik that do not depend on x (long double on the host)
+};
+constexpr int kObsFamilies = 6;
+
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
 // Where one sweep pass runs: a stream and the right-hand-side buffers it works in (X: the pass's columns in elimination order,
@@ -160,7 +173,7 @@ public:
     double con_ms() const { return con_.ms; }
     void con_get(double *At_host, long long ld, double *W_host);
     // X <- X (+ mu) - At W^-1 (A (X + mu) - e) on nvec columns of a device array (d_mu nullable); without constraints X += mu
-    void con_correct(double *d_X, long long ldx, long long nvec, const double *d_mu);
+    void con_correct(double *d_X, long long ldx, long long nvec, const double *d_mu, bool homogeneous = false);      // homogeneous: e = 0
     double ms_con_correct = 0;         // GPU time of the kernels of the most recent con_correct
     // A mu - e of the most recent con_correct (its first column), host copy of m values
     void con_residual(double *out_host);
@@ -206,6 +219,25 @@ public:
     void logpdf_grad(const RbmcSym &sym, const ConHost *A, const GradIO &io, long long *info_host);
     // out[k p + c] = sum_e w_e G[k nnz + e] J[k sj + c ldj + e], w_e the weights of the quadratic form; out: host, p per member
     void pattern_dot(const double *d_G, const double *d_J, long long ldj, long long sj, long long p, double *out_host);
+
+    // ---- Fisher scoring on the device (device_fisher.cpp, fisher.hip; gmrfx_obs_set, gmrfx_fisher_eval) ------------------------------
+    // obs_set expands y, aux and the observed mask to length-n arrays on the device (nobs = 0: drops them), built aside: a failed
+    // upload leaves the previous likelihood in place.
+    void obs_set(const ObsHost &o);
+    bool obs_held() const { return (bool)fisher_.y; }
+    // One pass over Symmetric(Q_prior) at the point d_x: score = (Q_p x - h) - g(x) and hess = d(x) (n each, device, either nullable),
+    // out_host = {1/2 x' Q_p x - x' h, sum of the x-dependent terms of loglik}; h = Q_p mu (d_mu nullable: 0). Needs set_prior with the
+    // diagonal map (position of (i, i) for every i) and a likelihood; no factorisation. Synchronises once.
+    void fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host);
+    // The Fisher-scoring loop of the reference (src/workspace/gaussian_approximation.jl:230-313 with _ga_line_search, _predict_converged
+    // and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409), control flow on the host, every vector in HBM.
+    // flags: bit 0 adaptive_stepsize, 1 retry_full, 2 predictive_convergence, 3 leave the handle factorised at Q_prior - H(x_final).
+    // d_x0 nullable (= mu, or 0); d_x: n out; d_hess: n out, nullable. result[8], dec_trace / alpha_trace (max_iter + 1, nullable): host.
+    // Returns 0, 1 when a factorisation failed (*info = 1 + the failing step; d_x = the last accepted iterate), 2 when the
+    // constraint's W = A Q^-1 A' did.
+    struct GaOpts { long long max_iter, max_ls; double mean_tol, dec_tol; int flags; };
+    int gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
+                               double *result, double *dec_trace, double *alpha_trace, long long *info);
 
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
@@ -472,6 +504,16 @@ private:
         long long dot_cap = 0, out_cap = 0;
         unsigned long long bt_serial = 0;       // 0: nothing cached
     } grad_;
+    // Fisher-scoring state: the likelihood by node (y, aux, mask: n each), the evaluation's partial sums (2 per workgroup) and results
+    struct FisherDev {
+        DevBuf<double> y, aux, part, out, spart, work;      // spart: the loop's reductions; work: its six vectors (on first use)
+        DevBuf<unsigned char> mask;
+        PinnedBuf<double> h_out;                             // 2 of the evaluation, then 4 of the reductions
+        int family = 0;
+        double param = 0, loglik_const = 0;
+    } fisher_;
+    std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
+    int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
     void grad_tables();
     void grad_drop_constraint() { grad_.acolptr.reset(); grad_.arow.reset(); grad_.aval.reset(); grad_.Bt.reset(); grad_.bt_serial = 0; }   // (behind a synchronisation)
     void grad_constraint_tables(const ConHost &A, int m, const double *d_B, int nb, long long n);

@@ -148,7 +148,7 @@ void Device::con_get(double *At_host, long long ld, double *W_host) {
     if (W_host) std::copy(con_.h_w.begin(), con_.h_w.end(), W_host);
 }
 
-void Device::con_correct(double *d_X, long long ldx, long long nvec, const double *d_mu) {
+void Device::con_correct(double *d_X, long long ldx, long long nvec, const double *d_mu, bool homogeneous) {
     HC(hipSetDevice(device));
     const int m = con_.m;
     const long long n = S_->n;
@@ -168,7 +168,7 @@ void Device::con_correct(double *d_X, long long ldx, long long nvec, const doubl
     for (long long j0 = 0; j0 < nvec; j0 += kConColBatch) {
         const int k = (int)std::min(kConColBatch, nvec - j0);
         double *X = d_X + j0 * ldx;
-        launch_con_ax(stream, con_.rowptr, con_.col, con_.val, con_.choff, con_.maxchunks, m, X, ldx, k, con_.part, d_mu ? nullptr : con_.e.get(),
+        launch_con_ax(stream, con_.rowptr, con_.col, con_.val, con_.choff, con_.maxchunks, m, X, ldx, k, con_.part, (d_mu || homogeneous) ? nullptr : con_.e.get(),
                       d_mu ? con_.amu.get() : nullptr, con_.R);
         launch_con_apply(stream, con_.B, con_.Linv, con_.R, d_mu, X, ldx, (int)n, m, k);
     }

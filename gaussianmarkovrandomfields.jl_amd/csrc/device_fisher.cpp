@@ -1,0 +1,216 @@
+// device_fisher.cpp -- the Device's side of Fisher scoring on the device (include/gmrfx.h: gmrfx_obs_set, gmrfx_fisher_eval; kernels in
+// fisher.hip). The reference's loop (src/workspace/gaussian_approximation.jl:191-313) computes loggrad, loghessian, loglik and
+// Q_p x - h on the host at every iterate; here the likelihood is state of the handle, expanded to one value per node, and one pass over
+// Symmetric(Q_prior) (the values gmrfx_set_prior keeps) gives all four. Only two numbers reach the host.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <stdexcept>
+
+#include "device.h"
+#include "kernels.h"
+
+namespace gmrfx {
+
+#define HC(x) hip_check((x), #x)
+
+void Device::obs_set(const ObsHost &o) {
+    HC(hipSetDevice(device));
+    if (sharded() || batched()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
+    FisherDev f;         // built aside: a failed upload leaves the previous likelihood in place
+    if (o.nobs > 0) {
+        const size_t n = (size_t)S_->n;
+        std::vector<double> y(n, 0.0), aux(o.aux.empty() ? 0 : n, 0.0);
+        std::vector<unsigned char> mask(n, 0);
+        for (long long k = 0; k < o.nobs; k++) {
+            const size_t i = (size_t)o.idx[(size_t)k];
+            y[i] = o.y[(size_t)k];
+            if (!aux.empty()) aux[i] = o.aux[(size_t)k];
+            mask[i] = 1;
+        }
+        f.y.alloc(n, &bytes_total, kTableMinBytes);
+        f.mask.alloc(n, &bytes_total, kTableMinBytes);
+        HC(hipMemcpy(f.y, y.data(), n * sizeof(double), hipMemcpyHostToDevice));
+        HC(hipMemcpy(f.mask, mask.data(), n, hipMemcpyHostToDevice));
+        if (!aux.empty()) {
+            f.aux.alloc(n, &bytes_total, kTableMinBytes);
+            HC(hipMemcpy(f.aux, aux.data(), n * sizeof(double), hipMemcpyHostToDevice));
+        }
+        f.part.alloc(2 * (size_t)fisher_blocks((int)n), &bytes_total, kTableMinBytes);
+        f.out.alloc(6, &bytes_total, kTableMinBytes);        // 2 of the evaluation, 4 of the reductions
+        f.spart.alloc(4 * (size_t)fisher_stat_blocks((int)n), &bytes_total, kTableMinBytes);
+        f.h_out.alloc(6);
+        f.family = o.family;
+        f.param = o.param;
+        f.loglik_const = o.loglik_const;
+    }
+    HC(hipStreamSynchronize(stream));        // (an evaluation in flight on an external stream still reads the old arrays)
+    fisher_ = std::move(f);
+}
+
+void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host) {
+    HC(hipSetDevice(device));
+    if (sharded() || batched()) throw std::invalid_argument("fisher_eval: batched and sharded handles are not supported");
+    if (!d_x || !out_host) throw std::invalid_argument("fisher_eval: x / out is null");
+    if (!d_prior_) throw std::invalid_argument("fisher_eval: gmrfx_set_prior has not been called");
+    const long long n = S_->n;
+    if (n > INT_MAX) throw std::invalid_argument("fisher_eval: more than 2^31 - 1 nodes");
+    if (prior_diag_ < 0) {
+        prior_diag_ = hmap_cnt_ == n ? 1 : 0;
+        for (long long i = 0; i < n && prior_diag_; i++)
+            if (h_hmap_[(size_t)i] != sym.diag[(size_t)i]) prior_diag_ = 0;
+    }
+    if (!prior_diag_) throw std::invalid_argument("fisher_eval: the map of gmrfx_set_prior is not the position of (i, i) for every i (diagonal Hessians only)");
+    if (!obs_held()) throw std::invalid_argument("fisher_eval: no observation likelihood is set (gmrfx_obs_set)");
+    sym_rows_upload(sym);
+    const FisherEval a{(int)n, fisher_.family, sym_rows_.rp, sym_rows_.col, sym_rows_.pos, d_prior_, d_x, d_mu, fisher_.y, fisher_.aux.get(),
+                       fisher_.mask, fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0, d_score, d_hess, fisher_.part};
+    launch_fisher_eval(stream, a, fisher_.out);
+    HC(hipMemcpyAsync(fisher_.h_out, fisher_.out, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    out_host[0] = fisher_.h_out[0];
+    out_host[1] = fisher_.h_out[1] + fisher_.loglik_const;
+}
+
+// ---- the loop ------------------------------------------------------------------------------------------------------------------------
+// _merit_atol (condition/gaussian_approximation.jl:245)
+static double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
+
+int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
+                                   double *result, double *dec_trace, double *alpha_trace, long long *info) {
+    HC(hipSetDevice(device));
+    if (!d_x || !result) throw std::invalid_argument("gaussian_approximation: x / result is null");
+    if (o.max_iter < 0 || o.max_ls < 0) throw std::invalid_argument("gaussian_approximation: max_iter / max_linesearch_iter is negative");
+    const long long n = S_->n;
+    const size_t nb = (size_t)n * sizeof(double);
+    const bool adaptive = o.flags & 1, retry_full = o.flags & 2, predictive = o.flags & 4, refactor_final = o.flags & 8;
+    if (!d_prior_ || !obs_held()) {       // (the evaluation's own refusals, with its messages, before anything is allocated or written)
+        double ev[2];
+        fisher_eval(sym, d_x, d_mu, nullptr, nullptr, ev);
+    }
+    if (!fisher_.work) fisher_.work.alloc(6 * (size_t)n, &bytes_total, kTableMinBytes);
+    double *xk = fisher_.work, *xnew = xk + n, *cand = xk + 2 * n, *step = xk + 3 * n, *score = xk + 4 * n, *hess = xk + 5 * n;
+    if (d_x0) HC(hipMemcpyAsync(xk, d_x0, nb, hipMemcpyDeviceToDevice, stream));
+    else if (d_mu) HC(hipMemcpyAsync(xk, d_mu, nb, hipMemcpyDeviceToDevice, stream));
+    else HC(hipMemsetAsync(xk, 0, nb, stream));
+    if (info) *info = 0;
+    for (long long k = 0; k <= o.max_iter; k++) {
+        if (dec_trace) dec_trace[k] = std::nan("");
+        if (alpha_trace) alpha_trace[k] = std::nan("");
+    }
+    double nfact = 0, nsolve = 0, nmerit = 0, alpha = 1.0, dec_prev = 0.0, dec = std::nan("");
+    // the four reductions of the loop, to the host: {sum a b, sum (c - d)^2, sum d^2, max |b|}
+    auto stats = [&](const double *a, const double *b, const double *c, const double *d, double *out4) {
+        launch_fisher_stats(stream, (int)n, a, b, c, d, fisher_.spart, fisher_.out.get() + 2);
+        HC(hipMemcpyAsync(fisher_.h_out + 2, fisher_.out.get() + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HC(hipStreamSynchronize(stream));
+        for (int q = 0; q < 4; q++) out4[q] = fisher_.h_out[2 + q];
+    };
+    auto merit = [&](const double *x) {
+        double e[2];
+        fisher_eval(sym, x, d_mu, nullptr, nullptr, e);
+        nmerit += 1;
+        return e[0] - e[1];
+    };
+    // the step - A~' W^-1 (A step) of _workspace_constrain_with_matrix; false: W is not positive definite
+    auto project = [&](double *s) {
+        if (con_.m <= 0) return true;
+        if (!con_prepare()) return false;
+        con_correct(s, n, 1, nullptr, true);
+        return true;
+    };
+    auto finish = [&](const double *xfinal, long long iters, bool converged, bool frozen, bool failed = false) -> int {
+        HC(hipMemcpyAsync(d_x, xfinal, nb, hipMemcpyDeviceToDevice, stream));
+        int rc = 0;
+        if (!failed && (d_hess || refactor_final)) {
+            double e[2];
+            fisher_eval(sym, xfinal, d_mu, nullptr, hess, e);      // the final H(x_final) (_workspace_build_result)
+            if (d_hess) HC(hipMemcpyAsync(d_hess, hess, nb, hipMemcpyDeviceToDevice, stream));
+            if (refactor_final) {
+                refactorize_update(hess, true);
+                nfact += 1;
+                const long long fc = fail_col();
+                if (fc >= 0) { if (info) *info = fc + 1; rc = 1; }
+            }
+        }
+        HC(hipStreamSynchronize(stream));
+        const double r[8] = {(double)iters, converged ? 1.0 : 0.0, alpha, dec, nfact, nsolve, nmerit, frozen ? 1.0 : 0.0};
+        std::copy(r, r + 8, result);
+        return rc;
+    };
+    for (long long iter = 1; iter <= o.max_iter; iter++) {
+        double ek[2], st[4];
+        fisher_eval(sym, xk, d_mu, score, hess, ek);
+        refactorize_update_solve(hess, true, score, n, 1, step, n, true);
+        nfact += 1; nsolve += 1;
+        const long long fc = fail_col();
+        if (fc >= 0) {
+            if (info) *info = fc + 1;
+            finish(xk, iter - 1, false, false, true);
+            return 1;
+        }
+        if (!project(step)) { finish(xk, iter - 1, false, false, true); return 2; }
+        const double alpha_prev = alpha;
+        const double *xn = xnew;
+        if (adaptive) {
+            // _ga_line_search, line by line
+            const double obj_current = ek[0] - ek[1];
+            const double obj_accept = obj_current + merit_atol(std::fabs(ek[0]) + std::fabs(ek[1]));
+            bool done = false;
+            if (retry_full && alpha < 1.0) {
+                launch_fisher_candidate(stream, (int)n, xk, step, 1.0, xnew);
+                if (merit(xnew) <= obj_accept) { alpha = 1.0; done = true; }
+            }
+            if (!done) {
+                bool accept = false;
+                for (long long ls = 1; ls <= o.max_ls; ls++) {
+                    launch_fisher_candidate(stream, (int)n, xk, step, alpha, cand);
+                    if (merit(cand) <= obj_accept) {
+                        alpha = std::sqrt(alpha);
+                        accept = true;
+                        break;
+                    }
+                    alpha *= 0.1;
+                    stats(nullptr, step, nullptr, nullptr, st);
+                    if (alpha * st[3] < o.dec_tol / 1000) { accept = true; break; }
+                }
+                if (accept) xn = cand;
+                else launch_fisher_candidate(stream, (int)n, xk, step, alpha, xnew);
+            }
+        } else launch_fisher_candidate(stream, (int)n, xk, step, 1.0, xnew);
+        stats(score, step, xn, xk, st);
+        dec = st[0];
+        const double mean_change = std::sqrt(st[1]), mean_change_rel = mean_change / std::max(std::sqrt(st[2]), 1.0e-10);
+        if (dec_trace) dec_trace[iter - 1] = dec;
+        if (alpha_trace) alpha_trace[iter - 1] = alpha;
+        if (dec < o.dec_tol || mean_change < o.mean_tol || mean_change_rel < o.mean_tol) return finish(xn, iter, true, false);
+        // _predict_converged, then _frozen_finish: three chord steps on the factorisation in hand, only the first decides
+        if (predictive && iter > 1 && alpha == 1.0 && alpha_prev == 1.0 && dec * (dec / dec_prev) * (dec / dec_prev) < o.dec_tol) {
+            double *xf = xn == cand ? xnew : cand;          // (the accepted iterate stays where it is until the look-ahead has decided)
+            HC(hipMemcpyAsync(xf, xn, nb, hipMemcpyDeviceToDevice, stream));
+            bool ok = true;
+            for (int j = 1; j <= 3 && ok; j++) {
+                double e[2];
+                fisher_eval(sym, xf, d_mu, score, nullptr, e);
+                solve(score, n, 1, step, n, true, 0);
+                nsolve += 1;
+                if (!project(step)) { finish(xn, iter, false, false, true); return 2; }
+                if (j == 1) {
+                    stats(score, step, nullptr, nullptr, st);
+                    if (!(st[0] < o.dec_tol)) { ok = false; break; }
+                    dec = st[0];
+                    if (dec_trace) dec_trace[iter] = dec;
+                    if (alpha_trace) alpha_trace[iter] = alpha;
+                }
+                launch_fisher_candidate(stream, (int)n, xf, step, 1.0, xf);
+            }
+            if (ok) return finish(xf, iter + 1, true, true);
+        }
+        dec_prev = dec;
+        if (xn != xk) HC(hipMemcpyAsync(xk, xn, nb, hipMemcpyDeviceToDevice, stream));
+    }
+    return finish(xk, o.max_iter, false, false);
+}
+
+}  // namespace gmrfx

@@ -228,4 +228,28 @@ void launch_grad_mubar(hipStream_t st, const GradMean &a, int nb);
 void launch_grad_dot(hipStream_t st, long long nnz, const unsigned char *wgt, const double *G, const double *J, long long ldj, long long sj, int p,
                      int nb, double *part, double *out);
 
+// fisher.hip -- one pass over Symmetric(Q_prior) for a Fisher-scoring iterate (gmrfx_fisher_eval): a lane group of kFisherLanes lanes per
+// row, kFisherRows rows per workgroup of 256 threads; the final pass adds the workgroups' partial sums with kFisherFinal threads.
+constexpr int kFisherLanes = 16, kFisherRows = 16, kFisherFinal = 256;
+struct FisherEval {
+    int n, family;
+    const long long *rp;         // Symmetric(Q) by rows (RbmcSym), as GradMean
+    const int *col, *pos;
+    const double *val, *x, *mu;  // the prior's values; the point; the prior mean (nullable: h = 0)
+    const double *y, *aux;       // the likelihood by node (aux nullable)
+    const unsigned char *mask;   // 1: the node has an observation
+    double param, logparam;
+    double *score, *hess;        // n each, either nullable
+    double *part;                // 2 per workgroup: energy, loglik
+};
+inline int fisher_blocks(int n) { return (n + kFisherRows - 1) / kFisherRows; }
+// out[0] = sum of the energy partials, out[1] = sum of the loglik partials (device)
+void launch_fisher_eval(hipStream_t st, const FisherEval &a, double *out);
+// the loop's vector work (gmrfx_gaussian_approximation): out = x - alpha s; and out4 = {sum a b, sum (c - d)^2, sum d^2, max |b|} over n
+// entries (a pair with a null member is left at 0), in chunks of kFisherStatChunk entries; part: 4 per chunk
+constexpr int kFisherStatChunk = 4096;
+inline int fisher_stat_blocks(int n) { return (n + kFisherStatChunk - 1) / kFisherStatChunk; }
+void launch_fisher_candidate(hipStream_t st, int n, const double *x, const double *s, double alpha, double *out);
+void launch_fisher_stats(hipStream_t st, int n, const double *a, const double *b, const double *c, const double *d, double *part, double *out4);
+
 }  // namespace gmrfx

@@ -493,6 +493,104 @@ class MI355XBackend:
         self.last_info = info.value
         return info.value
 
+    # -- Fisher scoring on the device (src/workspace/gaussian_approximation.jl:191-313; include/gmrfx.h "Fisher scoring") ------
+    OBS_FAMILIES = {"normal": 0, "poisson": 1, "bernoulli": 2, "binomial": 3, "negbin": 4, "gamma": 5}
+
+    def set_observations(self, family, y, indices=None, aux=None, param: float = 0.0, index_base: int = 0) -> None:
+        """The observation likelihood as state of the handle (gmrfx_obs_set). family: a name of OBS_FAMILIES or its id; y: one value
+        per observation; indices: the observed nodes (None: every node in order); aux: log exposure (Poisson, NegBin) or trials
+        (Binomial); param: sigma (Normal), r (NegBin), phi (Gamma). An empty y removes the likelihood."""
+        fam = self.OBS_FAMILIES[family] if isinstance(family, str) else int(family)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        ax = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).reshape(-1)
+        if (idx is not None and idx.size != yy.size) or (ax is not None and ax.size != yy.size):
+            raise ValueError("indices / aux do not have one entry per observation")
+        check(lib().gmrfx_obs_set(self._h, fam, yy.size, ptr(idx), int(index_base), ptr(yy), ptr(ax), float(param)), self._h)
+
+    def observations_info(self) -> dict:
+        fam, nobs, c = C.c_int32(0), C.c_int64(0), C.c_double(0.0)
+        check(lib().gmrfx_obs_info(self._h, C.byref(fam), C.byref(nobs), C.byref(c)), self._h)
+        return {"family": fam.value, "nobs": nobs.value, "loglik_const": c.value}
+
+    def fisher_eval(self, x, mean=None, want_score: bool = True, want_hess: bool = True):
+        """(score, hess, energy, loglik) at the point x (gmrfx_fisher_eval): score = Q_p x - Q_p mean - loggrad(x), hess = the diagonal
+        of loghessian(x), energy = x' Q_p x / 2 - x' Q_p mean, loglik(x); Q_p = the values of set_prior. score / hess are None when
+        not asked for."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        if xx.shape != (self.n,) or (mu is not None and mu.shape != (self.n,)):
+            raise ValueError("dimension mismatch")
+        score = np.empty(self.n) if want_score else None
+        hess = np.empty(self.n) if want_hess else None
+        out = np.empty(2)
+        check(lib().gmrfx_fisher_eval(self._h, ptr(xx), ptr(mu), ptr(score), ptr(hess), ptr(out)), self._h)
+        return score, hess, float(out[0]), float(out[1])
+
+    def fisher_eval_dev(self, d_x: int, d_mu: int = 0, d_score: int = 0, d_hess: int = 0):
+        """Device pointers: x (n), mean (n, 0 = zero), score and hess outputs (n each, 0 = not computed); returns (energy, loglik)."""
+        if not d_x:
+            raise ValueError("fisher_eval_dev: null pointer")
+        out = np.empty(2)
+        check(lib().gmrfx_fisher_eval_dev(self._h, d_x, d_mu or None, d_score or None, d_hess or None, ptr(out)), self._h)
+        return float(out[0]), float(out[1])
+
+    @staticmethod
+    def _ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final):
+        if step_recovery not in ("retry_full", "sqrt"):
+            raise ValueError("step_recovery must be 'retry_full' or 'sqrt'")
+        return int(adaptive_stepsize) | (int(step_recovery == "retry_full") << 1) | (int(predictive_convergence) << 2) | (int(refactorize_final) << 3)
+
+    @staticmethod
+    def _ga_info(res, dec, alp):
+        used = ~np.isnan(dec)
+        return {"iterations": int(res[0]), "converged": bool(res[1]), "alpha": float(res[2]), "newton_decrement": float(res[3]),
+                "factorizations": int(res[4]), "solves": int(res[5]), "merit_evaluations": int(res[6]), "frozen_finish": bool(res[7]),
+                "dec_trace": dec[used].copy(), "alpha_trace": alp[used].copy()}
+
+    def gaussian_approximation(self, mean=None, x0=None, max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5,
+                               adaptive_stepsize: bool = True, max_linesearch_iter: int = 10, step_recovery: str = "retry_full",
+                               predictive_convergence: bool = True, refactorize_final: bool = False):
+        """The reference's gaussian_approximation(prior::WorkspaceGMRF, obs_lik) on the device (gmrfx_gaussian_approximation): prior =
+        the values of set_prior with mean `mean`, likelihood = set_observations. Returns (mode, hess = the diagonal of
+        loghessian(mode), info dict of the counters and the decrement / alpha traces). A failed factorisation raises PosDefException;
+        last_info holds the failing step."""
+        mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        xs = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
+        if (mu is not None and mu.shape != (self.n,)) or (xs is not None and xs.shape != (self.n,)):
+            raise ValueError("dimension mismatch")
+        x, hess, res = np.empty(self.n), np.empty(self.n), np.zeros(8)
+        dec, alp = np.full(max_iter + 1, np.nan), np.full(max_iter + 1, np.nan)
+        info = C.c_int64(0)
+        flags = self._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+        rc = lib().gmrfx_gaussian_approximation(self._h, ptr(mu), ptr(xs), max_iter, max_linesearch_iter, float(mean_change_tol),
+                                                float(newton_dec_tol), flags, ptr(x), ptr(hess), ptr(res), ptr(dec), ptr(alp), C.byref(info))
+        self._selinv_cache = None
+        self._selinv_diag_cache = None
+        self.last_info = info.value
+        self.last_x = x
+        check(rc, self._h)
+        return x, hess, self._ga_info(res, dec, alp)
+
+    def gaussian_approximation_dev(self, d_x: int, d_hess: int = 0, d_mu: int = 0, d_x0: int = 0, max_iter: int = 50,
+                                   mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5, adaptive_stepsize: bool = True,
+                                   max_linesearch_iter: int = 10, step_recovery: str = "retry_full", predictive_convergence: bool = True,
+                                   refactorize_final: bool = False) -> dict:
+        """Device pointers: the mode x (n) and hess (n, 0 = not wanted) outputs, mean and x0 (n each, 0 = none). Returns the info dict."""
+        if not d_x:
+            raise ValueError("gaussian_approximation_dev: null pointer")
+        res = np.zeros(8)
+        dec, alp = np.full(max_iter + 1, np.nan), np.full(max_iter + 1, np.nan)
+        info = C.c_int64(0)
+        flags = self._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+        rc = lib().gmrfx_gaussian_approximation_dev(self._h, d_mu or None, d_x0 or None, max_iter, max_linesearch_iter, float(mean_change_tol),
+                                                    float(newton_dec_tol), flags, d_x, d_hess or None, ptr(res), ptr(dec), ptr(alp), C.byref(info))
+        self._selinv_cache = None
+        self._selinv_diag_cache = None
+        self.last_info = info.value
+        check(rc, self._h)
+        return self._ga_info(res, dec, alp)
+
     # -- sharded factorisation (include/gmrfx.h "sharded factorisation"; driver: gmrfx/shard.py) -------
     def refactorize_phase_dev(self, d_nzval_ptr: int, phase: int) -> None:
         check(lib().gmrfx_refactorize_phase(self._h, d_nzval_ptr, phase), self._h)

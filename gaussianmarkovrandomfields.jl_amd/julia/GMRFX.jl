@@ -368,6 +368,125 @@ end
 function logpdf_grad_dev! end   # ROCArray methods: ext/GMRFXAMDGPUExt.jl
 function pattern_dot_dev end
 
+# Fisher scoring on the device (include/gmrfx.h "Fisher scoring"): the observation likelihood as state of the handle. family: a key of
+# OBS_FAMILIES or its id; indices: the observed nodes, 1-based as the reference's `lik.indices` (nothing: every node in order); aux: log
+# exposure (Poisson, NegBin) or trials (Binomial); param: sigma / r / phi. An empty y removes the likelihood.
+const OBS_FAMILIES = (normal = 0, poisson = 1, bernoulli = 2, binomial = 3, negbin = 4, gamma = 5)
+function set_observations!(b::MI355XBackend, family::Union{Symbol, Integer}, y::Vector{Float64};
+                           indices::Union{Nothing, Vector{Int64}} = nothing, aux::Union{Nothing, Vector{Float64}} = nothing, param::Real = 0.0)
+    fam = family isa Symbol ? getfield(OBS_FAMILIES, family) : Int(family)
+    (indices === nothing || length(indices) == length(y)) && (aux === nothing || length(aux) == length(y)) ||
+        throw(DimensionMismatch("indices / aux must have one entry per observation"))
+    pidx = indices === nothing ? Ptr{Int64}(C_NULL) : pointer(indices)
+    paux = aux === nothing ? Ptr{Float64}(C_NULL) : pointer(aux)
+    GC.@preserve y indices aux check(ccall((:gmrfx_obs_set, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Int32, Ptr{Float64}, Ptr{Float64}, Float64),
+        b.h.ptr, Int32(fam), length(y), pidx, Int32(1), y, paux, Float64(param)), b.h)
+    return b
+end
+function observations_info(b::MI355XBackend)
+    fam = Ref{Int32}(0); nobs = Ref{Int64}(0); c = Ref{Float64}(0.0)
+    check(ccall((:gmrfx_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Float64}), b.h.ptr, fam, nobs, c), b.h)
+    return (family = fam[], nobs = nobs[], loglik_const = c[])
+end
+# (score, hess, energy, loglik) at x, one pass over the prior gmrfx_set_prior keeps: score = Q_p x - Q_p mean - loggrad(x), hess = the
+# diagonal of loghessian(x) -- the operands of one Newton step --, energy = x'Q_p x / 2 - x'Q_p mean, loglik(x)
+function fisher_eval(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, Vector{Float64}} = nothing)
+    length(x) == b.n && (mean === nothing || length(mean) == b.n) || throw(DimensionMismatch("x and mean must have n entries"))
+    score = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, b.n); out = zeros(2)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    GC.@preserve x mean score hess out check(ccall((:gmrfx_fisher_eval, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, x, mu, score, hess, out), b.h)
+    return score, hess, out[1], out[2]
+end
+function fisher_eval_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
+
+# The whole Fisher-scoring loop on the device (gmrfx_gaussian_approximation; include/gmrfx.h): prior = the values of set_prior! with
+# mean `mean`, likelihood = set_observations!, constraint = set_constraints! (projected with e = 0). Returns (mode, hess = the diagonal
+# of loghessian(mode), info) with info = (iterations, converged, alpha, newton_decrement, factorizations, solves, merit_evaluations,
+# frozen_finish, dec_trace, alpha_trace). A failed factorisation throws PosDefException.
+_ga_flags(adaptive_stepsize::Bool, step_recovery::Symbol, predictive_convergence::Bool, refactorize_final::Bool) =
+    Int32(adaptive_stepsize) | (Int32(G._retry_full_step(step_recovery)) << 1) | (Int32(predictive_convergence) << 2) | (Int32(refactorize_final) << 3)
+function _ga_info(res::Vector{Float64}, dec::Vector{Float64}, alp::Vector{Float64})
+    used = .!isnan.(dec)
+    return (iterations = Int(res[1]), converged = res[2] != 0, alpha = res[3], newton_decrement = res[4], factorizations = Int(res[5]),
+            solves = Int(res[6]), merit_evaluations = Int(res[7]), frozen_finish = res[8] != 0, dec_trace = dec[used], alpha_trace = alp[used])
+end
+function gaussian_approximation_device(b::MI355XBackend; mean::Union{Nothing, Vector{Float64}} = nothing, x0::Union{Nothing, Vector{Float64}} = nothing,
+                                       max_iter::Int = 50, mean_change_tol::Real = 1.0e-4, newton_dec_tol::Real = 1.0e-5,
+                                       adaptive_stepsize::Bool = true, max_linesearch_iter::Int = 10, step_recovery::Symbol = :retry_full,
+                                       predictive_convergence::Bool = true, refactorize_final::Bool = false)
+    (mean === nothing || length(mean) == b.n) && (x0 === nothing || length(x0) == b.n) || throw(DimensionMismatch("mean and x0 must have n entries"))
+    x = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, b.n); res = zeros(8)
+    dec = fill(NaN, max_iter + 1); alp = fill(NaN, max_iter + 1); info = Ref{Int64}(0)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    xs = x0 === nothing ? Ptr{Float64}(C_NULL) : pointer(x0)
+    flags = _ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+    code = GC.@preserve mean x0 x hess res dec alp ccall((:gmrfx_gaussian_approximation, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+        b.h.ptr, mu, xs, max_iter, max_linesearch_iter, Float64(mean_change_tol), Float64(newton_dec_tol), flags, x, hess, res, dec, alp, info)
+    b.selinv_cache = nothing
+    b.selinv_diag_cache = nothing
+    info[] > 0 && throw(PosDefException(Int(info[])))
+    check(code, b.h)
+    return x, hess, _ga_info(res, dec, alp)
+end
+function gaussian_approximation_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
+
+# gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313) for workspaces on
+# this backend and the pointwise exponential-family likelihoods the device evaluates: one method per likelihood type, each more
+# specific than the reference's (WorkspaceGMRF, ObservationLikelihood) method. Everything else -- other links, Student-t, generic and
+# AD likelihoods, LatentPrior -- keeps the reference's method by dispatch, and NormalLikelihood{IdentityLink} keeps the reference's
+# own conjugate method (linear_condition), as in the reference itself.
+_obs_indices(::Nothing) = nothing
+_obs_indices(idx) = collect(Int64, idx)
+_obs_offset(::Nothing, k::Int) = nothing
+_obs_offset(o::Real, k::Int) = fill(Float64(o), k)
+_obs_offset(o::AbstractVector, k::Int) = Vector{Float64}(o)
+device_likelihood(l::G.PoissonLikelihood{G.LogLink}) = (1, Vector{Float64}(l.y), _obs_indices(l.indices), _obs_offset(l.logexposure, length(l.y)), 0.0)
+device_likelihood(l::G.BernoulliLikelihood{G.LogitLink}) = (2, Vector{Float64}(l.y), _obs_indices(l.indices), nothing, 0.0)
+device_likelihood(l::G.BinomialLikelihood{G.LogitLink}) = (3, Vector{Float64}(l.y), _obs_indices(l.indices), Vector{Float64}(l.n), 0.0)
+device_likelihood(l::G.NegBinLikelihood{G.LogLink}) = (4, Vector{Float64}(l.y), _obs_indices(l.indices), _obs_offset(l.logexposure, length(l.y)), Float64(l.r))
+device_likelihood(l::G.GammaLikelihood{G.LogLink}) = (5, Vector{Float64}(l.y), _obs_indices(l.indices), nothing, Float64(l.phi))
+
+function _device_gaussian_approximation(prior::G.WorkspaceGMRF, obs_lik; x0::Union{Nothing, AbstractVector} = nothing, max_iter::Int = 50,
+                                        mean_change_tol::Real = 1.0e-4, newton_dec_tol::Real = 1.0e-5, adaptive_stepsize::Bool = true,
+                                        max_linesearch_iter::Int = 10, step_recovery::Symbol = :retry_full,
+                                        predictive_convergence::Bool = true, verbose::Bool = false)
+    ws = prior.workspace
+    b = ws.backend
+    ci = prior.constraints
+    if ci !== nothing && size(ci.matrix, 1) > MAX_DEVICE_CONSTRAINTS       # more rows than the device's constraint state takes: the reference's loop
+        return invoke(G.gaussian_approximation, Tuple{G.WorkspaceGMRF, G.ObservationLikelihood}, prior, obs_lik; x0, max_iter, mean_change_tol,
+                      newton_dec_tol, adaptive_stepsize, max_linesearch_iter, step_recovery, predictive_convergence, verbose)
+    end
+    G.ensure_loaded!(prior)
+    fam, y, idx, aux, param = device_likelihood(obs_lik)
+    Qp = copy(ws.Q.nzval)
+    diag_idx = G._diagonal_indices(ws.Q)
+    set_prior!(b, Qp, Vector{Int}(diag_idx))
+    set_observations!(b, fam, y; indices = idx, aux = aux, param = param)
+    sync_constraints!(b, ci)
+    x, hess, info = gaussian_approximation_device(b; mean = Vector{Float64}(prior.mean), x0 = x0 === nothing ? nothing : Vector{Float64}(x0),
+                                                  max_iter, mean_change_tol, newton_dec_tol, adaptive_stepsize, max_linesearch_iter,
+                                                  step_recovery, predictive_convergence)
+    verbose && println(info.converged ? "  Converged after $(info.iterations) iterations" : "  Reached max_iter without convergence")
+    # _workspace_build_result: ws.Q <- Q_p - H(x_final), not factorised eagerly; the constraints are re-applied by _build_result
+    G._update_hessian!(ws, Diagonal(hess), Qp, diag_idx, nothing)
+    return G._build_result(ws, x, ci)
+end
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.PoissonLikelihood{G.LogLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.BernoulliLikelihood{G.LogitLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.BinomialLikelihood{G.LogitLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.NegBinLikelihood{G.LogLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.GammaLikelihood{G.LogLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+
 # `_rand!` on given draws: X = P' L^-T Z + mean, then the constraint correction when the handle holds one
 function sample(b::MI355XBackend, Z::Matrix{Float64}, mean::Union{Nothing, Vector{Float64}} = nothing)
     X = similar(Z)

@@ -20,7 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
-import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev
+import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev, fisher_eval_dev!, gaussian_approximation_dev!, _ga_flags, _ga_info
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -143,6 +143,38 @@ function logpdf_grad_dev!(Qbar::ROCVector{Float64}, mubar::ROCVector{Float64}, b
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}),
         b.h.ptr, nz, devptr(z), mu, Float64(ybar), devptr(Qbar), devptr(mubar)), b.h)
     return Qbar, mubar
+end
+# one evaluation of a Fisher-scoring iterate with everything resident in HBM: score and hess are written, (energy, loglik) returned
+function fisher_eval_dev!(score::ROCVector{Float64}, hess::ROCVector{Float64}, b::MI355XBackend, x::ROCVector{Float64};
+                          mean::Union{Nothing, ROCVector{Float64}} = nothing)
+    length(x) == b.n && length(score) == b.n && length(hess) == b.n || throw(DimensionMismatch("x, score and hess must have n entries"))
+    AMDGPU.synchronize()
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : devptr(mean)
+    out = zeros(2)
+    GC.@preserve score hess x mean out check(ccall((:gmrfx_fisher_eval_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, devptr(x), mu, devptr(score), devptr(hess), out), b.h)
+    return out[1], out[2]
+end
+# the whole loop with the mode and the final Hessian written to ROCArrays; mean and x0 resident in HBM as well; returns the info tuple
+function gaussian_approximation_dev!(x::ROCVector{Float64}, hess::ROCVector{Float64}, b::MI355XBackend;
+                                     mean::Union{Nothing, ROCVector{Float64}} = nothing, x0::Union{Nothing, ROCVector{Float64}} = nothing,
+                                     max_iter::Int = 50, mean_change_tol::Real = 1.0e-4, newton_dec_tol::Real = 1.0e-5,
+                                     adaptive_stepsize::Bool = true, max_linesearch_iter::Int = 10, step_recovery::Symbol = :retry_full,
+                                     predictive_convergence::Bool = true, refactorize_final::Bool = false)
+    length(x) == b.n && length(hess) == b.n || throw(DimensionMismatch("x and hess must have n entries"))
+    AMDGPU.synchronize()
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : devptr(mean)
+    xs = x0 === nothing ? Ptr{Float64}(C_NULL) : devptr(x0)
+    res = zeros(8); dec = fill(NaN, max_iter + 1); alp = fill(NaN, max_iter + 1); info = Ref{Int64}(0)
+    flags = _ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+    code = GC.@preserve x hess mean x0 res dec alp ccall((:gmrfx_gaussian_approximation_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Int64}),
+        b.h.ptr, mu, xs, max_iter, max_linesearch_iter, Float64(mean_change_tol), Float64(newton_dec_tol), flags, devptr(x), devptr(hess), res, dec, alp, info)
+    _invalidate!(b)
+    info[] > 0 && throw(PosDefException(Int(info[])))
+    check(code, b.h)
+    return _ga_info(res, dec, alp)
 end
 # the members of a batch: Qbar nnz x B, mubar / Z / mean n x B; returns info
 function logpdf_grad_dev!(Qbar::ROCMatrix{Float64}, mubar::ROCMatrix{Float64}, bb::MI355XBatch, Z::ROCMatrix{Float64}, ybar::Vector{Float64};

@@ -633,6 +633,73 @@ int32_t gmrfx_batch_pattern_dot(gmrfx_handle *h, const double *G /* nnz x nbatch
 int32_t gmrfx_batch_pattern_dot_dev(gmrfx_handle *h, const double *d_G, const double *d_J, int64_t ldj, int64_t sj, int64_t p,
                                     double *out /* host, p x nbatch */);
 
+/* ---- Fisher scoring on the device: the observation likelihood as state of a plain handle, one fused evaluation ----------------------
+ * What the reference's Gaussian-approximation loop (src/workspace/gaussian_approximation.jl:191-313, line search and merit:
+ * src/arithmetic/condition/gaussian_approximation.jl:231-409) computes on the host at every iterate besides the factorisation --
+ * loggrad, loghessian, loglik, Q_p x - h -- for the pointwise exponential-family likelihoods with a canonical or log link
+ * (src/observation_models/exponential_family/canonical_implementations.jl:146-327, helpers.jl:5-31). eta_i = x[indices[i]]:
+ *   family  0 Normal / identity      param sigma                  g = (y - eta) / sigma^2          d = -1 / sigma^2
+ *           1 Poisson / log          aux = log exposure (NULL 0)  g = y - mu, mu = exp(eta + aux)  d = -mu
+ *           2 Bernoulli / logit                                   g = y - mu, mu = logistic(eta)   d = -mu (1 - mu)
+ *           3 Binomial / logit       aux = trials (required)      g = y - n mu                     d = -n mu (1 - mu)
+ *           4 NegBinomial / log      aux = log exposure, param r  g = r (y - mu) / (r + mu)        d = -r mu (r + y) / (r + mu)^2
+ *           5 Gamma / log            param phi                    g = phi (y / mu - 1)             d = -phi y / mu
+ * g = dl/deta, d = d2l/deta2, l the log density of one observation; a node without an observation has g = d = l = 0 exactly
+ * (_embed_grad, _embed_diag). Every term is evaluated in a form that is stable for every eta (csrc/fisher.hip, "STABLE FORMS").
+ * gmrfx_obs_set validates, sums the terms of loglik that do not depend on x in long double (loglik_const: -lgamma(y + 1), the
+ * binomial coefficients, the Normal / NegBinomial / Gamma constants) and expands y, aux and an observed mask to one value per node
+ * on the device. indices NULL = nodes 1 .. n in order (needs nobs == n). nobs = 0 removes the likelihood. gmrfx_clone carries it.
+ * Works on symbolic_only handles (validation and loglik_const only). gmrfx_obs_info: family (-1: none), nobs, loglik_const; each nullable.
+ * Refused with GMRFX_ERR_INVALID_ARG, a message and nothing changed: an unknown family, nobs outside [0, n], an index outside the
+ * range, a node observed twice (the reference's g[indices] .= g_obs would silently keep the last), indices == NULL with nobs != n,
+ * no aux for the binomial family, sigma / r / phi not positive, y (or aux) not finite, a negative count, a Bernoulli y above 1,
+ * y above the number of trials, a Gamma y that is not positive, a batched handle (gmrfx_batch_size > 1), a sharded handle.
+ * gmrfx_fisher_eval: at the point x, with Q_p the values gmrfx_set_prior keeps, h = Q_p mu (mu NULL: h = 0), in one pass over
+ * Symmetric(Q_p) (the triangle not in use is never read):
+ *   score_i = ((Q_p x)_i - h_i) - g_i(x_i)     the reference's neg_score_k; n values, nullable (not computed)
+ *   hess_i  = d_i(x_i)                          n values, nullable: the hvals of gmrfx_refactorize_update under the diagonal map
+ *   out[0]  = sum_i (0.5 x_i (Q_p x)_i - x_i h_i) = 1/2 x' Q_p x - x' h;   out[1] = loglik(x), loglik_const included
+ * in these associations. No atomics: every sum is formed in an order that depends on indices only; results are bit-reproducible,
+ * independent of the alignment of the operands, and the host and the _dev forms agree bit for bit. Needs no factorisation and leaves
+ * the handle's factorisation as it is.
+ * Errors: GMRFX_ERR_INVALID_ARG with a message when x or out is null, no likelihood is set, gmrfx_set_prior has not been called or
+ * was called with a map that is not "the position of (i, i) for every i" (cnt == n: diagonal Hessians only), a batched or sharded
+ * handle; GMRFX_ERR_NO_DEVICE for symbolic_only handles (after the argument checks that need no device state).
+ * LIMITS: plain handles, pointwise likelihoods with a diagonal Hessian, n < 2^31. Student-t (not concave), LatentPrior and generic
+ * likelihoods stay on the gmrfx_refactorize_update path, driven from the host. */
+int32_t gmrfx_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices /* nobs, nullable */, int32_t index_base,
+                      const double *y /* nobs */, const double *aux /* nobs, nullable */, double param);
+int32_t gmrfx_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const);
+int32_t gmrfx_fisher_eval(gmrfx_handle *h, const double *x, const double *mu /* nullable */, double *score /* n, nullable */,
+                          double *hess /* n, nullable */, double *out /* host, 2: energy, loglik */);
+int32_t gmrfx_fisher_eval_dev(gmrfx_handle *h, const double *d_x, const double *d_mu, double *d_score, double *d_hess,
+                              double *out /* host, 2: energy, loglik */);
+/* The loop itself: gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313)
+ * with _ga_line_search, _predict_converged and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409 restated
+ * line by line in host C++; every vector (x_k, step, score, hess, the line search's candidates) stays in HBM, the host reads a handful
+ * of scalars per iterate. Per iterate: gmrfx_fisher_eval at x_k, gmrfx_refactorize_update_solve_dev with its hess and score, with a
+ * constraint set the projection step - A~' W^-1 (A step) (the correction of gmrfx_constraints_correct with e = 0), the line search on
+ * merit = energy - loglik (accepting up to obj + 64 eps max(|energy| + |loglik|, 1); the full step is probed first under retry_full
+ * when alpha < 1; x0.1 per backtrack, alpha <- sqrt(alpha) on acceptance, exit when alpha |step|_inf < newton_dec_tol / 1000; NaN or
+ * +Inf merits are rejections), the three-way convergence test (Newton decrement dot(score, step), |x_new - x_k|, the same relative to
+ * |x_k|), the look-ahead and three chord steps on the factorisation in hand, of which only the first decides.
+ * mu NULL = zero prior mean; x0 NULL = mu. flags: bit 0 adaptive_stepsize, 1 step_recovery == :retry_full, 2 predictive_convergence,
+ * 3 leave the handle factorised at Q_prior - H(x_final) (without it the handle holds the last iterate's factor, as the reference's
+ * workspace does). x: the mode, n. hess: H(x_final), n, nullable. result (host, 8) = {iterations, converged, final alpha, last Newton
+ * decrement, factorisations, solves, merit evaluations, 1 if the frozen finish produced the result}. dec_trace / alpha_trace (host,
+ * max_iter + 1 each, nullable): per iterate, the frozen finish's deciding step after the last; unused entries are NaN.
+ * Errors: those of gmrfx_fisher_eval; INVALID_ARG for negative max_iter / max_linesearch_iter and unknown flag bits;
+ * GMRFX_ERR_NOT_POSDEF when a factorisation fails, with *info as gmrfx_refactorize reports it, x = the last accepted iterate and the
+ * handle usable afterwards (also when A Q^-1 A' fails, *info = 0). LIMITS: as gmrfx_fisher_eval. */
+int32_t gmrfx_gaussian_approximation(gmrfx_handle *h, const double *mu /* nullable */, const double *x0 /* nullable */, int64_t max_iter,
+                                     int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol, int32_t flags,
+                                     double *x /* n */, double *hess /* n, nullable */, double *result /* host, 8 */,
+                                     double *dec_trace /* host, max_iter + 1, nullable */, double *alpha_trace /* same */, int64_t *info);
+int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, const double *d_x0, int64_t max_iter,
+                                         int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol, int32_t flags,
+                                         double *d_x, double *d_hess, double *result /* host, 8 */, double *dec_trace /* host */,
+                                         double *alpha_trace /* host */, int64_t *info);
+
 #ifdef __cplusplus
 }
 #endif
