@@ -32,27 +32,55 @@ static double obs_loglik_const(const ObsHost &o) {
     return (double)c;
 }
 
+// ---- what gmrfx_obs_set and gmrfx_obs_set_design check alike (who: the prefix of the messages) -------------------------------------------
+static void obs_check_handle(const gmrfx_handle *h, const std::string &who) {
+    check_unsharded(h, (who + "sharded handles are not supported").c_str());
+    if (h->nbatch > 1) throw std::invalid_argument(who + "batched handles are not supported");
+}
+static void obs_check_family(const std::string &who, int32_t family) {
+    if (family < 0 || family >= kObsFamilies) throw std::invalid_argument(who + "unknown family (0 Normal, 1 Poisson, 2 Bernoulli, 3 Binomial, 4 NegativeBinomial, 5 Gamma)");
+}
+static void obs_check_operands(const std::string &who, int32_t family, const double *y, const double *aux, double param) {
+    if (!y) throw std::invalid_argument(who + "y is null");
+    if (family == 3 && !aux) throw std::invalid_argument(who + "the binomial family needs aux (the number of trials)");
+    if ((family == 0 || family == 4 || family == 5) && !(param > 0.0 && std::isfinite(param)))
+        throw std::invalid_argument(who + "sigma / r / phi must be positive and finite");
+}
+// y, aux, param and loglik_const of o, observation by observation
+static void obs_fill_values(ObsHost &o, const std::string &who, int32_t family, int64_t nobs, const double *y, const double *aux, double param) {
+    o.family = family; o.nobs = nobs; o.param = param;
+    o.y.assign(y, y + nobs);
+    if (aux && family != 0 && family != 2 && family != 5) o.aux.assign(aux, aux + nobs);      // (the others have no auxiliary number)
+    for (int64_t k = 0; k < nobs; k++) {
+        const double yk = o.y[(size_t)k];
+        const std::string at = " (observation " + std::to_string(k) + ")";
+        if (!std::isfinite(yk)) throw std::invalid_argument(who + "y is not finite" + at);
+        if (!o.aux.empty() && !std::isfinite(o.aux[(size_t)k])) throw std::invalid_argument(who + "aux is not finite" + at);
+        if (family >= 1 && family <= 4 && yk < 0.0) throw std::invalid_argument(who + "negative count" + at);
+        if (family == 2 && yk > 1.0) throw std::invalid_argument(who + "a Bernoulli observation above 1" + at);
+        if (family == 3 && !(o.aux[(size_t)k] >= 0.0 && yk <= o.aux[(size_t)k])) throw std::invalid_argument(who + "y exceeds the number of trials" + at);
+        if (family == 5 && !(yk > 0.0)) throw std::invalid_argument(who + "a Gamma observation must be positive" + at);
+    }
+    o.loglik_const = obs_loglik_const(o);
+}
+
 extern "C" int32_t gmrfx_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices, int32_t index_base, const double *y,
                                  const double *aux, double param) {
     return guarded(h, [&]() -> int32_t {
-        check_unsharded(h, "obs_set: sharded handles are not supported");
-        if (h->nbatch > 1) throw std::invalid_argument("obs_set: batched handles are not supported");
+        const std::string who = "obs_set: ";
+        obs_check_handle(h, who);
         const int64_t n = h->S.n;
-        if (nobs == 0) {        // removes the likelihood
+        if (nobs == 0) {        // removes the likelihood, of either form
             if (h->D) h->D->obs_set(ObsHost{});
             h->obs = ObsHost{};
             return GMRFX_OK;
         }
-        if (family < 0 || family >= kObsFamilies) throw std::invalid_argument("obs_set: unknown family (0 Normal, 1 Poisson, 2 Bernoulli, 3 Binomial, 4 NegativeBinomial, 5 Gamma)");
+        obs_check_family(who, family);
         if (nobs < 0 || nobs > n) throw std::invalid_argument("obs_set: nobs outside [0, n]");
         check_index_base(index_base, "obs_set: ");
         if (!indices && nobs != n) throw std::invalid_argument("obs_set: indices is null and nobs != n");
-        if (!y) throw std::invalid_argument("obs_set: y is null");
-        if (family == 3 && !aux) throw std::invalid_argument("obs_set: the binomial family needs aux (the number of trials)");
-        if ((family == 0 || family == 4 || family == 5) && !(param > 0.0 && std::isfinite(param)))
-            throw std::invalid_argument("obs_set: sigma / r / phi must be positive and finite");
+        obs_check_operands(who, family, y, aux, param);
         ObsHost o;
-        o.family = family; o.nobs = nobs; o.param = param;
         o.idx.resize((size_t)nobs);
         std::vector<unsigned char> seen((size_t)n, 0);
         for (int64_t k = 0; k < nobs; k++) {
@@ -62,23 +90,60 @@ extern "C" int32_t gmrfx_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, 
             seen[(size_t)i] = 1;
             o.idx[(size_t)k] = i;
         }
-        o.y.assign(y, y + nobs);
-        if (aux && family != 0 && family != 2 && family != 5) o.aux.assign(aux, aux + nobs);      // (the others have no auxiliary number)
-        for (int64_t k = 0; k < nobs; k++) {
-            const double yk = o.y[(size_t)k];
-            const std::string at = " (observation " + std::to_string(k) + ")";
-            if (!std::isfinite(yk)) throw std::invalid_argument("obs_set: y is not finite" + at);
-            if (!o.aux.empty() && !std::isfinite(o.aux[(size_t)k])) throw std::invalid_argument("obs_set: aux is not finite" + at);
-            if (family >= 1 && family <= 4 && yk < 0.0) throw std::invalid_argument("obs_set: negative count" + at);
-            if (family == 2 && yk > 1.0) throw std::invalid_argument("obs_set: a Bernoulli observation above 1" + at);
-            if (family == 3 && !(o.aux[(size_t)k] >= 0.0 && yk <= o.aux[(size_t)k])) throw std::invalid_argument("obs_set: y exceeds the number of trials" + at);
-            if (family == 5 && !(yk > 0.0)) throw std::invalid_argument("obs_set: a Gamma observation must be positive" + at);
-        }
-        o.loglik_const = obs_loglik_const(o);
+        obs_fill_values(o, who, family, nobs, y, aux, param);
         if (h->D) h->D->obs_set(o);
         h->obs = std::move(o);
         return GMRFX_OK;
     });
+}
+
+// The likelihood observed through eta = A x + b (A: nobs x n, CSC). The host analysis (fisher_design_plan.cpp) validates A and b and
+// builds the Hessian's positions and term lists; the plan replaces a node-form likelihood and the other way round.
+extern "C" int32_t gmrfx_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *colptr, const int64_t *rowval,
+                                        const double *nzval, int32_t index_base, const double *offset, const double *y, const double *aux,
+                                        double param) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "obs_set_design: ";
+        obs_check_handle(h, who);
+        const int64_t n = h->S.n;
+        obs_check_family(who, family);
+        if (nobs <= 0) throw std::invalid_argument(who + "nobs must be positive (gmrfx_obs_set with nobs = 0 removes the likelihood)");
+        check_index_base(index_base, who.c_str());
+        if (!colptr) throw std::invalid_argument(who + "colptr is null");
+        check_compressed_ptr(colptr, n, index_base, "obs_set_design: colptr");
+        design_check_sizes(n, nobs, colptr[n] - index_base);        // (before y, aux or A are read at those lengths)
+        if (colptr[n] > index_base && (!rowval || !nzval)) throw std::invalid_argument(who + "rowval / nzval is null");
+        obs_check_operands(who, family, y, aux, param);
+        ObsHost o;
+        obs_fill_values(o, who, family, nobs, y, aux, param);
+        if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+        auto plan = std::make_shared<DesignPlan>();
+        design_build_plan(h->rsym, n, h->S.nnz_in, nobs, colptr, rowval, nzval, index_base, offset, *plan);
+        o.design = std::move(plan);
+        if (h->D) h->D->obs_set(o);
+        h->obs = std::move(o);
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_obs_hess_map(const gmrfx_handle *h, int64_t *cnt, int64_t *map) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    return guarded(const_cast<gmrfx_handle *>(h), [&]() -> int32_t {
+        if (!h->obs.design) throw std::invalid_argument("obs_hess_map: no design likelihood is set (gmrfx_obs_set_design)");
+        const DesignPlan &P = *h->obs.design;
+        if (cnt) *cnt = P.cnt;
+        if (map) std::copy(P.map.begin(), P.map.end(), map);
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    const DesignPlan *P = h->obs.design.get();
+    if (nnz_a) *nnz_a = P ? P->nnz : -1;
+    if (cnt) *cnt = P ? P->cnt : -1;
+    if (terms) *terms = P ? P->terms : -1;
+    return GMRFX_OK;
 }
 
 extern "C" int32_t gmrfx_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const) {
@@ -88,6 +153,9 @@ extern "C" int32_t gmrfx_obs_info(const gmrfx_handle *h, int32_t *family, int64_
     if (loglik_const) *loglik_const = h->obs.loglik_const;
     return GMRFX_OK;
 }
+
+// entries of the Hessian vector: n in node form, the map's cnt in design form
+static int64_t obs_hess_len(const gmrfx_handle *h) { return h->obs.design ? h->obs.design->cnt : h->S.n; }
 
 // ---- score, hess, energy and loglik at a point, one pass over Symmetric(Q_prior) (Device::fisher_eval) --------------------------------
 // The per-iterate host work of the reference's loop (src/workspace/gaussian_approximation.jl:191-313: neg_score_k = Q_p x - h - loggrad,
@@ -104,15 +172,15 @@ static int32_t fisher_eval_impl(gmrfx_handle *h, const double *x, const double *
         double res[2] = {0.0, 0.0};
         if (dev) h->D->fisher_eval(h->rsym, x, mu, score, hess, res);
         else {
-            const int64_t n = h->S.n;
+            const int64_t n = h->S.n, hl = obs_hess_len(h);
             DevBlock bx, bm, bs, bh;
             stage_up(h, bx, x, n);
             if (mu) stage_up(h, bm, mu, n);
             if (score) stage_alloc(h, bs, n);
-            if (hess) stage_alloc(h, bh, n);
+            if (hess) stage_alloc(h, bh, hl);
             h->D->fisher_eval(h->rsym, bx, mu ? bm.get() : nullptr, score ? bs.get() : nullptr, hess ? bh.get() : nullptr, res);
             if (score) stage_down(h, bs, score, n, n, 1);
-            if (hess) stage_down(h, bh, hess, n, n, 1);
+            if (hess && hl > 0) stage_down(h, bh, hess, hl, hl, 1);
         }
         out[0] = res[0];
         out[1] = res[1];
@@ -143,16 +211,16 @@ static int32_t ga_impl(gmrfx_handle *h, const double *mu, const double *x0, int6
         int rc;
         if (dev) rc = h->D->gaussian_approximation(h->rsym, mu, x0, o, x, hess, result, dec_trace, alpha_trace, &inf);
         else {
-            const int64_t n = h->S.n;
+            const int64_t n = h->S.n, hl = obs_hess_len(h);
             DevBlock bm, b0, bx, bh;
             if (mu) stage_up(h, bm, mu, n);
             if (x0) stage_up(h, b0, x0, n);
             stage_alloc(h, bx, n);
-            if (hess) stage_alloc(h, bh, n);
+            if (hess) stage_alloc(h, bh, hl);
             rc = h->D->gaussian_approximation(h->rsym, mu ? bm.get() : nullptr, x0 ? b0.get() : nullptr, o, bx, hess ? bh.get() : nullptr, result,
                                               dec_trace, alpha_trace, &inf);
             stage_down(h, bx, x, n, n, 1);
-            if (hess && rc == 0) stage_down(h, bh, hess, n, n, 1);
+            if (hess && rc == 0 && hl > 0) stage_down(h, bh, hess, hl, hl, 1);
         }
         if (info) *info = inf;
         if (rc == 1) {

@@ -3,10 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "device_plan.h"
+#include "fisher_design_plan.h"
 #include "rbmc_plan.h"
 #include "resource.h"
 
@@ -63,12 +65,15 @@ struct ConHost {
 // Families (canonical or log link, reference canonical_implementations.jl:146-327): 0 Normal / identity (param sigma), 1 Poisson / log
 // (aux = log exposure), 2 Bernoulli / logit, 3 Binomial / logit (aux = trials), 4 NegativeBinomial / log (aux = log exposure, param r),
 // 5 Gamma / log (param phi). idx: the observed nodes, 0-based, in the caller's order; y and aux (empty: none) go with them.
+// design (gmrfx_obs_set_design): non-null when the likelihood is observed through eta = A x + b; idx is then empty and y / aux go
+// with the rows of A.
 struct ObsHost {
     int family = 0;
     long long nobs = 0;
     std::vector<long long> idx;
     std::vector<double> y, aux;
     double param = 0, loglik_const = 0;      // the sum of the terms of loglik that do not depend on x (long double on the host)
+    std::shared_ptr<const DesignPlan> design;
 };
 constexpr int kObsFamilies = 6;
 
@@ -225,9 +230,13 @@ public:
     // upload leaves the previous likelihood in place.
     void obs_set(const ObsHost &o);
     bool obs_held() const { return (bool)fisher_.y; }
+    // entries of the Hessian vector of fisher_eval / gaussian_approximation: n in node form, the map's cnt in design form
+    long long hess_len() const { return fisher_.design ? fisher_.design->cnt : S_->n; }
     // One pass over Symmetric(Q_prior) at the point d_x: score = (Q_p x - h) - g(x) and hess = d(x) (n each, device, either nullable),
     // out_host = {1/2 x' Q_p x - x' h, sum of the x-dependent terms of loglik}; h = Q_p mu (d_mu nullable: 0). Needs set_prior with the
     // diagonal map (position of (i, i) for every i) and a likelihood; no factorisation. Synchronises once.
+    // Design form (device_fisher.cpp, fisher_design.hip): eta = A x + b, score = (Q_p x - h) - A' g(eta), d_hess = the hess_len() values
+    // sum_t w_t d(eta_{i_t}) of A' D A in map order; needs set_prior with exactly the map of the plan.
     void fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host);
     // The Fisher-scoring loop of the reference (src/workspace/gaussian_approximation.jl:230-313 with _ga_line_search, _predict_converged
     // and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409), control flow on the host, every vector in HBM.
@@ -511,9 +520,19 @@ private:
         PinnedBuf<double> h_out;                             // 2 of the evaluation, then 4 of the reductions
         int family = 0;
         double param = 0, loglik_const = 0;
+        // design form: y / aux by observation (mask unused), the plan's tables, g and d by observation, the chunk tables of the long
+        // columns and term lists (choff: prefix sums of chunk counts; chs / chl: start and length of every chunk, columns' first)
+        std::shared_ptr<const DesignPlan> design;
+        DevBuf<long long> arp, acp, tptr, chs;
+        DevBuf<int> acol, arow, tobs, cchoff, tchoff, chl;
+        DevBuf<double> aval, acv, tw, offset, g, d, lpart, cpart;
+        int ncc = 0, nct = 0;
     } fisher_;
     std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
     int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
+    int prior_design_ = -1;               // the same against the map of the design plan (also reset by obs_set)
+    void obs_set_design(const ObsHost &o, FisherDev &f);
+    void fisher_eval_design(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host);
     void grad_tables();
     void grad_drop_constraint() { grad_.acolptr.reset(); grad_.arow.reset(); grad_.aval.reset(); grad_.Bt.reset(); grad_.bt_serial = 0; }   // (behind a synchronisation)
     void grad_constraint_tables(const ConHost &A, int m, const double *d_B, int nb, long long n);

@@ -18,7 +18,8 @@ void Device::obs_set(const ObsHost &o) {
     HC(hipSetDevice(device));
     if (sharded() || batched()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
     FisherDev f;         // built aside: a failed upload leaves the previous likelihood in place
-    if (o.nobs > 0) {
+    if (o.nobs > 0 && o.design) obs_set_design(o, f);
+    else if (o.nobs > 0) {
         const size_t n = (size_t)S_->n;
         std::vector<double> y(n, 0.0), aux(o.aux.empty() ? 0 : n, 0.0);
         std::vector<unsigned char> mask(n, 0);
@@ -46,6 +47,86 @@ void Device::obs_set(const ObsHost &o) {
     }
     HC(hipStreamSynchronize(stream));        // (an evaluation in flight on an external stream still reads the old arrays)
     fisher_ = std::move(f);
+    prior_design_ = -1;
+}
+
+// dst = a device copy of src, on the handle's books (i64 and long long: the same 8 bytes)
+template <class T, class U> static void fd_up(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) {
+    static_assert(sizeof(T) == sizeof(U), "fd_up copies bytes");
+    dst.alloc(src.size(), ledger, kTableMinBytes);
+    if (!src.empty()) hip_check(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+}
+
+// Design form: the plan's tables as they are, y / aux by observation, and the chunk tables of the segments longer than kDesignChunk
+void Device::obs_set_design(const ObsHost &o, FisherDev &f) {
+    const DesignPlan &P = *o.design;
+    const size_t n = (size_t)S_->n, nobs = (size_t)P.nobs;
+    if ((long long)n != P.n || n > (size_t)INT_MAX) throw std::invalid_argument("obs_set_design: the plan does not belong to this handle");
+    fd_up(f.y, o.y, &bytes_total);
+    if (!o.aux.empty()) fd_up(f.aux, o.aux, &bytes_total);
+    fd_up(f.arp, P.rptr, &bytes_total);
+    fd_up(f.acol, P.rcol, &bytes_total);
+    fd_up(f.aval, P.rval, &bytes_total);
+    fd_up(f.acp, P.cptr, &bytes_total);
+    fd_up(f.arow, P.crow, &bytes_total);
+    fd_up(f.acv, P.cval, &bytes_total);
+    fd_up(f.tptr, P.tptr, &bytes_total);
+    fd_up(f.tobs, P.tobs, &bytes_total);
+    fd_up(f.tw, P.tw, &bytes_total);
+    if (!P.offset.empty()) fd_up(f.offset, P.offset, &bytes_total);
+    std::vector<int> cchoff(n + 1, 0), tchoff((size_t)P.cnt + 1, 0), chl;
+    std::vector<long long> chs;
+    auto cut = [&](const std::vector<i64> &ptr, std::vector<int> &choff) {
+        for (size_t s = 0; s + 1 < ptr.size(); s++) {
+            const long long len = ptr[s + 1] - ptr[s];
+            const int nch = design_chunks(len);
+            for (int c = 0; c < nch; c++) {
+                chs.push_back(ptr[s] + (long long)c * kDesignChunk);
+                chl.push_back((int)std::min<long long>(kDesignChunk, len - (long long)c * kDesignChunk));
+            }
+            choff[s + 1] = (int)chs.size();
+        }
+    };
+    cut(P.cptr, cchoff);
+    f.ncc = (int)chs.size();
+    tchoff[0] = f.ncc;
+    cut(P.tptr, tchoff);
+    f.nct = (int)chs.size() - f.ncc;
+    fd_up(f.cchoff, cchoff, &bytes_total);
+    fd_up(f.tchoff, tchoff, &bytes_total);
+    fd_up(f.chs, chs, &bytes_total);
+    fd_up(f.chl, chl, &bytes_total);
+    f.g.alloc(nobs, &bytes_total, kTableMinBytes);
+    f.d.alloc(nobs, &bytes_total, kTableMinBytes);
+    f.cpart.alloc(chs.size(), &bytes_total, kTableMinBytes);
+    f.lpart.alloc((size_t)design_blocks((long long)nobs), &bytes_total, kTableMinBytes);
+    f.part.alloc((size_t)design_blocks((long long)n), &bytes_total, kTableMinBytes);
+    f.out.alloc(6, &bytes_total, kTableMinBytes);
+    f.spart.alloc(4 * (size_t)fisher_stat_blocks((int)n), &bytes_total, kTableMinBytes);
+    f.h_out.alloc(6);
+    f.family = o.family;
+    f.param = o.param;
+    f.loglik_const = o.loglik_const;
+    f.design = o.design;
+}
+
+void Device::fisher_eval_design(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host) {
+    const DesignPlan &P = *fisher_.design;
+    if (prior_design_ < 0) prior_design_ = (hmap_cnt_ == P.cnt && std::equal(P.map.begin(), P.map.end(), h_hmap_.begin())) ? 1 : 0;
+    if (!prior_design_)
+        throw std::invalid_argument("fisher_eval: the map of gmrfx_set_prior is not the map of gmrfx_obs_hess_map (the positions of A' D A, design form)");
+    sym_rows_upload(sym);
+    const FisherDesign a{(int)P.n, (int)P.nobs, (int)P.cnt, fisher_.family, sym_rows_.rp, sym_rows_.col, sym_rows_.pos, d_prior_, d_x, d_mu,
+                         fisher_.arp, fisher_.acol, fisher_.aval, fisher_.offset.get(), fisher_.acp, fisher_.arow, fisher_.acv,
+                         fisher_.tptr, fisher_.tobs, fisher_.tw, fisher_.cchoff, fisher_.tchoff, fisher_.chs, fisher_.chl, fisher_.ncc, fisher_.nct,
+                         fisher_.y, fisher_.aux.get(), fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0,
+                         fisher_.g, fisher_.d, fisher_.cpart, d_score, d_hess, fisher_.part, fisher_.lpart};
+    launch_fisher_design(stream, a, fisher_.out);
+    HC(hipMemcpyAsync(fisher_.h_out, fisher_.out, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    out_host[0] = fisher_.h_out[0];
+    out_host[1] = fisher_.h_out[1] + fisher_.loglik_const;
 }
 
 void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host) {
@@ -55,6 +136,7 @@ void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_
     if (!d_prior_) throw std::invalid_argument("fisher_eval: gmrfx_set_prior has not been called");
     const long long n = S_->n;
     if (n > INT_MAX) throw std::invalid_argument("fisher_eval: more than 2^31 - 1 nodes");
+    if (fisher_.design) return fisher_eval_design(sym, d_x, d_mu, d_score, d_hess, out_host);
     if (prior_diag_ < 0) {
         prior_diag_ = hmap_cnt_ == n ? 1 : 0;
         for (long long i = 0; i < n && prior_diag_; i++)
@@ -89,7 +171,8 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
         double ev[2];
         fisher_eval(sym, d_x, d_mu, nullptr, nullptr, ev);
     }
-    if (!fisher_.work) fisher_.work.alloc(6 * (size_t)n, &bytes_total, kTableMinBytes);
+    const long long hlen = hess_len();      // n in node form, the map's cnt in design form
+    if (!fisher_.work) fisher_.work.alloc(5 * (size_t)n + (size_t)hlen, &bytes_total, kTableMinBytes);
     double *xk = fisher_.work, *xnew = xk + n, *cand = xk + 2 * n, *step = xk + 3 * n, *score = xk + 4 * n, *hess = xk + 5 * n;
     if (d_x0) HC(hipMemcpyAsync(xk, d_x0, nb, hipMemcpyDeviceToDevice, stream));
     else if (d_mu) HC(hipMemcpyAsync(xk, d_mu, nb, hipMemcpyDeviceToDevice, stream));
@@ -126,7 +209,7 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
         if (!failed && (d_hess || refactor_final)) {
             double e[2];
             fisher_eval(sym, xfinal, d_mu, nullptr, hess, e);      // the final H(x_final) (_workspace_build_result)
-            if (d_hess) HC(hipMemcpyAsync(d_hess, hess, nb, hipMemcpyDeviceToDevice, stream));
+            if (d_hess && hlen > 0) HC(hipMemcpyAsync(d_hess, hess, (size_t)hlen * sizeof(double), hipMemcpyDeviceToDevice, stream));
             if (refactor_final) {
                 refactorize_update(hess, true);
                 nfact += 1;

@@ -10,10 +10,7 @@
 //   k_fisher_eval    a lane group of kFisherLanes lanes per row of Symmetric(Q_p) (the row structure RBMC and k_grad_mubar use: a gather,
 //                    nothing is scattered), kFisherRows rows per workgroup; one (energy, loglik) pair per workgroup
 //   k_fisher_final   the pairs of all workgroups, one workgroup of kFisherFinal threads
-// STABLE FORMS. Every exponential takes a non-positive argument or the linear predictor itself: logistic(t) = 1 / (1 + e^-t) for
-// t >= 0 and e^t / (1 + e^t) below, log(1 + e^t) = max(t, 0) + log1p(e^-|t|), 1 - logistic(t) = logistic(-t) (no cancellation), the
-// negative binomial through s = mu / (r + mu) = logistic(eta + aux - log r), log(r + mu) = max(log r, eta + aux) + log1p(e^-|..|).
-// Finite for every eta where the mathematics is (Bernoulli / binomial everywhere; the log links up to the overflow of mu itself).
+// STABLE FORMS of the six families: fisher_point.h, shared with fisher_design.hip.
 // DETERMINISM. No atomics. A lane adds its entries q0 + l, q0 + l + 16, ... in that order, the 16 lane sums meet in a fixed xor
 // butterfly, the rows of a workgroup in a fixed LDS tree, the workgroups' pairs in a fixed strided loop + tree. The differences and
 // products the interface pins are written with contraction off. Nothing depends on the alignment of x, mu, score or hess: all are read
@@ -21,50 +18,9 @@
 #include <hip/hip_runtime.h>
 
 #include "kernel_common.h"
+#include "fisher_point.h"
 
 namespace gmrfx {
-
-__device__ __forceinline__ double fisher_logistic(double t) {
-    if (t >= 0.0) return 1.0 / (1.0 + exp(-t));
-    const double e = exp(t);
-    return e / (1.0 + e);
-}
-__device__ __forceinline__ double fisher_log1pexp(double t) { return fmax(t, 0.0) + log1p(exp(-fabs(t))); }
-
-// g, d and the x-dependent part of the log-likelihood of one observed node
-__device__ __forceinline__ void fisher_point(int family, double eta, double y, double aux, double param, double logparam, double &g, double &d,
-                                             double &ll) {
-#pragma clang fp contract(off)
-    switch (family) {
-        case 0: {       // Normal / identity, param = sigma
-            const double inv = 1.0 / (param * param), r = y - eta;
-            g = r * inv; d = -inv; ll = -0.5 * inv * (r * r);
-            break;
-        }
-        case 1: {       // Poisson / log, aux = log exposure
-            const double e = eta + aux, m = exp(e);
-            g = y - m; d = -m; ll = y * e - m;
-            break;
-        }
-        case 2:         // Bernoulli / logit (one trial)
-        case 3: {       // Binomial / logit, aux = trials
-            const double nt = family == 3 ? aux : 1.0, m = fisher_logistic(eta), q = fisher_logistic(-eta);
-            g = y - nt * m; d = -(nt * m * q); ll = y * eta - nt * fisher_log1pexp(eta);
-            break;
-        }
-        case 4: {       // NegativeBinomial / log, aux = log exposure, param = r
-            const double e = eta + aux, t = e - logparam, s = fisher_logistic(t), q = fisher_logistic(-t);
-            g = y * q - param * s; d = -((param + y) * s * q);
-            ll = y * e - (param + y) * (fmax(logparam, e) + log1p(exp(-fabs(t))));
-            break;
-        }
-        default: {      // 5: Gamma / log, param = phi
-            const double w = y * exp(-eta);
-            g = param * (w - 1.0); d = -(param * w); ll = -(param * eta) - param * w;
-            break;
-        }
-    }
-}
 
 __global__ __launch_bounds__(256) void k_fisher_eval(const FisherEval a) {
     __shared__ double se[kFisherRows], sl[kFisherRows];

@@ -252,4 +252,40 @@ inline int fisher_stat_blocks(int n) { return (n + kFisherStatChunk - 1) / kFish
 void launch_fisher_candidate(hipStream_t st, int n, const double *x, const double *s, double alpha, double *out);
 void launch_fisher_stats(hipStream_t st, int n, const double *a, const double *b, const double *c, const double *d, double *part, double *out4);
 
+// fisher_design.hip -- the same evaluation through a sparse design matrix, eta = A x + b (gmrfx_obs_set_design). A lane group of
+// kDesignLanes lanes per row of A, per node and per Hessian position, kDesignRows of them per workgroup of 256 threads. A SEGMENT (a
+// column of A for A' g, a position's term list for A' D A) of at most kDesignChunk entries is summed by its lane group; a longer one is
+// cut into chunks of kDesignChunk entries, one workgroup each, whose sums the lane group then adds (design_chunks of them, in order).
+constexpr int kDesignLanes = 16, kDesignRows = 16, kDesignChunk = 512;
+static_assert(kDesignLanes == kFisherLanes && kDesignRows == kFisherRows, "the energy of the design form has the bits of the node form");
+inline int design_chunks(long long len) { return len > kDesignChunk ? (int)((len + kDesignChunk - 1) / kDesignChunk) : 0; }
+inline int design_blocks(long long rows) { return (int)((rows + kDesignRows - 1) / kDesignRows); }
+struct FisherDesign {
+    int n, nobs, cnt, family;
+    const long long *rp;         // Symmetric(Q) by rows, as FisherEval
+    const int *col, *pos;
+    const double *val, *x, *mu;
+    const long long *arp;        // A by rows: nobs + 1
+    const int *acol;
+    const double *aval, *offset; // offset nullable
+    const long long *acp;        // A by columns: n + 1
+    const int *arow;
+    const double *acv;
+    const long long *tptr;       // the term lists: cnt + 1
+    const int *tobs;
+    const double *tw;
+    const int *cchoff, *tchoff;  // n + 1 / cnt + 1: prefix sums of design_chunks over the columns / term lists (the latter from ncc on)
+    const long long *chs;        // ncc + nct: first entry of every chunk (columns' chunks first)
+    const int *chl;              // and its length
+    int ncc, nct;
+    const double *y, *aux;       // by observation (aux nullable)
+    double param, logparam;
+    double *g, *d;               // nobs each: work
+    double *cpart;               // ncc + nct chunk sums
+    double *score, *hess;        // n / cnt, either nullable
+    double *epart, *lpart;       // energy per workgroup of nodes, loglik per workgroup of observations
+};
+// out[0] = energy, out[1] = sum of the x-dependent terms of loglik (device)
+void launch_fisher_design(hipStream_t st, const FisherDesign &a, double *out);
+
 }  // namespace gmrfx

@@ -81,6 +81,7 @@ EXPORTS = [
     "gmrfx_batch_logpdf_grad", "gmrfx_batch_logpdf_grad_dev", "gmrfx_batch_pattern_dot", "gmrfx_batch_pattern_dot_dev",
     "gmrfx_obs_set", "gmrfx_obs_info", "gmrfx_fisher_eval", "gmrfx_fisher_eval_dev",
     "gmrfx_gaussian_approximation", "gmrfx_gaussian_approximation_dev",
+    "gmrfx_obs_set_design", "gmrfx_obs_hess_map", "gmrfx_obs_design_info",
 ]
 
 
@@ -219,6 +220,9 @@ def lib():
         L.gmrfx_batch_pattern_dot_dev.argtypes = [vp, vp, vp, i64, i64, i64, vp]
         L.gmrfx_obs_set.argtypes = [vp, i32, i64, vp, i32, vp, vp, dbl]
         L.gmrfx_obs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), C.POINTER(dbl)]
+        L.gmrfx_obs_set_design.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, dbl]
+        L.gmrfx_obs_hess_map.argtypes = [vp, C.POINTER(i64), vp]
+        L.gmrfx_obs_design_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.gmrfx_fisher_eval.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gmrfx_fisher_eval_dev.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gmrfx_gaussian_approximation.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]

@@ -513,22 +513,63 @@ class MI355XBackend:
         check(lib().gmrfx_obs_info(self._h, C.byref(fam), C.byref(nobs), C.byref(c)), self._h)
         return {"family": fam.value, "nobs": nobs.value, "loglik_const": c.value}
 
+    def set_design_observations(self, family, y, A, offset=None, aux=None, param: float = 0.0) -> None:
+        """The likelihood observed through eta = A x + offset (gmrfx_obs_set_design; the reference's LinearlyTransformedLikelihood).
+        A: any scipy sparse matrix, nobs x n, converted to sorted CSC (explicit zeros are kept, duplicates summed). The other
+        arguments as in set_observations, one entry per row of A. set_prior then takes observations_hess_map()."""
+        fam = self.OBS_FAMILIES[family] if isinstance(family, str) else int(family)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        Ac = sp.csc_matrix(A, dtype=np.float64)
+        if Ac.shape != (yy.size, self.n):
+            raise ValueError(f"A must be nobs x n = {yy.size} x {self.n}, got {Ac.shape}")
+        if not Ac.has_canonical_format:
+            Ac = Ac.copy()
+            Ac.sum_duplicates()
+        off = None if offset is None else np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+        ax = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).reshape(-1)
+        if (off is not None and off.size != yy.size) or (ax is not None and ax.size != yy.size):
+            raise ValueError("offset / aux do not have one entry per observation")
+        cp = np.ascontiguousarray(Ac.indptr, dtype=np.int64)
+        rv = np.ascontiguousarray(Ac.indices, dtype=np.int64)
+        nz = np.ascontiguousarray(Ac.data, dtype=np.float64)
+        check(lib().gmrfx_obs_set_design(self._h, fam, yy.size, ptr(cp), ptr(rv), ptr(nz), 0, ptr(off), ptr(yy), ptr(ax), float(param)), self._h)
+
+    def observations_hess_map(self) -> np.ndarray:
+        """0-based positions into nzval of the entries of A' D A, ascending (gmrfx_obs_hess_map): the hess_map of set_prior, and the
+        order of the Hessian values fisher_eval and gaussian_approximation return in design form."""
+        cnt = C.c_int64(0)
+        check(lib().gmrfx_obs_hess_map(self._h, C.byref(cnt), None), self._h)
+        m = np.empty(cnt.value, np.int64)
+        check(lib().gmrfx_obs_hess_map(self._h, C.byref(cnt), ptr(m)), self._h)
+        return m
+
+    def observations_design_info(self) -> dict:
+        a, c, t = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gmrfx_obs_design_info(self._h, C.byref(a), C.byref(c), C.byref(t)), self._h)
+        return {"nnz": a.value, "cnt": c.value, "terms": t.value}
+
+    def _hess_len(self) -> int:
+        """entries of the Hessian vector of the evaluation: n in node form, the map's cnt in design form"""
+        cnt = self.observations_design_info()["cnt"]
+        return self.n if cnt < 0 else cnt
+
     def fisher_eval(self, x, mean=None, want_score: bool = True, want_hess: bool = True):
         """(score, hess, energy, loglik) at the point x (gmrfx_fisher_eval): score = Q_p x - Q_p mean - loggrad(x), hess = the diagonal
-        of loghessian(x), energy = x' Q_p x / 2 - x' Q_p mean, loglik(x); Q_p = the values of set_prior. score / hess are None when
-        not asked for."""
+        of loghessian(x) (design form: the values of A' D A in the order of observations_hess_map()), energy = x' Q_p x / 2 -
+        x' Q_p mean, loglik(x); Q_p = the values of set_prior. score / hess are None when not asked for."""
         xx = np.ascontiguousarray(x, dtype=np.float64)
         mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
         if xx.shape != (self.n,) or (mu is not None and mu.shape != (self.n,)):
             raise ValueError("dimension mismatch")
         score = np.empty(self.n) if want_score else None
-        hess = np.empty(self.n) if want_hess else None
+        hess = np.empty(self._hess_len()) if want_hess else None
         out = np.empty(2)
         check(lib().gmrfx_fisher_eval(self._h, ptr(xx), ptr(mu), ptr(score), ptr(hess), ptr(out)), self._h)
         return score, hess, float(out[0]), float(out[1])
 
     def fisher_eval_dev(self, d_x: int, d_mu: int = 0, d_score: int = 0, d_hess: int = 0):
-        """Device pointers: x (n), mean (n, 0 = zero), score and hess outputs (n each, 0 = not computed); returns (energy, loglik)."""
+        """Device pointers: x (n), mean (n, 0 = zero), score (n) and hess (n; design form: cnt) outputs (0 = not computed); returns
+        (energy, loglik)."""
         if not d_x:
             raise ValueError("fisher_eval_dev: null pointer")
         out = np.empty(2)
@@ -559,7 +600,7 @@ class MI355XBackend:
         xs = None if x0 is None else np.ascontiguousarray(x0, dtype=np.float64)
         if (mu is not None and mu.shape != (self.n,)) or (xs is not None and xs.shape != (self.n,)):
             raise ValueError("dimension mismatch")
-        x, hess, res = np.empty(self.n), np.empty(self.n), np.zeros(8)
+        x, hess, res = np.empty(self.n), np.empty(self._hess_len()), np.zeros(8)
         dec, alp = np.full(max_iter + 1, np.nan), np.full(max_iter + 1, np.nan)
         info = C.c_int64(0)
         flags = self._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
@@ -576,7 +617,8 @@ class MI355XBackend:
                                    mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5, adaptive_stepsize: bool = True,
                                    max_linesearch_iter: int = 10, step_recovery: str = "retry_full", predictive_convergence: bool = True,
                                    refactorize_final: bool = False) -> dict:
-        """Device pointers: the mode x (n) and hess (n, 0 = not wanted) outputs, mean and x0 (n each, 0 = none). Returns the info dict."""
+        """Device pointers: the mode x (n) and hess (n; design form: cnt; 0 = not wanted) outputs, mean and x0 (n each, 0 = none).
+        Returns the info dict."""
         if not d_x:
             raise ValueError("gaussian_approximation_dev: null pointer")
         res = np.zeros(8)

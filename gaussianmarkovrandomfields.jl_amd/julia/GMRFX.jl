@@ -389,11 +389,42 @@ function observations_info(b::MI355XBackend)
     check(ccall((:gmrfx_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Float64}), b.h.ptr, fam, nobs, c), b.h)
     return (family = fam[], nobs = nobs[], loglik_const = c[])
 end
+# The likelihood observed through eta = A x + offset (gmrfx_obs_set_design; the reference's LinearlyTransformedLikelihood): A is handed
+# over as Julia holds it (CSC, 1-based). set_prior! then takes observations_hess_map(b) (1-based positions into nzval, ascending),
+# and fisher_eval / gaussian_approximation_device return the values of A' D A in that order.
+function set_design_observations!(b::MI355XBackend, family::Union{Symbol, Integer}, y::Vector{Float64}, A::SparseMatrixCSC{Float64, Int64};
+                                  offset::Union{Nothing, Vector{Float64}} = nothing, aux::Union{Nothing, Vector{Float64}} = nothing,
+                                  param::Real = 0.0)
+    fam = family isa Symbol ? getfield(OBS_FAMILIES, family) : Int(family)
+    size(A) == (length(y), b.n) || throw(DimensionMismatch("A must be nobs x n"))
+    (offset === nothing || length(offset) == length(y)) && (aux === nothing || length(aux) == length(y)) ||
+        throw(DimensionMismatch("offset / aux must have one entry per observation"))
+    poff = offset === nothing ? Ptr{Float64}(C_NULL) : pointer(offset)
+    paux = aux === nothing ? Ptr{Float64}(C_NULL) : pointer(aux)
+    GC.@preserve y A offset aux check(ccall((:gmrfx_obs_set_design, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64),
+        b.h.ptr, Int32(fam), length(y), A.colptr, A.rowval, A.nzval, Int32(1), poff, y, paux, Float64(param)), b.h)
+    return b
+end
+function observations_design_info(b::MI355XBackend)
+    a = Ref{Int64}(0); c = Ref{Int64}(0); t = Ref{Int64}(0)
+    check(ccall((:gmrfx_obs_design_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), b.h.ptr, a, c, t), b.h)
+    return (nnz = a[], cnt = c[], terms = t[])
+end
+function observations_hess_map(b::MI355XBackend)
+    cnt = Ref{Int64}(0)
+    check(ccall((:gmrfx_obs_hess_map, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}), b.h.ptr, cnt, C_NULL), b.h)
+    m = Vector{Int64}(undef, cnt[])
+    check(ccall((:gmrfx_obs_hess_map, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Int64}), b.h.ptr, cnt, m), b.h)
+    return m .+ 1
+end
+# entries of the Hessian vector: n in node form, the map's cnt in design form
+_hess_len(b::MI355XBackend) = (c = observations_design_info(b).cnt; c < 0 ? b.n : Int(c))
 # (score, hess, energy, loglik) at x, one pass over the prior gmrfx_set_prior keeps: score = Q_p x - Q_p mean - loggrad(x), hess = the
 # diagonal of loghessian(x) -- the operands of one Newton step --, energy = x'Q_p x / 2 - x'Q_p mean, loglik(x)
 function fisher_eval(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, Vector{Float64}} = nothing)
     length(x) == b.n && (mean === nothing || length(mean) == b.n) || throw(DimensionMismatch("x and mean must have n entries"))
-    score = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, b.n); out = zeros(2)
+    score = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, _hess_len(b)); out = zeros(2)
     mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
     GC.@preserve x mean score hess out check(ccall((:gmrfx_fisher_eval, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
@@ -418,7 +449,7 @@ function gaussian_approximation_device(b::MI355XBackend; mean::Union{Nothing, Ve
                                        adaptive_stepsize::Bool = true, max_linesearch_iter::Int = 10, step_recovery::Symbol = :retry_full,
                                        predictive_convergence::Bool = true, refactorize_final::Bool = false)
     (mean === nothing || length(mean) == b.n) && (x0 === nothing || length(x0) == b.n) || throw(DimensionMismatch("mean and x0 must have n entries"))
-    x = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, b.n); res = zeros(8)
+    x = Vector{Float64}(undef, b.n); hess = Vector{Float64}(undef, _hess_len(b)); res = zeros(8)
     dec = fill(NaN, max_iter + 1); alp = fill(NaN, max_iter + 1); info = Ref{Int64}(0)
     mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
     xs = x0 === nothing ? Ptr{Float64}(C_NULL) : pointer(x0)
@@ -450,6 +481,26 @@ device_likelihood(l::G.BinomialLikelihood{G.LogitLink}) = (3, Vector{Float64}(l.
 device_likelihood(l::G.NegBinLikelihood{G.LogLink}) = (4, Vector{Float64}(l.y), _obs_indices(l.indices), _obs_offset(l.logexposure, length(l.y)), Float64(l.r))
 device_likelihood(l::G.GammaLikelihood{G.LogLink}) = (5, Vector{Float64}(l.y), _obs_indices(l.indices), nothing, Float64(l.phi))
 
+# ws.Q <- Q_p - A' D A from the device's cnt values: the map addresses the triangle the handle reads, the workspace's Q may hold both,
+# so the mirrored entry (where it is stored) takes the same value. Then what _update_hessian! does after its own subtraction.
+function _subtract_design_hessian!(ws, Qp::Vector{Float64}, hmap::Vector{Int}, hess::Vector{Float64})
+    Q = ws.Q
+    cp, rv, nz = Q.colptr, Q.rowval, Q.nzval
+    copyto!(nz, Qp)
+    for (p, hv) in zip(hmap, hess)
+        c = searchsortedlast(cp, p)
+        r = rv[p]
+        nz[p] -= hv
+        if r != c       # entry (c, r): row c in column r
+            q = cp[r] - 1 + searchsortedfirst(view(rv, cp[r]:(cp[r + 1] - 1)), c)
+            q < cp[r + 1] && rv[q] == c && (nz[q] -= hv)
+        end
+    end
+    G._invalidate!(ws)
+    ws.loaded_version = 0
+    return nothing
+end
+
 function _device_gaussian_approximation(prior::G.WorkspaceGMRF, obs_lik; x0::Union{Nothing, AbstractVector} = nothing, max_iter::Int = 50,
                                         mean_change_tol::Real = 1.0e-4, newton_dec_tol::Real = 1.0e-5, adaptive_stepsize::Bool = true,
                                         max_linesearch_iter::Int = 10, step_recovery::Symbol = :retry_full,
@@ -461,19 +512,37 @@ function _device_gaussian_approximation(prior::G.WorkspaceGMRF, obs_lik; x0::Uni
         return invoke(G.gaussian_approximation, Tuple{G.WorkspaceGMRF, G.ObservationLikelihood}, prior, obs_lik; x0, max_iter, mean_change_tol,
                       newton_dec_tol, adaptive_stepsize, max_linesearch_iter, step_recovery, predictive_convergence, verbose)
     end
+    design = obs_lik isa G.LinearlyTransformedLikelihood
+    fam, y, idx, aux, param = device_likelihood(design ? obs_lik.base_likelihood : obs_lik)
+    if design && idx !== nothing        # a base likelihood with its own indices: not a row-per-observation design, the reference's loop
+        return invoke(G.gaussian_approximation, Tuple{G.WorkspaceGMRF, G.ObservationLikelihood}, prior, obs_lik; x0, max_iter, mean_change_tol,
+                      newton_dec_tol, adaptive_stepsize, max_linesearch_iter, step_recovery, predictive_convergence, verbose)
+    end
     G.ensure_loaded!(prior)
-    fam, y, idx, aux, param = device_likelihood(obs_lik)
     Qp = copy(ws.Q.nzval)
     diag_idx = G._diagonal_indices(ws.Q)
-    set_prior!(b, Qp, Vector{Int}(diag_idx))
-    set_observations!(b, fam, y; indices = idx, aux = aux, param = param)
+    hmap = nothing
+    if design       # eta = A x + b: the Hessian A' D A sits on the positions the handle computes once; pattern(A'A) outside Q throws, as _sparse_hessian_map does
+        A = obs_lik.design_matrix
+        off = obs_lik.offset === nothing ? nothing : Vector{Float64}(obs_lik.offset)
+        set_design_observations!(b, fam, y, SparseMatrixCSC{Float64, Int64}(A); offset = off, aux = aux, param = param)
+        hmap = Vector{Int}(observations_hess_map(b))
+        set_prior!(b, Qp, hmap)
+    else
+        set_prior!(b, Qp, Vector{Int}(diag_idx))
+        set_observations!(b, fam, y; indices = idx, aux = aux, param = param)
+    end
     sync_constraints!(b, ci)
     x, hess, info = gaussian_approximation_device(b; mean = Vector{Float64}(prior.mean), x0 = x0 === nothing ? nothing : Vector{Float64}(x0),
                                                   max_iter, mean_change_tol, newton_dec_tol, adaptive_stepsize, max_linesearch_iter,
                                                   step_recovery, predictive_convergence)
     verbose && println(info.converged ? "  Converged after $(info.iterations) iterations" : "  Reached max_iter without convergence")
     # _workspace_build_result: ws.Q <- Q_p - H(x_final), not factorised eagerly; the constraints are re-applied by _build_result
-    G._update_hessian!(ws, Diagonal(hess), Qp, diag_idx, nothing)
+    if design
+        _subtract_design_hessian!(ws, Qp, hmap, hess)
+    else
+        G._update_hessian!(ws, Diagonal(hess), Qp, diag_idx, nothing)
+    end
     return G._build_result(ws, x, ci)
 end
 G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.PoissonLikelihood{G.LogLink}; kw...) =
@@ -485,6 +554,12 @@ G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::
 G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.NegBinLikelihood{G.LogLink}; kw...) =
     _device_gaussian_approximation(prior, obs_lik; kw...)
 G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend}, obs_lik::G.GammaLikelihood{G.LogLink}; kw...) =
+    _device_gaussian_approximation(prior, obs_lik; kw...)
+# eta = A x + b with a sparse A over one of the likelihoods above; a dense A or another base keeps the reference's method
+const DeviceBaseLikelihood = Union{G.PoissonLikelihood{G.LogLink}, G.BernoulliLikelihood{G.LogitLink}, G.BinomialLikelihood{G.LogitLink},
+                                   G.NegBinLikelihood{G.LogLink}, G.GammaLikelihood{G.LogLink}}
+G.gaussian_approximation(prior::G.WorkspaceGMRF{<:Any, MI355XBackend},
+                         obs_lik::G.LinearlyTransformedLikelihood{<:DeviceBaseLikelihood, <:SparseMatrixCSC}; kw...) =
     _device_gaussian_approximation(prior, obs_lik; kw...)
 
 # `_rand!` on given draws: X = P' L^-T Z + mean, then the constraint correction when the handle holds one

@@ -645,7 +645,7 @@ int32_t gmrfx_batch_pattern_dot_dev(gmrfx_handle *h, const double *d_G, const do
  *           4 NegBinomial / log      aux = log exposure, param r  g = r (y - mu) / (r + mu)        d = -r mu (r + y) / (r + mu)^2
  *           5 Gamma / log            param phi                    g = phi (y / mu - 1)             d = -phi y / mu
  * g = dl/deta, d = d2l/deta2, l the log density of one observation; a node without an observation has g = d = l = 0 exactly
- * (_embed_grad, _embed_diag). Every term is evaluated in a form that is stable for every eta (csrc/fisher.hip, "STABLE FORMS").
+ * (_embed_grad, _embed_diag). Every term is evaluated in a form that is stable for every eta (csrc/fisher_point.h, "STABLE FORMS").
  * gmrfx_obs_set validates, sums the terms of loglik that do not depend on x in long double (loglik_const: -lgamma(y + 1), the
  * binomial coefficients, the Normal / NegBinomial / Gamma constants) and expands y, aux and an observed mask to one value per node
  * on the device. indices NULL = nodes 1 .. n in order (needs nobs == n). nobs = 0 removes the likelihood. gmrfx_clone carries it.
@@ -665,15 +665,44 @@ int32_t gmrfx_batch_pattern_dot_dev(gmrfx_handle *h, const double *d_G, const do
  * Errors: GMRFX_ERR_INVALID_ARG with a message when x or out is null, no likelihood is set, gmrfx_set_prior has not been called or
  * was called with a map that is not "the position of (i, i) for every i" (cnt == n: diagonal Hessians only), a batched or sharded
  * handle; GMRFX_ERR_NO_DEVICE for symbolic_only handles (after the argument checks that need no device state).
- * LIMITS: plain handles, pointwise likelihoods with a diagonal Hessian, n < 2^31. Student-t (not concave), LatentPrior and generic
- * likelihoods stay on the gmrfx_refactorize_update path, driven from the host. */
+ * LIMITS: plain handles, n < 2^31; pointwise likelihoods with a diagonal Hessian here, Hessians A' D A in the design form below.
+ * Student-t (not concave), LatentPrior and generic likelihoods stay on the gmrfx_refactorize_update path, driven from the host. */
 int32_t gmrfx_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices /* nobs, nullable */, int32_t index_base,
                       const double *y /* nobs */, const double *aux /* nobs, nullable */, double param);
 int32_t gmrfx_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const);
 int32_t gmrfx_fisher_eval(gmrfx_handle *h, const double *x, const double *mu /* nullable */, double *score /* n, nullable */,
-                          double *hess /* n, nullable */, double *out /* host, 2: energy, loglik */);
+                          double *hess /* n (design form: cnt), nullable */, double *out /* host, 2: energy, loglik */);
 int32_t gmrfx_fisher_eval_dev(gmrfx_handle *h, const double *d_x, const double *d_mu, double *d_score, double *d_hess,
                               double *out /* host, 2: energy, loglik */);
+/* ---- the same through a sparse design matrix: eta = A x + b (LinearlyTransformedLikelihood, src/observation_models/
+ * linearly_transformed.jl:313-340: loggrad = A' g(eta), loghessian = Symmetric(A' (D(eta) A))) ---------------------------------------
+ * gmrfx_obs_set_design: A is nobs x n in CSC as Julia holds it (colptr n + 1, row indices sorted and unique within a column), offset
+ * the nobs values of b (NULL: 0). Families, aux, param, loglik_const and every refusal are those of gmrfx_obs_set, except that two
+ * rows may observe the same node, empty rows (eta_i = b_i) and untouched columns are allowed, nobs may exceed n (nobs >= 1) and
+ * explicit zeros of A are kept as entries. Refused in addition (INVALID_ARG, a message, nothing changed): a colptr that is not
+ * monotone or does not start at index_base, a row index outside [0, nobs), unsorted or repeated row indices within a column, a
+ * non-finite value of A or offset, n / nobs / nnz(A) / the term count at 2^31 or above, and a pattern(A'A) that the handle's pattern
+ * does not contain (the first missing (j, k) is named; the reference's _sparse_hessian_map throws there too).
+ * The Hessian's positions are computed on the host, once: for every unordered pair (j, k) with a common row in A (j = k included) the
+ * position in the handle's nzval of that entry in the triangle the handle reads, each pair once, in ascending position order.
+ * gmrfx_obs_hess_map returns the list (cnt; map nullable, cnt values, 0-based): it is the map to give gmrfx_set_prior. With it the
+ * plan keeps, for every position p, the terms (i_t, w_t = A[i_t, j] A[i_t, k]) in ascending i_t.
+ * Setting one form replaces the other; gmrfx_obs_set with nobs = 0 removes either; gmrfx_clone carries the design form; symbolic_only
+ * handles validate, give loglik_const and the map. gmrfx_obs_info keeps its meaning; gmrfx_obs_design_info: nnz(A), cnt and the term
+ * count, each nullable, -1 each in node form or with no likelihood.
+ * gmrfx_fisher_eval[_dev] in design form needs gmrfx_set_prior with exactly that map (INVALID_ARG otherwise) and returns
+ *   score_j = ((Q_p x)_j - h_j) - (A' g(eta))_j    n values;        hess[p] = sum_t w_t d(eta_{i_t})    cnt values, the hvals of
+ *   gmrfx_refactorize_update under that map;  out[0] as above;  out[1] = sum_i l_i(eta_i) + loglik_const.
+ * No atomics; every sum in an order fixed by indices only (csrc/fisher_design.hip). With A = rows of the identity and no offset,
+ * score, energy and the entries of hess have the bits of the node form. gmrfx_gaussian_approximation[_dev] runs the same loop; its
+ * hess / d_hess output is then the cnt values in map order.
+ * Memory of the plan on the device: A by rows and by columns, 12 B per entry each, and 12 B per term (32-bit observation, weight).
+ * LIMITS: plain handles; sparse A; a theta-dependent A is set again by the caller (same pattern, same map). */
+int32_t gmrfx_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *colptr /* n + 1 */, const int64_t *rowval,
+                             const double *nzval, int32_t index_base, const double *offset /* nobs, nullable */, const double *y /* nobs */,
+                             const double *aux /* nobs, nullable */, double param);
+int32_t gmrfx_obs_hess_map(const gmrfx_handle *h, int64_t *cnt, int64_t *map /* nullable; cnt values, index base 0 */);
+int32_t gmrfx_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms);
 /* The loop itself: gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313)
  * with _ga_line_search, _predict_converged and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409 restated
  * line by line in host C++; every vector (x_k, step, score, hess, the line search's candidates) stays in HBM, the host reads a handful
@@ -693,7 +722,7 @@ int32_t gmrfx_fisher_eval_dev(gmrfx_handle *h, const double *d_x, const double *
  * handle usable afterwards (also when A Q^-1 A' fails, *info = 0). LIMITS: as gmrfx_fisher_eval. */
 int32_t gmrfx_gaussian_approximation(gmrfx_handle *h, const double *mu /* nullable */, const double *x0 /* nullable */, int64_t max_iter,
                                      int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol, int32_t flags,
-                                     double *x /* n */, double *hess /* n, nullable */, double *result /* host, 8 */,
+                                     double *x /* n */, double *hess /* n (design form: cnt), nullable */, double *result /* host, 8 */,
                                      double *dec_trace /* host, max_iter + 1, nullable */, double *alpha_trace /* same */, int64_t *info);
 int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, const double *d_x0, int64_t max_iter,
                                          int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol, int32_t flags,
