@@ -248,6 +248,15 @@ public:
     int gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
                                double *result, double *dec_trace, double *alpha_trace, long long *info);
 
+    // The pullback of gaussian_approximation at its mode d_x (device_ga_pullback.cpp, ga_pullback.hip; gmrfx_ga_pullback): from the
+    // cotangents of the mode (d_mubar, n) and of the posterior precision (d_Qbar, nnz on the pattern), either nullable, those of the
+    // prior's precision (d_Qbar_prior, nnz; may be d_Qbar itself) and mean (d_mubar_prior, n), lam = Q_post^-1 xbar (d_lambda, n), each
+    // nullable, and out_host = {parameter cotangent, lam' xbar}. flags: bit 0 projects lam with the constraint set (e = 0), bit 1
+    // refactorises at Q_prior - H(d_x) first; without it the handle's factor is taken to be that one. Returns 0, 1 when that
+    // factorisation failed (*info = 1 + the failing step), 2 when the constraint's W did.
+    struct GapIO { const double *d_x, *d_mu, *d_mubar, *d_Qbar; int flags; double *d_Qbar_prior, *d_mubar_prior, *d_lambda; };
+    int ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info);
+
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
     double ms_factor = 0, ms_solve = 0, ms_fwd = 0, ms_bwd = 0, ms_perm = 0, ms_bsolve = 0, ms_logdet = 0, ms_selinv = 0;
@@ -528,6 +537,16 @@ private:
         DevBuf<double> aval, acv, tw, offset, g, d, lpart, cpart;
         int ncc = 0, nct = 0;
     } fisher_;
+    // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
+    // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
+    struct GapDev {
+        DevBuf<long long> optr;
+        DevBuf<int> oidx;
+        DevBuf<double> ow, work, part, out;
+        PinnedBuf<double> h_out;
+    } gap_;
+    void gap_tables();
+    void fisher_check_map(const RbmcSym &sym);
     std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
     int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
     int prior_design_ = -1;               // the same against the map of the design plan (also reset by obs_set)

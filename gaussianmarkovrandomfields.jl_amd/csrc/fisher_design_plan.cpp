@@ -8,6 +8,7 @@
 #include <cmath>
 #include <stdexcept>
 #include <string>
+#include <utility>
 
 namespace gmrfx {
 
@@ -94,18 +95,34 @@ void design_build_plan(const RbmcSym &R, i64 n, i64 nnzq, i64 nobs, const int64_
             P.map.push_back(p);
         }
     P.cnt = (i64)P.map.size();
-    // pass 2: the same order again; rows ascend, so every term list does
+    // pass 2: the same order again; rows ascend, so every term list does. The same terms by observation (the transposed table): a
+    // row's pairs are one run of the generation order, sorted by map index afterwards
     P.tobs.resize((size_t)terms);
     P.tw.resize((size_t)terms);
+    P.optr.assign((size_t)nobs + 1, 0);
+    P.oidx.resize((size_t)terms);
+    P.ow.resize((size_t)terms);
+    std::vector<std::pair<i32, double>> rowlist;
     std::vector<i64> cur(P.tptr.begin(), P.tptr.end() - 1);
     t = 0;
-    for (i64 i = 0; i < nobs; i++)
+    for (i64 i = 0; i < nobs; i++) {
+        rowlist.clear();
         for (i64 a = P.rptr[(size_t)i]; a < P.rptr[(size_t)i + 1]; a++)
             for (i64 b = a; b < P.rptr[(size_t)i + 1]; b++) {
-                const i64 d = cur[(size_t)slot[(size_t)tpos[(size_t)t++]]]++;
+                const i32 s = slot[(size_t)tpos[(size_t)t++]];
+                const i64 d = cur[(size_t)s]++;
                 P.tobs[(size_t)d] = (i32)i;
                 P.tw[(size_t)d] = P.rval[(size_t)a] * P.rval[(size_t)b];
+                rowlist.emplace_back(s, a == b ? P.tw[(size_t)d] : 2.0 * P.tw[(size_t)d]);
             }
+        std::sort(rowlist.begin(), rowlist.end(), [](const std::pair<i32, double> &u, const std::pair<i32, double> &v) { return u.first < v.first; });
+        const i64 o0 = P.optr[(size_t)i];
+        for (size_t q = 0; q < rowlist.size(); q++) {
+            P.oidx[(size_t)o0 + q] = rowlist[q].first;
+            P.ow[(size_t)o0 + q] = rowlist[q].second;
+        }
+        P.optr[(size_t)i + 1] = o0 + (i64)rowlist.size();
+    }
     out = std::move(P);
 }
 

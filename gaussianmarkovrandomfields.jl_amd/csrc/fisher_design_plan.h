@@ -22,6 +22,12 @@ struct DesignPlan {
     std::vector<i64> map, tptr;
     std::vector<i32> tobs;
     std::vector<double> tw;
+    // The transpose of the term table (gmrfx_ga_pullback: c_i = a_i' G a_i): per observation i, at optr[i] .. optr[i + 1], the pairs of
+    // row i as (oidx = the pair's index p in map, ow = w_t, doubled off the diagonal), ascending in p and so in position. An index into
+    // map is below cnt <= terms < 2^31: 32 bits always do.
+    std::vector<i64> optr;
+    std::vector<i32> oidx;
+    std::vector<double> ow;
 };
 
 // Throws std::invalid_argument when n, nobs or nnz(A) is 2^31 or above: before anything of that length is read.

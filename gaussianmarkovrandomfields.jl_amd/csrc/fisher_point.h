@@ -51,4 +51,42 @@ __device__ __forceinline__ void fisher_point(int family, double eta, double y, d
     }
 }
 
+// What the pullback of the Gaussian approximation needs besides (gmrfx_ga_pullback): d3 = dd/deta, and the derivatives of g and d with
+// respect to the family's parameter (sigma, r, phi), gp and dp; both 0 for the families without one. The same stable forms: q - s and
+// q - m are differences of two numbers in [0, 1], each good to a few ulps of 1 -- the absolute error the bounds of the tests count.
+__device__ __forceinline__ void fisher_point_pullback(int family, double eta, double y, double aux, double param, double logparam, double &d3,
+                                                      double &gp, double &dp) {
+#pragma clang fp contract(off)
+    gp = 0.0; dp = 0.0;
+    switch (family) {
+        case 0: {       // g = (y - eta) / sigma^2, d = -1 / sigma^2
+            const double inv3 = 1.0 / (param * param * param);
+            d3 = 0.0; gp = -(2.0 * (y - eta) * inv3); dp = 2.0 * inv3;
+            break;
+        }
+        case 1:         // d = -m
+            d3 = -exp(eta + aux);
+            break;
+        case 2:
+        case 3: {       // d = -nt m q, (m q)' = m q (q - m)
+            const double nt = family == 3 ? aux : 1.0, m = fisher_logistic(eta), q = fisher_logistic(-eta);
+            d3 = -(nt * m * q * (q - m));
+            break;
+        }
+        case 4: {       // s = logistic(t), t = eta + aux - log r: ds/dr = -s q / r
+            const double t = (eta + aux) - logparam, s = fisher_logistic(t), q = fisher_logistic(-t);
+            const double c = (param + y) * s * q * (q - s);
+            d3 = -c;
+            gp = s * ((param + y) * q / param - 1.0);
+            dp = c / param - s * q;
+            break;
+        }
+        default: {      // 5: w = y e^-eta, g = phi (w - 1), d = -phi w
+            const double w = y * exp(-eta);
+            d3 = param * w; gp = w - 1.0; dp = -w;
+            break;
+        }
+    }
+}
+
 }  // namespace gmrfx

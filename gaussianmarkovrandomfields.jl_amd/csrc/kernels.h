@@ -288,4 +288,70 @@ struct FisherDesign {
 // out[0] = energy, out[1] = sum of the x-dependent terms of loglik (device)
 void launch_fisher_design(hipStream_t st, const FisherDesign &a, double *out);
 
+// ga_pullback.hip -- the array arithmetic of the implicit-function rule of the Gaussian approximation (gmrfx_ga_pullback). The solve
+// in the middle is the handle's own; these are the kernels on either side of it. Node form: one thread per node, kGapNode nodes per
+// workgroup. Design form: the lane-group layout of fisher_design.hip (kDesignLanes lanes per row of A / per node, kDesignRows per
+// workgroup), the columns of A cut into chunks by the same design_chunks() rule. The pattern and mean kernels have the layout of
+// k_grad_pattern / k_grad_mubar (device_plan.h: kGradLanes, kGradCols, kGradRows).
+constexpr int kGapNode = 256;
+inline int gap_node_blocks(int n) { return (n + kGapNode - 1) / kGapNode; }
+// workgroups of the per-observation kernels (k_gap_point*, k_gap_param*), and so the partial sums each of them leaves
+inline int gap_obs_blocks(bool design, long long n, long long nobs) { return design ? design_blocks(nobs) : gap_node_blocks((int)n); }
+struct GapPoint {
+    int n, nobs, family;
+    const double *G;             // the precision cotangent on the pattern (nnz)
+    const long long *hmap;       // the map of gmrfx_set_prior: the position of (i, i) in node form, of the plan's pairs in design form
+    const double *x, *mubar;     // the mode; the mean cotangent (nullable: 0)
+    const double *y, *aux;       // the likelihood, by node / by observation (aux nullable)
+    const unsigned char *mask;   // node form: 1 = observed
+    const long long *arp;        // design form: A by rows, the offset (nullable), the transposed term table of the plan
+    const int *acol;
+    const double *aval, *offset;
+    const long long *optr;
+    const int *oidx;
+    const double *ow;
+    double param, logparam;
+    double *t;                   // design form, nobs: t_i = c_i d3_i
+    double *xbar;                // node form: mubar_i - t_i, n
+    double *ppart;               // sum of c_i dp_i per workgroup
+};
+void launch_gap_point(hipStream_t st, const GapPoint &a, bool design);
+struct GapGather {
+    int n, ncc;
+    const long long *acp;        // A by columns
+    const int *arow;
+    const double *acv;
+    const int *cchoff;           // the chunk tables of the long columns (FisherDesign)
+    const long long *chs;
+    const int *chl;
+    const double *t, *mubar;     // mubar nullable
+    double *cpart, *xbar;
+};
+void launch_gap_gather(hipStream_t st, const GapGather &a);
+struct GapPattern {
+    int n;
+    const long long *colptr;     // the pattern of Q
+    const int *row;
+    const double *G;             // nullable: 0
+    const double *lam, *x, *mu;  // mu nullable
+    double *out;                 // nnz; may be G itself
+};
+void launch_gap_pattern(hipStream_t st, const GapPattern &a);
+// out_i = sum_q val[pos[q]] lam[col[q]] over row i of Symmetric(Q) (RbmcSym)
+void launch_gap_mean(hipStream_t st, int n, const long long *rp, const int *col, const int *pos, const double *val, const double *lam, double *out);
+struct GapParam {
+    int n, nobs, family;
+    const double *lam, *x;
+    const double *y, *aux;
+    const unsigned char *mask;
+    const long long *arp;        // design form: eta is formed again beside A lam, in the same pass over the row
+    const int *acol;
+    const double *aval, *offset;
+    double param, logparam;
+    double *gpart;               // sum of (A lam)_i gp_i per workgroup
+};
+void launch_gap_param(hipStream_t st, const GapParam &a, bool design);
+// out[0] = sum gpart - sum ppart (np / ng = 0: that sum is 0)
+void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, double *out);
+
 }  // namespace gmrfx

@@ -82,6 +82,7 @@ EXPORTS = [
     "gmrfx_obs_set", "gmrfx_obs_info", "gmrfx_fisher_eval", "gmrfx_fisher_eval_dev",
     "gmrfx_gaussian_approximation", "gmrfx_gaussian_approximation_dev",
     "gmrfx_obs_set_design", "gmrfx_obs_hess_map", "gmrfx_obs_design_info",
+    "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
 ]
 
 
@@ -227,6 +228,9 @@ def lib():
         L.gmrfx_fisher_eval_dev.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gmrfx_gaussian_approximation.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]
         L.gmrfx_gaussian_approximation_dev.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]
+        L.gmrfx_ga_pullback.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.gmrfx_ga_pullback_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.gmrfx_obs_design_rows.argtypes = [vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

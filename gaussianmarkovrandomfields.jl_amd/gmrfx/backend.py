@@ -633,6 +633,56 @@ class MI355XBackend:
         check(rc, self._h)
         return self._ga_info(res, dec, alp)
 
+    # -- the pullback of gaussian_approximation (src/workspace/autodiff.jl:140-202; include/gmrfx.h "The pullback of the Gaussian approximation")
+    def ga_pullback(self, x, mean=None, mubar=None, Qbar=None, project: bool = False, refactorize: bool = False,
+                    want_Qbar_prior: bool = True, want_mubar_prior: bool = True, want_lambda: bool = True):
+        """The implicit-function rule at the mode x (gmrfx_ga_pullback). mubar (n) / Qbar (nnz, on the pattern, the convention of
+        logpdf_grad): the cotangents of the posterior mean / precision, either None (zero). Returns (Qbar_prior, mubar_prior, lambda,
+        param_bar, lambda' xbar); the arrays not asked for are None. project: lambda <- lambda - A~' W^-1 (A lambda) with the
+        constraint set; refactorize: factorise Q_prior - H(x) first (otherwise the handle holds it: gaussian_approximation with
+        refactorize_final=True)."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        mu = None if mean is None else np.ascontiguousarray(mean, dtype=np.float64)
+        mb = None if mubar is None else np.ascontiguousarray(mubar, dtype=np.float64)
+        qb = None if Qbar is None else np.ascontiguousarray(Qbar, dtype=np.float64)
+        if xx.shape != (self.n,) or any(v is not None and v.shape != (self.n,) for v in (mu, mb)) or (qb is not None and qb.shape != (self._nnz,)):
+            raise ValueError("dimension mismatch")
+        qp = np.empty(self._nnz) if want_Qbar_prior else None
+        mp = np.empty(self.n) if want_mubar_prior else None
+        lam = np.empty(self.n) if want_lambda else None
+        out = np.empty(2)
+        flags = int(bool(project)) | (int(bool(refactorize)) << 1)
+        rc = lib().gmrfx_ga_pullback(self._h, ptr(xx), ptr(mu), ptr(mb), ptr(qb), flags, ptr(qp), ptr(mp), ptr(lam), ptr(out))
+        if refactorize:
+            self._selinv_cache = None
+            self._selinv_diag_cache = None
+        check(rc, self._h)
+        return qp, mp, lam, float(out[0]), float(out[1])
+
+    def ga_pullback_dev(self, d_x: int, d_mu: int = 0, d_mubar: int = 0, d_Qbar: int = 0, d_Qbar_prior: int = 0, d_mubar_prior: int = 0,
+                        d_lambda: int = 0, project: bool = False, refactorize: bool = False):
+        """Device pointers (0 = absent); d_Qbar_prior may be d_Qbar. Returns (param_bar, lambda' xbar)."""
+        if not d_x:
+            raise ValueError("ga_pullback_dev: null pointer")
+        out = np.empty(2)
+        flags = int(bool(project)) | (int(bool(refactorize)) << 1)
+        rc = lib().gmrfx_ga_pullback_dev(self._h, d_x, d_mu or None, d_mubar or None, d_Qbar or None, flags, d_Qbar_prior or None,
+                                         d_mubar_prior or None, d_lambda or None, ptr(out))
+        if refactorize:
+            self._selinv_cache = None
+            self._selinv_diag_cache = None
+        check(rc, self._h)
+        return float(out[0]), float(out[1])
+
+    def observations_design_rows(self):
+        """(ptr, pos, w): the design plan's terms by observation (gmrfx_obs_design_rows) -- row i's pairs at ptr[i] .. ptr[i + 1] as
+        0-based positions into nzval, ascending, and weights A_ij A_ik, doubled off the diagonal."""
+        terms = self.observations_design_info()["terms"]
+        nobs = self.observations_info()["nobs"]
+        p, pos, w = np.empty(nobs + 1, np.int64), np.empty(max(terms, 0), np.int64), np.empty(max(terms, 0))
+        check(lib().gmrfx_obs_design_rows(self._h, ptr(p), ptr(pos), ptr(w)), self._h)
+        return p, pos, w
+
     # -- sharded factorisation (include/gmrfx.h "sharded factorisation"; driver: gmrfx/shard.py) -------
     def refactorize_phase_dev(self, d_nzval_ptr: int, phase: int) -> None:
         check(lib().gmrfx_refactorize_phase(self._h, d_nzval_ptr, phase), self._h)

@@ -465,6 +465,38 @@ function gaussian_approximation_device(b::MI355XBackend; mean::Union{Nothing, Ve
 end
 function gaussian_approximation_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
 
+# The pullback of gaussian_approximation at its mode x (gmrfx_ga_pullback; include/gmrfx.h; the rule of src/workspace/autodiff.jl:140-202):
+# from the cotangents of the posterior mean (mubar, n) and precision (Qbar, nnz values on the pattern, the convention of logpdf_grad),
+# either `nothing`, returns (Qbar_prior, mubar_prior, lambda, param_bar, lambda' xbar). project: lambda <- lambda - A~' W^-1 (A lambda)
+# with the constraint set; refactorize: factorise Q_prior - H(x) first (otherwise the handle holds it: refactorize_final = true above).
+function pattern_nnz(b::MI355XBackend)
+    r = Ref{Int64}(0)
+    check(ccall((:gmrfx_pattern_nnz, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}), b.h.ptr, r), b.h)
+    return Int(r[])
+end
+function ga_pullback(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, Vector{Float64}} = nothing,
+                     mubar::Union{Nothing, Vector{Float64}} = nothing, Qbar::Union{Nothing, Vector{Float64}} = nothing,
+                     project::Bool = false, refactorize::Bool = false)
+    nnz = pattern_nnz(b)
+    length(x) == b.n && (mean === nothing || length(mean) == b.n) && (mubar === nothing || length(mubar) == b.n) &&
+        (Qbar === nothing || length(Qbar) == nnz) || throw(DimensionMismatch("x, mean, mubar need n entries, Qbar nnz"))
+    qp = Vector{Float64}(undef, nnz); mp = Vector{Float64}(undef, b.n); lam = Vector{Float64}(undef, b.n); out = zeros(2)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    mb = mubar === nothing ? Ptr{Float64}(C_NULL) : pointer(mubar)
+    qb = Qbar === nothing ? Ptr{Float64}(C_NULL) : pointer(Qbar)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    code = GC.@preserve x mean mubar Qbar qp mp lam out ccall((:gmrfx_ga_pullback, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, x, mu, mb, qb, flags, qp, mp, lam, out)
+    if refactorize
+        b.selinv_cache = nothing
+        b.selinv_diag_cache = nothing
+    end
+    check(code, b.h)
+    return qp, mp, lam, out[1], out[2]
+end
+function ga_pullback_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
+
 # gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313) for workspaces on
 # this backend and the pointwise exponential-family likelihoods the device evaluates: one method per likelihood type, each more
 # specific than the reference's (WorkspaceGMRF, ObservationLikelihood) method. Everything else -- other links, Student-t, generic and

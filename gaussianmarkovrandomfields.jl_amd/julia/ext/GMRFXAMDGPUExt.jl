@@ -20,7 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
-import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev, fisher_eval_dev!, gaussian_approximation_dev!, _ga_flags, _ga_info
+import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev, fisher_eval_dev!, gaussian_approximation_dev!, ga_pullback_dev!, _ga_flags, _ga_info
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -175,6 +175,24 @@ function gaussian_approximation_dev!(x::ROCVector{Float64}, hess::ROCVector{Floa
     info[] > 0 && throw(PosDefException(Int(info[])))
     check(code, b.h)
     return _ga_info(res, dec, alp)
+end
+# the pullback of gaussian_approximation with everything resident in HBM (gmrfx_ga_pullback_dev): Qbar_prior (nnz; may be Qbar itself),
+# mubar_prior and lambda (n) are written, each optional; returns (param_bar, lambda' xbar)
+function ga_pullback_dev!(b::MI355XBackend, x::ROCVector{Float64}; mean::Union{Nothing, ROCVector{Float64}} = nothing,
+                          mubar::Union{Nothing, ROCVector{Float64}} = nothing, Qbar::Union{Nothing, ROCVector{Float64}} = nothing,
+                          Qbar_prior::Union{Nothing, ROCVector{Float64}} = nothing, mubar_prior::Union{Nothing, ROCVector{Float64}} = nothing,
+                          lambda::Union{Nothing, ROCVector{Float64}} = nothing, project::Bool = false, refactorize::Bool = false)
+    length(x) == b.n || throw(DimensionMismatch("x must have n entries"))
+    AMDGPU.synchronize()
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : devptr(a)
+    out = zeros(2)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    code = GC.@preserve x mean mubar Qbar Qbar_prior mubar_prior lambda out ccall((:gmrfx_ga_pullback_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, devptr(x), p(mean), p(mubar), p(Qbar), flags, p(Qbar_prior), p(mubar_prior), p(lambda), out)
+    refactorize && _invalidate!(b)
+    check(code, b.h)
+    return out[1], out[2]
 end
 # the members of a batch: Qbar nnz x B, mubar / Z / mean n x B; returns info
 function logpdf_grad_dev!(Qbar::ROCMatrix{Float64}, mubar::ROCMatrix{Float64}, bb::MI355XBatch, Z::ROCMatrix{Float64}, ybar::Vector{Float64};

@@ -729,6 +729,51 @@ int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, co
                                          double *d_x, double *d_hess, double *result /* host, 8 */, double *dec_trace /* host */,
                                          double *alpha_trace /* host */, int64_t *info);
 
+/* ---- The pullback of the Gaussian approximation (implicit-function rule) -------------------------------------------------------------
+ * Reverse-mode rule of gaussian_approximation(prior, obs_lik) at its mode x (src/workspace/autodiff.jl:140-202; for plain GMRFs
+ * src/autodiff/gaussian_approximation.jl:278-347), the step between gmrfx_logpdf_grad and gmrfx_pattern_dot when hyper-parameters are
+ * fitted on the Laplace marginal likelihood. Inputs: the cotangent of the posterior mean, mubar (n), and of the posterior precision
+ * Q_post = Q_prior - H(x), Qbar: a symmetric matrix on the stored entries of the pattern, nnz values in the pattern's order, an entry
+ * carrying its value whichever triangle it lies in (the convention of gmrfx_logpdf_grad: dL = sum_ij Qbar_ij dQ_ij over all (i, j)).
+ * Either may be NULL (zero), not both. With r = x - mu, a_i row i of A (node form: a unit vector), g, d as above, d3 = dd/deta and
+ * gp, dp the derivatives of g and d by the family's parameter (sigma, r, phi; 0 for Poisson, Bernoulli, Binomial):
+ *   c_i  = a_i' Qbar a_i          node form: the diagonal entry Qbar[map[i]]; design form: the sum over the pairs (j <= k) of row i of
+ *                                 (j == k ? 1 : 2) A_ij A_ik Qbar[position of (j, k)], the positions of gmrfx_obs_hess_map
+ *   xbar = mubar - A' (c . d3(eta))
+ *   lam  = Q_post^-1 xbar         the handle's factor; flags bit 0 and a constraint set: lam <- lam - A~' W^-1 (A lam), the correction
+ *                                 the loop applies to its steps (e = 0); without the bit the plain solve of the workspace rule
+ *   Qbar_prior[e = (i, j)] = Qbar[e] - 0.5 (lam_i r_j + lam_j r_i)        nnz, in that association, no contraction; Qbar NULL: 0 - ...
+ *   mubar_prior = Q_p lam                                                 n; Symmetric(Q_p), the values gmrfx_set_prior keeps
+ *   out[0] = sum_i (A lam)_i gp_i - sum_i c_i dp_i                        the cotangent of sigma / r / phi
+ *   out[1] = lam' xbar                                                    a check value
+ *   family   d3                       gp                           dp                                     (m the mean, q = 1 - m)
+ *   Normal   0                        -2 (y - eta) / sigma^3       2 / sigma^3
+ *   Poisson  -m                       0                            0
+ *   Bern/Bin -n m q (q - m)           0                            0
+ *   NegBin   -(r + y) s q (q - s)     s ((r + y) q / r - 1)        -s q + (r + y) s q (q - s) / r        s = mu / (r + mu), q = 1 - s
+ *   Gamma    phi w                    w - 1                        -w                                     w = y exp(-eta)
+ * in the stable forms of csrc/fisher_point.h. Qbar_prior, mubar_prior and lambda (= lam, n) are each nullable, not all three;
+ * Qbar_prior may be Qbar itself. flags bit 1: refactorise at Q_prior - H(x) first (gmrfx_fisher_eval, then gmrfx_refactorize_update);
+ * without it the handle must hold that factor already -- gmrfx_gaussian_approximation with its flag bit 3 leaves it.
+ * No atomics: every sum is formed in an order that depends on indices only; results are bit-reproducible, independent of the
+ * alignment of the operands (8 bytes suffice), the host and the _dev forms agree bit for bit, and a selection matrix A without offset
+ * gives the arrays of the node form bit for bit. Work memory on the device: 2 n + nobs doubles, and in design form the plan's
+ * transposed term table, 12 B per term, uploaded on the first call; gmrfx_clone carries nothing new.
+ * gmrfx_obs_design_rows reads that table: ptr (nobs + 1), and per term the position in nzval and the weight (doubled off the diagonal),
+ * positions ascending within a row; each nullable.
+ * Errors: those of gmrfx_fisher_eval (x or out null, no likelihood, no prior, a map that is not the likelihood's, a batched or sharded
+ * handle; GMRFX_ERR_NO_DEVICE for symbolic_only handles after the argument checks that need no device state); INVALID_ARG for unknown
+ * flag bits, mubar and Qbar both null, every output null, bit 0 without a constraint; GMRFX_ERR_NOT_FACTORIZED without bit 1 before
+ * the first factorisation; GMRFX_ERR_NOT_POSDEF when the factorisation of bit 1 or the constraint's W fails (outputs untouched).
+ * LIMITS: as gmrfx_fisher_eval. The tangents of y, aux, the offset and the values of A are not computed. A row's term list is summed
+ * by one lane group whatever its length (a row of k entries has k (k + 1) / 2 terms). */
+int32_t gmrfx_ga_pullback(gmrfx_handle *h, const double *x, const double *mu /* nullable */, const double *mubar /* n, nullable */,
+                          const double *Qbar /* nnz, nullable */, int32_t flags, double *Qbar_prior /* nnz, nullable */,
+                          double *mubar_prior /* n, nullable */, double *lambda /* n, nullable */, double *out /* host, 2 */);
+int32_t gmrfx_ga_pullback_dev(gmrfx_handle *h, const double *d_x, const double *d_mu, const double *d_mubar, const double *d_Qbar, int32_t flags,
+                              double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda, double *out /* host, 2 */);
+int32_t gmrfx_obs_design_rows(const gmrfx_handle *h, int64_t *ptr /* nobs + 1 */, int64_t *pos /* terms */, double *w /* terms */);
+
 #ifdef __cplusplus
 }
 #endif
