@@ -3,29 +3,27 @@
 #include <cmath>
 
 #include "api_common.h"
+#include "obs_const.h"
 
-// The terms of loglik that do not depend on x (canonical_implementations.jl:18-119, Distributions' logpdf), summed in long double:
+// The terms of loglik that do not depend on x (canonical_implementations.jl:18-119, Distributions' logpdf), summed in long double
+// (the terms themselves: obs_const.h, shared with gmrfx_obs_pointwise_const):
 //   Normal  nobs (-1/2 log 2 pi - log sigma)          Poisson  -sum lgamma(y + 1)          Bernoulli  0
 //   Binomial  sum lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1)
 //   NegBin  sum lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log r          Gamma  nobs (phi log phi - lgamma(phi)) + (phi - 1) sum log y
 static double obs_loglik_const(const ObsHost &o) {
     long double c = 0.0L;
     const long double p = (long double)o.param, nobs = (long double)o.nobs;
-    switch (o.family) {
-        case 0: c = nobs * (-0.5L * std::log(2.0L * std::acos(-1.0L)) - std::log(p)); break;
-        case 1: for (double y : o.y) c -= std::lgamma((long double)y + 1.0L); break;
+    const int f = o.family;
+    switch (f) {
+        case 0: c = nobs * obs_const_shared(f, p); break;
+        case 1: for (double y : o.y) c += obs_const_own(f, y, 0.0L, p); break;
         case 3:
-            for (size_t k = 0; k < o.y.size(); k++) {
-                const long double y = o.y[k], nt = o.aux[k];
-                c += std::lgamma(nt + 1.0L) - std::lgamma(y + 1.0L) - std::lgamma(nt - y + 1.0L);
-            }
+            for (size_t k = 0; k < o.y.size(); k++) c += obs_const_own(f, o.y[k], o.aux[k], p);
             break;
-        case 4:
-            for (double y : o.y) c += std::lgamma((long double)y + p) - std::lgamma(p) - std::lgamma((long double)y + 1.0L) + p * std::log(p);
-            break;
+        case 4: for (double y : o.y) c += obs_const_own(f, y, 0.0L, p); break;
         case 5:
-            c = nobs * (p * std::log(p) - std::lgamma(p));
-            for (double y : o.y) c += (p - 1.0L) * std::log((long double)y);
+            c = nobs * obs_const_shared(f, p);
+            for (double y : o.y) c += obs_const_own(f, y, 0.0L, p);
             break;
         default: break;
     }

@@ -257,6 +257,19 @@ public:
     struct GapIO { const double *d_x, *d_mu, *d_mubar, *d_Qbar; int flags; double *d_Qbar_prior, *d_mubar_prior, *d_lambda; };
     int ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info);
 
+    // ---- the linear predictor's marginals and the predictive scores (device_predictive.cpp, predictive.hip) -------------------------
+    // Per observation, in the caller's order (the indices of gmrfx_obs_set / the rows of A): the mean of the linear predictor at d_x
+    // (n), its variance under the handle's factorisation (the selected inverse is computed if absent) and the full log density at
+    // the mean; device arrays of nobs, each nullable. flags bit 0: subtract the constraint's correction and clamp at 0. o: the
+    // handle's host copy of the likelihood (the observation order and the constants go up on the first call after obs_set).
+    // Returns 0, or 2 when the constraint's W is not positive definite (nothing written).
+    struct PredIO { const double *d_x; int flags; double *d_mu_eta, *d_v_eta, *d_pll; };
+    int predictor_marginals(const RbmcSym &sym, const ObsHost &o, const PredIO &io);
+    // The quadrature scores over N(d_mu[i], d_v[i]) (device, nobs each) with K nodes z and weights w of the standard normal (host):
+    // lpd, lcpo, elp, vlp per observation (device, each nullable) and their totals out4_host, computed either way.
+    struct ScoreIO { const double *d_mu, *d_v; int K; const double *z, *w; double *d_lpd, *d_lcpo, *d_elp, *d_vlp; };
+    void predictive_scores(const ObsHost &o, const ScoreIO &io, double *out4_host);
+
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
     double ms_factor = 0, ms_solve = 0, ms_fwd = 0, ms_bwd = 0, ms_perm = 0, ms_bsolve = 0, ms_logdet = 0, ms_selinv = 0;
@@ -546,6 +559,17 @@ private:
         PinnedBuf<double> h_out;
     } gap_;
     void gap_tables();
+    void gap_term_table();       // the plan's transposed term table alone (also what gmrfx_predictor_marginals needs of the pullback's state)
+    // predictive state, built on the first gmrfx_predictor_marginals / gmrfx_predictive_scores for the likelihood in place (obs_set
+    // drops it): the observed nodes in the caller's order (node form, 4 nobs bytes), the constants c (8 nobs), the plan's map (design
+    // form, 8 cnt), the scores' partial sums (4 per workgroup), totals and quadrature rule
+    struct PredDev {
+        DevBuf<int> idx;
+        DevBuf<long long> hmap;
+        DevBuf<double> c, part, out, quad;
+        PinnedBuf<double> h_out, h_quad;
+    } pred_;
+    void pred_tables(const ObsHost &o);
     void fisher_check_map(const RbmcSym &sym);
     std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
     int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
@@ -562,6 +586,9 @@ private:
 };
 
 void hip_check(hipError_t e, const char *what);
+
+// out[k] = the term of observation k's log density that does not depend on x (obs_const.h), rounded to double; no device
+void obs_pointwise_const(const ObsHost &o, double *out);
 
 // slicing of a column-major n x nrhs host array for the page-locked staging ring (device.cpp: host_upload / host_download)
 struct HostIoPlan { long long cols_per = 1, ppc = 1, rows_per = 0, slot_doubles = 0, nsl = 0, reserve = 0; };

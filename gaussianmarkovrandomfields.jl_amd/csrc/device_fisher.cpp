@@ -48,6 +48,7 @@ void Device::obs_set(const ObsHost &o) {
     HC(hipStreamSynchronize(stream));        // (an evaluation in flight on an external stream still reads the old arrays)
     fisher_ = std::move(f);
     gap_ = GapDev{};         // (the pullback's tables belong to the likelihood: rebuilt on its next call)
+    pred_ = PredDev{};       // (and so do the predictive calls')
     prior_design_ = -1;
 }
 

@@ -40,6 +40,20 @@ template <class T, class U> static void gap_up(DevBuf<T> &dst, const std::vector
     if (!src.empty()) hip_check(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
 }
 
+// The plan's transposed term table on the device (design form; 12 B per term): uploaded by whichever of gmrfx_ga_pullback and
+// gmrfx_predictor_marginals needs it first, kept until obs_set drops the pullback's state.
+void Device::gap_term_table() {
+    const DesignPlan *P = fisher_.design.get();
+    if (!P || gap_.optr) return;
+    DevBuf<long long> optr;      // built aside: an upload that fails half-way leaves nothing behind
+    DevBuf<int> oidx;
+    DevBuf<double> ow;
+    gap_up(optr, P->optr, &bytes_total);
+    gap_up(oidx, P->oidx, &bytes_total);
+    gap_up(ow, P->ow, &bytes_total);
+    gap_.optr = std::move(optr); gap_.oidx = std::move(oidx); gap_.ow = std::move(ow);
+}
+
 // The first pullback for a likelihood: the plan's transposed term table goes up (design form), the work arrays are allocated.
 // O(n + nobs) doubles beside the table.
 void Device::gap_tables() {
@@ -47,17 +61,14 @@ void Device::gap_tables() {
     const size_t n = (size_t)S_->n;
     const DesignPlan *P = fisher_.design.get();
     const size_t nobs = P ? (size_t)P->nobs : 0;
-    GapDev g;        // built aside: an upload that fails half-way leaves nothing behind
-    if (P) {
-        gap_up(g.optr, P->optr, &bytes_total);
-        gap_up(g.oidx, P->oidx, &bytes_total);
-        gap_up(g.ow, P->ow, &bytes_total);
-    }
-    g.work.alloc(2 * n + nobs, &bytes_total, kTableMinBytes);
-    g.part.alloc(2 * (size_t)gap_obs_blocks(P != nullptr, (long long)n, (long long)nobs), &bytes_total, kTableMinBytes);
-    g.out.alloc(1, &bytes_total, kTableMinBytes);
-    g.h_out.alloc(1);
-    gap_ = std::move(g);
+    gap_term_table();
+    DevBuf<double> work, part, out;      // built aside, as the table
+    PinnedBuf<double> h_out;
+    work.alloc(2 * n + nobs, &bytes_total, kTableMinBytes);
+    part.alloc(2 * (size_t)gap_obs_blocks(P != nullptr, (long long)n, (long long)nobs), &bytes_total, kTableMinBytes);
+    out.alloc(1, &bytes_total, kTableMinBytes);
+    h_out.alloc(1);
+    gap_.part = std::move(part); gap_.out = std::move(out); gap_.h_out = std::move(h_out); gap_.work = std::move(work);
 }
 
 int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info) {

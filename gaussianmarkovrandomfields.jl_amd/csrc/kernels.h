@@ -354,4 +354,42 @@ void launch_gap_param(hipStream_t st, const GapParam &a, bool design);
 // out[0] = sum gpart - sum ppart (np / ng = 0: that sum is 0)
 void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, double *out);
 
+// predictive.hip -- the marginals of the linear predictor (gmrfx_predictor_marginals) and the quadrature scores over them
+// (gmrfx_predictive_scores). Node form: one thread per observation, kPredNode per workgroup. Design form and the scores: the lane-group
+// layout of fisher_design.hip (kDesignLanes lanes per observation, kDesignRows observations per workgroup of 256 threads).
+constexpr int kPredNode = 256, kPredMaxNodes = 64, kPredNodesPerLane = kPredMaxNodes / kDesignLanes;
+struct PredMarg {
+    int n, nobs, m, family;      // m: columns of B to subtract (0: no correction, no clamp)
+    const double *x;             // the posterior mean, n
+    const int *idx;              // node form: the observed node of every observation, in the caller's order
+    const int *dpos;             // node form: position of (j, j) in the pattern, per node (RbmcSym::diag)
+    const long long *arp;        // design form: A by rows, the offset (nullable), the transposed term table and the plan's map
+    const int *acol;
+    const double *aval, *offset;
+    const long long *optr;
+    const int *oidx;
+    const double *ow;
+    const long long *hmap;
+    const long long *zoff;       // offset of every stored entry of Q in the selected-inverse panels (null: no variance wanted)
+    const double *Z;
+    const double *B;             // the constraint's B = Q^-1 A' L_c^-T, n x m column-major
+    const double *y, *aux;       // by node (node form) / by observation (design form); aux nullable
+    const double *c;             // the constant of every observation's log density, nobs
+    double param, logparam;
+    double *mu_eta, *v_eta, *pll;        // nobs each, each nullable
+};
+void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design);
+struct PredScores {
+    int nobs, K, family;
+    const double *mu, *v;        // nobs each
+    const int *idx;              // node form: y / aux are by node; null: by observation
+    const double *y, *aux, *c;
+    const double *z, *w;         // K quadrature nodes and weights of the standard normal
+    double param, logparam;
+    double *lpd, *lcpo, *elp, *vlp;      // nobs each, each nullable
+    double *part;                // 4 per workgroup
+};
+// out4 (device) = the totals of lpd, lcpo, elp, vlp
+void launch_pred_scores(hipStream_t st, const PredScores &a, double *out4);
+
 }  // namespace gmrfx

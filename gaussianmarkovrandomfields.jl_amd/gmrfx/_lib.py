@@ -83,6 +83,8 @@ EXPORTS = [
     "gmrfx_gaussian_approximation", "gmrfx_gaussian_approximation_dev",
     "gmrfx_obs_set_design", "gmrfx_obs_hess_map", "gmrfx_obs_design_info",
     "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
+    "gmrfx_obs_pointwise_const", "gmrfx_predictor_marginals", "gmrfx_predictor_marginals_dev",
+    "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
 ]
 
 
@@ -231,6 +233,11 @@ def lib():
         L.gmrfx_ga_pullback.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.gmrfx_ga_pullback_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.gmrfx_obs_design_rows.argtypes = [vp, vp, vp, vp]
+        L.gmrfx_obs_pointwise_const.argtypes = [vp, vp]
+        L.gmrfx_predictor_marginals.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.gmrfx_predictor_marginals_dev.argtypes = [vp, vp, i32, vp, vp, vp]
+        L.gmrfx_predictive_scores.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_predictive_scores_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

@@ -683,6 +683,79 @@ class MI355XBackend:
         check(lib().gmrfx_obs_design_rows(self._h, ptr(p), ptr(pos), ptr(w)), self._h)
         return p, pos, w
 
+    # -- the linear predictor's marginals and the predictive scores (src/linear_predictor_marginals.jl:58-195; include/gmrfx.h
+    # "Linear-predictor marginals and predictive scores")
+    def observations_pointwise_const(self) -> np.ndarray:
+        """c_i: the terms of every observation's log density that do not depend on x (gmrfx_obs_pointwise_const); no device needed."""
+        c = np.empty(self.observations_info()["nobs"])
+        check(lib().gmrfx_obs_pointwise_const(self._h, ptr(c)), self._h)
+        return c
+
+    def predictor_marginals(self, x, constraint_correction: bool = False, want_mean: bool = True, want_var: bool = True,
+                            want_pll: bool = True):
+        """(mu_eta, v_eta, pll) per observation in the caller's order (gmrfx_predictor_marginals): mean and variance of the linear
+        predictor under N(x, Sigma) with Sigma the inverse of the matrix the handle holds factorised (gaussian_approximation with
+        refactorize_final=True leaves Q_post), and the full log density at the mean. constraint_correction: subtract the constraint's
+        term from the variance and clamp at 0. The arrays not asked for are None."""
+        xx = np.ascontiguousarray(x, dtype=np.float64)
+        if xx.shape != (self.n,):
+            raise ValueError("dimension mismatch")
+        nobs = self.observations_info()["nobs"]
+        mu = np.empty(nobs) if want_mean else None
+        v = np.empty(nobs) if want_var else None
+        pll = np.empty(nobs) if want_pll else None
+        check(lib().gmrfx_predictor_marginals(self._h, ptr(xx), int(bool(constraint_correction)), ptr(mu), ptr(v), ptr(pll)), self._h)
+        return mu, v, pll
+
+    def predictor_marginals_dev(self, d_x: int, d_mu_eta: int = 0, d_v_eta: int = 0, d_pll: int = 0, constraint_correction: bool = False) -> None:
+        """Device pointers: x (n) and the outputs (nobs each, 0 = not computed)."""
+        if not d_x:
+            raise ValueError("predictor_marginals_dev: null pointer")
+        check(lib().gmrfx_predictor_marginals_dev(self._h, d_x, int(bool(constraint_correction)), d_mu_eta or None, d_v_eta or None,
+                                                  d_pll or None), self._h)
+
+    @staticmethod
+    def gauss_hermite(K: int):
+        """(nodes, weights) of the K-point Gauss-Hermite rule for the standard normal, the weights divided by their sum."""
+        z, w = np.polynomial.hermite_e.hermegauss(int(K))
+        return np.ascontiguousarray(z, dtype=np.float64), np.ascontiguousarray(w / w.sum(), dtype=np.float64)
+
+    @staticmethod
+    def _score_totals(out):
+        return {"lpd": float(out[0]), "lcpo": float(out[1]), "elp": float(out[2]), "p_waic": float(out[3]),
+                "waic": float(-2.0 * (out[0] - out[3]))}
+
+    def predictive_scores(self, mu_eta, v_eta, nodes, weights, want_arrays: bool = True):
+        """((lpd, lcpo, elp, vlp), totals) over eta_i ~ N(mu_eta_i, v_eta_i) with the caller's quadrature rule of the standard normal
+        (gmrfx_predictive_scores; gauss_hermite(K) gives one): log pointwise predictive density, log CPO, expected log density and
+        its variance per observation, and the dict of their totals lpd, lcpo, elp, p_waic, waic = -2 (lpd - p_waic)."""
+        mu = np.ascontiguousarray(mu_eta, dtype=np.float64)
+        v = np.ascontiguousarray(v_eta, dtype=np.float64)
+        z = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        nobs = self.observations_info()["nobs"]
+        if mu.shape != (nobs,) or v.shape != (nobs,) or z.shape != w.shape:
+            raise ValueError("dimension mismatch")
+        arrs = tuple(np.empty(nobs) for _ in range(4)) if want_arrays else (None,) * 4
+        out = np.empty(4)
+        check(lib().gmrfx_predictive_scores(self._h, ptr(mu), ptr(v), z.size, ptr(z), ptr(w), *(ptr(a) for a in arrs), ptr(out)), self._h)
+        return arrs, self._score_totals(out)
+
+    def predictive_scores_dev(self, d_mu_eta: int, d_v_eta: int, nodes, weights, d_lpd: int = 0, d_lcpo: int = 0, d_elp: int = 0,
+                              d_vlp: int = 0) -> dict:
+        """Device pointers for mu_eta, v_eta and the outputs (nobs each; 0 = not wanted); nodes and weights on the host. Returns the
+        totals."""
+        if not d_mu_eta or not d_v_eta:
+            raise ValueError("predictive_scores_dev: null pointer")
+        z = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if z.shape != w.shape:
+            raise ValueError("dimension mismatch")
+        out = np.empty(4)
+        check(lib().gmrfx_predictive_scores_dev(self._h, d_mu_eta, d_v_eta, z.size, ptr(z), ptr(w), d_lpd or None, d_lcpo or None,
+                                                d_elp or None, d_vlp or None, ptr(out)), self._h)
+        return self._score_totals(out)
+
     # -- sharded factorisation (include/gmrfx.h "sharded factorisation"; driver: gmrfx/shard.py) -------
     def refactorize_phase_dev(self, d_nzval_ptr: int, phase: int) -> None:
         check(lib().gmrfx_refactorize_phase(self._h, d_nzval_ptr, phase), self._h)
@@ -1346,3 +1419,9 @@ class MI355XBatchBackend:
         out = np.empty((p, self.nbatch), order="F")
         check(lib().gmrfx_batch_pattern_dot_dev(self._h, d_G, d_J, ldj, sj, p, out.ctypes.data), self._h)
         return out
+
+
+def gauss_hermite(K: int):
+    """(nodes, weights) of the K-point Gauss-Hermite rule for the standard normal (numpy.polynomial.hermite_e.hermegauss), the weights
+    divided by their sum: the rule predictive_scores takes."""
+    return MI355XBackend.gauss_hermite(K)

@@ -497,6 +497,39 @@ function ga_pullback(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, 
 end
 function ga_pullback_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
 
+# linear_predictor_marginals(ga, obs_lik) of the reference (src/linear_predictor_marginals.jl:58-195) and pointwise_loglik at the mean,
+# on the device (gmrfx_predictor_marginals; include/gmrfx.h): (mean, variance, pointwise log density) of every observation's linear
+# predictor, in the caller's order, under the factorisation the handle holds (refactorize_final = true above leaves Q_post).
+# constraint_correction: the correction and clamp of _subtract_constraint_correction!.
+function observations_pointwise_const(b::MI355XBackend)
+    fam = Ref{Int32}(0); nobs = Ref{Int64}(0); c0 = Ref{Float64}(0.0)
+    check(ccall((:gmrfx_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ref{Float64}), b.h.ptr, fam, nobs, c0), b.h)
+    c = Vector{Float64}(undef, nobs[])
+    GC.@preserve c check(ccall((:gmrfx_obs_pointwise_const, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h.ptr, c), b.h)
+    return c
+end
+function predictor_marginals(b::MI355XBackend, x::Vector{Float64}; constraint_correction::Bool = false)
+    length(x) == b.n || throw(DimensionMismatch("x must have n entries"))
+    nobs = length(observations_pointwise_const(b))
+    mu = Vector{Float64}(undef, nobs); v = Vector{Float64}(undef, nobs); pll = Vector{Float64}(undef, nobs)
+    GC.@preserve x mu v pll check(ccall((:gmrfx_predictor_marginals, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, x, Int32(constraint_correction), mu, v, pll), b.h)
+    return mu, v, pll
+end
+# The quadrature scores over eta_i ~ N(mu_eta_i, v_eta_i) (gmrfx_predictive_scores): nodes and weights of the standard normal from the
+# caller. Returns (lpd, lcpo, elp, vlp) per observation and the totals (lpd, lcpo, elp, p_waic, waic = -2 (lpd - p_waic)).
+function predictive_scores(b::MI355XBackend, mu_eta::Vector{Float64}, v_eta::Vector{Float64}, nodes::Vector{Float64}, weights::Vector{Float64})
+    nobs = length(mu_eta)
+    length(v_eta) == nobs && length(nodes) == length(weights) || throw(DimensionMismatch("mu_eta / v_eta and nodes / weights must pair up"))
+    lpd = Vector{Float64}(undef, nobs); lcpo = Vector{Float64}(undef, nobs); elp = Vector{Float64}(undef, nobs); vlp = Vector{Float64}(undef, nobs)
+    out = zeros(4)
+    GC.@preserve mu_eta v_eta nodes weights lpd lcpo elp vlp out check(ccall((:gmrfx_predictive_scores, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        b.h.ptr, mu_eta, v_eta, length(nodes), nodes, weights, lpd, lcpo, elp, vlp, out), b.h)
+    return (lpd = lpd, lcpo = lcpo, elp = elp, vlp = vlp), (lpd = out[1], lcpo = out[2], elp = out[3], p_waic = out[4], waic = -2 * (out[1] - out[4]))
+end
+
 # gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313) for workspaces on
 # this backend and the pointwise exponential-family likelihoods the device evaluates: one method per likelihood type, each more
 # specific than the reference's (WorkspaceGMRF, ObservationLikelihood) method. Everything else -- other links, Student-t, generic and

@@ -774,6 +774,60 @@ int32_t gmrfx_ga_pullback_dev(gmrfx_handle *h, const double *d_x, const double *
                               double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda, double *out /* host, 2 */);
 int32_t gmrfx_obs_design_rows(const gmrfx_handle *h, int64_t *ptr /* nobs + 1 */, int64_t *pos /* terms */, double *w /* terms */);
 
+/* ---- Linear-predictor marginals and predictive scores ----------------------------------------------------------------------------------
+ * What follows a fit: linear_predictor_marginals(ga, obs_lik) of the reference (src/linear_predictor_marginals.jl:58-195, with the
+ * constraint correction and clamp of _subtract_constraint_correction!, :189-195) and pointwise_loglik (src/observation_models/
+ * exponential_family/pointwise_implementations.jl), the inputs of posterior predictive checks and WAIC / CPO accumulators. Plain
+ * handles with a likelihood set (gmrfx_obs_set or gmrfx_obs_set_design; the six families), observations in the caller's order: the
+ * order of `indices` in node form, the rows of A in design form. With Sigma the selected inverse of the factorisation the handle holds
+ * (gmrfx_gaussian_approximation with its flag bit 3 leaves that of Q_post), a_i row i of A (node form: a unit vector):
+ *   mu_eta_i = (A x)_i + b_i            node form: x[idx_i]. Design form: the eta gmrfx_fisher_eval forms, bit for bit
+ *   v_eta_i  = a_i' Sigma a_i           node form: Sigma[idx_i, idx_i]; design form: the sum over the pairs (j <= k) of row i of
+ *                                       (j == k ? 1 : 2) A_ij A_ik Sigma[position of (j, k)] (the table of gmrfx_obs_design_rows); an
+ *                                       empty row gives +0.0
+ *   flags bit 0, with a constraint set:  v_eta_i <- max(v_eta_i - sum_{l < m} ((a_i B)_l)^2, 0), B = Q^-1 A_c' L_c^-T read where the
+ *                                       constraint keeps it (n x m, column-major; no transposed copy is built); a NaN stays a NaN.
+ *                                       Without the bit there is no clamp
+ *   pll_i    = l_i(mu_eta_i) + c_i      the full log density of observation i at the mean; c_i: gmrfx_obs_pointwise_const
+ * x: n values (the mode, already projected under a constraint); mu_eta, v_eta, pll: nobs each, each nullable, not all three. v_eta
+ * needs a factorisation and computes the selected inverse if this factorisation has none yet; mu_eta and pll need neither.
+ * gmrfx_obs_pointwise_const: c_i, the terms of the log density that do not depend on x, each computed in long double and rounded
+ * (Normal -1/2 log 2 pi - log sigma; Poisson -lgamma(y + 1); Bernoulli 0; Binomial the log binomial coefficient; NegBin lgamma(y + r) -
+ * lgamma(r) - lgamma(y + 1) + r log r; Gamma phi log phi - lgamma(phi) + (phi - 1) log y). Works on symbolic_only handles; their sum is
+ * the loglik_const of gmrfx_obs_info.
+ *
+ * gmrfx_predictive_scores: with s_i = sqrt(v_eta_i) and l_k = l_i(mu_eta_i + s_i z_k) + c_i over the caller's K nodes z and weights w
+ * of the standard normal (host arrays in both forms; 1 <= K <= 64, all finite, weights positive; the library holds no rule and does
+ * not normalise):
+ *   elp_i  = sum_k w_k l_k                                      vlp_i = sum_k w_k (l_k - elp_i)^2
+ *   lpd_i  = M + log sum_k w_k exp(l_k - M),  M = max_k l_k     (-inf when every l_k is)
+ *   lcpo_i = -(M' + log sum_k w_k exp(-l_k - M')),  M' = max_k -l_k      (-inf when some l_k is -inf)
+ * A NaN or negative v_eta_i gives NaN in all four; where elp_i is -inf, vlp_i is NaN. mu_eta, v_eta: nobs values each (normally the
+ * outputs above, left on the device); lpd, lcpo, elp, vlp: nobs each, each nullable; out[4] (host): the totals sum_i lpd_i, lcpo_i,
+ * elp_i, vlp_i, computed whether or not the arrays are asked for (p_waic = out[3], WAIC = -2 (out[0] - out[3]): the caller's).
+ * No atomics: every sum is formed in an order that depends on indices only; results are bit-reproducible, independent of the
+ * alignment of the operands (8 bytes suffice), the host and the _dev forms agree bit for bit, and a selection matrix A without offset
+ * gives mu_eta, v_eta and pll of the node form bit for bit. Device memory added on the first call after gmrfx_obs_set[_design]: 8 nobs
+ * bytes (c), 4 nobs (the observation order, node form) or 8 cnt (the plan's map, design form), and in design form, for v_eta, the
+ * plan's transposed term table (12 B per term, shared with gmrfx_ga_pullback; none of its work vectors); gmrfx_clone carries nothing new.
+ * Errors: INVALID_ARG (with a message, nothing written) for x null, every output null, unknown flag bits, bit 0 without a constraint,
+ * no likelihood, a batched or sharded handle; for the scores mu_eta / v_eta / out null and a refused quadrature rule. Then
+ * GMRFX_ERR_NO_DEVICE for symbolic_only handles, GMRFX_ERR_NOT_FACTORIZED when v_eta is asked for before the first factorisation,
+ * GMRFX_ERR_NOT_POSDEF when the constraint's W fails (outputs untouched).
+ * LIMITS: plain handles; n, nobs < 2^31; K <= 64. A row's term list is summed by one lane group whatever its length (a row of k entries
+ * has k (k + 1) / 2 terms), and with bit 0 a row costs m lane-group sums. */
+int32_t gmrfx_obs_pointwise_const(const gmrfx_handle *h, double *out /* nobs */);
+int32_t gmrfx_predictor_marginals(gmrfx_handle *h, const double *x /* n */, int32_t flags, double *mu_eta /* nobs, nullable */,
+                                  double *v_eta /* nobs, nullable */, double *pll /* nobs, nullable */);
+int32_t gmrfx_predictor_marginals_dev(gmrfx_handle *h, const double *d_x, int32_t flags, double *d_mu_eta, double *d_v_eta, double *d_pll);
+int32_t gmrfx_predictive_scores(gmrfx_handle *h, const double *mu_eta /* nobs */, const double *v_eta /* nobs */, int64_t K,
+                                const double *z /* host, K */, const double *w /* host, K */, double *lpd /* nobs, nullable */,
+                                double *lcpo /* nobs, nullable */, double *elp /* nobs, nullable */, double *vlp /* nobs, nullable */,
+                                double *out /* host, 4 */);
+int32_t gmrfx_predictive_scores_dev(gmrfx_handle *h, const double *d_mu_eta, const double *d_v_eta, int64_t K, const double *z /* host, K */,
+                                    const double *w /* host, K */, double *d_lpd, double *d_lcpo, double *d_elp, double *d_vlp,
+                                    double *out /* host, 4 */);
+
 #ifdef __cplusplus
 }
 #endif
