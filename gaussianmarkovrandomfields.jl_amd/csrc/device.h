@@ -135,6 +135,9 @@ public:
     // ---- batched handles (gmrfx_create_batched): nbatch members of n_member nodes, the forest diag(Q_1 .. Q_B) -------------------
     void set_batch(int nbatch, long long n_member, long long nnz_member);
     bool batched() const { return (bool)h_bdiag_; }
+    // more than one member: what the plain-handle-only calls (obs_set, fisher_eval, ga_pullback, predictor_marginals, predictive_scores)
+    // refuse. NOT batched(): a plain handle becomes a batch of one on its first gmrfx_batch_* call and stays a plain handle to them.
+    bool many_members() const { return nbatch_ > 1; }
     // per-member log det / pivot status (1 + member-local column, 0 = fine) of the current factorisation, host arrays of nbatch
     void batch_diag(double *logdet_out, long long *info_out);
     // quad[k nvec + v] = (x_vk - mu_k)' Q_k (x_vk - mu_k), device operands: x_vk = d_X + k sx + v ldx, Q_k = d_nz + k nnz_member,

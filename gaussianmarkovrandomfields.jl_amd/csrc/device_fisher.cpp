@@ -16,7 +16,7 @@ namespace gmrfx {
 
 void Device::obs_set(const ObsHost &o) {
     HC(hipSetDevice(device));
-    if (sharded() || batched()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
+    if (sharded() || many_members()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
     FisherDev f;         // built aside: a failed upload leaves the previous likelihood in place
     if (o.nobs > 0 && o.design) obs_set_design(o, f);
     else if (o.nobs > 0) {
@@ -133,7 +133,7 @@ void Device::fisher_eval_design(const RbmcSym &sym, const double *d_x, const dou
 
 void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host) {
     HC(hipSetDevice(device));
-    if (sharded() || batched()) throw std::invalid_argument("fisher_eval: batched and sharded handles are not supported");
+    if (sharded() || many_members()) throw std::invalid_argument("fisher_eval: batched and sharded handles are not supported");
     if (!d_x || !out_host) throw std::invalid_argument("fisher_eval: x / out is null");
     if (!d_prior_) throw std::invalid_argument("fisher_eval: gmrfx_set_prior has not been called");
     const long long n = S_->n;

@@ -73,7 +73,7 @@ void Device::gap_tables() {
 
 int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info) {
     HC(hipSetDevice(device));
-    if (sharded() || batched()) throw std::invalid_argument("ga_pullback: batched and sharded handles are not supported");
+    if (sharded() || many_members()) throw std::invalid_argument("ga_pullback: batched and sharded handles are not supported");
     if (!io.d_x || !out_host) throw std::invalid_argument("ga_pullback: x / out is null");
     if (!obs_held()) throw std::invalid_argument("ga_pullback: no observation likelihood is set (gmrfx_obs_set)");
     const long long n = S_->n;

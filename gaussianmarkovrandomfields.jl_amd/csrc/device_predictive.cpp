@@ -54,7 +54,7 @@ void Device::pred_tables(const ObsHost &o) {
 
 int Device::predictor_marginals(const RbmcSym &sym, const ObsHost &o, const PredIO &io) {
     HC(hipSetDevice(device));
-    if (sharded() || batched()) throw std::invalid_argument("predictor_marginals: batched and sharded handles are not supported");
+    if (sharded() || many_members()) throw std::invalid_argument("predictor_marginals: batched and sharded handles are not supported");
     if (!io.d_x) throw std::invalid_argument("predictor_marginals: x is null");
     if (!io.d_mu_eta && !io.d_v_eta && !io.d_pll) throw std::invalid_argument("predictor_marginals: every output is null");
     if (!obs_held() || o.nobs <= 0) throw std::invalid_argument("predictor_marginals: no observation likelihood is set (gmrfx_obs_set)");
@@ -85,7 +85,7 @@ int Device::predictor_marginals(const RbmcSym &sym, const ObsHost &o, const Pred
 
 void Device::predictive_scores(const ObsHost &o, const ScoreIO &io, double *out4_host) {
     HC(hipSetDevice(device));
-    if (sharded() || batched()) throw std::invalid_argument("predictive_scores: batched and sharded handles are not supported");
+    if (sharded() || many_members()) throw std::invalid_argument("predictive_scores: batched and sharded handles are not supported");
     if (!io.d_mu || !io.d_v || !out4_host) throw std::invalid_argument("predictive_scores: mu_eta / v_eta / out is null");
     if (!obs_held() || o.nobs <= 0) throw std::invalid_argument("predictive_scores: no observation likelihood is set (gmrfx_obs_set)");
     if (io.K < 1 || io.K > kPredMaxNodes || !io.z || !io.w) throw std::invalid_argument("predictive_scores: K must be 1 .. 64, with nodes and weights");
