@@ -1,0 +1,189 @@
+// api_batch_fisher.cpp -- the C ABI of include/gmrfx.h: Fisher scoring and the Gaussian approximation for every member of a batched
+// handle (Device::bobs_set, Device::batch_fisher_eval, Device::batch_gaussian_approximation; csrc/batch_fisher.hip). A plain handle is
+// a batch of one to these calls, as to every gmrfx_batch_* call; gmrfx_obs_set and its family keep refusing batched handles.
+#include "api_obs.h"
+
+// what every call here refuses about the handle itself, before anything else is looked at
+static void bf_check_handle(const gmrfx_handle *h, const std::string &who) {
+    check_unsharded(h, (who + "sharded handles are not supported").c_str());
+    if (h->nbatch > kBatchFisherMaxMembers) throw std::invalid_argument(who + "more than 65535 members");
+    if (h->obs.design) throw std::invalid_argument(who + "the design form (eta = A x + b, gmrfx_obs_set_design) is not supported");
+    if (h->bcon.m > 0 || h->con.m > 0) throw std::invalid_argument(who + "a constraint set is not supported (clear it first)");
+}
+// the member's sizes, on plain handles too
+static int64_t bf_n(const gmrfx_handle *h) { return h->nbatch > 1 ? h->n_member : h->S.n; }
+// a plain handle's batch buffers, on its first batch call (need_batch without the NO_DEVICE answer: symbolic_only handles pass)
+static void bf_ensure_batch(gmrfx_handle *h) {
+    if (h->D && !h->D->batched()) h->D->set_batch(1, h->S.n, h->S.nnz_in);
+}
+static void bf_check_stride(const std::string &who, const char *what, int64_t s, int64_t n, bool zero_ok = false) {
+    if (zero_ok && s == 0) return;
+    if (s < n) throw std::invalid_argument(who + what + ": member stride smaller than n");
+}
+
+extern "C" int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_set_prior: ";
+        bf_check_handle(h, who);
+        if (!prior_nzval) throw std::invalid_argument(who + "prior_nzval is null");
+        if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);       // (refuses a pattern without a stored diagonal)
+        if (int32_t e = need_device(h, false)) return e;
+        bf_ensure_batch(h);
+        // the diagonal map, member after member: the forest's own diagonal positions
+        std::vector<long long> map(h->rsym.diag.begin(), h->rsym.diag.end());
+        h->D->set_prior(prior_nzval, map.data(), (long long)map.size());
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices, int32_t index_base, const double *y,
+                                       const double *aux, const double *param) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_obs_set: ";
+        bf_check_handle(h, who);
+        const int64_t n = bf_n(h), nb = h->nbatch;
+        if (nobs == 0) {
+            if (h->D) h->D->bobs_set(h->rsym, BObsHost{});
+            h->bobs = BObsHost{};
+            return GMRFX_OK;
+        }
+        obs_check_family(who, family);
+        if (nobs < 0 || nobs > n) throw std::invalid_argument(who + "nobs outside [0, n]");
+        check_index_base(index_base, who.c_str());
+        if (!indices && nobs != n) throw std::invalid_argument(who + "indices is null and nobs != n");
+        if (!param) throw std::invalid_argument(who + "param is null (one value per member)");
+        BObsHost o;
+        o.idx.resize((size_t)nobs);
+        std::vector<unsigned char> seen((size_t)n, 0);
+        for (int64_t k = 0; k < nobs; k++) {
+            const int64_t i = indices ? indices[k] - index_base : k;
+            if (i < 0 || i >= n) throw std::invalid_argument(who + "index " + std::to_string(k) + " is outside the range");
+            if (seen[(size_t)i]) throw std::invalid_argument(who + "node " + std::to_string(i + index_base) + " is observed twice");
+            seen[(size_t)i] = 1;
+            o.idx[(size_t)k] = i;
+        }
+        o.family = family; o.nobs = nobs;
+        o.param.resize((size_t)nb); o.loglik_const.resize((size_t)nb);
+        for (int64_t k = 0; k < nb; k++) {          // every check of gmrfx_obs_set, member by member; loglik_const in long double each
+            const std::string wk = who + "member " + std::to_string(k) + ": ";
+            obs_check_operands(wk, family, y, aux, param[k]);
+            ObsHost ok;
+            obs_fill_values(ok, wk, family, nobs, y, aux, param[k]);
+            o.param[(size_t)k] = param[k];
+            o.loglik_const[(size_t)k] = ok.loglik_const;
+            if (k == nb - 1) { o.y = std::move(ok.y); o.aux = std::move(ok.aux); }
+        }
+        if (h->D) {
+            bf_ensure_batch(h);
+            if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+            h->D->bobs_set(h->rsym, o);
+        }
+        h->bobs = std::move(o);
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_batch_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    if (family) *family = h->bobs.nobs > 0 ? h->bobs.family : -1;
+    if (nobs) *nobs = h->bobs.nobs;
+    if (loglik_const)
+        for (int64_t k = 0; k < h->nbatch; k++) loglik_const[k] = h->bobs.nobs > 0 ? h->bobs.loglik_const[(size_t)k] : 0.0;
+    return GMRFX_OK;
+}
+
+static int32_t bf_eval_impl(gmrfx_handle *h, const double *x, int64_t sx, const double *mu, int64_t smu, const uint8_t *active, double *score,
+                            double *hess, int64_t ss, double *out, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_fisher_eval: ";
+        bf_check_handle(h, who);
+        if (!x) throw std::invalid_argument(who + "x is null");
+        if (!out) throw std::invalid_argument(who + "out is null");
+        const int64_t n = bf_n(h), nb = h->nbatch;
+        bf_check_stride(who, "x", sx, n);
+        if (mu) bf_check_stride(who, "mu", smu, n, true);
+        if (score || hess) bf_check_stride(who, "score / hess", ss, n);
+        if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
+        if (int32_t e = need_batch(h, false)) return e;
+        if (dev) {
+            h->D->batch_fisher_eval(Device::BEvalIO{x, sx, mu, smu, active, score, hess, ss}, out);
+            return GMRFX_OK;
+        }
+        DevBlock bx, bm, bs, bh;
+        stage_up(h, bx, x, sx, n, 1, sx, nb);
+        if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
+        // the outputs go up first: a member that is masked out keeps what the caller's arrays hold
+        if (score) stage_up(h, bs, score, ss, n, 1, ss, nb);
+        if (hess) stage_up(h, bh, hess, ss, n, 1, ss, nb);
+        h->D->batch_fisher_eval(Device::BEvalIO{bx, n, mu ? bm.get() : nullptr, smu == 0 ? 0 : n, active, score ? bs.get() : nullptr,
+                                                hess ? bh.get() : nullptr, n}, out);
+        if (score) stage_down(h, bs, score, ss, n, 1, ss, nb);
+        if (hess) stage_down(h, bh, hess, ss, n, 1, ss, nb);
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_batch_fisher_eval(gmrfx_handle *h, const double *x, int64_t sx, const double *mu, int64_t smu, const uint8_t *active,
+                                           double *score, double *hess, int64_t ss, double *out) {
+    return bf_eval_impl(h, x, sx, mu, smu, active, score, hess, ss, out, false);
+}
+extern "C" int32_t gmrfx_batch_fisher_eval_dev(gmrfx_handle *h, const double *d_x, int64_t sx, const double *d_mu, int64_t smu,
+                                               const uint8_t *active, double *d_score, double *d_hess, int64_t ss, double *out) {
+    return bf_eval_impl(h, d_x, sx, d_mu, smu, active, d_score, d_hess, ss, out, true);
+}
+
+static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const double *x0, int64_t sx0, int64_t max_iter, int64_t max_ls,
+                          double mean_tol, double dec_tol, int32_t flags, double *x, int64_t sx, double *hess, int64_t sh, double *result,
+                          double *totals, double *dec_trace, double *alpha_trace, int64_t *info, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_gaussian_approximation: ";
+        bf_check_handle(h, who);
+        if (!x || !result) throw std::invalid_argument(who + "x / result is null");
+        if (max_iter < 0 || max_ls < 0) throw std::invalid_argument(who + "max_iter / max_linesearch_iter is negative");
+        if (flags < 0 || flags > 15) throw std::invalid_argument(who + "unknown flag bits");
+        const int64_t n = bf_n(h), nb = h->nbatch;
+        bf_check_stride(who, "x", sx, n);
+        if (mu) bf_check_stride(who, "mu", smu, n, true);
+        if (x0) bf_check_stride(who, "x0", sx0, n);
+        if (hess) bf_check_stride(who, "hess", sh, n);
+        if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
+        if (int32_t e = need_batch(h, false)) return e;
+        const Device::GaOpts o{max_iter, max_ls, mean_tol, dec_tol, flags};
+        std::vector<long long> inf((size_t)nb, 0);
+        int rc;
+        if (dev) rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu, smu, x0, sx0, x, sx, hess, sh}, o, result, totals, dec_trace, alpha_trace, inf.data());
+        else {
+            DevBlock bm, b0, bx, bh;
+            if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
+            if (x0) stage_up(h, b0, x0, n, n, 1, sx0, nb);
+            stage_alloc(h, bx, n * nb);
+            if (hess) stage_up(h, bh, hess, n, n, 1, sh, nb);      // (a failed member's slice keeps what the caller's array holds)
+            rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu ? bm.get() : nullptr, smu == 0 ? 0 : n, x0 ? b0.get() : nullptr, n, bx, n,
+                                                                  hess ? bh.get() : nullptr, n}, o, result, totals, dec_trace, alpha_trace, inf.data());
+            stage_down(h, bx, x, n, n, 1, sx, nb);
+            if (hess) stage_down(h, bh, hess, n, n, 1, sh, nb);
+        }
+        if (info) std::copy(inf.begin(), inf.end(), info);
+        if (rc == 1) {
+            int64_t k = 0;
+            while (k < nb && inf[(size_t)k] == 0) k++;
+            h->err = who + "member " + std::to_string(k) + ": Q_prior - H is not positive definite (non-positive pivot at elimination step " +
+                     std::to_string(k < nb ? inf[(size_t)k] : 0) + ")";
+            return GMRFX_ERR_NOT_POSDEF;
+        }
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_batch_gaussian_approximation(gmrfx_handle *h, const double *mu, int64_t smu, const double *x0, int64_t sx0, int64_t max_iter,
+                                                      int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol, int32_t flags,
+                                                      double *x, int64_t sx, double *hess, int64_t sh, double *result, double *totals,
+                                                      double *dec_trace, double *alpha_trace, int64_t *info) {
+    return bf_ga_impl(h, mu, smu, x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, x, sx, hess, sh, result, totals,
+                      dec_trace, alpha_trace, info, false);
+}
+extern "C" int32_t gmrfx_batch_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, int64_t smu, const double *d_x0, int64_t sx0,
+                                                          int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                                          double newton_dec_tol, int32_t flags, double *d_x, int64_t sx, double *d_hess, int64_t sh,
+                                                          double *result, double *totals, double *dec_trace, double *alpha_trace, int64_t *info) {
+    return bf_ga_impl(h, d_mu, smu, d_x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, d_x, sx, d_hess, sh, result,
+                      totals, dec_trace, alpha_trace, info, true);
+}

@@ -33,6 +33,8 @@ struct gmrfx_handle {
     ConHost bcon;
     // the observation likelihood of Fisher scoring (gmrfx_obs_set): host copy, also on symbolic_only handles; obs.nobs = 0: none
     ObsHost obs;
+    // the likelihood of the batch calls (gmrfx_batch_obs_set): one data set, one parameter per member; bobs.nobs = 0: none
+    BObsHost bobs;
     // host analysis of the RBMC variance estimators (gmrfx_rbmc_plan / gmrfx_rbmc_var), built lazily: the symmetric row structure
     // once, the block plan of the most recent enclosure_size
     RbmcSym rsym;

@@ -75,6 +75,12 @@ extern "C" int32_t gmrfx_clone(const gmrfx_handle *h, gmrfx_handle **out) {
         if (c->D && c->bcon.m > 0) c->D->bcon_set(c->bcon);
         c->obs = h->obs;        // the likelihood travels too (the prior's values do not: the clone calls gmrfx_set_prior itself)
         if (c->D && c->obs.nobs > 0) c->D->obs_set(c->obs);
+        c->bobs = h->bobs;      // and so does the batch calls' (gmrfx_batch_obs_set)
+        if (c->D && c->bobs.nobs > 0) {
+            if (!c->D->batched()) c->D->set_batch(1, c->S.n, c->S.nnz_in);
+            if (!c->rsym.built) rbmc_build_sym(c->S, c->rsym);
+            c->D->bobs_set(c->rsym, c->bobs);
+        }
     } catch (const std::exception &e) {
         g_create_err = e.what();
         return GMRFX_ERR_HIP;

@@ -76,6 +76,15 @@ struct ObsHost {
     std::shared_ptr<const DesignPlan> design;
 };
 constexpr int kObsFamilies = 6;
+// The likelihood of a batched handle (gmrfx_batch_obs_set): ONE data set (idx, y, aux as in ObsHost) and one parameter per member, with
+// the member's loglik_const; nobs = 0: none. A plain handle keeps one too, as a batch of one, beside the ObsHost of gmrfx_obs_set.
+constexpr int kBatchFisherMaxMembers = 65535;      // the member is the second dimension of the launch grid
+struct BObsHost {
+    int family = 0;
+    long long nobs = 0;
+    std::vector<long long> idx;
+    std::vector<double> y, aux, param, loglik_const;      // param, loglik_const: one per member
+};
 
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
@@ -250,6 +259,25 @@ public:
     struct GaOpts { long long max_iter, max_ls; double mean_tol, dec_tol; int flags; };
     int gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
                                double *result, double *dec_trace, double *alpha_trace, long long *info);
+
+    // ---- the same for every member of a batched handle (device_batch_fisher.cpp, batch_fisher.hip; gmrfx_batch_obs_set,
+    // gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation). Node form, no constraints. The prior's values and the diagonal map
+    // are those of set_prior on the forest (gmrfx_batch_set_prior builds the map).
+    void bobs_set(const RbmcSym &sym, const BObsHost &o);
+    bool bobs_held() const { return (bool)bfisher_.y; }
+    // Member k's evaluation at d_x + k sx with the mean d_mu + k smu (nullable; smu = 0: one mean): score / hess at + k ss (either
+    // nullable), out_host[2 k ..] = {energy, loglik}. active (host, nbatch bytes, nullable = all): a member whose byte is 0 is skipped
+    // and nothing of it is written, on the device or in out_host. One synchronisation.
+    struct BEvalIO { const double *d_x; long long sx; const double *d_mu; long long smu; const unsigned char *active; double *d_score, *d_hess; long long ss; };
+    void batch_fisher_eval(const BEvalIO &io, double *out_host);
+    // The loop of gaussian_approximation for all members in lockstep: one forest-wide launch per step, member k seeing exactly the
+    // sequence of operations its own plain loop would perform. d_x0 nullable (= mu, or 0). result: host, 10 per member (the plain
+    // call's eight, then energy and loglik at the member's x); totals: host, 3 (forest factorisations, solves, evaluations launched);
+    // dec_trace / alpha_trace: host, (max_iter + 1) per member, nullable; info: host, one per member. Returns 0, or 1 when a member's
+    // factorisation failed (info[k] = 1 + its failing step, its x = its last accepted iterate, everybody else complete).
+    struct BGaIO { const double *d_mu; long long smu; const double *d_x0; long long sx0; double *d_x; long long sx; double *d_hess; long long sh; };
+    int batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, double *result, double *totals, double *dec_trace, double *alpha_trace,
+                                     long long *info);
 
     // The pullback of gaussian_approximation at its mode d_x (device_ga_pullback.cpp, ga_pullback.hip; gmrfx_ga_pullback): from the
     // cotangents of the mode (d_mubar, n) and of the posterior precision (d_Qbar, nnz on the pattern), either nullable, those of the
@@ -553,6 +581,21 @@ private:
         DevBuf<double> aval, acv, tw, offset, g, d, lpart, cpart;
         int ncc = 0, nct = 0;
     } fisher_;
+    // the same for the members of a batch: ONE data set by node and the member's row structure (the forest's first n_member rows), the
+    // members' parameters and their logs, the partial sums (2 per workgroup and 4 per chunk, per member), the results (6 per member:
+    // 2 of the evaluation, then 4 of the reductions) with their pinned copy, the loop's control words (nbatch step lengths, then
+    // nbatch mask bytes) with theirs, and the loop's six work vectors of the forest's length (on first use)
+    struct BFisherDev {
+        DevBuf<double> y, aux, param, logparam, part, out, spart, work, ctl;
+        DevBuf<unsigned char> mask;
+        DevBuf<long long> rp;
+        DevBuf<int> col, pos;
+        PinnedBuf<double> h_out, h_ctl;
+        std::vector<double> loglik_const;
+        int family = 0;
+    } bfisher_;
+    void bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask);
+    void bfisher_check_prior();
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
     // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
     struct GapDev {

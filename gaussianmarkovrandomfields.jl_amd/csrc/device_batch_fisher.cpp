@@ -1,0 +1,343 @@
+// device_batch_fisher.cpp -- Fisher scoring for every member of a batched handle (include/gmrfx.h: gmrfx_batch_obs_set,
+// gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation; kernels in batch_fisher.hip). The handle is the forest diag(Q_1 .. Q_B):
+// the priors' values (set_prior on the forest) are the members' one after the other, refactorize_update_solve factors and solves all
+// members in one pass, batch_diag reports per member. What is added here is the likelihood evaluation with per-member reductions and
+// the loop that lets every member take its own line search and stop at its own iterate.
+// THE LOCKSTEP INVARIANT. Member k sees exactly the sequence of operations Device::gaussian_approximation performs on a plain handle
+// of Q_p,k and param[k]: the same evaluations at the same points, the same factorisations and solves, the same reductions, the same
+// decisions. A step of the loop is ONE forest-wide launch masked to the members it concerns; a member that has stopped is masked out
+// of every launch that writes its slices, its hess slice above all: every later forest factorisation then reproduces its factor bit
+// for bit (a member's factor depends on its own values only), so it ends holding the factor of its own last iterate.
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <stdexcept>
+
+#include "device.h"
+#include "kernels.h"
+
+namespace gmrfx {
+
+#define HC(x) hip_check((x), #x)
+
+void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
+    HC(hipSetDevice(device));
+    if (sharded()) throw std::invalid_argument("batch_obs_set: sharded handles are not supported");
+    BFisherDev f;        // built aside: a failed upload leaves the previous likelihood in place
+    if (o.nobs > 0) {
+        const size_t n = (size_t)nmember_, nb = (size_t)nbatch_;
+        if (n == 0 || n > (size_t)INT_MAX || o.param.size() != nb) throw std::invalid_argument("batch_obs_set: the likelihood does not belong to this handle");
+        std::vector<double> y(n, 0.0), aux(o.aux.empty() ? 0 : n, 0.0), lp(nb, 0.0);
+        std::vector<unsigned char> mask(n, 0);
+        for (long long k = 0; k < o.nobs; k++) {
+            const size_t i = (size_t)o.idx[(size_t)k];
+            y[i] = o.y[(size_t)k];
+            if (!aux.empty()) aux[i] = o.aux[(size_t)k];
+            mask[i] = 1;
+        }
+        for (size_t k = 0; k < nb; k++) lp[k] = o.family == 4 ? std::log(o.param[k]) : 0.0;
+        // the member's rows: the forest's first n (columns and positions of member 0 are the member's own)
+        const size_t ne = (size_t)sym.rowptr[n];
+        std::vector<int> pos(ne);
+        for (size_t q = 0; q < ne; q++) pos[q] = (int)sym.pos[q];
+        auto up = [&](auto &dst, const auto *src, size_t cnt) {
+            dst.alloc(cnt, &bytes_total, kTableMinBytes);
+            if (cnt > 0) HC(hipMemcpy(dst, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
+        };
+        up(f.y, y.data(), n);
+        up(f.mask, mask.data(), n);
+        if (!aux.empty()) up(f.aux, aux.data(), n);
+        up(f.param, o.param.data(), nb);
+        up(f.logparam, lp.data(), nb);
+        up(f.rp, reinterpret_cast<const long long *>(sym.rowptr.data()), n + 1);
+        up(f.col, sym.col.data(), ne);
+        up(f.pos, pos.data(), ne);
+        f.part.alloc(2 * nb * (size_t)fisher_blocks((int)n), &bytes_total, kTableMinBytes);
+        f.spart.alloc(4 * nb * (size_t)fisher_stat_blocks((int)n), &bytes_total, kTableMinBytes);
+        f.out.alloc(6 * nb, &bytes_total, kTableMinBytes);
+        f.ctl.alloc(2 * nb, &bytes_total, kTableMinBytes);
+        f.h_out.alloc(6 * (long long)nb);
+        f.h_ctl.alloc(2 * (long long)nb);
+        f.family = o.family;
+        f.loglik_const = o.loglik_const;
+    }
+    HC(hipStreamSynchronize(stream));
+    bfisher_ = std::move(f);
+}
+
+// the map of set_prior must be the forest's diagonal, member after member (what gmrfx_batch_set_prior installs)
+void Device::bfisher_check_prior() {
+    if (!d_prior_) throw std::invalid_argument("batch_fisher_eval: gmrfx_batch_set_prior has not been called");
+    if (hmap_cnt_ != S_->n) throw std::invalid_argument("batch_fisher_eval: the map of the prior is not the members' diagonals (gmrfx_batch_set_prior installs it)");
+    if (!bobs_held()) throw std::invalid_argument("batch_fisher_eval: no observation likelihood is set (gmrfx_batch_obs_set)");
+}
+
+// the control words of the next launches: nbatch step lengths (nullable: kept), then the mask bytes. The pinned copy is rewritten
+// only behind a synchronisation: a copy enqueued earlier may still be reading it.
+void Device::bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask) {
+    const size_t nb = (size_t)nbatch_;
+    HC(hipStreamSynchronize(stream));
+    unsigned char *hm = reinterpret_cast<unsigned char *>(bfisher_.h_ctl + nb);
+    std::copy(mask.begin(), mask.end(), hm);
+    if (alpha) {
+        std::copy(alpha->begin(), alpha->end(), (double *)bfisher_.h_ctl);
+        HC(hipMemcpyAsync(bfisher_.ctl, bfisher_.h_ctl, nb * sizeof(double) + nb, hipMemcpyHostToDevice, stream));
+    } else HC(hipMemcpyAsync(bfisher_.ctl.get() + nb, hm, nb, hipMemcpyHostToDevice, stream));
+}
+
+void Device::batch_fisher_eval(const BEvalIO &io, double *out_host) {
+    HC(hipSetDevice(device));
+    if (!io.d_x || !out_host) throw std::invalid_argument("batch_fisher_eval: x / out is null");
+    bfisher_check_prior();
+    const int n = (int)nmember_, nb = nbatch_;
+    const unsigned char *d_act = nullptr;
+    if (io.active) {
+        bfisher_ctl(nullptr, std::vector<unsigned char>(io.active, io.active + nb));
+        d_act = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
+    }
+    const FisherEvalBatch a{n, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, nnz_member_, io.d_x, io.sx, io.d_mu, io.smu,
+                            bfisher_.y, bfisher_.aux.get(), bfisher_.mask, bfisher_.param, bfisher_.logparam, d_act, io.d_score, io.d_hess, io.ss,
+                            bfisher_.part};
+    launch_fisher_eval_batch(stream, a, nb, bfisher_.out);
+    HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    for (int k = 0; k < nb; k++) {
+        if (io.active && !io.active[k]) continue;
+        out_host[2 * k] = bfisher_.h_out[2 * k];
+        out_host[2 * k + 1] = bfisher_.h_out[2 * k + 1] + bfisher_.loglik_const[(size_t)k];
+    }
+}
+
+// _merit_atol (condition/gaussian_approximation.jl:245)
+static double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
+
+int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, double *result, double *totals, double *dec_trace, double *alpha_trace,
+                                         long long *info) {
+    HC(hipSetDevice(device));
+    if (!io.d_x || !result) throw std::invalid_argument("batch_gaussian_approximation: x / result is null");
+    if (o.max_iter < 0 || o.max_ls < 0) throw std::invalid_argument("batch_gaussian_approximation: max_iter / max_linesearch_iter is negative");
+    bfisher_check_prior();
+    if (!h_bdiag_) throw std::invalid_argument("not a batched handle");
+    const long long n = nmember_, N = S_->n;
+    const int nb = nbatch_;
+    const size_t nbytes = (size_t)n * sizeof(double);
+    const bool adaptive = o.flags & 1, retry_full = o.flags & 2, predictive = o.flags & 4, refactor_final = o.flags & 8;
+    if (!bfisher_.work) bfisher_.work.alloc(6 * (size_t)N, &bytes_total, kTableMinBytes);
+    // xk: the iterates; cand: every candidate of the line search, so the accepted iterate of every member; xf: the frozen finish's
+    // points. The chord steps of the look-ahead are solved into xk, which nobody reads between an iterate's reductions and the copy
+    // cand -> xk that ends it: the steps and iterates of the members that did not fire stay as they are.
+    double *xk = bfisher_.work, *cand = xk + N, *xf = xk + 2 * N, *step = xk + 3 * N, *score = xk + 4 * N, *hess = xk + 5 * N;
+    for (int k = 0; k < nb; k++) {
+        double *dst = xk + k * n;
+        if (io.d_x0) HC(hipMemcpyAsync(dst, io.d_x0 + k * io.sx0, nbytes, hipMemcpyDeviceToDevice, stream));
+        else if (io.d_mu) HC(hipMemcpyAsync(dst, io.d_mu + k * io.smu, nbytes, hipMemcpyDeviceToDevice, stream));
+        else HC(hipMemsetAsync(dst, 0, nbytes, stream));
+        if (info) info[k] = 0;
+    }
+    const long long tl = o.max_iter + 1;
+    for (long long q = 0; q < tl * nb; q++) {
+        if (dec_trace) dec_trace[q] = std::nan("");
+        if (alpha_trace) alpha_trace[q] = std::nan("");
+    }
+    enum { kRun, kConverged, kMaxIter, kFailed };
+    struct Member { int status = kRun; double alpha = 1.0, alpha_prev = 1.0, dec_prev = 0.0, dec = std::nan(""), nfact = 0, nsolve = 0, nmerit = 0;
+                    long long iters = 0; bool frozen = false; };
+    std::vector<Member> m((size_t)nb);
+    double tot_fact = 0, tot_solve = 0, tot_eval = 0;
+    std::vector<double> ev(2 * (size_t)nb), st(4 * (size_t)nb), al((size_t)nb, 1.0), obj_accept((size_t)nb), stepinf((size_t)nb);
+    std::vector<long long> binfo((size_t)nb);
+    const unsigned char *d_mask = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
+    const double *d_alpha = bfisher_.ctl;
+    auto any = [](const std::vector<unsigned char> &v) { return std::find(v.begin(), v.end(), (unsigned char)1) != v.end(); };
+    // an evaluation over the members of `mask` (already on the device): their pairs to ev
+    auto eval = [&](const double *x, long long sx, double *sc, double *hs, const std::vector<unsigned char> &mask) {
+        const FisherEvalBatch a{(int)n, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, nnz_member_, x, sx, io.d_mu, io.smu,
+                                bfisher_.y, bfisher_.aux.get(), bfisher_.mask, bfisher_.param, bfisher_.logparam, d_mask, sc, hs, n, bfisher_.part};
+        launch_fisher_eval_batch(stream, a, nb, bfisher_.out);
+        HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HC(hipStreamSynchronize(stream));
+        tot_eval += 1;
+        for (int k = 0; k < nb; k++)
+            if (mask[(size_t)k]) { ev[2 * k] = bfisher_.h_out[2 * k]; ev[2 * k + 1] = bfisher_.h_out[2 * k + 1] + bfisher_.loglik_const[(size_t)k]; }
+    };
+    // the four reductions over the members of `mask`, to st
+    auto stats = [&](const double *a, const double *b, const double *c, const double *d, const std::vector<unsigned char> &mask) {
+        bfisher_ctl(nullptr, mask);
+        launch_fisher_stats_batch(stream, (int)n, nb, a, b, c, d, n, d_mask, bfisher_.spart, bfisher_.out.get() + 2 * nb);
+        HC(hipMemcpyAsync(bfisher_.h_out + 2 * nb, bfisher_.out.get() + 2 * nb, 4 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HC(hipStreamSynchronize(stream));
+        for (int k = 0; k < nb; k++)
+            if (mask[(size_t)k]) std::copy(bfisher_.h_out + 2 * nb + 4 * k, bfisher_.h_out + 2 * nb + 4 * k + 4, st.begin() + 4 * k);
+    };
+    // candidates x_k - al[k] step_k into cand and the merit there, for the members of `mask`: merit to ev
+    auto probe = [&](const std::vector<unsigned char> &mask) {
+        bfisher_ctl(&al, mask);
+        launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+        eval(cand, n, nullptr, nullptr, mask);
+        for (int k = 0; k < nb; k++)
+            if (mask[(size_t)k]) m[(size_t)k].nmerit += 1;
+    };
+    auto stop = [&](int k, int status, const double *x, long long iters, bool frozen) {
+        Member &mk = m[(size_t)k];
+        mk.status = status; mk.iters = iters; mk.frozen = frozen;
+        HC(hipMemcpyAsync(io.d_x + k * io.sx, x + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
+    };
+    std::vector<unsigned char> run((size_t)nb, 1), mask((size_t)nb);
+    for (long long iter = 1; iter <= o.max_iter && any(run); iter++) {
+        bfisher_ctl(nullptr, run);
+        eval(xk, n, score, hess, run);
+        std::vector<double> ek = ev;
+        refactorize_update_solve(hess, true, score, N, 1, step, N, true);
+        tot_fact += 1; tot_solve += 1;
+        batch_diag(nullptr, binfo.data());
+        for (int k = 0; k < nb; k++) {
+            if (!run[(size_t)k]) continue;
+            Member &mk = m[(size_t)k];
+            mk.nfact += 1; mk.nsolve += 1;
+            if (binfo[(size_t)k] != 0) {
+                if (info) info[k] = binfo[(size_t)k];
+                stop(k, kFailed, xk, iter - 1, false);
+                run[(size_t)k] = 0;
+            }
+            mk.alpha_prev = mk.alpha;
+        }
+        if (!any(run)) break;
+        if (adaptive) {
+            // _ga_line_search per member, in rounds: a round forms the candidates of the members still searching and evaluates them
+            bool have_inf = false;
+            std::vector<unsigned char> searching = run, exhausted((size_t)nb, 0);
+            std::vector<long long> ls((size_t)nb, 0);
+            for (int k = 0; k < nb; k++)
+                obj_accept[(size_t)k] = (ek[2 * k] - ek[2 * k + 1]) + merit_atol(std::fabs(ek[2 * k]) + std::fabs(ek[2 * k + 1]));
+            if (retry_full) {       // round 0: the full step, for the members whose alpha is below 1
+                for (int k = 0; k < nb; k++) { mask[(size_t)k] = run[(size_t)k] && m[(size_t)k].alpha < 1.0; al[(size_t)k] = 1.0; }
+                if (any(mask)) {
+                    probe(mask);
+                    for (int k = 0; k < nb; k++)
+                        if (mask[(size_t)k] && ev[2 * k] - ev[2 * k + 1] <= obj_accept[(size_t)k]) { m[(size_t)k].alpha = 1.0; searching[(size_t)k] = 0; }
+                }
+            }
+            for (;;) {
+                for (int k = 0; k < nb; k++) {
+                    if (searching[(size_t)k] && ls[(size_t)k] >= o.max_ls) { searching[(size_t)k] = 0; exhausted[(size_t)k] = 1; }
+                    al[(size_t)k] = m[(size_t)k].alpha;
+                }
+                if (!any(searching)) break;
+                probe(searching);
+                bool backtracked = false;
+                for (int k = 0; k < nb; k++) {
+                    if (!searching[(size_t)k]) continue;
+                    Member &mk = m[(size_t)k];
+                    ls[(size_t)k] += 1;
+                    if (ev[2 * k] - ev[2 * k + 1] <= obj_accept[(size_t)k]) { mk.alpha = std::sqrt(mk.alpha); searching[(size_t)k] = 0; }
+                    else { mk.alpha *= 0.1; backtracked = true; }
+                }
+                if (backtracked) {
+                    if (!have_inf) {        // |step_k|_inf, once per iterate
+                        stats(nullptr, step, nullptr, nullptr, run);
+                        for (int k = 0; k < nb; k++) stepinf[(size_t)k] = st[4 * k + 3];
+                        have_inf = true;
+                    }
+                    for (int k = 0; k < nb; k++)
+                        if (searching[(size_t)k] && m[(size_t)k].alpha * stepinf[(size_t)k] < o.dec_tol / 1000) searching[(size_t)k] = 0;
+                }
+            }
+            if (any(exhausted)) {
+                bfisher_ctl(&al, exhausted);
+                launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+            }
+        } else {
+            std::fill(al.begin(), al.end(), 1.0);
+            bfisher_ctl(&al, run);
+            launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+        }
+        stats(score, step, cand, xk, run);
+        std::vector<unsigned char> fire((size_t)nb, 0);
+        for (int k = 0; k < nb; k++) {
+            if (!run[(size_t)k]) continue;
+            Member &mk = m[(size_t)k];
+            mk.dec = st[4 * k];
+            const double mean_change = std::sqrt(st[4 * k + 1]), mean_change_rel = mean_change / std::max(std::sqrt(st[4 * k + 2]), 1.0e-10);
+            if (dec_trace) dec_trace[k * tl + iter - 1] = mk.dec;
+            if (alpha_trace) alpha_trace[k * tl + iter - 1] = mk.alpha;
+            if (mk.dec < o.dec_tol || mean_change < o.mean_tol || mean_change_rel < o.mean_tol) {
+                stop(k, kConverged, cand, iter, false);
+                run[(size_t)k] = 0;
+            } else if (predictive && iter > 1 && mk.alpha == 1.0 && mk.alpha_prev == 1.0 &&
+                       mk.dec * (mk.dec / mk.dec_prev) * (mk.dec / mk.dec_prev) < o.dec_tol)
+                fire[(size_t)k] = 1;
+        }
+        // _predict_converged, then _frozen_finish for the members that fired: three chord steps on the factorisation in hand, only the
+        // first decides, per member
+        if (any(fire)) {
+            for (int k = 0; k < nb; k++)
+                if (fire[(size_t)k]) HC(hipMemcpyAsync(xf + k * n, cand + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
+            std::fill(al.begin(), al.end(), 1.0);
+            for (int j = 1; j <= 3 && any(fire); j++) {
+                bfisher_ctl(&al, fire);
+                eval(xf, n, score, nullptr, fire);
+                solve(score, N, 1, xk, N, true, 0);
+                tot_solve += 1;
+                for (int k = 0; k < nb; k++)
+                    if (fire[(size_t)k]) m[(size_t)k].nsolve += 1;
+                if (j == 1) {
+                    stats(score, xk, nullptr, nullptr, fire);
+                    for (int k = 0; k < nb; k++) {
+                        if (!fire[(size_t)k]) continue;
+                        if (!(st[4 * k] < o.dec_tol)) { fire[(size_t)k] = 0; continue; }
+                        m[(size_t)k].dec = st[4 * k];
+                        if (dec_trace) dec_trace[k * tl + iter] = st[4 * k];
+                        if (alpha_trace) alpha_trace[k * tl + iter] = m[(size_t)k].alpha;
+                    }
+                    if (!any(fire)) break;
+                    bfisher_ctl(&al, fire);
+                }
+                launch_fisher_candidate_batch(stream, (int)n, nb, xf, n, xk, n, d_alpha, d_mask, xf, n);
+            }
+            for (int k = 0; k < nb; k++)
+                if (fire[(size_t)k]) { stop(k, kConverged, xf, iter + 1, true); run[(size_t)k] = 0; }
+        }
+        for (int k = 0; k < nb; k++)
+            if (run[(size_t)k]) {
+                m[(size_t)k].dec_prev = m[(size_t)k].dec;
+                HC(hipMemcpyAsync(xk + k * n, cand + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
+            }
+    }
+    for (int k = 0; k < nb; k++)
+        if (run[(size_t)k]) stop(k, kMaxIter, xk, o.max_iter, false);
+    // energy, loglik and H at every member's x (_workspace_build_result); the stopped members' hess slices may be written now: the
+    // only factorisation still to come is the one that wants them
+    std::fill(mask.begin(), mask.end(), (unsigned char)1);
+    bfisher_ctl(nullptr, mask);
+    eval(io.d_x, io.sx, nullptr, hess, mask);
+    int rc = 0;
+    bool any_ok = false;
+    for (int k = 0; k < nb; k++) {
+        if (m[(size_t)k].status == kFailed) { rc = 1; continue; }
+        any_ok = true;
+        if (io.d_hess) HC(hipMemcpyAsync(io.d_hess + k * io.sh, hess + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
+    }
+    if (refactor_final && any_ok) {
+        refactorize_update(hess, true);
+        tot_fact += 1;
+        batch_diag(nullptr, binfo.data());
+        for (int k = 0; k < nb; k++) {
+            if (m[(size_t)k].status == kFailed) continue;
+            m[(size_t)k].nfact += 1;
+            if (binfo[(size_t)k] != 0) { if (info) info[k] = binfo[(size_t)k]; rc = 1; }
+        }
+    }
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    for (int k = 0; k < nb; k++) {
+        const Member &mk = m[(size_t)k];
+        const double r[10] = {(double)mk.iters, mk.status == kConverged ? 1.0 : 0.0, mk.alpha, mk.dec, mk.nfact, mk.nsolve, mk.nmerit,
+                              mk.frozen ? 1.0 : 0.0, ev[2 * k], ev[2 * k + 1]};
+        std::copy(r, r + 10, result + 10 * k);
+    }
+    if (totals) { totals[0] = tot_fact; totals[1] = tot_solve; totals[2] = tot_eval; }
+    return rc;
+}
+
+}  // namespace gmrfx

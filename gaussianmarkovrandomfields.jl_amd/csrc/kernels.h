@@ -252,6 +252,39 @@ inline int fisher_stat_blocks(int n) { return (n + kFisherStatChunk - 1) / kFish
 void launch_fisher_candidate(hipStream_t st, int n, const double *x, const double *s, double alpha, double *out);
 void launch_fisher_stats(hipStream_t st, int n, const double *a, const double *b, const double *c, const double *d, double *part, double *out4);
 
+// batch_fisher.hip -- the same three pieces for the members of a batched handle (gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation):
+// the member in the grid's second dimension, ONE copy of the member's row structure, per-member values / points / parameters. A workgroup
+// never spans two members; the partial sums are kept per member and reduced by one workgroup per member in the order of the plain
+// kernels, so member k's results have the bits of the plain kernels on Q_p,k, param[k] and x_k. mask (nbatch bytes, nullable = all): a
+// member whose byte is 0 is skipped by every workgroup before its first load, and nothing of it is written.
+struct FisherEvalBatch {
+    int n, family;
+    const long long *rp;         // the MEMBER's Symmetric(Q) by rows: n + 1
+    const int *col, *pos;
+    const double *val;           // the priors' values, member k at + k nnz
+    long long nnz;
+    const double *x;             // member k's point at + k sx
+    long long sx;
+    const double *mu;            // nullable; member k's mean at + k smu (smu = 0: one mean for all)
+    long long smu;
+    const double *y, *aux;       // ONE data set, by node (aux nullable)
+    const unsigned char *mask;   // 1: the node has an observation
+    const double *param, *logparam;      // nbatch each
+    const unsigned char *active; // nbatch, nullable
+    double *score, *hess;        // member k at + k ss, either nullable
+    long long ss;
+    double *part;                // 2 per workgroup, member k's at + 2 k fisher_blocks(n)
+};
+// out[2 k], out[2 k + 1] = member k's energy and loglik sums (device); inactive members' pairs are left as they are
+void launch_fisher_eval_batch(hipStream_t st, const FisherEvalBatch &a, int nbatch, double *out);
+// out_k = x_k - alpha[k] s_k for the members whose byte in active is set (nullable = all); out may be x
+void launch_fisher_candidate_batch(hipStream_t st, int n, int nbatch, const double *x, long long sx, const double *s, long long ss,
+                                   const double *alpha, const unsigned char *active, double *out, long long so);
+// the four reductions of launch_fisher_stats per member: out4[4 k ..]; a, b, c, d: member k at + k s (one stride: the loop's work vectors);
+// part: 4 per chunk, member k's at + 4 k fisher_stat_blocks(n)
+void launch_fisher_stats_batch(hipStream_t st, int n, int nbatch, const double *a, const double *b, const double *c, const double *d, long long s,
+                               const unsigned char *active, double *part, double *out4);
+
 // fisher_design.hip -- the same evaluation through a sparse design matrix, eta = A x + b (gmrfx_obs_set_design). A lane group of
 // kDesignLanes lanes per row of A, per node and per Hessian position, kDesignRows of them per workgroup of 256 threads. A SEGMENT (a
 // column of A for A' g, a position's term list for A' D A) of at most kDesignChunk entries is summed by its lane group; a longer one is

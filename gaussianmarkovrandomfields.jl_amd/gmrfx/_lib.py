@@ -85,6 +85,8 @@ EXPORTS = [
     "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
     "gmrfx_obs_pointwise_const", "gmrfx_predictor_marginals", "gmrfx_predictor_marginals_dev",
     "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
+    "gmrfx_batch_set_prior", "gmrfx_batch_obs_set", "gmrfx_batch_obs_info", "gmrfx_batch_fisher_eval", "gmrfx_batch_fisher_eval_dev",
+    "gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev",
 ]
 
 
@@ -238,6 +240,13 @@ def lib():
         L.gmrfx_predictor_marginals_dev.argtypes = [vp, vp, i32, vp, vp, vp]
         L.gmrfx_predictive_scores.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.gmrfx_predictive_scores_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_set_prior.argtypes = [vp, vp]
+        L.gmrfx_batch_obs_set.argtypes = [vp, i32, i64, vp, i32, vp, vp, vp]
+        L.gmrfx_batch_obs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp]
+        L.gmrfx_batch_fisher_eval.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp]
+        L.gmrfx_batch_fisher_eval_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp]
+        for nm in ("gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev"):
+            getattr(L, nm).argtypes = [vp, vp, i64, vp, i64, i64, i64, dbl, dbl, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

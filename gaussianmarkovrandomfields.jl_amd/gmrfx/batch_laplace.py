@@ -1,0 +1,162 @@
+"""MI355XBatchLaplace -- a batched handle with the non-Gaussian path: one observation data set, one prior precision and one
+likelihood parameter per member, Fisher scoring and the Gaussian approximation for all members in one pass over the forest
+(include/gmrfx.h: gmrfx_batch_set_prior, gmrfx_batch_obs_set, gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation).
+The hyper-parameter sweep of a model with Poisson, binomial or similar observations: one Laplace approximation per theta_k."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import ERR_NOT_POSDEF, check, lib, ptr
+from .backend import MI355XBackend, MI355XBatchBackend
+
+
+class MI355XBatchLaplace(MI355XBatchBackend):
+    """Everything MI355XBatchBackend does, plus the likelihood. Shapes: NZ (nnz, B); points, means, scores and Hessians (n, B)."""
+
+    OBS_FAMILIES = MI355XBackend.OBS_FAMILIES
+
+    def clone(self) -> "MI355XBatchLaplace":
+        other = super().clone()
+        other.__class__ = MI355XBatchLaplace
+        return other
+
+    def _points(self, X, what: str, shared_ok: bool = False):
+        """(n, B) -> (Fortran array, member stride); (n,) with shared_ok -> (array, 0)"""
+        if X is None:
+            return None, 0
+        X = np.asarray(X, dtype=np.float64)
+        if shared_ok and X.shape == (self.n,):
+            return np.ascontiguousarray(X), 0
+        if X.shape != (self.n, self.nbatch):
+            raise ValueError(f"{what} must have shape (n, nbatch) = ({self.n}, {self.nbatch})" + (" or (n,)" if shared_ok else "") + f", got {X.shape}")
+        return np.asfortranarray(X), self.n
+
+    def _active(self, active):
+        if active is None:
+            return None
+        a = np.ascontiguousarray(np.asarray(active).astype(bool), dtype=np.uint8).reshape(-1)
+        if a.size != self.nbatch:
+            raise ValueError("active must have one entry per member")
+        return a
+
+    def set_prior(self, NZ) -> None:
+        """The members' prior precisions, (nnz, B); the diagonal Hessian map of every member is installed by the library."""
+        nz = self._values(NZ)
+        check(lib().gmrfx_batch_set_prior(self._h, ptr(nz)), self._h)
+
+    def set_observations(self, family, y, indices=None, aux=None, param=0.0, index_base: int = 0) -> None:
+        """ONE data set for all members (as MI355XBackend.set_observations) and one param per member: a scalar, or an array of length B.
+        An empty y removes the likelihood."""
+        fam = self.OBS_FAMILIES[family] if isinstance(family, str) else int(family)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        idx = None if indices is None else np.ascontiguousarray(indices, dtype=np.int64).reshape(-1)
+        ax = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).reshape(-1)
+        if (idx is not None and idx.size != yy.size) or (ax is not None and ax.size != yy.size):
+            raise ValueError("indices / aux do not have one entry per observation")
+        pp = np.asarray(param, dtype=np.float64)
+        pp = np.full(self.nbatch, float(pp)) if pp.ndim == 0 else np.ascontiguousarray(pp).reshape(-1)
+        if pp.size != self.nbatch:
+            raise ValueError("param must be a scalar or have one entry per member")
+        check(lib().gmrfx_batch_obs_set(self._h, fam, yy.size, ptr(idx), int(index_base), ptr(yy), ptr(ax), ptr(pp)), self._h)
+
+    def observations_info(self) -> dict:
+        fam, nobs, c = C.c_int32(0), C.c_int64(0), np.zeros(self.nbatch)
+        check(lib().gmrfx_batch_obs_info(self._h, C.byref(fam), C.byref(nobs), ptr(c)), self._h)
+        return {"family": fam.value, "nobs": nobs.value, "loglik_const": c}
+
+    def fisher_eval(self, X, mean=None, active=None, want_score: bool = True, want_hess: bool = True, score=None, hess=None):
+        """(score (n, B), hess (n, B), energy (B,), loglik (B,)) at the members' points X (n, B); mean: (n,) for every member or (n, B).
+        active: B flags; a member whose flag is 0 is skipped and its columns of score / hess (pass arrays to see that; fresh ones are
+        NaN there) and its energy / loglik (NaN) are left untouched."""
+        Xf, sx = self._points(X, "X")
+        mu, smu = self._points(mean, "mean", shared_ok=True)
+        act = self._active(active)
+
+        def _out(given, want):
+            if not want and given is None:
+                return None
+            if given is None:
+                return np.full((self.n, self.nbatch), np.nan, order="F")
+            if given.shape != (self.n, self.nbatch) or not given.flags.f_contiguous or given.dtype != np.float64:
+                raise ValueError("score / hess must be Fortran float64 arrays of shape (n, nbatch)")
+            return given
+        sc, hs = _out(score, want_score), _out(hess, want_hess)
+        out = np.full((2, self.nbatch), np.nan, order="F")
+        check(lib().gmrfx_batch_fisher_eval(self._h, ptr(Xf), sx, ptr(mu), smu, ptr(act), ptr(sc), ptr(hs), self.n, ptr(out)), self._h)
+        return sc, hs, out[0].copy(), out[1].copy()
+
+    def fisher_eval_dev(self, d_x: int, sx: int, d_mu: int = 0, smu: int = 0, active=None, d_score: int = 0, d_hess: int = 0, ss: int = 0, out=None):
+        """Device pointers with member strides (smu = 0: one mean); returns (energy (B,), loglik (B,)); `out` (2, B) Fortran is filled
+        in place when given (inactive members' pairs stay as they are)."""
+        if not d_x:
+            raise ValueError("fisher_eval_dev: null pointer")
+        act = self._active(active)
+        if out is None:
+            out = np.full((2, self.nbatch), np.nan, order="F")
+        check(lib().gmrfx_batch_fisher_eval_dev(self._h, d_x, sx, d_mu or None, smu, ptr(act), d_score or None, d_hess or None, ss or self.n,
+                                                ptr(out)), self._h)
+        return out[0].copy(), out[1].copy()
+
+    def _ga_info(self, res, totals, dec, alp, info, rc):
+        return {"iterations": res[0].astype(np.int64), "converged": res[1] != 0, "alpha": res[2].copy(), "decrement": res[3].copy(),
+                "factorizations": res[4].astype(np.int64), "solves": res[5].astype(np.int64), "merit_evaluations": res[6].astype(np.int64),
+                "frozen_finish": res[7] != 0, "energy": res[8].copy(), "loglik": res[9].copy(), "info": info.copy(),
+                "dec_trace": [dec[~np.isnan(dec[:, k]), k].copy() for k in range(self.nbatch)],
+                "alpha_trace": [alp[~np.isnan(alp[:, k]), k].copy() for k in range(self.nbatch)],
+                "totals": {"factorizations": int(totals[0]), "solves": int(totals[1]), "evaluations": int(totals[2])},
+                "posdef": rc != ERR_NOT_POSDEF}
+
+    def gaussian_approximation(self, mean=None, x0=None, max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5,
+                               adaptive_stepsize: bool = True, max_linesearch_iter: int = 10, step_recovery: str = "retry_full",
+                               predictive_convergence: bool = True, refactorize_final: bool = False):
+        """The Gaussian approximation of every member (gmrfx_batch_gaussian_approximation): (X (n, B), H (n, B), info). info holds
+        per-member arrays (iterations, converged, alpha, decrement, factorizations, solves, merit_evaluations, frozen_finish, energy,
+        loglik, info; dec_trace and alpha_trace as lists of arrays) and the forest-level `totals`. A member whose factorisation failed
+        does not raise: info["info"][k] > 0, X[:, k] is its last accepted iterate and H[:, k] is NaN; the others are complete."""
+        mu, smu = self._points(mean, "mean", shared_ok=True)
+        xs, sx0 = self._points(x0, "x0")
+        X = np.empty((self.n, self.nbatch), order="F")
+        H = np.full((self.n, self.nbatch), np.nan, order="F")
+        res, totals = np.zeros((10, self.nbatch), order="F"), np.zeros(3)
+        dec, alp = (np.full((max_iter + 1, self.nbatch), np.nan, order="F") for _ in range(2))
+        info = np.zeros(self.nbatch, np.int64)
+        flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+        rc = lib().gmrfx_batch_gaussian_approximation(self._h, ptr(mu), smu, ptr(xs), sx0, max_iter, max_linesearch_iter, float(mean_change_tol),
+                                                      float(newton_dec_tol), flags, ptr(X), self.n, ptr(H), self.n, ptr(res), ptr(totals),
+                                                      ptr(dec), ptr(alp), ptr(info))
+        self._info = info.copy()
+        if rc != ERR_NOT_POSDEF:
+            check(rc, self._h)
+        self._laplace = (res[8].copy(), res[9].copy())
+        return X, H, self._ga_info(res, totals, dec, alp, info, rc)
+
+    def gaussian_approximation_dev(self, d_x: int, sx: int, d_hess: int = 0, sh: int = 0, d_mu: int = 0, smu: int = 0, d_x0: int = 0, sx0: int = 0,
+                                   max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5, adaptive_stepsize: bool = True,
+                                   max_linesearch_iter: int = 10, step_recovery: str = "retry_full", predictive_convergence: bool = True,
+                                   refactorize_final: bool = False) -> dict:
+        """Device pointers with member strides: the modes x and hess (0 = not wanted) outputs, mean (smu = 0: one mean) and x0.
+        Returns the info dict."""
+        if not d_x:
+            raise ValueError("gaussian_approximation_dev: null pointer")
+        res, totals = np.zeros((10, self.nbatch), order="F"), np.zeros(3)
+        dec, alp = (np.full((max_iter + 1, self.nbatch), np.nan, order="F") for _ in range(2))
+        info = np.zeros(self.nbatch, np.int64)
+        flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
+        rc = lib().gmrfx_batch_gaussian_approximation_dev(self._h, d_mu or None, smu, d_x0 or None, sx0 or self.n, max_iter, max_linesearch_iter,
+                                                          float(mean_change_tol), float(newton_dec_tol), flags, d_x, sx, d_hess or None,
+                                                          sh or self.n, ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info))
+        self._info = info.copy()
+        if rc != ERR_NOT_POSDEF:
+            check(rc, self._h)
+        self._laplace = (res[8].copy(), res[9].copy())
+        return self._ga_info(res, totals, dec, alp, info, rc)
+
+    def laplace_terms(self) -> dict:
+        """energy and loglik at the modes of the last gaussian_approximation and logdet of the factor in hand, per member. With
+        log det Q_p,k the Laplace marginal likelihood of member k is loglik - energy' + (log det Q_p,k - logdet) / 2, where energy' is
+        the energy plus mu' Q_p,k mu / 2 (zero for a zero prior mean). After refactorize_final=True the factor is that of the mode."""
+        if getattr(self, "_laplace", None) is None:
+            raise ValueError("laplace_terms: gaussian_approximation has not been called")
+        return {"energy": self._laplace[0].copy(), "loglik": self._laplace[1].copy(), "logdet": self.logdet()}

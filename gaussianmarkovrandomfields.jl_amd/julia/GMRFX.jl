@@ -960,6 +960,66 @@ function constrained_var(bb::MI355XBatch)
     return out
 end
 
+# ---- the non-Gaussian path for every member (include/gmrfx.h: gmrfx_batch_set_prior .. gmrfx_batch_gaussian_approximation) ----------------
+# the members' prior precisions, nnz x nbatch; the library installs every member's diagonal Hessian map
+function set_prior!(bb::MI355XBatch, NZ::Matrix{Float64})
+    size(NZ) == (bb.nnz, bb.nbatch) || throw(DimensionMismatch("NZ must be nnz x nbatch"))
+    GC.@preserve NZ check(ccall((:gmrfx_batch_set_prior, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, NZ), bb.h)
+    return nothing
+end
+# ONE data set for all members (family id 0 .. 5, y, 1-based indices or nothing, aux or nothing) and one param per member
+function set_observations!(bb::MI355XBatch, family::Integer, y::Vector{Float64}, param::Vector{Float64};
+                           indices::Union{Nothing, Vector{Int64}} = nothing, aux::Union{Nothing, Vector{Float64}} = nothing)
+    length(param) == bb.nbatch || throw(DimensionMismatch("param must have one entry per member"))
+    idx = indices === nothing ? Ptr{Int64}(C_NULL) : pointer(indices)
+    ax = aux === nothing ? Ptr{Float64}(C_NULL) : pointer(aux)
+    GC.@preserve y param indices aux check(ccall((:gmrfx_batch_obs_set, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        bb.h.ptr, Int32(family), length(y), idx, Int32(1), y, ax, param), bb.h)
+    return nothing
+end
+function observations_info(bb::MI355XBatch)
+    fam = Ref{Int32}(0); nobs = Ref{Int64}(0); c = zeros(bb.nbatch)
+    GC.@preserve c check(ccall((:gmrfx_batch_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ptr{Float64}), bb.h.ptr, fam, nobs, c), bb.h)
+    return (family = fam[], nobs = nobs[], loglik_const = c)
+end
+# (score, hess, energy, loglik) at the members' points X (n x nbatch); mean n x nbatch or nothing; active: one byte per member or nothing
+function fisher_eval(bb::MI355XBatch, X::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing,
+                     active::Union{Nothing, Vector{UInt8}} = nothing)
+    size(X) == (bb.n, bb.nbatch) || throw(DimensionMismatch("X must be n x nbatch"))
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    active === nothing || length(active) == bb.nbatch || throw(DimensionMismatch("active must have one entry per member"))
+    score = fill(NaN, bb.n, bb.nbatch); hess = fill(NaN, bb.n, bb.nbatch); out = fill(NaN, 2, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    act = active === nothing ? Ptr{UInt8}(C_NULL) : pointer(active)
+    GC.@preserve X mean active score hess out check(ccall((:gmrfx_batch_fisher_eval, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
+        bb.h.ptr, X, bb.n, mu, bb.n, act, score, hess, bb.n, out), bb.h)
+    return score, hess, out[1, :], out[2, :]
+end
+# The Gaussian approximation of every member: (X, H, result 10 x nbatch, totals, dec_trace, alpha_trace, info). A member whose
+# factorisation failed does not throw: info[k] > 0, X[:, k] its last accepted iterate, H[:, k] NaN.
+function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Float64}} = nothing, x0::Union{Nothing, Matrix{Float64}} = nothing,
+                                max_iter::Integer = 50, max_linesearch_iter::Integer = 10, mean_change_tol::Real = 1e-4,
+                                newton_dec_tol::Real = 1e-5, flags::Integer = 7)
+    mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
+    x0 === nothing || size(x0) == (bb.n, bb.nbatch) || throw(DimensionMismatch("x0 must be n x nbatch"))
+    X = Matrix{Float64}(undef, bb.n, bb.nbatch); H = fill(NaN, bb.n, bb.nbatch)
+    result = zeros(10, bb.nbatch); totals = zeros(3)
+    dec = fill(NaN, max_iter + 1, bb.nbatch); alp = fill(NaN, max_iter + 1, bb.nbatch)
+    inf = zeros(Int64, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    xs = x0 === nothing ? Ptr{Float64}(C_NULL) : pointer(x0)
+    rc = GC.@preserve mean x0 X H result totals dec alp inf ccall((:gmrfx_batch_gaussian_approximation, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, mu, bb.n, xs, bb.n, Int64(max_iter), Int64(max_linesearch_iter), Float64(mean_change_tol), Float64(newton_dec_tol),
+        Int32(flags), X, bb.n, H, bb.n, result, totals, dec, alp, inf)
+    bb.info .= inf
+    rc == 5 || check(rc, bb.h)          # GMRFX_ERR_NOT_POSDEF: reported per member in info
+    return X, H, result, totals, dec, alp, inf
+end
+
 # deepcopy(bb) (Newton loops copy their caches) reaches the owning Handle: a copy of a handle is a clone of the native one
 # (gmrfx_clone), never a second owner of the same pointer
 function Base.deepcopy_internal(h::Handle, stackdict::IdDict)

@@ -729,6 +729,61 @@ int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, co
                                          double *d_x, double *d_hess, double *result /* host, 8 */, double *dec_trace /* host */,
                                          double *alpha_trace /* host */, int64_t *info);
 
+/* ---- Fisher scoring and the Gaussian approximation for every member of a batched handle ---------------------------------------------
+ * The hyper-parameter sweep of a model with non-Gaussian observations: one Gaussian approximation per theta_k, all in one pass over the
+ * forest of gmrfx_create_batched. Node form (eta_i = x_i), the six families of gmrfx_obs_set, no constraints; a plain handle is a batch of
+ * one. gmrfx_obs_set, gmrfx_fisher_eval and gmrfx_gaussian_approximation keep refusing batched handles; the state set here is separate
+ * from theirs.
+ *   gmrfx_batch_set_prior    keeps the nnz x nbatch values (member-major, as gmrfx_batch_refactorize takes them) on the device and
+ *                            installs the diagonal Hessian map of every member (the position of (i, i) in member k's values): the
+ *                            caller builds no forest-wide map. INVALID_ARG for a pattern without a stored diagonal.
+ *   gmrfx_batch_obs_set      ONE data set for all members (y, aux, indices as in gmrfx_obs_set; stored once, n values) and one param
+ *                            (sigma, r, phi) per member. The same validation and refusals as gmrfx_obs_set, applied to every param[k];
+ *                            loglik_const is summed per member in long double. nobs = 0 removes it; gmrfx_clone carries it; works on
+ *                            symbolic_only handles.
+ *   gmrfx_batch_obs_info     family (-1: none), nobs, loglik_const (nbatch values), each nullable.
+ *   gmrfx_batch_fisher_eval  per member exactly what gmrfx_fisher_eval returns for Q_p,k, param[k] and x_k, bit for bit: member k's point
+ *                            at x + k sx, its mean at mu + k smu (mu nullable; smu = 0: one mean for all), score and hess (either nullable)
+ *                            at + k ss, out[2 k ..] = {energy, loglik}. active (host, nbatch bytes, nullable = all): a member whose byte
+ *                            is 0 is skipped; its slices of score and hess and its pair of out are left untouched.
+ *   gmrfx_batch_gaussian_approximation   the loop of gmrfx_gaussian_approximation (same flags, same rules) for all members in lockstep:
+ *                            one forest-wide launch per step, every member taking its own line search, look-ahead and frozen finish and
+ *                            stopping at its own iterate. x0 nullable (= mu, or 0), member k's at + k sx0; x (sx) the modes; hess (sh,
+ *                            nullable) H(x_k). result (host, 10 per member): the plain call's eight numbers, counted as that member's own
+ *                            plain loop would count them, then energy and loglik at x_k. totals (host, 3, nullable): the forest-level
+ *                            factorisations, solves and evaluations actually launched. dec_trace / alpha_trace (host, (max_iter + 1) per
+ *                            member, nullable). info (nbatch, nullable). Returns GMRFX_ERR_NOT_POSDEF when any member's factorisation
+ *                            failed: info[k] is then as gmrfx_batch_refactorize reports it, x_k that member's last accepted iterate and
+ *                            its hess slice untouched; every other member is complete and correct, and the handle stays usable. A
+ *                            stopped member's values no longer change, so without flag bit 3 it ends holding the factor of its own last
+ *                            iterate; with it, one more forest factorisation at H(x_k) covers every member that did not fail.
+ * No atomics; bit-reproducible; the host and the _dev forms agree bit for bit; a member's results do not depend on the other members.
+ * Device memory: the data set (17 n bytes), the member's row structure, 6 n nbatch doubles of work vectors on the first loop.
+ * Errors (INVALID_ARG with a message, nothing changed): a sharded handle, more than 65535 members, a constraint set (gmrfx_constraints_set
+ * or gmrfx_batch_constraints_set), a plain handle holding the design form, null x / out / result, a stride below n (smu = 0 excepted), no
+ * likelihood, no prior. GMRFX_ERR_NO_DEVICE for symbolic_only handles after these checks.
+ * LIMITS: node form only, no constraints (both left to a follow-up); nbatch <= 65535; n < 2^31. */
+int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval /* nnz x nbatch */);
+int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices /* nobs, nullable */, int32_t index_base,
+                            const double *y /* nobs */, const double *aux /* nobs, nullable */, const double *param /* nbatch */);
+int32_t gmrfx_batch_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const /* nbatch */);
+int32_t gmrfx_batch_fisher_eval(gmrfx_handle *h, const double *x, int64_t sx, const double *mu /* nullable */, int64_t smu,
+                                const uint8_t *active /* host, nbatch, nullable */, double *score /* nullable */, double *hess /* nullable */,
+                                int64_t ss, double *out /* host, 2 x nbatch */);
+int32_t gmrfx_batch_fisher_eval_dev(gmrfx_handle *h, const double *d_x, int64_t sx, const double *d_mu, int64_t smu,
+                                    const uint8_t *active /* host */, double *d_score, double *d_hess, int64_t ss, double *out /* host */);
+int32_t gmrfx_batch_gaussian_approximation(gmrfx_handle *h, const double *mu /* nullable */, int64_t smu, const double *x0 /* nullable */,
+                                           int64_t sx0, int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                           double newton_dec_tol, int32_t flags, double *x, int64_t sx, double *hess /* nullable */,
+                                           int64_t sh, double *result /* host, 10 x nbatch */, double *totals /* host, 3, nullable */,
+                                           double *dec_trace /* host, (max_iter + 1) x nbatch, nullable */, double *alpha_trace /* same */,
+                                           int64_t *info /* nbatch, nullable */);
+int32_t gmrfx_batch_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, int64_t smu, const double *d_x0, int64_t sx0,
+                                               int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol, double newton_dec_tol,
+                                               int32_t flags, double *d_x, int64_t sx, double *d_hess, int64_t sh, double *result /* host */,
+                                               double *totals /* host */, double *dec_trace /* host */, double *alpha_trace /* host */,
+                                               int64_t *info);
+
 /* ---- The pullback of the Gaussian approximation (implicit-function rule) -------------------------------------------------------------
  * Reverse-mode rule of gaussian_approximation(prior, obs_lik) at its mode x (src/workspace/autodiff.jl:140-202; for plain GMRFs
  * src/autodiff/gaussian_approximation.jl:278-347), the step between gmrfx_logpdf_grad and gmrfx_pattern_dot when hyper-parameters are

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""B Gaussian approximations of one hyper-parameter sweep: gmrfx_batch_gaussian_approximation_dev on a batched handle against the same
+B approximations on ONE plain handle, one after the other (gmrfx_set_prior + gmrfx_obs_set + gmrfx_gaussian_approximation_dev per
+member), in the same process and run.
+
+Problem (DESIGN.md section 6a's): a 2-D Matern (alpha = 2) precision on a jittered g x g mesh, g = 100 (n = 10 000), B = 50 values of
+(range, tau) on one pattern, Poisson counts on every node (one data set), zero prior mean, x0 = 0, flag bit 3 (the handle is left
+factorised at every mode). Operands live in HBM. Reported: milliseconds per sweep and per member, median / minimum / maximum / the
+quartiles over --reps timed repetitions after --warmup, the GPU synchronised around each timed region; the per-member iteration
+counts of both routes, ASSERTED equal; the largest difference of the modes; the forest-level totals; the source tree hash. The
+plain route's per-member set_prior (nnz doubles over PCIe) and obs_set are part of what a sweep on one plain handle costs and are
+timed with it; "plain_loop_only" times the plain loops alone on B handles prepared beforehand.
+usage: tools/batch_ga_bench.py [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gaussianmarkovrandomfields.jl_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import gmrfx  # noqa: E402
+from gmrfx import _lib, spde  # noqa: E402
+
+
+def members(g, B, rng):
+    mesh = spde.grid_mesh_2d(g, g, jitter=0.25, seed=0)
+    Qs = [spde.matern_precision(mesh, 0, float(rng.uniform(0.15, 0.4)), tau=float(rng.uniform(0.5, 2.0))).tocsc() for _ in range(B)]
+    for Q in Qs:
+        Q.sort_indices()
+        assert np.array_equal(Q.indptr, Qs[0].indptr) and np.array_equal(Q.indices, Qs[0].indices), "pattern changed with the values"
+    return Qs, mesh.points
+
+
+def diag_positions(Q):
+    out = np.empty(Q.shape[0], np.int64)
+    for j in range(Q.shape[0]):
+        r = Q.indices[Q.indptr[j]:Q.indptr[j + 1]]
+        out[j] = Q.indptr[j] + int(np.searchsorted(r, j))
+    return out
+
+
+def timed(fn, reps, warmup):
+    for _ in range(warmup):
+        fn()
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    q = np.percentile(ts, [0, 25, 50, 75, 100])
+    return {"median_ms": float(q[2]), "min_ms": float(q[0]), "q25_ms": float(q[1]), "q75_ms": float(q[3]), "max_ms": float(q[4])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--grid", type=int, default=100)
+    ap.add_argument("--batch", type=int, default=50)
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    B, g = a.batch, a.grid
+    Qs, pts = members(g, B, np.random.default_rng(g))
+    n = Qs[0].shape[0]
+    NZ = np.asfortranarray(np.stack([Q.data for Q in Qs], axis=1))
+    y = np.random.default_rng(1).poisson(20.0, n).astype(float)
+    dpos = diag_positions(Qs[0])
+    kw = dict(refactorize_final=True)
+
+    bb = gmrfx.MI355XBatchLaplace(Qs[0], B, coords=pts, device=0)
+    bb.set_observations("poisson", y, param=0.0)
+    perm = bb.ordering_permutation()
+    dX = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    dX0 = torch.zeros(n * B, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    res = {}
+
+    def batched():
+        bb.set_prior(NZ)
+        res["b"] = bb.gaussian_approximation_dev(dX.data_ptr(), n, d_x0=dX0.data_ptr(), sx0=n, **kw)
+    t_b = timed(batched, a.reps, a.warmup)
+    Xb = dX.cpu().numpy().reshape(B, n).copy()
+
+    plain = gmrfx.MI355XBackend(Qs[0], ordering=perm, device=0, factorize=False)
+    dx = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    its = np.zeros(B, np.int64)
+
+    def sequential():
+        for k in range(B):
+            plain.set_prior(NZ[:, k], dpos)
+            plain.set_observations("poisson", y)
+            i = plain.gaussian_approximation_dev(dx.data_ptr() + 8 * k * n, d_x0=dX0.data_ptr(), **kw)
+            its[k] = i["iterations"]
+    t_s = timed(sequential, a.reps, a.warmup)
+    Xs = dx.cpu().numpy().reshape(B, n).copy()
+    plain.close()
+
+    many = []
+    for k in range(B):
+        p = gmrfx.MI355XBackend(Qs[0], ordering=perm, device=0, factorize=False)
+        p.set_prior(NZ[:, k], dpos)
+        p.set_observations("poisson", y)
+        many.append(p)
+
+    def loops_only():
+        for k, p in enumerate(many):
+            p.gaussian_approximation_dev(dx.data_ptr() + 8 * k * n, d_x0=dX0.data_ptr(), **kw)
+    t_l = timed(loops_only, a.reps, a.warmup)
+    for p in many:
+        p.close()
+
+    ib = res["b"]
+    assert np.array_equal(ib["iterations"], its), (ib["iterations"], its)
+    row = {"tool": "tools/batch_ga_bench.py", "device": torch.cuda.get_device_name(0), "source_tree_hash": _lib.source_tree_hash(),
+           "n": n, "grid": g, "B": B, "family": "poisson", "reps": a.reps, "warmup": a.warmup,
+           "batched": t_b, "one_plain_handle_sequential": t_s, "plain_loop_only": t_l,
+           "ms_per_member_batched": t_b["median_ms"] / B, "ms_per_member_sequential": t_s["median_ms"] / B,
+           "speedup_vs_sequential": t_s["median_ms"] / t_b["median_ms"], "speedup_vs_loops_only": t_l["median_ms"] / t_b["median_ms"],
+           "iterations": ib["iterations"].tolist(), "iteration_counts_agree": True, "totals": ib["totals"],
+           "sum_member_factorizations": int(ib["factorizations"].sum()), "max_abs_mode_diff": float(np.abs(Xb - Xs).max())}
+    print(json.dumps(row), flush=True)
+    bb.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(row, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
