@@ -1,5 +1,5 @@
 // api_batch_fisher.cpp -- the C ABI of include/gmrfx.h: Fisher scoring and the Gaussian approximation for every member of a batched
-// handle (Device::bobs_set, Device::batch_fisher_eval, Device::batch_gaussian_approximation; csrc/batch_fisher.hip). A plain handle is
+// handle (Device::bobs_set, Device::batch_fisher_eval, Device::batch_gaussian_approximation; csrc/fisher.hip). A plain handle is
 // a batch of one to these calls, as to every gmrfx_batch_* call; gmrfx_obs_set and its family keep refusing batched handles.
 #include "api_obs.h"
 

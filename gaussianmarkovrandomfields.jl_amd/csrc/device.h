@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <functional>
 #include <memory>
 #include <string>
@@ -85,6 +87,14 @@ struct BObsHost {
     std::vector<long long> idx;
     std::vector<double> y, aux, param, loglik_const;      // param, loglik_const: one per member
 };
+// what the node form of either likelihood puts on the device: (idx, y, aux) expanded to one value per node, mask = 1 where a node has
+// an observation, 0 elsewhere (aux stays empty when there is none)
+struct ObsByNode { std::vector<double> y, aux; std::vector<unsigned char> mask; };
+ObsByNode obs_by_node(size_t n, long long nobs, const std::vector<long long> &idx, const std::vector<double> &y, const std::vector<double> &aux);
+// the log r the negative binomial's stable forms take beside r (fisher_point.h); the other families do not read it
+inline double fisher_logparam(int family, double param) { return family == 4 ? std::log(param) : 0.0; }
+// _merit_atol (condition/gaussian_approximation.jl:245): the line search's slack on the merit, for both loops
+inline double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
 
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
@@ -260,7 +270,7 @@ public:
     int gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
                                double *result, double *dec_trace, double *alpha_trace, long long *info);
 
-    // ---- the same for every member of a batched handle (device_batch_fisher.cpp, batch_fisher.hip; gmrfx_batch_obs_set,
+    // ---- the same for every member of a batched handle (device_batch_fisher.cpp, fisher.hip; gmrfx_batch_obs_set,
     // gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation). Node form, no constraints. The prior's values and the diagonal map
     // are those of set_prior on the forest (gmrfx_batch_set_prior builds the map).
     void bobs_set(const RbmcSym &sym, const BObsHost &o);
@@ -596,6 +606,9 @@ private:
     } bfisher_;
     void bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask);
     void bfisher_check_prior();
+    // the members' evaluation (BEvalIO, its mask already on the device: d_active) into bfisher_.h_out, 2 per member; synchronises
+    void bfisher_eval(const double *d_x, long long sx, const double *d_mu, long long smu, const unsigned char *d_active, double *d_score,
+                      double *d_hess, long long ss);
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
     // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
     struct GapDev {

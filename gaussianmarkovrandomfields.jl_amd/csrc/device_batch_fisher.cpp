@@ -1,5 +1,5 @@
 // device_batch_fisher.cpp -- Fisher scoring for every member of a batched handle (include/gmrfx.h: gmrfx_batch_obs_set,
-// gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation; kernels in batch_fisher.hip). The handle is the forest diag(Q_1 .. Q_B):
+// gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation; kernels in fisher.hip). The handle is the forest diag(Q_1 .. Q_B):
 // the priors' values (set_prior on the forest) are the members' one after the other, refactorize_update_solve factors and solves all
 // members in one pass, batch_diag reports per member. What is added here is the likelihood evaluation with per-member reductions and
 // the loop that lets every member take its own line search and stop at its own iterate.
@@ -27,15 +27,9 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     if (o.nobs > 0) {
         const size_t n = (size_t)nmember_, nb = (size_t)nbatch_;
         if (n == 0 || n > (size_t)INT_MAX || o.param.size() != nb) throw std::invalid_argument("batch_obs_set: the likelihood does not belong to this handle");
-        std::vector<double> y(n, 0.0), aux(o.aux.empty() ? 0 : n, 0.0), lp(nb, 0.0);
-        std::vector<unsigned char> mask(n, 0);
-        for (long long k = 0; k < o.nobs; k++) {
-            const size_t i = (size_t)o.idx[(size_t)k];
-            y[i] = o.y[(size_t)k];
-            if (!aux.empty()) aux[i] = o.aux[(size_t)k];
-            mask[i] = 1;
-        }
-        for (size_t k = 0; k < nb; k++) lp[k] = o.family == 4 ? std::log(o.param[k]) : 0.0;
+        const ObsByNode b = obs_by_node(n, o.nobs, o.idx, o.y, o.aux);
+        std::vector<double> lp(nb);
+        for (size_t k = 0; k < nb; k++) lp[k] = fisher_logparam(o.family, o.param[k]);
         // the member's rows: the forest's first n (columns and positions of member 0 are the member's own)
         const size_t ne = (size_t)sym.rowptr[n];
         std::vector<int> pos(ne);
@@ -44,9 +38,9 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
             dst.alloc(cnt, &bytes_total, kTableMinBytes);
             if (cnt > 0) HC(hipMemcpy(dst, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
         };
-        up(f.y, y.data(), n);
-        up(f.mask, mask.data(), n);
-        if (!aux.empty()) up(f.aux, aux.data(), n);
+        up(f.y, b.y.data(), n);
+        up(f.mask, b.mask.data(), n);
+        if (!b.aux.empty()) up(f.aux, b.aux.data(), n);
         up(f.param, o.param.data(), nb);
         up(f.logparam, lp.data(), nb);
         up(f.rp, reinterpret_cast<const long long *>(sym.rowptr.data()), n + 1);
@@ -85,22 +79,27 @@ void Device::bfisher_ctl(const std::vector<double> *alpha, const std::vector<uns
     } else HC(hipMemcpyAsync(bfisher_.ctl.get() + nb, hm, nb, hipMemcpyHostToDevice, stream));
 }
 
+void Device::bfisher_eval(const double *d_x, long long sx, const double *d_mu, long long smu, const unsigned char *d_active, double *d_score,
+                          double *d_hess, long long ss) {
+    const FisherEval a{(int)nmember_, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, d_x, d_mu, bfisher_.y,
+                       bfisher_.aux.get(), bfisher_.mask, 0.0, 0.0, d_score, d_hess, bfisher_.part, nnz_member_, sx, smu, ss,
+                       bfisher_.param, bfisher_.logparam, d_active};
+    launch_fisher_eval(stream, a, nbatch_, bfisher_.out);
+    HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nbatch_ * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+}
+
 void Device::batch_fisher_eval(const BEvalIO &io, double *out_host) {
     HC(hipSetDevice(device));
     if (!io.d_x || !out_host) throw std::invalid_argument("batch_fisher_eval: x / out is null");
     bfisher_check_prior();
-    const int n = (int)nmember_, nb = nbatch_;
+    const int nb = nbatch_;
     const unsigned char *d_act = nullptr;
     if (io.active) {
         bfisher_ctl(nullptr, std::vector<unsigned char>(io.active, io.active + nb));
         d_act = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
     }
-    const FisherEvalBatch a{n, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, nnz_member_, io.d_x, io.sx, io.d_mu, io.smu,
-                            bfisher_.y, bfisher_.aux.get(), bfisher_.mask, bfisher_.param, bfisher_.logparam, d_act, io.d_score, io.d_hess, io.ss,
-                            bfisher_.part};
-    launch_fisher_eval_batch(stream, a, nb, bfisher_.out);
-    HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HC(hipStreamSynchronize(stream));
+    bfisher_eval(io.d_x, io.sx, io.d_mu, io.smu, d_act, io.d_score, io.d_hess, io.ss);
     HC(hipGetLastError());
     for (int k = 0; k < nb; k++) {
         if (io.active && !io.active[k]) continue;
@@ -108,9 +107,6 @@ void Device::batch_fisher_eval(const BEvalIO &io, double *out_host) {
         out_host[2 * k + 1] = bfisher_.h_out[2 * k + 1] + bfisher_.loglik_const[(size_t)k];
     }
 }
-
-// _merit_atol (condition/gaussian_approximation.jl:245)
-static double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
 
 int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, double *result, double *totals, double *dec_trace, double *alpha_trace,
                                          long long *info) {
@@ -149,14 +145,13 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     std::vector<long long> binfo((size_t)nb);
     const unsigned char *d_mask = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
     const double *d_alpha = bfisher_.ctl;
+    const FisherMembers masked{(int)n, nb, n, d_mask};      // the loop's vectors: member k's at + k n, the members of the mask on the device
+    // out_k = x_k - alpha_k s_k with the step lengths of the control words
+    auto candidate = [&](const double *x, const double *s, double *out) { launch_fisher_candidate(stream, masked, x, s, 0.0, d_alpha, out); };
     auto any = [](const std::vector<unsigned char> &v) { return std::find(v.begin(), v.end(), (unsigned char)1) != v.end(); };
     // an evaluation over the members of `mask` (already on the device): their pairs to ev
     auto eval = [&](const double *x, long long sx, double *sc, double *hs, const std::vector<unsigned char> &mask) {
-        const FisherEvalBatch a{(int)n, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, nnz_member_, x, sx, io.d_mu, io.smu,
-                                bfisher_.y, bfisher_.aux.get(), bfisher_.mask, bfisher_.param, bfisher_.logparam, d_mask, sc, hs, n, bfisher_.part};
-        launch_fisher_eval_batch(stream, a, nb, bfisher_.out);
-        HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HC(hipStreamSynchronize(stream));
+        bfisher_eval(x, sx, io.d_mu, io.smu, d_mask, sc, hs, n);
         tot_eval += 1;
         for (int k = 0; k < nb; k++)
             if (mask[(size_t)k]) { ev[2 * k] = bfisher_.h_out[2 * k]; ev[2 * k + 1] = bfisher_.h_out[2 * k + 1] + bfisher_.loglik_const[(size_t)k]; }
@@ -164,7 +159,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     // the four reductions over the members of `mask`, to st
     auto stats = [&](const double *a, const double *b, const double *c, const double *d, const std::vector<unsigned char> &mask) {
         bfisher_ctl(nullptr, mask);
-        launch_fisher_stats_batch(stream, (int)n, nb, a, b, c, d, n, d_mask, bfisher_.spart, bfisher_.out.get() + 2 * nb);
+        launch_fisher_stats(stream, masked, a, b, c, d, bfisher_.spart, bfisher_.out.get() + 2 * nb);
         HC(hipMemcpyAsync(bfisher_.h_out + 2 * nb, bfisher_.out.get() + 2 * nb, 4 * (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
         HC(hipStreamSynchronize(stream));
         for (int k = 0; k < nb; k++)
@@ -173,7 +168,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     // candidates x_k - al[k] step_k into cand and the merit there, for the members of `mask`: merit to ev
     auto probe = [&](const std::vector<unsigned char> &mask) {
         bfisher_ctl(&al, mask);
-        launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+        candidate(xk, step, cand);
         eval(cand, n, nullptr, nullptr, mask);
         for (int k = 0; k < nb; k++)
             if (mask[(size_t)k]) m[(size_t)k].nmerit += 1;
@@ -245,12 +240,12 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
             }
             if (any(exhausted)) {
                 bfisher_ctl(&al, exhausted);
-                launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+                candidate(xk, step, cand);
             }
         } else {
             std::fill(al.begin(), al.end(), 1.0);
             bfisher_ctl(&al, run);
-            launch_fisher_candidate_batch(stream, (int)n, nb, xk, n, step, n, d_alpha, d_mask, cand, n);
+            candidate(xk, step, cand);
         }
         stats(score, step, cand, xk, run);
         std::vector<unsigned char> fire((size_t)nb, 0);
@@ -293,7 +288,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
                     if (!any(fire)) break;
                     bfisher_ctl(&al, fire);
                 }
-                launch_fisher_candidate_batch(stream, (int)n, nb, xf, n, xk, n, d_alpha, d_mask, xf, n);
+                candidate(xf, xk, xf);
             }
             for (int k = 0; k < nb; k++)
                 if (fire[(size_t)k]) { stop(k, kConverged, xf, iter + 1, true); run[(size_t)k] = 0; }

@@ -14,6 +14,17 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
+ObsByNode obs_by_node(size_t n, long long nobs, const std::vector<long long> &idx, const std::vector<double> &y, const std::vector<double> &aux) {
+    ObsByNode b{std::vector<double>(n, 0.0), std::vector<double>(aux.empty() ? 0 : n, 0.0), std::vector<unsigned char>(n, 0)};
+    for (long long k = 0; k < nobs; k++) {
+        const size_t i = (size_t)idx[(size_t)k];
+        b.y[i] = y[(size_t)k];
+        if (!aux.empty()) b.aux[i] = aux[(size_t)k];
+        b.mask[i] = 1;
+    }
+    return b;
+}
+
 void Device::obs_set(const ObsHost &o) {
     HC(hipSetDevice(device));
     if (sharded() || many_members()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
@@ -21,21 +32,14 @@ void Device::obs_set(const ObsHost &o) {
     if (o.nobs > 0 && o.design) obs_set_design(o, f);
     else if (o.nobs > 0) {
         const size_t n = (size_t)S_->n;
-        std::vector<double> y(n, 0.0), aux(o.aux.empty() ? 0 : n, 0.0);
-        std::vector<unsigned char> mask(n, 0);
-        for (long long k = 0; k < o.nobs; k++) {
-            const size_t i = (size_t)o.idx[(size_t)k];
-            y[i] = o.y[(size_t)k];
-            if (!aux.empty()) aux[i] = o.aux[(size_t)k];
-            mask[i] = 1;
-        }
+        const ObsByNode b = obs_by_node(n, o.nobs, o.idx, o.y, o.aux);
         f.y.alloc(n, &bytes_total, kTableMinBytes);
         f.mask.alloc(n, &bytes_total, kTableMinBytes);
-        HC(hipMemcpy(f.y, y.data(), n * sizeof(double), hipMemcpyHostToDevice));
-        HC(hipMemcpy(f.mask, mask.data(), n, hipMemcpyHostToDevice));
-        if (!aux.empty()) {
+        HC(hipMemcpy(f.y, b.y.data(), n * sizeof(double), hipMemcpyHostToDevice));
+        HC(hipMemcpy(f.mask, b.mask.data(), n, hipMemcpyHostToDevice));
+        if (!b.aux.empty()) {
             f.aux.alloc(n, &bytes_total, kTableMinBytes);
-            HC(hipMemcpy(f.aux, aux.data(), n * sizeof(double), hipMemcpyHostToDevice));
+            HC(hipMemcpy(f.aux, b.aux.data(), n * sizeof(double), hipMemcpyHostToDevice));
         }
         f.part.alloc(2 * (size_t)fisher_blocks((int)n), &bytes_total, kTableMinBytes);
         f.out.alloc(6, &bytes_total, kTableMinBytes);        // 2 of the evaluation, 4 of the reductions
@@ -121,7 +125,7 @@ void Device::fisher_eval_design(const RbmcSym &sym, const double *d_x, const dou
     const FisherDesign a{(int)P.n, (int)P.nobs, (int)P.cnt, fisher_.family, sym_rows_.rp, sym_rows_.col, sym_rows_.pos, d_prior_, d_x, d_mu,
                          fisher_.arp, fisher_.acol, fisher_.aval, fisher_.offset.get(), fisher_.acp, fisher_.arow, fisher_.acv,
                          fisher_.tptr, fisher_.tobs, fisher_.tw, fisher_.cchoff, fisher_.tchoff, fisher_.chs, fisher_.chl, fisher_.ncc, fisher_.nct,
-                         fisher_.y, fisher_.aux.get(), fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0,
+                         fisher_.y, fisher_.aux.get(), fisher_.param, fisher_logparam(fisher_.family, fisher_.param),
                          fisher_.g, fisher_.d, fisher_.cpart, d_score, d_hess, fisher_.part, fisher_.lpart};
     launch_fisher_design(stream, a, fisher_.out);
     HC(hipMemcpyAsync(fisher_.h_out, fisher_.out, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -147,9 +151,10 @@ void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_
     if (!prior_diag_) throw std::invalid_argument("fisher_eval: the map of gmrfx_set_prior is not the position of (i, i) for every i (diagonal Hessians only)");
     if (!obs_held()) throw std::invalid_argument("fisher_eval: no observation likelihood is set (gmrfx_obs_set)");
     sym_rows_upload(sym);
+    // one member: the member fields stay zero (strides 0, the parameter by value, nobody masked)
     const FisherEval a{(int)n, fisher_.family, sym_rows_.rp, sym_rows_.col, sym_rows_.pos, d_prior_, d_x, d_mu, fisher_.y, fisher_.aux.get(),
-                       fisher_.mask, fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0, d_score, d_hess, fisher_.part};
-    launch_fisher_eval(stream, a, fisher_.out);
+                       fisher_.mask, fisher_.param, fisher_logparam(fisher_.family, fisher_.param), d_score, d_hess, fisher_.part};
+    launch_fisher_eval(stream, a, 1, fisher_.out);
     HC(hipMemcpyAsync(fisher_.h_out, fisher_.out, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
@@ -158,9 +163,6 @@ void Device::fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_
 }
 
 // ---- the loop ------------------------------------------------------------------------------------------------------------------------
-// _merit_atol (condition/gaussian_approximation.jl:245)
-static double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
-
 int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
                                    double *result, double *dec_trace, double *alpha_trace, long long *info) {
     HC(hipSetDevice(device));
@@ -185,9 +187,12 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
         if (alpha_trace) alpha_trace[k] = std::nan("");
     }
     double nfact = 0, nsolve = 0, nmerit = 0, alpha = 1.0, dec_prev = 0.0, dec = std::nan("");
+    const FisherMembers one{(int)n, 1, 0, nullptr};       // the loop's vectors are one member's
+    // out = x - al step (al changes between launches: by value, nothing goes up)
+    auto candidate = [&](const double *x, double al, double *out) { launch_fisher_candidate(stream, one, x, step, al, nullptr, out); };
     // the four reductions of the loop, to the host: {sum a b, sum (c - d)^2, sum d^2, max |b|}
     auto stats = [&](const double *a, const double *b, const double *c, const double *d, double *out4) {
-        launch_fisher_stats(stream, (int)n, a, b, c, d, fisher_.spart, fisher_.out.get() + 2);
+        launch_fisher_stats(stream, one, a, b, c, d, fisher_.spart, fisher_.out.get() + 2);
         HC(hipMemcpyAsync(fisher_.h_out + 2, fisher_.out.get() + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
         HC(hipStreamSynchronize(stream));
         for (int q = 0; q < 4; q++) out4[q] = fisher_.h_out[2 + q];
@@ -244,13 +249,13 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
             const double obj_accept = obj_current + merit_atol(std::fabs(ek[0]) + std::fabs(ek[1]));
             bool done = false;
             if (retry_full && alpha < 1.0) {
-                launch_fisher_candidate(stream, (int)n, xk, step, 1.0, xnew);
+                candidate(xk, 1.0, xnew);
                 if (merit(xnew) <= obj_accept) { alpha = 1.0; done = true; }
             }
             if (!done) {
                 bool accept = false;
                 for (long long ls = 1; ls <= o.max_ls; ls++) {
-                    launch_fisher_candidate(stream, (int)n, xk, step, alpha, cand);
+                    candidate(xk, alpha, cand);
                     if (merit(cand) <= obj_accept) {
                         alpha = std::sqrt(alpha);
                         accept = true;
@@ -261,9 +266,9 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
                     if (alpha * st[3] < o.dec_tol / 1000) { accept = true; break; }
                 }
                 if (accept) xn = cand;
-                else launch_fisher_candidate(stream, (int)n, xk, step, alpha, xnew);
+                else candidate(xk, alpha, xnew);
             }
-        } else launch_fisher_candidate(stream, (int)n, xk, step, 1.0, xnew);
+        } else candidate(xk, 1.0, xnew);
         stats(score, step, xn, xk, st);
         dec = st[0];
         const double mean_change = std::sqrt(st[1]), mean_change_rel = mean_change / std::max(std::sqrt(st[2]), 1.0e-10);
@@ -288,7 +293,7 @@ int Device::gaussian_approximation(const RbmcSym &sym, const double *d_mu, const
                     if (dec_trace) dec_trace[iter] = dec;
                     if (alpha_trace) alpha_trace[iter] = alpha;
                 }
-                launch_fisher_candidate(stream, (int)n, xf, step, 1.0, xf);
+                candidate(xf, 1.0, xf);
             }
             if (ok) return finish(xf, iter + 1, true, true);
         }

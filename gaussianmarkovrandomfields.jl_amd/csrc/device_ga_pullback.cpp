@@ -101,7 +101,7 @@ int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, l
     const int nblk = gap_obs_blocks(design, n, nobs);
     double *xbar = gap_.work, *lam = xbar + n, *t = lam + n;
     double *gpart = gap_.part, *ppart = gpart + nblk;
-    const double logparam = fisher_.family == 4 ? std::log(fisher_.param) : 0.0;
+    const double logparam = fisher_logparam(fisher_.family, fisher_.param);
     const bool has_param = fisher_.family == 0 || fisher_.family == 4 || fisher_.family == 5;
     // ---- xbar = mubar - A' (c . d3) -------------------------------------------------------------------------------------------------
     if (io.d_Qbar) {
@@ -141,7 +141,7 @@ int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, l
         HC(hipMemcpyAsync(gap_.h_out, gap_.out, sizeof(double), hipMemcpyDeviceToHost, stream));
     }
     // lam' xbar by the loop's own reduction (sum a b of launch_fisher_stats)
-    launch_fisher_stats(stream, (int)n, lam, xbar, nullptr, nullptr, fisher_.spart, fisher_.out.get() + 2);
+    launch_fisher_stats(stream, FisherMembers{(int)n, 1, 0, nullptr}, lam, xbar, nullptr, nullptr, fisher_.spart, fisher_.out.get() + 2);
     HC(hipMemcpyAsync(fisher_.h_out + 2, fisher_.out.get() + 2, sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());

@@ -76,7 +76,7 @@ int Device::predictor_marginals(const RbmcSym &sym, const ObsHost &o, const Pred
     const PredMarg a{(int)n, (int)o.nobs, m, fisher_.family, io.d_x, pred_.idx.get(), sym_rows_.dpos.get(), fisher_.arp.get(), fisher_.acol.get(),
                      fisher_.aval.get(), fisher_.offset.get(), gap_.optr.get(), gap_.oidx.get(), gap_.ow.get(), pred_.hmap.get(),
                      io.d_v_eta ? grad_.zoff.get() : nullptr, d_Z_, m > 0 ? con_.B.get() : nullptr, fisher_.y.get(), fisher_.aux.get(), pred_.c.get(),
-                     fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0, io.d_mu_eta, io.d_v_eta, io.d_pll};
+                     fisher_.param, fisher_logparam(fisher_.family, fisher_.param), io.d_mu_eta, io.d_v_eta, io.d_pll};
     launch_pred_marginals(stream, a, design);
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
@@ -95,7 +95,7 @@ void Device::predictive_scores(const ObsHost &o, const ScoreIO &io, double *out4
     std::copy(io.w, io.w + io.K, pred_.h_quad + kPredMaxNodes);
     HC(hipMemcpyAsync(pred_.quad, pred_.h_quad, 2 * kPredMaxNodes * sizeof(double), hipMemcpyHostToDevice, stream));
     const PredScores a{(int)o.nobs, io.K, fisher_.family, io.d_mu, io.d_v, pred_.idx.get(), fisher_.y.get(), fisher_.aux.get(), pred_.c.get(),
-                       pred_.quad.get(), pred_.quad.get() + kPredMaxNodes, fisher_.param, fisher_.family == 4 ? std::log(fisher_.param) : 0.0,
+                       pred_.quad.get(), pred_.quad.get() + kPredMaxNodes, fisher_.param, fisher_logparam(fisher_.family, fisher_.param),
                        io.d_lpd, io.d_lcpo, io.d_elp, io.d_vlp, pred_.part.get()};
     launch_pred_scores(stream, a, pred_.out);
     HC(hipMemcpyAsync(pred_.h_out, pred_.out, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));

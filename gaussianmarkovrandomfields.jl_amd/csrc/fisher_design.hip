@@ -9,7 +9,7 @@
 //   k_design_eta     a lane group per row of A: eta_i, then g_i, d_i and l_i (fisher_point.h); one loglik partial per workgroup
 //   k_design_chunks  one workgroup per chunk of kDesignChunk entries of a long column of A (sum A_ij g_i; when the score is wanted) or
 //                    term list (sum w_t d_i; when the Hessian is)
-//   k_design_score   a lane group per node: the pass of k_fisher_eval over Symmetric(Q_p), then the gather over column j of A
+//   k_design_score   a lane group per node: the pass of k_fisher_eval over Symmetric(Q_p) (fisher_gather.h), then the gather over column j of A
 //   k_design_hess    a lane group per Hessian position over its term list
 //   k_design_final   the energy and loglik partials of all workgroups, one workgroup of kFisherFinal threads
 // A short segment is read entry by entry by its lane group; of a long one the lane group adds the chunk sums.
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernel_common.h"
+#include "fisher_gather.h"
 #include "fisher_point.h"
 
 namespace gmrfx {
@@ -99,13 +100,7 @@ __global__ __launch_bounds__(256) void k_design_score(const FisherDesign a) {
     double en = 0.0;
     if (i < a.n) {
         double s = 0.0, t = 0.0;
-        const long long q1 = a.rp[i + 1];
-        for (long long q = a.rp[i] + l; q < q1; q += kDesignLanes) {
-            const double v = a.val[a.pos[q]];
-            const int c = a.col[q];
-            s = __builtin_fma(v, a.x[c], s);
-            if (a.mu) t = __builtin_fma(v, a.mu[c], t);
-        }
+        fisher_row_gather(i, l, a.rp, a.col, a.pos, a.val, a.x, a.mu, s, t);
         s = design_group_sum(s);
         t = design_group_sum(t);
         double ag = 0.0;

@@ -228,62 +228,44 @@ void launch_grad_mubar(hipStream_t st, const GradMean &a, int nb);
 void launch_grad_dot(hipStream_t st, long long nnz, const unsigned char *wgt, const double *G, const double *J, long long ldj, long long sj, int p,
                      int nb, double *part, double *out);
 
-// fisher.hip -- one pass over Symmetric(Q_prior) for a Fisher-scoring iterate (gmrfx_fisher_eval): a lane group of kFisherLanes lanes per
-// row, kFisherRows rows per workgroup of 256 threads; the final pass adds the workgroups' partial sums with kFisherFinal threads.
+// fisher.hip -- one pass over Symmetric(Q_prior) for a Fisher-scoring iterate (gmrfx_fisher_eval, gmrfx_batch_fisher_eval): a lane group of
+// kFisherLanes lanes per row, kFisherRows rows per workgroup of 256 threads; the final pass adds the workgroups' partial sums with
+// kFisherFinal threads. nbatch members (a plain handle is one, with strides 0): the member in the grid's second dimension, ONE copy of
+// the member's row structure and ONE data set, per-member values / points / parameters. A workgroup never spans two members; the partial
+// sums are kept per member and reduced by one workgroup per member, so member k's results have the bits of a plain handle of Q_p,k,
+// param[k] and x_k. active (nbatch bytes, nullable = all): a member whose byte is 0 is skipped by every workgroup before its first load,
+// and nothing of it is written. A per-member scalar is the by-value argument unless its device array (nbatch) is non-null.
 constexpr int kFisherLanes = 16, kFisherRows = 16, kFisherFinal = 256;
 struct FisherEval {
     int n, family;
-    const long long *rp;         // Symmetric(Q) by rows (RbmcSym), as GradMean
+    const long long *rp;         // the MEMBER's Symmetric(Q) by rows (RbmcSym), as GradMean: n + 1
     const int *col, *pos;
-    const double *val, *x, *mu;  // the prior's values; the point; the prior mean (nullable: h = 0)
-    const double *y, *aux;       // the likelihood by node (aux nullable)
+    const double *val, *x, *mu;  // the priors' values; the points; the prior means (nullable: h = 0)
+    const double *y, *aux;       // ONE likelihood by node (aux nullable)
     const unsigned char *mask;   // 1: the node has an observation
     double param, logparam;
     double *score, *hess;        // n each, either nullable
-    double *part;                // 2 per workgroup: energy, loglik
+    double *part;                // 2 per workgroup: energy, loglik; member k's at + 2 k fisher_blocks(n)
+    // the members, behind what one member needs (a plain handle leaves them zero and its workgroups never fetch them)
+    long long nnz, sx, smu, ss;  // member k's val at + k nnz, x at + k sx, mu at + k smu (0: one mean for all), score / hess at + k ss
+    const double *param_k, *logparam_k;  // nullable: one per member, in place of param / logparam
+    const unsigned char *active; // nullable
 };
 inline int fisher_blocks(int n) { return (n + kFisherRows - 1) / kFisherRows; }
-// out[0] = sum of the energy partials, out[1] = sum of the loglik partials (device)
-void launch_fisher_eval(hipStream_t st, const FisherEval &a, double *out);
-// the loop's vector work (gmrfx_gaussian_approximation): out = x - alpha s; and out4 = {sum a b, sum (c - d)^2, sum d^2, max |b|} over n
-// entries (a pair with a null member is left at 0), in chunks of kFisherStatChunk entries; part: 4 per chunk
+// out[2 k] = member k's sum of the energy partials, out[2 k + 1] = of the loglik partials (device); inactive members' pairs are left
+void launch_fisher_eval(hipStream_t st, const FisherEval &a, int nbatch, double *out);
+// the loop's vector work (gmrfx_gaussian_approximation, gmrfx_batch_gaussian_approximation) on vectors of n entries per member, member
+// k's at + k stride (the loop's work vectors), for the members whose byte in active is set (nullable = all)
+struct FisherMembers { int n, nbatch; long long stride; const unsigned char *active; };
+// out_k = x_k - alpha s_k (alpha_k non-null: alpha_k[k] s_k); out may be x
+void launch_fisher_candidate(hipStream_t st, const FisherMembers &m, const double *x, const double *s, double alpha, const double *alpha_k,
+                             double *out);
+// out4[4 k ..] = {sum a b, sum (c - d)^2, sum d^2, max |b|} over member k's entries (a pair with a null member is left at 0), in chunks
+// of kFisherStatChunk entries; part: 4 per chunk, member k's at + 4 k fisher_stat_blocks(n)
 constexpr int kFisherStatChunk = 4096;
 inline int fisher_stat_blocks(int n) { return (n + kFisherStatChunk - 1) / kFisherStatChunk; }
-void launch_fisher_candidate(hipStream_t st, int n, const double *x, const double *s, double alpha, double *out);
-void launch_fisher_stats(hipStream_t st, int n, const double *a, const double *b, const double *c, const double *d, double *part, double *out4);
-
-// batch_fisher.hip -- the same three pieces for the members of a batched handle (gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation):
-// the member in the grid's second dimension, ONE copy of the member's row structure, per-member values / points / parameters. A workgroup
-// never spans two members; the partial sums are kept per member and reduced by one workgroup per member in the order of the plain
-// kernels, so member k's results have the bits of the plain kernels on Q_p,k, param[k] and x_k. mask (nbatch bytes, nullable = all): a
-// member whose byte is 0 is skipped by every workgroup before its first load, and nothing of it is written.
-struct FisherEvalBatch {
-    int n, family;
-    const long long *rp;         // the MEMBER's Symmetric(Q) by rows: n + 1
-    const int *col, *pos;
-    const double *val;           // the priors' values, member k at + k nnz
-    long long nnz;
-    const double *x;             // member k's point at + k sx
-    long long sx;
-    const double *mu;            // nullable; member k's mean at + k smu (smu = 0: one mean for all)
-    long long smu;
-    const double *y, *aux;       // ONE data set, by node (aux nullable)
-    const unsigned char *mask;   // 1: the node has an observation
-    const double *param, *logparam;      // nbatch each
-    const unsigned char *active; // nbatch, nullable
-    double *score, *hess;        // member k at + k ss, either nullable
-    long long ss;
-    double *part;                // 2 per workgroup, member k's at + 2 k fisher_blocks(n)
-};
-// out[2 k], out[2 k + 1] = member k's energy and loglik sums (device); inactive members' pairs are left as they are
-void launch_fisher_eval_batch(hipStream_t st, const FisherEvalBatch &a, int nbatch, double *out);
-// out_k = x_k - alpha[k] s_k for the members whose byte in active is set (nullable = all); out may be x
-void launch_fisher_candidate_batch(hipStream_t st, int n, int nbatch, const double *x, long long sx, const double *s, long long ss,
-                                   const double *alpha, const unsigned char *active, double *out, long long so);
-// the four reductions of launch_fisher_stats per member: out4[4 k ..]; a, b, c, d: member k at + k s (one stride: the loop's work vectors);
-// part: 4 per chunk, member k's at + 4 k fisher_stat_blocks(n)
-void launch_fisher_stats_batch(hipStream_t st, int n, int nbatch, const double *a, const double *b, const double *c, const double *d, long long s,
-                               const unsigned char *active, double *part, double *out4);
+void launch_fisher_stats(hipStream_t st, const FisherMembers &m, const double *a, const double *b, const double *c, const double *d, double *part,
+                         double *out4);
 
 // fisher_design.hip -- the same evaluation through a sparse design matrix, eta = A x + b (gmrfx_obs_set_design). A lane group of
 // kDesignLanes lanes per row of A, per node and per Hessian position, kDesignRows of them per workgroup of 256 threads. A SEGMENT (a

@@ -71,7 +71,7 @@ def restate(c, k, dtype):
     return ref.newton_loop(lc.dense(c["Qs"][k]), None, member_obs(c, k), x0=c["x0"][:, k], dtype=dtype, **c["kw"])
 
 
-# ---- the evaluation's shapes: the smallest at which batch_fisher.hip can go wrong --------------------------------------------------------
+# ---- the evaluation's shapes: the smallest at which the members of fisher.hip can go wrong --------------------------------------------------
 def eval_shapes():
     """name -> M: n = 1, 15, 16, 17 (tridiagonal: both sides of a workgroup of 16 rows), 40 (arrowhead: rows of 2 and of 40 entries), 60,
     256, 4097 (tridiagonal, one entry past a chunk of the reductions)"""

@@ -114,7 +114,7 @@ def test_masked_members_keep_their_frame(shape, B):
 @pytest.mark.parametrize("shape,B,adaptive", [("tri17", 3, False), ("tri17", 3, True), ("tri4097", 2, True), ("arrow40", 50, False),
                                               ("matern256", 3, True)])
 def test_first_iterate_has_the_bits_of_the_plain_loop(shape, B, adaptive):
-    """max_iter = 1: x_1 = x_0 - alpha_k step_k through k_fisher_candidate_batch and the batched reductions; Poisson with large counts
+    """max_iter = 1: x_1 = x_0 - alpha_k step_k through k_fisher_candidate and the reductions with more than one member; Poisson with large counts
     from x0 = 0 backtracks under adaptive_stepsize"""
     M = SHAPES[shape]
     n = M.shape[0]
