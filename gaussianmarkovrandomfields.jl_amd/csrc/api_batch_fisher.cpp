@@ -1,6 +1,7 @@
 // api_batch_fisher.cpp -- the C ABI of include/gmrfx.h: Fisher scoring and the Gaussian approximation for every member of a batched
-// handle (Device::bobs_set, Device::batch_fisher_eval, Device::batch_gaussian_approximation; csrc/fisher.hip). A plain handle is
-// a batch of one to these calls, as to every gmrfx_batch_* call; gmrfx_obs_set and its family keep refusing batched handles.
+// handle (Device::bobs_set, Device::batch_fisher_eval, Device::batch_gaussian_approximation; csrc/fisher.hip, csrc/fisher_design.hip),
+// in node form (gmrfx_batch_obs_set) or through a design matrix (gmrfx_batch_obs_set_design). A plain handle is a batch of one to
+// these calls, as to every gmrfx_batch_* call; gmrfx_obs_set and its family keep refusing batched handles.
 #include "api_obs.h"
 
 // what every call here refuses about the handle itself, before anything else is looked at
@@ -12,13 +13,16 @@ static void bf_check_handle(const gmrfx_handle *h, const std::string &who) {
 }
 // the member's sizes, on plain handles too
 static int64_t bf_n(const gmrfx_handle *h) { return h->nbatch > 1 ? h->n_member : h->S.n; }
+static int64_t bf_nnz(const gmrfx_handle *h) { return h->nbatch > 1 ? h->nnz_member : h->S.nnz_in; }
+// entries of a member's Hessian vector: n in node form, the plan's cnt in design form
+static int64_t bf_hess_len(const gmrfx_handle *h) { return h->bobs.design ? h->bobs.design->cnt : bf_n(h); }
 // a plain handle's batch buffers, on its first batch call (need_batch without the NO_DEVICE answer: symbolic_only handles pass)
 static void bf_ensure_batch(gmrfx_handle *h) {
     if (h->D && !h->D->batched()) h->D->set_batch(1, h->S.n, h->S.nnz_in);
 }
-static void bf_check_stride(const std::string &who, const char *what, int64_t s, int64_t n, bool zero_ok = false) {
+static void bf_check_stride(const std::string &who, const char *what, int64_t s, int64_t n, bool zero_ok = false, const char *len = "n") {
     if (zero_ok && s == 0) return;
-    if (s < n) throw std::invalid_argument(who + what + ": member stride smaller than n");
+    if (s < n) throw std::invalid_argument(who + what + ": member stride smaller than " + len);
 }
 
 extern "C" int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval) {
@@ -29,9 +33,16 @@ extern "C" int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nz
         if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);       // (refuses a pattern without a stored diagonal)
         if (int32_t e = need_device(h, false)) return e;
         bf_ensure_batch(h);
-        // the diagonal map, member after member: the forest's own diagonal positions
-        std::vector<long long> map(h->rsym.diag.begin(), h->rsym.diag.end());
-        h->D->set_prior(prior_nzval, map.data(), (long long)map.size());
+        // the map of the likelihood in place, member after member: the forest's own diagonal positions (none, or the node form), or
+        // the plan's positions in one member's values shifted by k nnz_member (design form)
+        std::vector<long long> map;
+        if (const DesignPlan *P = h->bobs.design.get()) {
+            const int64_t nnz = bf_nnz(h);
+            map.reserve((size_t)(P->cnt * h->nbatch));
+            for (int64_t k = 0; k < h->nbatch; k++)
+                for (i64 p : P->map) map.push_back(p + k * nnz);
+        } else map.assign(h->rsym.diag.begin(), h->rsym.diag.end());
+        h->D->bset_prior(prior_nzval, map, (bool)h->bobs.design);
         return GMRFX_OK;
     });
 }
@@ -83,6 +94,78 @@ extern "C" int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t 
     });
 }
 
+// The same likelihood observed through eta = A x + b (A: nobs x n_member, CSC): the checks of gmrfx_obs_set_design and, member by
+// member, those of gmrfx_batch_obs_set; the plan (fisher_design_plan.cpp) is built on the MEMBER's pattern, which the forest's first
+// n_member rows of Symmetric(Q) are. Either batch form replaces the other.
+extern "C" int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *colptr, const int64_t *rowval,
+                                              const double *nzval, int32_t index_base, const double *offset, const double *y, const double *aux,
+                                              const double *param) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_obs_set_design: ";
+        bf_check_handle(h, who);
+        const int64_t n = bf_n(h), nb = h->nbatch;
+        if (nobs == 0) {
+            if (h->D) h->D->bobs_set(h->rsym, BObsHost{});
+            h->bobs = BObsHost{};
+            return GMRFX_OK;
+        }
+        obs_check_family(who, family);
+        if (nobs < 0) throw std::invalid_argument(who + "nobs is negative");
+        check_index_base(index_base, who.c_str());
+        if (!colptr) throw std::invalid_argument(who + "colptr is null");
+        check_compressed_ptr(colptr, n, index_base, "batch_obs_set_design: colptr");
+        design_check_sizes(n, nobs, colptr[n] - index_base);        // (before y, aux or A are read at those lengths)
+        if (colptr[n] > index_base && (!rowval || !nzval)) throw std::invalid_argument(who + "rowval / nzval is null");
+        if (!param) throw std::invalid_argument(who + "param is null (one value per member)");
+        BObsHost o;
+        o.family = family; o.nobs = nobs;
+        o.param.resize((size_t)nb); o.loglik_const.resize((size_t)nb);
+        for (int64_t k = 0; k < nb; k++) {          // every check of gmrfx_obs_set_design on the values, member by member
+            const std::string wk = who + "member " + std::to_string(k) + ": ";
+            obs_check_operands(wk, family, y, aux, param[k]);
+            ObsHost ok;
+            obs_fill_values(ok, wk, family, nobs, y, aux, param[k]);
+            o.param[(size_t)k] = param[k];
+            o.loglik_const[(size_t)k] = ok.loglik_const;
+            if (k == nb - 1) { o.y = std::move(ok.y); o.aux = std::move(ok.aux); }
+        }
+        if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+        auto plan = std::make_shared<DesignPlan>();
+        design_build_plan(h->rsym, n, bf_nnz(h), nobs, colptr, rowval, nzval, index_base, offset, *plan);
+        o.design = std::move(plan);
+        if (h->D) {
+            bf_ensure_batch(h);
+            h->D->bobs_set(h->rsym, o);
+        }
+        h->bobs = std::move(o);
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_batch_obs_hess_map(const gmrfx_handle *h, int64_t *map, int64_t cap, int64_t *cnt) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    return guarded(const_cast<gmrfx_handle *>(h), [&]() -> int32_t {
+        const std::string who = "batch_obs_hess_map: ";
+        if (!h->bobs.design) throw std::invalid_argument(who + "no design likelihood is set (gmrfx_batch_obs_set_design)");
+        const DesignPlan &P = *h->bobs.design;
+        if (cnt) *cnt = P.cnt;
+        if (map) {
+            if (cap < P.cnt) throw std::invalid_argument(who + "cap is smaller than cnt");
+            std::copy(P.map.begin(), P.map.end(), map);
+        }
+        return GMRFX_OK;
+    });
+}
+
+extern "C" int32_t gmrfx_batch_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms) {
+    if (!h) return GMRFX_ERR_INVALID_ARG;
+    const DesignPlan *P = h->bobs.design.get();
+    if (nnz_a) *nnz_a = P ? P->nnz : -1;
+    if (cnt) *cnt = P ? P->cnt : -1;
+    if (terms) *terms = P ? P->terms : -1;
+    return GMRFX_OK;
+}
+
 extern "C" int32_t gmrfx_batch_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const) {
     if (!h) return GMRFX_ERR_INVALID_ARG;
     if (family) *family = h->bobs.nobs > 0 ? h->bobs.family : -1;
@@ -102,11 +185,13 @@ static int32_t bf_eval_impl(gmrfx_handle *h, const double *x, int64_t sx, const 
         const int64_t n = bf_n(h), nb = h->nbatch;
         bf_check_stride(who, "x", sx, n);
         if (mu) bf_check_stride(who, "mu", smu, n, true);
-        if (score || hess) bf_check_stride(who, "score / hess", ss, n);
+        const int64_t hl = bf_hess_len(h);
+        if (score) bf_check_stride(who, "score", ss, n);
+        if (hess) bf_check_stride(who, "hess", ss, hl, false, h->bobs.design ? "cnt" : "n");
         if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
         if (int32_t e = need_batch(h, false)) return e;
         if (dev) {
-            h->D->batch_fisher_eval(Device::BEvalIO{x, sx, mu, smu, active, score, hess, ss}, out);
+            h->D->batch_fisher_eval(Device::BEvalIO{x, sx, mu, smu, active, score, hess, ss, ss}, out);
             return GMRFX_OK;
         }
         DevBlock bx, bm, bs, bh;
@@ -114,11 +199,11 @@ static int32_t bf_eval_impl(gmrfx_handle *h, const double *x, int64_t sx, const 
         if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
         // the outputs go up first: a member that is masked out keeps what the caller's arrays hold
         if (score) stage_up(h, bs, score, ss, n, 1, ss, nb);
-        if (hess) stage_up(h, bh, hess, ss, n, 1, ss, nb);
+        if (hess && hl > 0) stage_up(h, bh, hess, ss, hl, 1, ss, nb);       // (hl rows per member: n in node form, cnt in design form)
         h->D->batch_fisher_eval(Device::BEvalIO{bx, n, mu ? bm.get() : nullptr, smu == 0 ? 0 : n, active, score ? bs.get() : nullptr,
-                                                hess ? bh.get() : nullptr, n}, out);
+                                                hess ? bh.get() : nullptr, n, hl}, out);
         if (score) stage_down(h, bs, score, ss, n, 1, ss, nb);
-        if (hess) stage_down(h, bh, hess, ss, n, 1, ss, nb);
+        if (hess && hl > 0) stage_down(h, bh, hess, ss, hl, 1, ss, nb);
         return GMRFX_OK;
     });
 }
@@ -144,7 +229,8 @@ static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const 
         bf_check_stride(who, "x", sx, n);
         if (mu) bf_check_stride(who, "mu", smu, n, true);
         if (x0) bf_check_stride(who, "x0", sx0, n);
-        if (hess) bf_check_stride(who, "hess", sh, n);
+        const int64_t hl = bf_hess_len(h);
+        if (hess) bf_check_stride(who, "hess", sh, hl, false, h->bobs.design ? "cnt" : "n");
         if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
         if (int32_t e = need_batch(h, false)) return e;
         const Device::GaOpts o{max_iter, max_ls, mean_tol, dec_tol, flags};
@@ -156,11 +242,11 @@ static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const 
             if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
             if (x0) stage_up(h, b0, x0, n, n, 1, sx0, nb);
             stage_alloc(h, bx, n * nb);
-            if (hess) stage_up(h, bh, hess, n, n, 1, sh, nb);      // (a failed member's slice keeps what the caller's array holds)
+            if (hess && hl > 0) stage_up(h, bh, hess, hl, hl, 1, sh, nb);      // (a failed member's slice keeps what the caller's array holds)
             rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu ? bm.get() : nullptr, smu == 0 ? 0 : n, x0 ? b0.get() : nullptr, n, bx, n,
-                                                                  hess ? bh.get() : nullptr, n}, o, result, totals, dec_trace, alpha_trace, inf.data());
+                                                                  hess ? bh.get() : nullptr, hl}, o, result, totals, dec_trace, alpha_trace, inf.data());
             stage_down(h, bx, x, n, n, 1, sx, nb);
-            if (hess) stage_down(h, bh, hess, n, n, 1, sh, nb);
+            if (hess && hl > 0) stage_down(h, bh, hess, hl, hl, 1, sh, nb);
         }
         if (info) std::copy(inf.begin(), inf.end(), info);
         if (rc == 1) {

@@ -877,6 +877,8 @@ void Device::set_prior(const double *prior_nzval, const long long *map, long lon
     h_hmap_.assign(map, map + cnt);
     prior_diag_ = -1;
     prior_design_ = -1;
+    bprior_design_ = false;      // (bset_prior says otherwise)
+    bprior_map_ok_ = -1;
     if (cnt > 0) HC(hipMemcpyAsync(d_hmap_, map, (size_t)cnt * sizeof(long long), hipMemcpyHostToDevice, stream));
     HC(hipStreamSynchronize(stream));
 }

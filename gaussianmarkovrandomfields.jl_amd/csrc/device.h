@@ -86,6 +86,7 @@ struct BObsHost {
     long long nobs = 0;
     std::vector<long long> idx;
     std::vector<double> y, aux, param, loglik_const;      // param, loglik_const: one per member
+    std::shared_ptr<const DesignPlan> design;             // gmrfx_batch_obs_set_design: the plan on the MEMBER's pattern (idx empty)
 };
 // what the node form of either likelihood puts on the device: (idx, y, aux) expanded to one value per node, mask = 1 where a node has
 // an observation, 0 elsewhere (aux stays empty when there is none)
@@ -271,14 +272,19 @@ public:
                                double *result, double *dec_trace, double *alpha_trace, long long *info);
 
     // ---- the same for every member of a batched handle (device_batch_fisher.cpp, fisher.hip; gmrfx_batch_obs_set,
-    // gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation). Node form, no constraints. The prior's values and the diagonal map
-    // are those of set_prior on the forest (gmrfx_batch_set_prior builds the map).
+    // gmrfx_batch_obs_set_design, gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation). Node or design form, no constraints. The
+    // prior's values and the Hessian map are those of set_prior on the forest (gmrfx_batch_set_prior builds the map).
     void bobs_set(const RbmcSym &sym, const BObsHost &o);
     bool bobs_held() const { return (bool)bfisher_.y; }
-    // Member k's evaluation at d_x + k sx with the mean d_mu + k smu (nullable; smu = 0: one mean): score / hess at + k ss (either
-    // nullable), out_host[2 k ..] = {energy, loglik}. active (host, nbatch bytes, nullable = all): a member whose byte is 0 is skipped
-    // and nothing of it is written, on the device or in out_host. One synchronisation.
-    struct BEvalIO { const double *d_x; long long sx; const double *d_mu; long long smu; const unsigned char *active; double *d_score, *d_hess; long long ss; };
+    // entries of a member's Hessian vector: n_member in node form, the plan's cnt in design form
+    long long bhess_len() const { return bfisher_.design ? bfisher_.design->cnt : nmember_; }
+    // set_prior on the forest with the map of the batch likelihood in place: the forest's diagonal (no likelihood, node form), or the
+    // member's plan map shifted by k nnz_member for k = 0 .. nbatch - 1 (design form); map: the forest's, as the caller built it
+    void bset_prior(const double *prior_nzval, const std::vector<long long> &map, bool design);
+    // Member k's evaluation at d_x + k sx with the mean d_mu + k smu (nullable; smu = 0: one mean): score at + k ss, hess (bhess_len()
+    // entries) at + k sh (either nullable), out_host[2 k ..] = {energy, loglik}. active (host, nbatch bytes, nullable = all): a member
+    // whose byte is 0 is skipped and nothing of it is written, on the device or in out_host. One synchronisation.
+    struct BEvalIO { const double *d_x; long long sx; const double *d_mu; long long smu; const unsigned char *active; double *d_score, *d_hess; long long ss, sh; };
     void batch_fisher_eval(const BEvalIO &io, double *out_host);
     // The loop of gaussian_approximation for all members in lockstep: one forest-wide launch per step, member k seeing exactly the
     // sequence of operations its own plain loop would perform. d_x0 nullable (= mu, or 0). result: host, 10 per member (the plain
@@ -576,26 +582,35 @@ private:
         long long dot_cap = 0, out_cap = 0;
         unsigned long long bt_serial = 0;       // 0: nothing cached
     } grad_;
+    // design form, what a plain and a batched likelihood hold alike (design_upload): the plan, its tables as they are, and the chunk
+    // tables of the long columns and term lists (choff: prefix sums of chunk counts; chs / chl: start and length of every chunk,
+    // columns' first). One copy, whatever the number of members.
+    struct DesignTables {
+        std::shared_ptr<const DesignPlan> design;
+        DevBuf<long long> arp, acp, tptr, chs;
+        DevBuf<int> acol, arow, tobs, cchoff, tchoff, chl;
+        DevBuf<double> aval, acv, tw, offset;
+        int ncc = 0, nct = 0;
+    };
+    void design_upload(const std::shared_ptr<const DesignPlan> &plan, DesignTables &t);
     // Fisher-scoring state: the likelihood by node (y, aux, mask: n each), the evaluation's partial sums (2 per workgroup) and results
-    struct FisherDev {
+    struct FisherDev : DesignTables {
         DevBuf<double> y, aux, part, out, spart, work;      // spart: the loop's reductions; work: its six vectors (on first use)
         DevBuf<unsigned char> mask;
         PinnedBuf<double> h_out;                             // 2 of the evaluation, then 4 of the reductions
         int family = 0;
         double param = 0, loglik_const = 0;
-        // design form: y / aux by observation (mask unused), the plan's tables, g and d by observation, the chunk tables of the long
-        // columns and term lists (choff: prefix sums of chunk counts; chs / chl: start and length of every chunk, columns' first)
-        std::shared_ptr<const DesignPlan> design;
-        DevBuf<long long> arp, acp, tptr, chs;
-        DevBuf<int> acol, arow, tobs, cchoff, tchoff, chl;
-        DevBuf<double> aval, acv, tw, offset, g, d, lpart, cpart;
-        int ncc = 0, nct = 0;
+        // design form: y / aux by observation (mask unused), the tables above, g and d by observation, the chunk and loglik partial sums
+        DevBuf<double> g, d, lpart, cpart;
     } fisher_;
     // the same for the members of a batch: ONE data set by node and the member's row structure (the forest's first n_member rows), the
     // members' parameters and their logs, the partial sums (2 per workgroup and 4 per chunk, per member), the results (6 per member:
     // 2 of the evaluation, then 4 of the reductions) with their pinned copy, the loop's control words (nbatch step lengths, then
     // nbatch mask bytes) with theirs, and the loop's six work vectors of the forest's length (on first use)
-    struct BFisherDev {
+    // Design form (gmrfx_batch_obs_set_design): y / aux by observation (mask unused), the tables once, and per member g, d (nobs each),
+    // the chunk sums (ncc + nct), the energy partials (part: design_blocks(n_member)) and the loglik partials (lpart: design_blocks(nobs));
+    // the Hessian has cnt entries per member and the work area 5 n nbatch + cnt nbatch doubles.
+    struct BFisherDev : DesignTables {
         DevBuf<double> y, aux, param, logparam, part, out, spart, work, ctl;
         DevBuf<unsigned char> mask;
         DevBuf<long long> rp;
@@ -603,12 +618,19 @@ private:
         PinnedBuf<double> h_out, h_ctl;
         std::vector<double> loglik_const;
         int family = 0;
+        DevBuf<double> g, d, lpart, cpart;
     } bfisher_;
+    void bobs_set_design(const BObsHost &o, BFisherDev &f);      // (what the design form adds to bobs_set)
+    // the map gmrfx_batch_set_prior installed: false: the forest's diagonal (node form), true: the replicated map of a design plan;
+    // bprior_map_ok_: -1 not compared with the plan in place since then, 0 / 1 (also reset by bobs_set)
+    bool bprior_design_ = false;
+    int bprior_map_ok_ = -1;
     void bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask);
     void bfisher_check_prior();
     // the members' evaluation (BEvalIO, its mask already on the device: d_active) into bfisher_.h_out, 2 per member; synchronises
+    // (score at + k ss, hess at + k sh)
     void bfisher_eval(const double *d_x, long long sx, const double *d_mu, long long smu, const unsigned char *d_active, double *d_score,
-                      double *d_hess, long long ss);
+                      double *d_hess, long long ss, long long sh);
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
     // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
     struct GapDev {

@@ -1,5 +1,5 @@
 // device_batch_fisher.cpp -- Fisher scoring for every member of a batched handle (include/gmrfx.h: gmrfx_batch_obs_set,
-// gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation; kernels in fisher.hip). The handle is the forest diag(Q_1 .. Q_B):
+// gmrfx_batch_obs_set_design, gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation; kernels in fisher.hip and fisher_design.hip). The handle is the forest diag(Q_1 .. Q_B):
 // the priors' values (set_prior on the forest) are the members' one after the other, refactorize_update_solve factors and solves all
 // members in one pass, batch_diag reports per member. What is added here is the likelihood evaluation with per-member reductions and
 // the loop that lets every member take its own line search and stop at its own iterate.
@@ -20,6 +20,12 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
+// dst = a device copy of cnt entries of src, on the handle's books
+template <class B, class T> static void bf_up(B &dst, const T *src, size_t cnt, double *ledger) {
+    dst.alloc(cnt, ledger, kTableMinBytes);
+    if (cnt > 0) hip_check(hipMemcpy(dst, src, cnt * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+}
+
 void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     HC(hipSetDevice(device));
     if (sharded()) throw std::invalid_argument("batch_obs_set: sharded handles are not supported");
@@ -27,26 +33,18 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     if (o.nobs > 0) {
         const size_t n = (size_t)nmember_, nb = (size_t)nbatch_;
         if (n == 0 || n > (size_t)INT_MAX || o.param.size() != nb) throw std::invalid_argument("batch_obs_set: the likelihood does not belong to this handle");
-        const ObsByNode b = obs_by_node(n, o.nobs, o.idx, o.y, o.aux);
+        // what both forms hold: the members' parameters, the member's rows (the forest's first n: columns and positions of member 0
+        // are the member's own), the loop's reductions, results and control words
         std::vector<double> lp(nb);
         for (size_t k = 0; k < nb; k++) lp[k] = fisher_logparam(o.family, o.param[k]);
-        // the member's rows: the forest's first n (columns and positions of member 0 are the member's own)
         const size_t ne = (size_t)sym.rowptr[n];
         std::vector<int> pos(ne);
         for (size_t q = 0; q < ne; q++) pos[q] = (int)sym.pos[q];
-        auto up = [&](auto &dst, const auto *src, size_t cnt) {
-            dst.alloc(cnt, &bytes_total, kTableMinBytes);
-            if (cnt > 0) HC(hipMemcpy(dst, src, cnt * sizeof(*src), hipMemcpyHostToDevice));
-        };
-        up(f.y, b.y.data(), n);
-        up(f.mask, b.mask.data(), n);
-        if (!b.aux.empty()) up(f.aux, b.aux.data(), n);
-        up(f.param, o.param.data(), nb);
-        up(f.logparam, lp.data(), nb);
-        up(f.rp, reinterpret_cast<const long long *>(sym.rowptr.data()), n + 1);
-        up(f.col, sym.col.data(), ne);
-        up(f.pos, pos.data(), ne);
-        f.part.alloc(2 * nb * (size_t)fisher_blocks((int)n), &bytes_total, kTableMinBytes);
+        bf_up(f.param, o.param.data(), nb, &bytes_total);
+        bf_up(f.logparam, lp.data(), nb, &bytes_total);
+        bf_up(f.rp, reinterpret_cast<const long long *>(sym.rowptr.data()), n + 1, &bytes_total);
+        bf_up(f.col, sym.col.data(), ne, &bytes_total);
+        bf_up(f.pos, pos.data(), ne, &bytes_total);
         f.spart.alloc(4 * nb * (size_t)fisher_stat_blocks((int)n), &bytes_total, kTableMinBytes);
         f.out.alloc(6 * nb, &bytes_total, kTableMinBytes);
         f.ctl.alloc(2 * nb, &bytes_total, kTableMinBytes);
@@ -54,16 +52,56 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
         f.h_ctl.alloc(2 * (long long)nb);
         f.family = o.family;
         f.loglik_const = o.loglik_const;
+        if (o.design) bobs_set_design(o, f);
+        else {          // node form: the data set by node, one (energy, loglik) pair per workgroup and member
+            const ObsByNode b = obs_by_node(n, o.nobs, o.idx, o.y, o.aux);
+            bf_up(f.y, b.y.data(), n, &bytes_total);
+            bf_up(f.mask, b.mask.data(), n, &bytes_total);
+            if (!b.aux.empty()) bf_up(f.aux, b.aux.data(), n, &bytes_total);
+            f.part.alloc(2 * nb * (size_t)fisher_blocks((int)n), &bytes_total, kTableMinBytes);
+        }
     }
     HC(hipStreamSynchronize(stream));
     bfisher_ = std::move(f);
+    bprior_map_ok_ = -1;
 }
 
-// the map of set_prior must be the forest's diagonal, member after member (what gmrfx_batch_set_prior installs)
+// Design form, what it adds to bobs_set: the tables of design_upload once, ONE data set by observation, and every member's work:
+// g, d (nobs), chunk sums (ncc + nct), energy and loglik partials (design_blocks of n and of nobs)
+void Device::bobs_set_design(const BObsHost &o, BFisherDev &f) {
+    const DesignPlan &P = *o.design;
+    const size_t n = (size_t)nmember_, nb = (size_t)nbatch_, nobs = (size_t)P.nobs;
+    if ((long long)n != P.n || o.y.size() != nobs) throw std::invalid_argument("batch_obs_set_design: the plan does not belong to this handle");
+    bf_up(f.y, o.y.data(), nobs, &bytes_total);
+    if (!o.aux.empty()) bf_up(f.aux, o.aux.data(), nobs, &bytes_total);
+    design_upload(o.design, f);
+    f.g.alloc(nobs * nb, &bytes_total, kTableMinBytes);
+    f.d.alloc(nobs * nb, &bytes_total, kTableMinBytes);
+    f.cpart.alloc((size_t)(f.ncc + f.nct) * nb, &bytes_total, kTableMinBytes);
+    f.lpart.alloc((size_t)design_blocks((long long)nobs) * nb, &bytes_total, kTableMinBytes);
+    f.part.alloc((size_t)design_blocks((long long)n) * nb, &bytes_total, kTableMinBytes);
+}
+
+void Device::bset_prior(const double *prior_nzval, const std::vector<long long> &map, bool design) {
+    set_prior(prior_nzval, map.data(), (long long)map.size());
+    bprior_design_ = design;
+}
+
+// the map of set_prior must be the one the likelihood in place needs, member after member (what gmrfx_batch_set_prior installs): the
+// forest's diagonal in node form, the plan's map shifted by k nnz_member in design form
 void Device::bfisher_check_prior() {
     if (!d_prior_) throw std::invalid_argument("batch_fisher_eval: gmrfx_batch_set_prior has not been called");
-    if (hmap_cnt_ != S_->n) throw std::invalid_argument("batch_fisher_eval: the map of the prior is not the members' diagonals (gmrfx_batch_set_prior installs it)");
     if (!bobs_held()) throw std::invalid_argument("batch_fisher_eval: no observation likelihood is set (gmrfx_batch_obs_set)");
+    if (bfisher_.design) {
+        const DesignPlan &P = *bfisher_.design;
+        if (bprior_map_ok_ < 0)
+            bprior_map_ok_ = (bprior_design_ && hmap_cnt_ == P.cnt * nbatch_ && std::equal(P.map.begin(), P.map.end(), h_hmap_.begin())) ? 1 : 0;
+        if (!bprior_map_ok_)
+            throw std::invalid_argument("batch_fisher_eval: the map of the prior is not the one of the design likelihood in place (call "
+                                        "gmrfx_batch_set_prior again after changing the likelihood's form)");
+    } else if (bprior_design_ || hmap_cnt_ != S_->n)
+        throw std::invalid_argument("batch_fisher_eval: the map of the prior is not the members' diagonals (call gmrfx_batch_set_prior again after "
+                                    "changing the likelihood's form; it installs the map)");
 }
 
 // the control words of the next launches: nbatch step lengths (nullable: kept), then the mask bytes. The pinned copy is rewritten
@@ -80,7 +118,19 @@ void Device::bfisher_ctl(const std::vector<double> *alpha, const std::vector<uns
 }
 
 void Device::bfisher_eval(const double *d_x, long long sx, const double *d_mu, long long smu, const unsigned char *d_active, double *d_score,
-                          double *d_hess, long long ss) {
+                          double *d_hess, long long ss, long long sh) {
+    if (bfisher_.design) {
+        const DesignPlan &P = *bfisher_.design;
+        const BFisherDev &f = bfisher_;
+        const FisherDesign a{(int)P.n, (int)P.nobs, (int)P.cnt, f.family, f.rp, f.col, f.pos, d_prior_, d_x, d_mu,
+                             f.arp, f.acol, f.aval, f.offset.get(), f.acp, f.arow, f.acv, f.tptr, f.tobs, f.tw, f.cchoff, f.tchoff, f.chs, f.chl,
+                             f.ncc, f.nct, f.y, f.aux.get(), 0.0, 0.0, f.g, f.d, f.cpart, d_score, d_hess, f.part, f.lpart,
+                             nnz_member_, sx, smu, ss, sh, f.param, f.logparam, d_active};
+        launch_fisher_design(stream, a, nbatch_, f.out);
+        HC(hipMemcpyAsync(bfisher_.h_out, bfisher_.out, 2 * (size_t)nbatch_ * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HC(hipStreamSynchronize(stream));
+        return;
+    }
     const FisherEval a{(int)nmember_, bfisher_.family, bfisher_.rp, bfisher_.col, bfisher_.pos, d_prior_, d_x, d_mu, bfisher_.y,
                        bfisher_.aux.get(), bfisher_.mask, 0.0, 0.0, d_score, d_hess, bfisher_.part, nnz_member_, sx, smu, ss,
                        bfisher_.param, bfisher_.logparam, d_active};
@@ -99,7 +149,7 @@ void Device::batch_fisher_eval(const BEvalIO &io, double *out_host) {
         bfisher_ctl(nullptr, std::vector<unsigned char>(io.active, io.active + nb));
         d_act = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
     }
-    bfisher_eval(io.d_x, io.sx, io.d_mu, io.smu, d_act, io.d_score, io.d_hess, io.ss);
+    bfisher_eval(io.d_x, io.sx, io.d_mu, io.smu, d_act, io.d_score, io.d_hess, io.ss, io.sh);
     HC(hipGetLastError());
     for (int k = 0; k < nb; k++) {
         if (io.active && !io.active[k]) continue;
@@ -119,7 +169,10 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     const int nb = nbatch_;
     const size_t nbytes = (size_t)n * sizeof(double);
     const bool adaptive = o.flags & 1, retry_full = o.flags & 2, predictive = o.flags & 4, refactor_final = o.flags & 8;
-    if (!bfisher_.work) bfisher_.work.alloc(6 * (size_t)N, &bytes_total, kTableMinBytes);
+    // a member's Hessian vector: n entries in node form, the plan's cnt in design form (bobs_set drops the work area with the likelihood,
+    // so it is sized for the form in place)
+    const long long hl = bhess_len();
+    if (!bfisher_.work) bfisher_.work.alloc(5 * (size_t)N + (size_t)hl * (size_t)nb, &bytes_total, kTableMinBytes);
     // xk: the iterates; cand: every candidate of the line search, so the accepted iterate of every member; xf: the frozen finish's
     // points. The chord steps of the look-ahead are solved into xk, which nobody reads between an iterate's reductions and the copy
     // cand -> xk that ends it: the steps and iterates of the members that did not fire stay as they are.
@@ -151,7 +204,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     auto any = [](const std::vector<unsigned char> &v) { return std::find(v.begin(), v.end(), (unsigned char)1) != v.end(); };
     // an evaluation over the members of `mask` (already on the device): their pairs to ev
     auto eval = [&](const double *x, long long sx, double *sc, double *hs, const std::vector<unsigned char> &mask) {
-        bfisher_eval(x, sx, io.d_mu, io.smu, d_mask, sc, hs, n);
+        bfisher_eval(x, sx, io.d_mu, io.smu, d_mask, sc, hs, n, hl);
         tot_eval += 1;
         for (int k = 0; k < nb; k++)
             if (mask[(size_t)k]) { ev[2 * k] = bfisher_.h_out[2 * k]; ev[2 * k + 1] = bfisher_.h_out[2 * k + 1] + bfisher_.loglik_const[(size_t)k]; }
@@ -311,7 +364,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
     for (int k = 0; k < nb; k++) {
         if (m[(size_t)k].status == kFailed) { rc = 1; continue; }
         any_ok = true;
-        if (io.d_hess) HC(hipMemcpyAsync(io.d_hess + k * io.sh, hess + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
+        if (io.d_hess && hl > 0) HC(hipMemcpyAsync(io.d_hess + k * io.sh, hess + k * hl, (size_t)hl * sizeof(double), hipMemcpyDeviceToDevice, stream));
     }
     if (refactor_final && any_ok) {
         refactorize_update(hess, true);

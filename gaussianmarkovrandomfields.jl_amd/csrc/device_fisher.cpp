@@ -63,24 +63,20 @@ template <class T, class U> static void fd_up(DevBuf<T> &dst, const std::vector<
     if (!src.empty()) hip_check(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
 }
 
-// Design form: the plan's tables as they are, y / aux by observation, and the chunk tables of the segments longer than kDesignChunk
-void Device::obs_set_design(const ObsHost &o, FisherDev &f) {
-    const DesignPlan &P = *o.design;
-    const size_t n = (size_t)S_->n, nobs = (size_t)P.nobs;
-    if ((long long)n != P.n || n > (size_t)INT_MAX) throw std::invalid_argument("obs_set_design: the plan does not belong to this handle");
-    fd_up(f.y, o.y, &bytes_total);
-    if (!o.aux.empty()) fd_up(f.aux, o.aux, &bytes_total);
-    fd_up(f.arp, P.rptr, &bytes_total);
-    fd_up(f.acol, P.rcol, &bytes_total);
-    fd_up(f.aval, P.rval, &bytes_total);
-    fd_up(f.acp, P.cptr, &bytes_total);
-    fd_up(f.arow, P.crow, &bytes_total);
-    fd_up(f.acv, P.cval, &bytes_total);
-    fd_up(f.tptr, P.tptr, &bytes_total);
-    fd_up(f.tobs, P.tobs, &bytes_total);
-    fd_up(f.tw, P.tw, &bytes_total);
-    if (!P.offset.empty()) fd_up(f.offset, P.offset, &bytes_total);
-    std::vector<int> cchoff(n + 1, 0), tchoff((size_t)P.cnt + 1, 0), chl;
+// The plan's tables as they are and the chunk tables of the segments longer than kDesignChunk, for a plain or a batched likelihood
+void Device::design_upload(const std::shared_ptr<const DesignPlan> &plan, DesignTables &t) {
+    const DesignPlan &P = *plan;
+    fd_up(t.arp, P.rptr, &bytes_total);
+    fd_up(t.acol, P.rcol, &bytes_total);
+    fd_up(t.aval, P.rval, &bytes_total);
+    fd_up(t.acp, P.cptr, &bytes_total);
+    fd_up(t.arow, P.crow, &bytes_total);
+    fd_up(t.acv, P.cval, &bytes_total);
+    fd_up(t.tptr, P.tptr, &bytes_total);
+    fd_up(t.tobs, P.tobs, &bytes_total);
+    fd_up(t.tw, P.tw, &bytes_total);
+    if (!P.offset.empty()) fd_up(t.offset, P.offset, &bytes_total);
+    std::vector<int> cchoff((size_t)P.n + 1, 0), tchoff((size_t)P.cnt + 1, 0), chl;
     std::vector<long long> chs;
     auto cut = [&](const std::vector<i64> &ptr, std::vector<int> &choff) {
         for (size_t s = 0; s + 1 < ptr.size(); s++) {
@@ -94,17 +90,28 @@ void Device::obs_set_design(const ObsHost &o, FisherDev &f) {
         }
     };
     cut(P.cptr, cchoff);
-    f.ncc = (int)chs.size();
-    tchoff[0] = f.ncc;
+    t.ncc = (int)chs.size();
+    tchoff[0] = t.ncc;
     cut(P.tptr, tchoff);
-    f.nct = (int)chs.size() - f.ncc;
-    fd_up(f.cchoff, cchoff, &bytes_total);
-    fd_up(f.tchoff, tchoff, &bytes_total);
-    fd_up(f.chs, chs, &bytes_total);
-    fd_up(f.chl, chl, &bytes_total);
+    t.nct = (int)chs.size() - t.ncc;
+    fd_up(t.cchoff, cchoff, &bytes_total);
+    fd_up(t.tchoff, tchoff, &bytes_total);
+    fd_up(t.chs, chs, &bytes_total);
+    fd_up(t.chl, chl, &bytes_total);
+    t.design = plan;
+}
+
+// Design form: the tables of design_upload, y / aux by observation, and one member's work
+void Device::obs_set_design(const ObsHost &o, FisherDev &f) {
+    const DesignPlan &P = *o.design;
+    const size_t n = (size_t)S_->n, nobs = (size_t)P.nobs;
+    if ((long long)n != P.n || n > (size_t)INT_MAX) throw std::invalid_argument("obs_set_design: the plan does not belong to this handle");
+    fd_up(f.y, o.y, &bytes_total);
+    if (!o.aux.empty()) fd_up(f.aux, o.aux, &bytes_total);
+    design_upload(o.design, f);
     f.g.alloc(nobs, &bytes_total, kTableMinBytes);
     f.d.alloc(nobs, &bytes_total, kTableMinBytes);
-    f.cpart.alloc(chs.size(), &bytes_total, kTableMinBytes);
+    f.cpart.alloc((size_t)(f.ncc + f.nct), &bytes_total, kTableMinBytes);
     f.lpart.alloc((size_t)design_blocks((long long)nobs), &bytes_total, kTableMinBytes);
     f.part.alloc((size_t)design_blocks((long long)n), &bytes_total, kTableMinBytes);
     f.out.alloc(6, &bytes_total, kTableMinBytes);
@@ -113,7 +120,6 @@ void Device::obs_set_design(const ObsHost &o, FisherDev &f) {
     f.family = o.family;
     f.param = o.param;
     f.loglik_const = o.loglik_const;
-    f.design = o.design;
 }
 
 void Device::fisher_eval_design(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host) {
@@ -126,8 +132,8 @@ void Device::fisher_eval_design(const RbmcSym &sym, const double *d_x, const dou
                          fisher_.arp, fisher_.acol, fisher_.aval, fisher_.offset.get(), fisher_.acp, fisher_.arow, fisher_.acv,
                          fisher_.tptr, fisher_.tobs, fisher_.tw, fisher_.cchoff, fisher_.tchoff, fisher_.chs, fisher_.chl, fisher_.ncc, fisher_.nct,
                          fisher_.y, fisher_.aux.get(), fisher_.param, fisher_logparam(fisher_.family, fisher_.param),
-                         fisher_.g, fisher_.d, fisher_.cpart, d_score, d_hess, fisher_.part, fisher_.lpart};
-    launch_fisher_design(stream, a, fisher_.out);
+                         fisher_.g, fisher_.d, fisher_.cpart, d_score, d_hess, fisher_.part, fisher_.lpart};      // (one member: the rest stays zero)
+    launch_fisher_design(stream, a, 1, fisher_.out);
     HC(hipMemcpyAsync(fisher_.h_out, fisher_.out, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());

@@ -299,9 +299,16 @@ struct FisherDesign {
     double *cpart;               // ncc + nct chunk sums
     double *score, *hess;        // n / cnt, either nullable
     double *epart, *lpart;       // energy per workgroup of nodes, loglik per workgroup of observations
+    // the members, behind what one member needs (a plain handle leaves them zero): member k's val at + k nnz, x at + k sx, mu at + k smu
+    // (0: one mean for all), score at + k ss, hess at + k sh (>= cnt), g and d at + k nobs, cpart at + k (ncc + nct), epart at
+    // + k design_blocks(n), lpart at + k design_blocks(nobs); the tables, y, aux and offset are one copy
+    long long nnz, sx, smu, ss, sh;
+    const double *param_k, *logparam_k;  // nullable: one per member, in place of param / logparam
+    const unsigned char *active; // nullable = all; a member whose byte is 0 is skipped and nothing of it is written
 };
-// out[0] = energy, out[1] = sum of the x-dependent terms of loglik (device)
-void launch_fisher_design(hipStream_t st, const FisherDesign &a, double *out);
+// nbatch members (a plain handle: 1): out[2 k] = member k's energy, out[2 k + 1] = its sum of the x-dependent terms of loglik (device);
+// inactive members' pairs are left
+void launch_fisher_design(hipStream_t st, const FisherDesign &a, int nbatch, double *out);
 
 // ga_pullback.hip -- the array arithmetic of the implicit-function rule of the Gaussian approximation (gmrfx_ga_pullback). The solve
 // in the middle is the handle's own; these are the kernels on either side of it. Node form: one thread per node, kGapNode nodes per

@@ -87,6 +87,7 @@ EXPORTS = [
     "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
     "gmrfx_batch_set_prior", "gmrfx_batch_obs_set", "gmrfx_batch_obs_info", "gmrfx_batch_fisher_eval", "gmrfx_batch_fisher_eval_dev",
     "gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev",
+    "gmrfx_batch_obs_set_design", "gmrfx_batch_obs_hess_map", "gmrfx_batch_obs_design_info",
 ]
 
 
@@ -106,7 +107,39 @@ def source_tree_hash() -> str:
     return h.hexdigest()[:16]
 
 
-def lib():
+class _PartialCDLL(C.CDLL):
+    """a build that lacks newer exports (load_from): a missing gmrfx_* symbol becomes a stub that only carries the prototype"""
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            if not name.startswith("gmrfx_"):
+                raise
+            stub = type("missing_export", (), {})()
+            setattr(self, name, stub)
+            return stub
+
+
+def load_from(path):
+    """Another build of the library (an older one may lack newer exports) with every prototype set, beside the one lib() holds: for
+    A/B tools that alternate two builds in one process. use(L) makes the binding's calls go to it."""
+    global _lib, _LIBPATH
+    keep = (_lib, _LIBPATH)
+    _lib, _LIBPATH = None, os.path.abspath(path)
+    try:
+        return lib(_PartialCDLL)
+    finally:
+        _lib, _LIBPATH = keep
+
+
+def use(L):
+    """the library (lib() or load_from()) every later call of the binding goes to; handles stay with the library that made them"""
+    global _lib
+    _lib = L
+
+
+def lib(cdll=C.CDLL):
     """Load libgmrfx.so; fails loudly if it has not been built (no fallback of any kind)."""
     global _lib
     if _lib is None:
@@ -121,7 +154,7 @@ def lib():
                 import torch  # noqa: F401
             except Exception:
                 pass
-        L = C.CDLL(_LIBPATH)
+        L = cdll(_LIBPATH)
         vp, i64, i32, dbl = C.c_void_p, C.c_int64, C.c_int32, C.c_double
         L.gmrfx_last_create_error.restype = C.c_char_p
         L.gmrfx_last_error.restype = C.c_char_p
@@ -243,6 +276,9 @@ def lib():
         L.gmrfx_batch_set_prior.argtypes = [vp, vp]
         L.gmrfx_batch_obs_set.argtypes = [vp, i32, i64, vp, i32, vp, vp, vp]
         L.gmrfx_batch_obs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp]
+        L.gmrfx_batch_obs_set_design.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.gmrfx_batch_obs_hess_map.argtypes = [vp, vp, i64, C.POINTER(i64)]
+        L.gmrfx_batch_obs_design_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
         L.gmrfx_batch_fisher_eval.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp]
         L.gmrfx_batch_fisher_eval_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp]
         for nm in ("gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev"):

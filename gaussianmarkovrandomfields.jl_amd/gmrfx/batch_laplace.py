@@ -1,19 +1,23 @@
 """MI355XBatchLaplace -- a batched handle with the non-Gaussian path: one observation data set, one prior precision and one
 likelihood parameter per member, Fisher scoring and the Gaussian approximation for all members in one pass over the forest
-(include/gmrfx.h: gmrfx_batch_set_prior, gmrfx_batch_obs_set, gmrfx_batch_fisher_eval, gmrfx_batch_gaussian_approximation).
-The hyper-parameter sweep of a model with Poisson, binomial or similar observations: one Laplace approximation per theta_k."""
+(include/gmrfx.h: gmrfx_batch_set_prior, gmrfx_batch_obs_set, gmrfx_batch_obs_set_design, gmrfx_batch_fisher_eval,
+gmrfx_batch_gaussian_approximation). The hyper-parameter sweep of a model with Poisson, binomial or similar observations: one Laplace
+approximation per theta_k. The observations sit on nodes (set_observations) or are seen through a sparse design matrix, eta = A x + b
+(set_design_observations: points inside mesh triangles, intercepts, group effects)."""
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
+import scipy.sparse as sp
 
 from ._lib import ERR_NOT_POSDEF, check, lib, ptr
 from .backend import MI355XBackend, MI355XBatchBackend
 
 
 class MI355XBatchLaplace(MI355XBatchBackend):
-    """Everything MI355XBatchBackend does, plus the likelihood. Shapes: NZ (nnz, B); points, means, scores and Hessians (n, B)."""
+    """Everything MI355XBatchBackend does, plus the likelihood. Shapes: NZ (nnz, B); points, means and scores (n, B); Hessians (n, B) in
+    node form and (cnt, B) in design form, in the order of observations_hess_map()."""
 
     OBS_FAMILIES = MI355XBackend.OBS_FAMILIES
 
@@ -42,7 +46,9 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         return a
 
     def set_prior(self, NZ) -> None:
-        """The members' prior precisions, (nnz, B); the diagonal Hessian map of every member is installed by the library."""
+        """The members' prior precisions, (nnz, B); the Hessian map of every member is installed by the library, for the likelihood in
+        place: the diagonal (none yet, or set_observations) or the map of the design form. Call it again after changing the
+        likelihood's form."""
         nz = self._values(NZ)
         check(lib().gmrfx_batch_set_prior(self._h, ptr(nz)), self._h)
 
@@ -61,6 +67,51 @@ class MI355XBatchLaplace(MI355XBatchBackend):
             raise ValueError("param must be a scalar or have one entry per member")
         check(lib().gmrfx_batch_obs_set(self._h, fam, yy.size, ptr(idx), int(index_base), ptr(yy), ptr(ax), ptr(pp)), self._h)
 
+    def set_design_observations(self, family, y, A, b=None, aux=None, param=0.0) -> None:
+        """ONE data set for all members observed through eta = A x + b (gmrfx_batch_obs_set_design; as
+        MI355XBackend.set_design_observations: A any scipy sparse matrix, nobs x n) and one param per member: a scalar, or an array of
+        length B. Replaces a node-form likelihood; an empty y removes the likelihood. set_prior (again) installs the members' maps."""
+        fam = self.OBS_FAMILIES[family] if isinstance(family, str) else int(family)
+        yy = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        Ac = sp.csc_matrix(A, dtype=np.float64)
+        if Ac.shape != (yy.size, self.n):
+            raise ValueError(f"A must be nobs x n = {yy.size} x {self.n}, got {Ac.shape}")
+        if not Ac.has_canonical_format:
+            Ac = Ac.copy()
+            Ac.sum_duplicates()
+        off = None if b is None else np.ascontiguousarray(b, dtype=np.float64).reshape(-1)
+        ax = None if aux is None else np.ascontiguousarray(aux, dtype=np.float64).reshape(-1)
+        if (off is not None and off.size != yy.size) or (ax is not None and ax.size != yy.size):
+            raise ValueError("b / aux do not have one entry per observation")
+        pp = np.asarray(param, dtype=np.float64)
+        pp = np.full(self.nbatch, float(pp)) if pp.ndim == 0 else np.ascontiguousarray(pp).reshape(-1)
+        if pp.size != self.nbatch:
+            raise ValueError("param must be a scalar or have one entry per member")
+        cp = np.ascontiguousarray(Ac.indptr, dtype=np.int64)
+        rv = np.ascontiguousarray(Ac.indices, dtype=np.int64)
+        nz = np.ascontiguousarray(Ac.data, dtype=np.float64)
+        check(lib().gmrfx_batch_obs_set_design(self._h, fam, yy.size, ptr(cp), ptr(rv), ptr(nz), 0, ptr(off), ptr(yy), ptr(ax), ptr(pp)), self._h)
+
+    def observations_hess_map(self) -> np.ndarray:
+        """0-based positions into ONE member's values of the entries of A' D A, ascending (gmrfx_batch_obs_hess_map): the order of the
+        Hessian values fisher_eval and gaussian_approximation return per member in design form."""
+        cnt = C.c_int64(0)
+        check(lib().gmrfx_batch_obs_hess_map(self._h, None, 0, C.byref(cnt)), self._h)
+        m = np.empty(cnt.value, np.int64)
+        check(lib().gmrfx_batch_obs_hess_map(self._h, ptr(m), m.size, C.byref(cnt)), self._h)
+        return m
+
+    def observations_design_info(self) -> dict:
+        """nnz(A), cnt and the term count of the design plan (-1 each in node form)"""
+        a, c, t = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(lib().gmrfx_batch_obs_design_info(self._h, C.byref(a), C.byref(c), C.byref(t)), self._h)
+        return {"nnz": a.value, "cnt": c.value, "terms": t.value}
+
+    def _hess_len(self) -> int:
+        """entries of a member's Hessian vector: n in node form, the map's cnt in design form"""
+        cnt = self.observations_design_info()["cnt"]
+        return self.n if cnt < 0 else cnt
+
     def observations_info(self) -> dict:
         fam, nobs, c = C.c_int32(0), C.c_int64(0), np.zeros(self.nbatch)
         check(lib().gmrfx_batch_obs_info(self._h, C.byref(fam), C.byref(nobs), ptr(c)), self._h)
@@ -68,34 +119,42 @@ class MI355XBatchLaplace(MI355XBatchBackend):
 
     def fisher_eval(self, X, mean=None, active=None, want_score: bool = True, want_hess: bool = True, score=None, hess=None):
         """(score (n, B), hess (n, B), energy (B,), loglik (B,)) at the members' points X (n, B); mean: (n,) for every member or (n, B).
-        active: B flags; a member whose flag is 0 is skipped and its columns of score / hess (pass arrays to see that; fresh ones are
-        NaN there) and its energy / loglik (NaN) are left untouched."""
+        Design form: hess is (cnt, B). Both outputs are views of arrays of max(n, cnt) rows (one member stride serves both); arrays
+        passed in must have that many rows. active: B flags; a member whose flag is 0 is skipped and its columns of score / hess (pass
+        arrays to see that; fresh ones are NaN there) and its energy / loglik (NaN) are left untouched."""
         Xf, sx = self._points(X, "X")
         mu, smu = self._points(mean, "mean", shared_ok=True)
         act = self._active(active)
+        hl = self._hess_len()
+        ld = max(self.n, hl)
 
         def _out(given, want):
             if not want and given is None:
                 return None
             if given is None:
-                return np.full((self.n, self.nbatch), np.nan, order="F")
-            if given.shape != (self.n, self.nbatch) or not given.flags.f_contiguous or given.dtype != np.float64:
-                raise ValueError("score / hess must be Fortran float64 arrays of shape (n, nbatch)")
+                return np.full((ld, self.nbatch), np.nan, order="F")
+            if given.shape != (ld, self.nbatch) or not given.flags.f_contiguous or given.dtype != np.float64:
+                raise ValueError("score / hess must be Fortran float64 arrays of shape (max(n, cnt), nbatch)")
             return given
         sc, hs = _out(score, want_score), _out(hess, want_hess)
         out = np.full((2, self.nbatch), np.nan, order="F")
-        check(lib().gmrfx_batch_fisher_eval(self._h, ptr(Xf), sx, ptr(mu), smu, ptr(act), ptr(sc), ptr(hs), self.n, ptr(out)), self._h)
+        check(lib().gmrfx_batch_fisher_eval(self._h, ptr(Xf), sx, ptr(mu), smu, ptr(act), ptr(sc), ptr(hs), ld, ptr(out)), self._h)
+        if ld != self.n and sc is not None:
+            sc = sc[:self.n]
+        if ld != hl and hs is not None:
+            hs = hs[:hl]
         return sc, hs, out[0].copy(), out[1].copy()
 
     def fisher_eval_dev(self, d_x: int, sx: int, d_mu: int = 0, smu: int = 0, active=None, d_score: int = 0, d_hess: int = 0, ss: int = 0, out=None):
-        """Device pointers with member strides (smu = 0: one mean); returns (energy (B,), loglik (B,)); `out` (2, B) Fortran is filled
-        in place when given (inactive members' pairs stay as they are)."""
+        """Device pointers with member strides (smu = 0: one mean; ss serves score and hess: at least n for score, at least cnt for a
+        design-form hess; default max(n, cnt)); returns (energy (B,), loglik (B,)); `out` (2, B) Fortran is filled in place when given
+        (inactive members' pairs stay as they are)."""
         if not d_x:
             raise ValueError("fisher_eval_dev: null pointer")
         act = self._active(active)
         if out is None:
             out = np.full((2, self.nbatch), np.nan, order="F")
-        check(lib().gmrfx_batch_fisher_eval_dev(self._h, d_x, sx, d_mu or None, smu, ptr(act), d_score or None, d_hess or None, ss or self.n,
+        check(lib().gmrfx_batch_fisher_eval_dev(self._h, d_x, sx, d_mu or None, smu, ptr(act), d_score or None, d_hess or None, ss or max(self.n, self._hess_len()),
                                                 ptr(out)), self._h)
         return out[0].copy(), out[1].copy()
 
@@ -111,20 +170,22 @@ class MI355XBatchLaplace(MI355XBatchBackend):
     def gaussian_approximation(self, mean=None, x0=None, max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5,
                                adaptive_stepsize: bool = True, max_linesearch_iter: int = 10, step_recovery: str = "retry_full",
                                predictive_convergence: bool = True, refactorize_final: bool = False):
-        """The Gaussian approximation of every member (gmrfx_batch_gaussian_approximation): (X (n, B), H (n, B), info). info holds
+        """The Gaussian approximation of every member (gmrfx_batch_gaussian_approximation): (X (n, B), H, info); H is (n, B) in node form
+        and (cnt, B) in design form (the values of A' D_k A at the mode, in the order of observations_hess_map()). info holds
         per-member arrays (iterations, converged, alpha, decrement, factorizations, solves, merit_evaluations, frozen_finish, energy,
         loglik, info; dec_trace and alpha_trace as lists of arrays) and the forest-level `totals`. A member whose factorisation failed
         does not raise: info["info"][k] > 0, X[:, k] is its last accepted iterate and H[:, k] is NaN; the others are complete."""
         mu, smu = self._points(mean, "mean", shared_ok=True)
         xs, sx0 = self._points(x0, "x0")
+        hl = self._hess_len()
         X = np.empty((self.n, self.nbatch), order="F")
-        H = np.full((self.n, self.nbatch), np.nan, order="F")
+        H = np.full((hl, self.nbatch), np.nan, order="F")
         res, totals = np.zeros((10, self.nbatch), order="F"), np.zeros(3)
         dec, alp = (np.full((max_iter + 1, self.nbatch), np.nan, order="F") for _ in range(2))
         info = np.zeros(self.nbatch, np.int64)
         flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
         rc = lib().gmrfx_batch_gaussian_approximation(self._h, ptr(mu), smu, ptr(xs), sx0, max_iter, max_linesearch_iter, float(mean_change_tol),
-                                                      float(newton_dec_tol), flags, ptr(X), self.n, ptr(H), self.n, ptr(res), ptr(totals),
+                                                      float(newton_dec_tol), flags, ptr(X), self.n, ptr(H), hl, ptr(res), ptr(totals),
                                                       ptr(dec), ptr(alp), ptr(info))
         self._info = info.copy()
         if rc != ERR_NOT_POSDEF:
@@ -136,8 +197,8 @@ class MI355XBatchLaplace(MI355XBatchBackend):
                                    max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5, adaptive_stepsize: bool = True,
                                    max_linesearch_iter: int = 10, step_recovery: str = "retry_full", predictive_convergence: bool = True,
                                    refactorize_final: bool = False) -> dict:
-        """Device pointers with member strides: the modes x and hess (0 = not wanted) outputs, mean (smu = 0: one mean) and x0.
-        Returns the info dict."""
+        """Device pointers with member strides: the modes x and hess (0 = not wanted; sh at least n, or cnt in design form, which is
+        the default) outputs, mean (smu = 0: one mean) and x0. Returns the info dict."""
         if not d_x:
             raise ValueError("gaussian_approximation_dev: null pointer")
         res, totals = np.zeros((10, self.nbatch), order="F"), np.zeros(3)
@@ -146,7 +207,7 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
         rc = lib().gmrfx_batch_gaussian_approximation_dev(self._h, d_mu or None, smu, d_x0 or None, sx0 or self.n, max_iter, max_linesearch_iter,
                                                           float(mean_change_tol), float(newton_dec_tol), flags, d_x, sx, d_hess or None,
-                                                          sh or self.n, ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info))
+                                                          sh or self._hess_len(), ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info))
         self._info = info.copy()
         if rc != ERR_NOT_POSDEF:
             check(rc, self._h)

@@ -961,7 +961,8 @@ function constrained_var(bb::MI355XBatch)
 end
 
 # ---- the non-Gaussian path for every member (include/gmrfx.h: gmrfx_batch_set_prior .. gmrfx_batch_gaussian_approximation) ----------------
-# the members' prior precisions, nnz x nbatch; the library installs every member's diagonal Hessian map
+# the members' prior precisions, nnz x nbatch; the library installs every member's Hessian map for the likelihood in place
+# (the diagonal, or the design form's: call it again after changing the likelihood's form)
 function set_prior!(bb::MI355XBatch, NZ::Matrix{Float64})
     size(NZ) == (bb.nnz, bb.nbatch) || throw(DimensionMismatch("NZ must be nnz x nbatch"))
     GC.@preserve NZ check(ccall((:gmrfx_batch_set_prior, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, NZ), bb.h)
@@ -978,33 +979,69 @@ function set_observations!(bb::MI355XBatch, family::Integer, y::Vector{Float64},
         bb.h.ptr, Int32(family), length(y), idx, Int32(1), y, ax, param), bb.h)
     return nothing
 end
+# The same data set observed through eta = A x + offset (gmrfx_batch_obs_set_design): A as Julia holds it (CSC, 1-based), nobs x n of the
+# MEMBER. Replaces the node form; call set_prior! again afterwards, it installs the members' maps. fisher_eval and gaussian_approximation
+# then return cnt Hessian values per member, in the order of observations_hess_map(bb).
+function set_design_observations!(bb::MI355XBatch, family::Integer, y::Vector{Float64}, A::SparseMatrixCSC{Float64, Int64},
+                                  param::Vector{Float64}; offset::Union{Nothing, Vector{Float64}} = nothing,
+                                  aux::Union{Nothing, Vector{Float64}} = nothing)
+    length(param) == bb.nbatch || throw(DimensionMismatch("param must have one entry per member"))
+    size(A) == (length(y), bb.n) || throw(DimensionMismatch("A must be nobs x n"))
+    (offset === nothing || length(offset) == length(y)) && (aux === nothing || length(aux) == length(y)) ||
+        throw(DimensionMismatch("offset / aux must have one entry per observation"))
+    poff = offset === nothing ? Ptr{Float64}(C_NULL) : pointer(offset)
+    paux = aux === nothing ? Ptr{Float64}(C_NULL) : pointer(aux)
+    GC.@preserve y A offset aux param check(ccall((:gmrfx_batch_obs_set_design, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        bb.h.ptr, Int32(family), length(y), A.colptr, A.rowval, A.nzval, Int32(1), poff, y, paux, param), bb.h)
+    return nothing
+end
+function observations_design_info(bb::MI355XBatch)
+    a = Ref{Int64}(0); c = Ref{Int64}(0); t = Ref{Int64}(0)
+    check(ccall((:gmrfx_batch_obs_design_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), bb.h.ptr, a, c, t), bb.h)
+    return (nnz = a[], cnt = c[], terms = t[])
+end
+# 1-based positions into ONE member's values of the entries of A' D A, ascending
+function observations_hess_map(bb::MI355XBatch)
+    cnt = Ref{Int64}(0)
+    check(ccall((:gmrfx_batch_obs_hess_map, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ref{Int64}), bb.h.ptr, C_NULL, Int64(0), cnt), bb.h)
+    m = Vector{Int64}(undef, cnt[])
+    check(ccall((:gmrfx_batch_obs_hess_map, LIB), Int32, (Ptr{Cvoid}, Ptr{Int64}, Int64, Ref{Int64}), bb.h.ptr, m, Int64(length(m)), cnt), bb.h)
+    return m .+ 1
+end
+# entries of a member's Hessian vector: n in node form, the map's cnt in design form
+_hess_len(bb::MI355XBatch) = (c = observations_design_info(bb).cnt; c < 0 ? bb.n : Int(c))
 function observations_info(bb::MI355XBatch)
     fam = Ref{Int32}(0); nobs = Ref{Int64}(0); c = zeros(bb.nbatch)
     GC.@preserve c check(ccall((:gmrfx_batch_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ptr{Float64}), bb.h.ptr, fam, nobs, c), bb.h)
     return (family = fam[], nobs = nobs[], loglik_const = c)
 end
-# (score, hess, energy, loglik) at the members' points X (n x nbatch); mean n x nbatch or nothing; active: one byte per member or nothing
+# (score, hess, energy, loglik) at the members' points X (n x nbatch); mean n x nbatch or nothing; active: one byte per member or nothing;
+# hess: n x nbatch in node form, cnt x nbatch in design form (both outputs go down at one member stride, max(n, cnt))
 function fisher_eval(bb::MI355XBatch, X::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing,
                      active::Union{Nothing, Vector{UInt8}} = nothing)
     size(X) == (bb.n, bb.nbatch) || throw(DimensionMismatch("X must be n x nbatch"))
     mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
     active === nothing || length(active) == bb.nbatch || throw(DimensionMismatch("active must have one entry per member"))
-    score = fill(NaN, bb.n, bb.nbatch); hess = fill(NaN, bb.n, bb.nbatch); out = fill(NaN, 2, bb.nbatch)
+    hl = _hess_len(bb); ld = max(bb.n, hl)
+    score = fill(NaN, ld, bb.nbatch); hess = fill(NaN, ld, bb.nbatch); out = fill(NaN, 2, bb.nbatch)
     mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
     act = active === nothing ? Ptr{UInt8}(C_NULL) : pointer(active)
     GC.@preserve X mean active score hess out check(ccall((:gmrfx_batch_fisher_eval, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{UInt8}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}),
-        bb.h.ptr, X, bb.n, mu, bb.n, act, score, hess, bb.n, out), bb.h)
-    return score, hess, out[1, :], out[2, :]
+        bb.h.ptr, X, bb.n, mu, bb.n, act, score, hess, ld, out), bb.h)
+    return score[1:bb.n, :], hess[1:hl, :], out[1, :], out[2, :]
 end
 # The Gaussian approximation of every member: (X, H, result 10 x nbatch, totals, dec_trace, alpha_trace, info). A member whose
-# factorisation failed does not throw: info[k] > 0, X[:, k] its last accepted iterate, H[:, k] NaN.
+# factorisation failed does not throw: info[k] > 0, X[:, k] its last accepted iterate, H[:, k] NaN. H: n x nbatch in node form, cnt x nbatch
+# in design form.
 function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Float64}} = nothing, x0::Union{Nothing, Matrix{Float64}} = nothing,
                                 max_iter::Integer = 50, max_linesearch_iter::Integer = 10, mean_change_tol::Real = 1e-4,
                                 newton_dec_tol::Real = 1e-5, flags::Integer = 7)
     mean === nothing || size(mean) == (bb.n, bb.nbatch) || throw(DimensionMismatch("mean must be n x nbatch"))
     x0 === nothing || size(x0) == (bb.n, bb.nbatch) || throw(DimensionMismatch("x0 must be n x nbatch"))
-    X = Matrix{Float64}(undef, bb.n, bb.nbatch); H = fill(NaN, bb.n, bb.nbatch)
+    hl = _hess_len(bb)
+    X = Matrix{Float64}(undef, bb.n, bb.nbatch); H = fill(NaN, hl, bb.nbatch)
     result = zeros(10, bb.nbatch); totals = zeros(3)
     dec = fill(NaN, max_iter + 1, bb.nbatch); alp = fill(NaN, max_iter + 1, bb.nbatch)
     inf = zeros(Int64, bb.nbatch)
@@ -1014,7 +1051,7 @@ function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Flo
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
         bb.h.ptr, mu, bb.n, xs, bb.n, Int64(max_iter), Int64(max_linesearch_iter), Float64(mean_change_tol), Float64(newton_dec_tol),
-        Int32(flags), X, bb.n, H, bb.n, result, totals, dec, alp, inf)
+        Int32(flags), X, bb.n, H, hl, result, totals, dec, alp, inf)
     bb.info .= inf
     rc == 5 || check(rc, bb.h)          # GMRFX_ERR_NOT_POSDEF: reported per member in info
     return X, H, result, totals, dec, alp, inf

@@ -731,21 +731,35 @@ int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, co
 
 /* ---- Fisher scoring and the Gaussian approximation for every member of a batched handle ---------------------------------------------
  * The hyper-parameter sweep of a model with non-Gaussian observations: one Gaussian approximation per theta_k, all in one pass over the
- * forest of gmrfx_create_batched. Node form (eta_i = x_i), the six families of gmrfx_obs_set, no constraints; a plain handle is a batch of
- * one. gmrfx_obs_set, gmrfx_fisher_eval and gmrfx_gaussian_approximation keep refusing batched handles; the state set here is separate
+ * forest of gmrfx_create_batched. Node form (eta_i = x_i) or design form (eta = A x + b, gmrfx_batch_obs_set_design), the six families of
+ * gmrfx_obs_set, no constraints; a plain handle is a batch of one. gmrfx_obs_set, gmrfx_fisher_eval and gmrfx_gaussian_approximation keep refusing batched handles; the state set here is separate
  * from theirs.
  *   gmrfx_batch_set_prior    keeps the nnz x nbatch values (member-major, as gmrfx_batch_refactorize takes them) on the device and
- *                            installs the diagonal Hessian map of every member (the position of (i, i) in member k's values): the
- *                            caller builds no forest-wide map. INVALID_ARG for a pattern without a stored diagonal.
+ *                            installs the Hessian map of the batch likelihood in place at the time of the call, for every member: the
+ *                            position of (i, i) in member k's values (no likelihood, or the node form), or the map of
+ *                            gmrfx_batch_obs_hess_map shifted by k nnz (design form). The caller builds no forest-wide map. After changing
+ *                            the likelihood's FORM call it again: the evaluation refuses a map that is not the one the likelihood in
+ *                            place needs. INVALID_ARG for a pattern without a stored diagonal.
  *   gmrfx_batch_obs_set      ONE data set for all members (y, aux, indices as in gmrfx_obs_set; stored once, n values) and one param
  *                            (sigma, r, phi) per member. The same validation and refusals as gmrfx_obs_set, applied to every param[k];
  *                            loglik_const is summed per member in long double. nobs = 0 removes it; gmrfx_clone carries it; works on
  *                            symbolic_only handles.
+ *   gmrfx_batch_obs_set_design   the same through a design matrix, eta = A x + b: A (nobs x n, CSC), offset, y and aux as in
+ *                            gmrfx_obs_set_design, ONE copy for all members, and one param per member. Every check of gmrfx_obs_set_design
+ *                            (the first pair of pattern(A'A) that Q does not store is named in the caller's base; the 2^31 limits) and,
+ *                            member by member, every check of gmrfx_batch_obs_set. The plan is built on the member's pattern. nobs = 0
+ *                            removes the likelihood; setting either batch form replaces the other. Works on symbolic_only handles.
+ *   gmrfx_batch_obs_hess_map     the member's map: cnt positions (index base 0) in ONE member's value array, the list gmrfx_obs_hess_map
+ *                            returns on a plain handle of that pattern (map nullable; cap: its capacity, INVALID_ARG when below cnt). A
+ *                            member's Hessian vector then has cnt entries in that order, in gmrfx_batch_fisher_eval and the loop.
+ *   gmrfx_batch_obs_design_info  nnz(A), cnt and the term count of the plan (-1 each without one), as gmrfx_obs_design_info.
  *   gmrfx_batch_obs_info     family (-1: none), nobs, loglik_const (nbatch values), each nullable.
  *   gmrfx_batch_fisher_eval  per member exactly what gmrfx_fisher_eval returns for Q_p,k, param[k] and x_k, bit for bit: member k's point
  *                            at x + k sx, its mean at mu + k smu (mu nullable; smu = 0: one mean for all), score and hess (either nullable)
  *                            at + k ss, out[2 k ..] = {energy, loglik}. active (host, nbatch bytes, nullable = all): a member whose byte
- *                            is 0 is skipped; its slices of score and hess and its pair of out are left untouched.
+ *                            is 0 is skipped; its slices of score and hess and its pair of out are left untouched. Design form: per
+ *                            member what gmrfx_fisher_eval returns in design form, bit for bit; hess has cnt entries per member, and ss
+ *                            must be at least n when score is non-null and at least cnt when hess is.
  *   gmrfx_batch_gaussian_approximation   the loop of gmrfx_gaussian_approximation (same flags, same rules) for all members in lockstep:
  *                            one forest-wide launch per step, every member taking its own line search, look-ahead and frozen finish and
  *                            stopping at its own iterate. x0 nullable (= mu, or 0), member k's at + k sx0; x (sx) the modes; hess (sh,
@@ -756,16 +770,25 @@ int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, co
  *                            failed: info[k] is then as gmrfx_batch_refactorize reports it, x_k that member's last accepted iterate and
  *                            its hess slice untouched; every other member is complete and correct, and the handle stays usable. A
  *                            stopped member's values no longer change, so without flag bit 3 it ends holding the factor of its own last
- *                            iterate; with it, one more forest factorisation at H(x_k) covers every member that did not fail.
+ *                            iterate; with it, one more forest factorisation at H(x_k) covers every member that did not fail. Design
+ *                            form: hess has cnt entries per member (sh >= cnt); a plan with cnt = 0 runs with Q_post = Q_p.
  * No atomics; bit-reproducible; the host and the _dev forms agree bit for bit; a member's results do not depend on the other members.
- * Device memory: the data set (17 n bytes), the member's row structure, 6 n nbatch doubles of work vectors on the first loop.
+ * Device memory: the data set (17 n bytes), the member's row structure, 6 n nbatch doubles of work vectors on the first loop. Design
+ * form: the plan's tables and the data set once, (2 nobs + ncc + nct + design blocks) nbatch doubles of evaluation work (ncc + nct: the
+ * chunks of the columns and term lists longer than 512 entries), (5 n + cnt) nbatch doubles of work vectors on the first loop.
  * Errors (INVALID_ARG with a message, nothing changed): a sharded handle, more than 65535 members, a constraint set (gmrfx_constraints_set
- * or gmrfx_batch_constraints_set), a plain handle holding the design form, null x / out / result, a stride below n (smu = 0 excepted), no
- * likelihood, no prior. GMRFX_ERR_NO_DEVICE for symbolic_only handles after these checks.
- * LIMITS: node form only, no constraints (both left to a follow-up); nbatch <= 65535; n < 2^31. */
+ * or gmrfx_batch_constraints_set), a plain handle holding the design form of gmrfx_obs_set_design, null x / out / result, a stride below n
+ * (smu = 0 excepted; hess: below cnt in design form), no likelihood, no prior, a prior whose map is not the likelihood's.
+ * GMRFX_ERR_NO_DEVICE for symbolic_only handles after these checks.
+ * LIMITS: no constraints, no batched pullback or predictive scores (left to follow-ups); nbatch <= 65535; n < 2^31. */
 int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval /* nnz x nbatch */);
 int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices /* nobs, nullable */, int32_t index_base,
                             const double *y /* nobs */, const double *aux /* nobs, nullable */, const double *param /* nbatch */);
+int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *colptr /* n + 1 */, const int64_t *rowval,
+                                   const double *nzval, int32_t index_base, const double *offset /* nobs, nullable */,
+                                   const double *y /* nobs */, const double *aux /* nobs, nullable */, const double *param /* nbatch */);
+int32_t gmrfx_batch_obs_hess_map(const gmrfx_handle *h, int64_t *map /* nullable; cnt values, index base 0 */, int64_t cap, int64_t *cnt);
+int32_t gmrfx_batch_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms);
 int32_t gmrfx_batch_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const /* nbatch */);
 int32_t gmrfx_batch_fisher_eval(gmrfx_handle *h, const double *x, int64_t sx, const double *mu /* nullable */, int64_t smu,
                                 const uint8_t *active /* host, nbatch, nullable */, double *score /* nullable */, double *hess /* nullable */,

@@ -10,7 +10,14 @@ quartiles over --reps timed repetitions after --warmup, the GPU synchronised aro
 counts of both routes, ASSERTED equal; the largest difference of the modes; the forest-level totals; the source tree hash. The
 plain route's per-member set_prior (nnz doubles over PCIe) and obs_set are part of what a sweep on one plain handle costs and are
 timed with it; "plain_loop_only" times the plain loops alone on B handles prepared beforehand.
-usage: tools/batch_ga_bench.py [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
+
+--design: the same sweep observed through a design matrix. 3 n point observations, each inside a random mesh
+triangle with three barycentric weights, plus an intercept column: the latent vector is the field and one intercept node with a proper
+N(0, 1 / 0.01) prior, every row of A observes it with weight 1 (n + 1 nodes; the members' pattern is united with pattern(A'A), explicit
+zeros; the dense intercept column is pinned to the end of the elimination order, PinDenseColumns). gmrfx_batch_obs_set_design once, then
+gmrfx_batch_set_prior + gmrfx_batch_gaussian_approximation_dev per sweep, against ONE plain handle whose design likelihood is set once
+(the plan does not depend on theta) and which takes gmrfx_set_prior + gmrfx_gaussian_approximation_dev per member.
+usage: tools/batch_ga_bench.py [--design] [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
 import argparse
 import json
 import os
@@ -21,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "gaussianmarkovrandomfields.jl_amd"))
 
 import numpy as np  # noqa: E402
+import scipy.sparse as sp  # noqa: E402
 import torch  # noqa: E402
 
 import gmrfx  # noqa: E402
@@ -34,6 +42,96 @@ def members(g, B, rng):
         Q.sort_indices()
         assert np.array_equal(Q.indptr, Qs[0].indptr) and np.array_equal(Q.indices, Qs[0].indices), "pattern changed with the values"
     return Qs, mesh.points
+
+
+def design_problem(g, B, rng):
+    """(members on n + 1 nodes with pattern(A'A) stored, coords, A (3 n x (n + 1)), y)"""
+    mesh = spde.grid_mesh_2d(g, g, jitter=0.25, seed=0)
+    n = mesh.points.shape[0]
+    nobs = 3 * n
+    cells = np.asarray(mesh.cells)
+    tri = cells[rng.integers(0, cells.shape[0], nobs)]
+    A = sp.csr_matrix((rng.dirichlet(np.ones(3), nobs).ravel(), (np.repeat(np.arange(nobs), 3), tri.ravel())), shape=(nobs, n))
+    A.sum_duplicates()
+    A = sp.hstack([A, sp.csr_matrix(np.ones((nobs, 1)))], format="csr")
+    P = sp.csr_matrix(A, copy=True)
+    P.data[:] = 1.0
+    P = sp.coo_matrix(P.T @ P)
+    Qs = []
+    for _ in range(B):
+        M = spde.matern_precision(mesh, 0, float(rng.uniform(0.15, 0.4)), tau=float(rng.uniform(0.5, 2.0)))
+        C = sp.coo_matrix(sp.block_diag([M, sp.csc_matrix([[0.01]])]))
+        Q = sp.csc_matrix((np.r_[C.data, np.zeros(P.nnz)], (np.r_[C.row, P.row], np.r_[C.col, P.col])), shape=(n + 1, n + 1))
+        Q.sort_indices()
+        Qs.append(Q)
+        assert np.array_equal(Q.indptr, Qs[0].indptr) and np.array_equal(Q.indices, Qs[0].indices), "pattern changed with the values"
+    pts = np.vstack([mesh.points, mesh.points.mean(axis=0)])
+    return Qs, pts, A, rng.poisson(20.0, nobs).astype(float)
+
+
+def design(a):
+    B, g = a.batch, a.grid
+    Qs, pts, A, y = design_problem(g, B, np.random.default_rng(g))
+    n, nobs = Qs[0].shape[0], A.shape[0]
+    NZ = np.asfortranarray(np.stack([Q.data for Q in Qs], axis=1))
+    kw = dict(refactorize_final=True)
+    bb = gmrfx.MI355XBatchLaplace(Qs[0], B, ordering=gmrfx.PinDenseColumns(), coords=pts, device=0)
+    bb.set_design_observations("poisson", y, A, param=0.0)
+    info = bb.observations_design_info()
+    perm = bb.ordering_permutation()
+    dX = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    dX0 = torch.zeros(n * B, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    res = {}
+
+    def batched():
+        bb.set_prior(NZ)
+        res["b"] = bb.gaussian_approximation_dev(dX.data_ptr(), n, d_x0=dX0.data_ptr(), sx0=n, **kw)
+    t_b = timed(batched, a.reps, a.warmup)
+    Xb = dX.cpu().numpy().reshape(B, n).copy()
+
+    plain = gmrfx.MI355XBackend(Qs[0], ordering=perm, device=0, factorize=False)
+    plain.set_design_observations("poisson", y, A)
+    hmap = plain.observations_hess_map()
+    assert np.array_equal(hmap, bb.observations_hess_map())
+    dx = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    its = np.zeros(B, np.int64)
+
+    def sequential():
+        for k in range(B):
+            plain.set_prior(NZ[:, k], hmap)
+            i = plain.gaussian_approximation_dev(dx.data_ptr() + 8 * k * n, d_x0=dX0.data_ptr(), **kw)
+            its[k] = i["iterations"]
+    t_s = timed(sequential, a.reps, a.warmup)
+    Xs = dx.cpu().numpy().reshape(B, n).copy()
+    plain.close()
+
+    many = []
+    for k in range(B):
+        p = gmrfx.MI355XBackend(Qs[0], ordering=perm, device=0, factorize=False)
+        p.set_design_observations("poisson", y, A)
+        p.set_prior(NZ[:, k], hmap)
+        many.append(p)
+
+    def loops_only():
+        for k, p in enumerate(many):
+            p.gaussian_approximation_dev(dx.data_ptr() + 8 * k * n, d_x0=dX0.data_ptr(), **kw)
+    t_l = timed(loops_only, a.reps, a.warmup)
+    for p in many:
+        p.close()
+
+    ib = res["b"]
+    assert np.array_equal(ib["iterations"], its), (ib["iterations"], its)
+    row = {"tool": "tools/batch_ga_bench.py --design", "device": torch.cuda.get_device_name(0), "source_tree_hash": _lib.source_tree_hash(),
+           "n": n, "nobs": nobs, "nnz_A": info["nnz"], "cnt": info["cnt"], "terms": info["terms"], "grid": g, "B": B, "family": "poisson",
+           "reps": a.reps, "warmup": a.warmup, "batched": t_b, "one_plain_handle_sequential": t_s, "plain_loop_only": t_l,
+           "ms_per_member_batched": t_b["median_ms"] / B, "ms_per_member_sequential": t_s["median_ms"] / B,
+           "speedup_vs_sequential": t_s["median_ms"] / t_b["median_ms"], "speedup_vs_loops_only": t_l["median_ms"] / t_b["median_ms"],
+           "iterations": ib["iterations"].tolist(), "iteration_counts_agree": True, "converged": bool(ib["converged"].all()), "totals": ib["totals"],
+           "sum_member_factorizations": int(ib["factorizations"].sum()), "max_abs_mode_diff": float(np.abs(Xb - Xs).max())}
+    print(json.dumps(row), flush=True)
+    bb.close()
+    return row
 
 
 def diag_positions(Q):
@@ -64,8 +162,16 @@ def main():
     ap.add_argument("--batch", type=int, default=50)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--design", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.design:
+        row = design(a)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(row, f, indent=1)
+        return
     B, g = a.batch, a.grid
     Qs, pts = members(g, B, np.random.default_rng(g))
     n = Qs[0].shape[0]
