@@ -5,11 +5,13 @@
 #include "api_obs.h"
 
 // what every call here refuses about the handle itself, before anything else is looked at
-static void bf_check_handle(const gmrfx_handle *h, const std::string &who) {
+// (bcon_ok: the calls that work with a batch constraint held -- the prior's values and the constrained loop; a plain constraint
+// stays refused everywhere. The unconstrained loop and the evaluation refuse both: they would silently ignore the constraint.)
+static void bf_check_handle(const gmrfx_handle *h, const std::string &who, bool bcon_ok = false) {
     check_unsharded(h, (who + "sharded handles are not supported").c_str());
     if (h->nbatch > kBatchFisherMaxMembers) throw std::invalid_argument(who + "more than 65535 members");
     if (h->obs.design) throw std::invalid_argument(who + "the design form (eta = A x + b, gmrfx_obs_set_design) is not supported");
-    if (h->bcon.m > 0 || h->con.m > 0) throw std::invalid_argument(who + "a constraint set is not supported (clear it first)");
+    if ((h->bcon.m > 0 && !bcon_ok) || h->con.m > 0) throw std::invalid_argument(who + "a constraint set is not supported (clear it first)");
 }
 // the member's sizes, on plain handles too
 static int64_t bf_n(const gmrfx_handle *h) { return h->nbatch > 1 ? h->n_member : h->S.n; }
@@ -28,7 +30,7 @@ static void bf_check_stride(const std::string &who, const char *what, int64_t s,
 extern "C" int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval) {
     return guarded(h, [&]() -> int32_t {
         const std::string who = "batch_set_prior: ";
-        bf_check_handle(h, who);
+        bf_check_handle(h, who, true);
         if (!prior_nzval) throw std::invalid_argument(who + "prior_nzval is null");
         if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);       // (refuses a pattern without a stored diagonal)
         if (int32_t e = need_device(h, false)) return e;
@@ -142,6 +144,26 @@ extern "C" int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, i
     });
 }
 
+// The members' parameters replaced in place, in node or design form: the validation of gmrfx_batch_obs_set on every param[k], loglik_const
+// per member in long double from the data the handle keeps (read in place, validated when it was set). Nothing else of the likelihood changes (no data goes up, no plan is
+// rebuilt), so it also works while a batch constraint is held.
+extern "C" int32_t gmrfx_batch_obs_set_param(gmrfx_handle *h, const double *param) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_obs_set_param: ";
+        if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
+        if (!param) throw std::invalid_argument(who + "param is null (one value per member)");
+        const int64_t nb = h->nbatch;
+        const BObsHost &b = h->bobs;        // (its y and aux were validated when they were set: only the parameters are new)
+        for (int64_t k = 0; k < nb; k++) obs_check_param(who + "member " + std::to_string(k) + ": ", b.family, param[k]);
+        std::vector<double> p(param, param + nb), c((size_t)nb);
+        for (int64_t k = 0; k < nb; k++) c[(size_t)k] = obs_loglik_const(b.family, b.nobs, b.y, b.aux, param[k]);
+        if (h->D) h->D->bobs_set_param(p, c);
+        h->bobs.param = std::move(p);
+        h->bobs.loglik_const = std::move(c);
+        return GMRFX_OK;
+    });
+}
+
 extern "C" int32_t gmrfx_batch_obs_hess_map(const gmrfx_handle *h, int64_t *map, int64_t cap, int64_t *cnt) {
     if (!h) return GMRFX_ERR_INVALID_ARG;
     return guarded(const_cast<gmrfx_handle *>(h), [&]() -> int32_t {
@@ -218,10 +240,16 @@ extern "C" int32_t gmrfx_batch_fisher_eval_dev(gmrfx_handle *h, const double *d_
 
 static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const double *x0, int64_t sx0, int64_t max_iter, int64_t max_ls,
                           double mean_tol, double dec_tol, int32_t flags, double *x, int64_t sx, double *hess, int64_t sh, double *result,
-                          double *totals, double *dec_trace, double *alpha_trace, int64_t *info, bool dev) {
+                          double *totals, double *dec_trace, double *alpha_trace, int64_t *info, bool dev, bool constrained = false,
+                          int64_t *cinfo = nullptr, double *residual = nullptr) {
     return guarded(h, [&]() -> int32_t {
-        const std::string who = "batch_gaussian_approximation: ";
-        bf_check_handle(h, who);
+        const std::string who = constrained ? "batch_constrained_gaussian_approximation: " : "batch_gaussian_approximation: ";
+        if (constrained) {
+            if (h->con.m > 0 && h->bcon.m == 0)
+                throw std::invalid_argument(who + "the handle holds a plain constraint (gmrfx_constraints_set); set it with gmrfx_batch_constraints_set");
+            if (h->bcon.m == 0) throw std::invalid_argument(who + "no batch constraint is held (gmrfx_batch_constraints_set); without one call gmrfx_batch_gaussian_approximation");
+        }
+        bf_check_handle(h, who, constrained);
         if (!x || !result) throw std::invalid_argument(who + "x / result is null");
         if (max_iter < 0 || max_ls < 0) throw std::invalid_argument(who + "max_iter / max_linesearch_iter is negative");
         if (flags < 0 || flags > 15) throw std::invalid_argument(who + "unknown flag bits");
@@ -234,9 +262,10 @@ static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const 
         if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
         if (int32_t e = need_batch(h, false)) return e;
         const Device::GaOpts o{max_iter, max_ls, mean_tol, dec_tol, flags};
-        std::vector<long long> inf((size_t)nb, 0);
+        std::vector<long long> inf((size_t)nb, 0), cin((size_t)nb, 0);
         int rc;
-        if (dev) rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu, smu, x0, sx0, x, sx, hess, sh}, o, result, totals, dec_trace, alpha_trace, inf.data());
+        if (dev) rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu, smu, x0, sx0, x, sx, hess, sh}, o, result, totals, dec_trace, alpha_trace, inf.data(),
+                                                         cin.data(), residual);
         else {
             DevBlock bm, b0, bx, bh;
             if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
@@ -244,11 +273,19 @@ static int32_t bf_ga_impl(gmrfx_handle *h, const double *mu, int64_t smu, const 
             stage_alloc(h, bx, n * nb);
             if (hess && hl > 0) stage_up(h, bh, hess, hl, hl, 1, sh, nb);      // (a failed member's slice keeps what the caller's array holds)
             rc = h->D->batch_gaussian_approximation(Device::BGaIO{mu ? bm.get() : nullptr, smu == 0 ? 0 : n, x0 ? b0.get() : nullptr, n, bx, n,
-                                                                  hess ? bh.get() : nullptr, hl}, o, result, totals, dec_trace, alpha_trace, inf.data());
+                                                                  hess ? bh.get() : nullptr, hl}, o, result, totals, dec_trace, alpha_trace, inf.data(),
+                                                     cin.data(), residual);
             stage_down(h, bx, x, n, n, 1, sx, nb);
             if (hess && hl > 0) stage_down(h, bh, hess, hl, hl, 1, sh, nb);
         }
         if (info) std::copy(inf.begin(), inf.end(), info);
+        if (cinfo) std::copy(cin.begin(), cin.end(), cinfo);
+        if (rc & 2) {
+            int64_t k = 0;
+            while (k < nb && cin[(size_t)k] <= 0) k++;
+            h->err = who + "A Q^-1 A' of member " + std::to_string(k) + " is not positive definite (rank-deficient constraint matrix)";
+            return GMRFX_ERR_NOT_POSDEF;
+        }
         if (rc == 1) {
             int64_t k = 0;
             while (k < nb && inf[(size_t)k] == 0) k++;
@@ -272,4 +309,23 @@ extern "C" int32_t gmrfx_batch_gaussian_approximation_dev(gmrfx_handle *h, const
                                                           double *result, double *totals, double *dec_trace, double *alpha_trace, int64_t *info) {
     return bf_ga_impl(h, d_mu, smu, d_x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, d_x, sx, d_hess, sh, result,
                       totals, dec_trace, alpha_trace, info, true);
+}
+
+// With a batch constraint held (gmrfx_batch_constraints_set): the same loop with every step projected onto A s = 0, as the plain loop
+// does under gmrfx_constraints_set. Entry points of their own: the unconstrained calls keep refusing such a handle.
+extern "C" int32_t gmrfx_batch_constrained_gaussian_approximation(gmrfx_handle *h, const double *mu, int64_t smu, const double *x0, int64_t sx0,
+                                                                  int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                                                  double newton_dec_tol, int32_t flags, double *x, int64_t sx, double *hess, int64_t sh,
+                                                                  double *result, double *totals, double *dec_trace, double *alpha_trace, int64_t *info,
+                                                                  int64_t *cinfo, double *residual) {
+    return bf_ga_impl(h, mu, smu, x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, x, sx, hess, sh, result, totals,
+                      dec_trace, alpha_trace, info, false, true, cinfo, residual);
+}
+extern "C" int32_t gmrfx_batch_constrained_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, int64_t smu, const double *d_x0, int64_t sx0,
+                                                                      int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                                                      double newton_dec_tol, int32_t flags, double *d_x, int64_t sx, double *d_hess,
+                                                                      int64_t sh, double *result, double *totals, double *dec_trace,
+                                                                      double *alpha_trace, int64_t *info, int64_t *cinfo, double *residual) {
+    return bf_ga_impl(h, d_mu, smu, d_x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, d_x, sx, d_hess, sh, result,
+                      totals, dec_trace, alpha_trace, info, true, true, cinfo, residual);
 }

@@ -11,25 +11,25 @@
 //   Normal  nobs (-1/2 log 2 pi - log sigma)          Poisson  -sum lgamma(y + 1)          Bernoulli  0
 //   Binomial  sum lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1)
 //   NegBin  sum lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log r          Gamma  nobs (phi log phi - lgamma(phi)) + (phi - 1) sum log y
-inline double obs_loglik_const(const ObsHost &o) {
+inline double obs_loglik_const(int f, long long nobs_, const std::vector<double> &ys, const std::vector<double> &aux, double param) {
     long double c = 0.0L;
-    const long double p = (long double)o.param, nobs = (long double)o.nobs;
-    const int f = o.family;
+    const long double p = (long double)param, nobs = (long double)nobs_;
     switch (f) {
         case 0: c = nobs * obs_const_shared(f, p); break;
-        case 1: for (double y : o.y) c += obs_const_own(f, y, 0.0L, p); break;
+        case 1: for (double y : ys) c += obs_const_own(f, y, 0.0L, p); break;
         case 3:
-            for (size_t k = 0; k < o.y.size(); k++) c += obs_const_own(f, o.y[k], o.aux[k], p);
+            for (size_t k = 0; k < ys.size(); k++) c += obs_const_own(f, ys[k], aux[k], p);
             break;
-        case 4: for (double y : o.y) c += obs_const_own(f, y, 0.0L, p); break;
+        case 4: for (double y : ys) c += obs_const_own(f, y, 0.0L, p); break;
         case 5:
             c = nobs * obs_const_shared(f, p);
-            for (double y : o.y) c += obs_const_own(f, y, 0.0L, p);
+            for (double y : ys) c += obs_const_own(f, y, 0.0L, p);
             break;
         default: break;
     }
     return (double)c;
 }
+inline double obs_loglik_const(const ObsHost &o) { return obs_loglik_const(o.family, o.nobs, o.y, o.aux, o.param); }
 
 // ---- what gmrfx_obs_set and gmrfx_obs_set_design check alike (who: the prefix of the messages) -------------------------------------------
 inline void obs_check_handle(const gmrfx_handle *h, const std::string &who) {
@@ -39,11 +39,14 @@ inline void obs_check_handle(const gmrfx_handle *h, const std::string &who) {
 inline void obs_check_family(const std::string &who, int32_t family) {
     if (family < 0 || family >= kObsFamilies) throw std::invalid_argument(who + "unknown family (0 Normal, 1 Poisson, 2 Bernoulli, 3 Binomial, 4 NegativeBinomial, 5 Gamma)");
 }
+inline void obs_check_param(const std::string &who, int32_t family, double param) {
+    if ((family == 0 || family == 4 || family == 5) && !(param > 0.0 && std::isfinite(param)))
+        throw std::invalid_argument(who + "sigma / r / phi must be positive and finite");
+}
 inline void obs_check_operands(const std::string &who, int32_t family, const double *y, const double *aux, double param) {
     if (!y) throw std::invalid_argument(who + "y is null");
     if (family == 3 && !aux) throw std::invalid_argument(who + "the binomial family needs aux (the number of trials)");
-    if ((family == 0 || family == 4 || family == 5) && !(param > 0.0 && std::isfinite(param)))
-        throw std::invalid_argument(who + "sigma / r / phi must be positive and finite");
+    obs_check_param(who, family, param);
 }
 // y, aux, param and loglik_const of o, observation by observation
 inline void obs_fill_values(ObsHost &o, const std::string &who, int32_t family, int64_t nobs, const double *y, const double *aux, double param) {

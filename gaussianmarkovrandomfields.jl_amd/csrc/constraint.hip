@@ -10,10 +10,15 @@
 //   k_con_var        out_i = max(sigma_i - sum_j B_ij^2, 0)
 //   k_batch_con_chol L_c, L_c^-1, log det W and the pivot status of every member of a batched handle, one workgroup per member
 //   k_batch_con_quad |L_c^-1 r|^2 per member
+//   k_batch_con_maxabs max_r |r| per member (the residual A x - e the batched Gaussian approximation reports)
 //   k_batch_con_void NaN into At_k and W_k of the members whose factorisation failed
 // MEMBERS (batched handles, gmrfx_batch_constraints_*). Every kernel above takes a member index from its grid and member strides:
 // member k's At / B at + k n m, L_c^-1 at + k m m, R at + k m cols, the chunk sums at + k totchunks cols, X at + k sx, mu at
 // + k smu. A plain handle is one member; its arithmetic is what it was.
+// ACTIVE (k_con_ax_part, k_con_ax_final, k_con_apply_*; the conventions of FisherEval::active): nbatch bytes on the device, null =
+// every member. A workgroup of a member whose byte is 0 returns on its first statement (uniform, ahead of every barrier and load) and
+// nothing of that member is written: not X, not R, not the chunk sums. The batched Gaussian approximation projects the steps of
+// the members a step concerns this way (Device::bcon_project).
 // DETERMINISM. Every sum has one fixed order that depends on the operands' INDICES only: a thread of k_con_ax_part takes
 // the entry pairs t, t + 256, ... of its chunk in that order, the 256 thread sums meet in a fixed LDS tree, the chunk sums
 // are added in chunk order by one thread; no floating-point atomics anywhere. Whether a pair of neighbouring entries is
@@ -44,7 +49,8 @@ __global__ __launch_bounds__(256) void k_con_scatter(const long long *__restrict
 __global__ __launch_bounds__(256) void k_con_ax_part(const long long *__restrict__ rowptr, const int *__restrict__ col,
                                                      const double *__restrict__ val, const int *__restrict__ choff,
                                                      const double *__restrict__ X, long long ldx, int k, double *__restrict__ part,
-                                                     int maxchunks, long long sx) {
+                                                     int maxchunks, long long sx, const unsigned char *__restrict__ active) {
+    if (active && !active[blockIdx.x / maxchunks]) return;
     constexpr int KT = kConColTile;
     __shared__ double red[KT][256];
     const int r = blockIdx.z, mb = blockIdx.x / maxchunks, c = blockIdx.x - mb * maxchunks, tid = threadIdx.x;
@@ -93,7 +99,9 @@ __global__ __launch_bounds__(256) void k_con_ax_part(const long long *__restrict
 }
 
 __global__ __launch_bounds__(256) void k_con_ax_final(const int *__restrict__ choff, const double *__restrict__ part, int m, int k,
-                                                      const double *__restrict__ e, const double *__restrict__ add, double *__restrict__ R) {
+                                                      const double *__restrict__ e, const double *__restrict__ add, double *__restrict__ R,
+                                                      const unsigned char *__restrict__ active) {
+    if (active && !active[blockIdx.y]) return;
     const int idx = blockIdx.x * 256 + threadIdx.x, mb = blockIdx.y;         // add: m values per member
     if (idx >= m * k) return;
     const int r = idx % m, j = idx / m;
@@ -156,7 +164,8 @@ __device__ __forceinline__ void con_form_t(double *Ts, const double *__restrict_
 template <int MQ>     // k-steps of 4: m <= 4 MQ
 __global__ __launch_bounds__(256) void k_con_apply_mfma(const double *__restrict__ B, const double *__restrict__ Linv, const double *__restrict__ R,
                                                         const double *__restrict__ mu, double *__restrict__ X, long long ldx, int n, int m, int k,
-                                                        long long sx, long long smu) {
+                                                        long long sx, long long smu, const unsigned char *__restrict__ active) {
+    if (active && !active[blockIdx.z]) return;
     __shared__ double Ts[4 * MQ * 65];
     const int jc0 = blockIdx.y * 64;
     {
@@ -210,7 +219,8 @@ __global__ __launch_bounds__(256) void k_con_apply_mfma(const double *__restrict
 template <int M>
 __global__ __launch_bounds__(256) void k_con_apply_vec(const double *__restrict__ B, const double *__restrict__ Linv, const double *__restrict__ R,
                                                        const double *__restrict__ mu, double *__restrict__ X, long long ldx, int n, int k,
-                                                       long long sx, long long smu) {
+                                                       long long sx, long long smu, const unsigned char *__restrict__ active) {
+    if (active && !active[blockIdx.z]) return;
     __shared__ double Ts[(M > 0 ? M : 1) * 65];
     const int jc0 = blockIdx.y * 64;
     {
@@ -330,6 +340,20 @@ __global__ __launch_bounds__(64) void k_batch_con_quad(const double *__restrict_
     }
 }
 
+// out[k] = max_r |R[k m + r]| for the members whose byte in active is set (nullable = all); the others' entries are left
+__global__ __launch_bounds__(64) void k_batch_con_maxabs(const double *__restrict__ R, int m, int nb, const unsigned char *__restrict__ active,
+                                                         double *__restrict__ out) {
+    const int mb = blockIdx.x * 64 + threadIdx.x;
+    if (mb >= nb || (active && !active[mb])) return;
+    double s = 0.0;
+    for (int r = 0; r < m; r++) {
+        const double v = fabs(R[(long long)mb * m + r]);
+        s = (v != v || v > s) ? v : s;          // (a NaN stays one)
+        if (v != v) break;
+    }
+    out[mb] = s;
+}
+
 // the members whose factorisation failed (cinfo = -1): At_k and W_k become NaN too, whatever the sweeps made of a broken factor
 __global__ __launch_bounds__(256) void k_batch_con_void(const long long *__restrict__ cinfo, double *__restrict__ At, long long nat,
                                                         double *__restrict__ W, int nw) {
@@ -357,6 +381,11 @@ void launch_batch_con_quad(hipStream_t st, const double *Linv, const double *R, 
     hipLaunchKernelGGL(k_batch_con_quad, dim3((unsigned)nb), dim3(64), 0, st, Linv, R, sr, m, quad);
 }
 
+void launch_batch_con_maxabs(hipStream_t st, const double *R, int m, int nb, const unsigned char *active, double *out) {
+    if (m <= 0 || nb <= 0) return;
+    hipLaunchKernelGGL(k_batch_con_maxabs, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, R, m, nb, active, out);
+}
+
 void launch_con_scatter(hipStream_t st, const long long *rowptr, const int *col, const double *val, int n, int m, long long maxlen, double *out,
                         int nb) {
     if (m <= 0 || maxlen <= 0) return;
@@ -365,11 +394,12 @@ void launch_con_scatter(hipStream_t st, const long long *rowptr, const int *col,
 }
 
 void launch_con_ax(hipStream_t st, const long long *rowptr, const int *col, const double *val, const int *choff, int maxchunks, int m,
-                   const double *X, long long ldx, int k, double *part, const double *e, const double *add, double *R, int nb, long long sx) {
+                   const double *X, long long ldx, int k, double *part, const double *e, const double *add, double *R, int nb, long long sx,
+                   const unsigned char *active) {
     if (m <= 0 || k <= 0) return;
     hipLaunchKernelGGL(k_con_ax_part, dim3((unsigned)maxchunks * (unsigned)nb, (unsigned)((k + kConColTile - 1) / kConColTile), (unsigned)m),
-                       dim3(256), 0, st, rowptr, col, val, choff, X, ldx, k, part, maxchunks, sx);
-    hipLaunchKernelGGL(k_con_ax_final, dim3((unsigned)((m * k + 255) / 256), (unsigned)nb), dim3(256), 0, st, choff, part, m, k, e, add, R);
+                       dim3(256), 0, st, rowptr, col, val, choff, X, ldx, k, part, maxchunks, sx, active);
+    hipLaunchKernelGGL(k_con_ax_final, dim3((unsigned)((m * k + 255) / 256), (unsigned)nb), dim3(256), 0, st, choff, part, m, k, e, add, R, active);
 }
 
 void launch_con_trsm(hipStream_t st, const double *At, const double *Linv, int n, int m, double *B, int nb) {
@@ -383,15 +413,15 @@ void launch_con_var(hipStream_t st, const double *B, int n, int m, double *sig, 
 }
 
 void launch_con_apply(hipStream_t st, const double *B, const double *Linv, const double *R, const double *mu, double *X, long long ldx, int n,
-                      int m, int k, int nb, long long sx, long long smu) {
+                      int m, int k, int nb, long long sx, long long smu, const unsigned char *active) {
     if (n <= 0 || k <= 0 || (m <= 0 && !mu)) return;
     const unsigned gy = (unsigned)((k + 63) / 64);
 #define GMRFX_CON_VEC(M)                                                                                                                  \
     hipLaunchKernelGGL(k_con_apply_vec<M>, dim3((unsigned)std::min<long long>(((long long)n + 255) / 256, kConApplyGroups), gy, (unsigned)nb), dim3(256), 0, st, B, \
-                       Linv, R, mu, X, ldx, n, k, sx, smu)
+                       Linv, R, mu, X, ldx, n, k, sx, smu, active)
 #define GMRFX_CON_MFMA(MQ)                                                                                                                \
     hipLaunchKernelGGL(k_con_apply_mfma<MQ>, dim3((unsigned)std::min<long long>(((long long)n + 63) / 64, kConApplyGroups), gy, (unsigned)nb), dim3(256), 0, st, B, \
-                       Linv, R, mu, X, ldx, n, m, k, sx, smu)
+                       Linv, R, mu, X, ldx, n, m, k, sx, smu, active)
     if (m <= 0) GMRFX_CON_VEC(0);
     else if (m == 1) GMRFX_CON_VEC(1);
     else if (m == 2) GMRFX_CON_VEC(2);

@@ -218,6 +218,14 @@ public:
     void bcon_set(const ConHost &c);
     int bcon_m() const { return bcon_.m; }
     bool bcon_prepare();
+    // the same refresh, handing back cinfo per member instead of folding it into one answer (the lockstep loop stops members alone)
+    const std::vector<long long> &bcon_prepare_members() { bcon_prepare(); return bcon_.h_cinfo; }
+    // S_k <- S_k - At_k W_k^-1 (A S_k) for the members whose byte in d_active (nbatch bytes on the device, nullable = all) is set:
+    // the one-column, e = 0 case of bcon_correct on the operands bcon_prepare left, S_k = d_S + k stride. Enqueues only: the
+    // caller's next synchronisation covers it. A member whose W_k failed must be masked out (its L_ck^-1 is NaN).
+    void bcon_project(double *d_S, long long stride, const unsigned char *d_active);
+    // out_host[k] = max_r |(A x_k - e)_r|, x_k = d_x + k sx, for the members whose byte in d_active is set (the others: left)
+    void bcon_residual(const double *d_x, long long sx, const unsigned char *d_active, const unsigned char *active_host, double *out_host);
     const std::vector<double> &bcon_logdet_w() const { return bcon_.h_logdet; }
     const std::vector<long long> &bcon_cinfo() const { return bcon_.h_cinfo; }
     double bcon_ms() const { return bcon_.ms; }
@@ -292,8 +300,16 @@ public:
     // dec_trace / alpha_trace: host, (max_iter + 1) per member, nullable; info: host, one per member. Returns 0, or 1 when a member's
     // factorisation failed (info[k] = 1 + its failing step, its x = its last accepted iterate, everybody else complete).
     struct BGaIO { const double *d_mu; long long smu; const double *d_x0; long long sx0; double *d_x; long long sx; double *d_hess; long long sh; };
+    // With a batch constraint held (bcon_m() > 0) every step is projected as the plain loop projects it: bcon_prepare + bcon_project
+    // after the refactorize_update_solve of every iterate (masked to the running members) and bcon_project after each chord solve of
+    // the frozen finish (masked to the firing members, same factor, no re-preparation). cinfo (host, nbatch, nullable): 0, 1 + the
+    // failing pivot of W_k (that member stops alone, its x its last accepted iterate), -1 beside a failed factorisation; residual
+    // (host, nbatch, nullable): max_r |(A x_k - e)_r| of the members that did not fail (NaN for the others). Bit 1 of the return
+    // value: some member's W_k failed.
     int batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, double *result, double *totals, double *dec_trace, double *alpha_trace,
-                                     long long *info);
+                                     long long *info, long long *cinfo = nullptr, double *residual = nullptr);
+    // the members' likelihood parameters replaced in place (gmrfx_batch_obs_set_param): param and loglik_const, nbatch each
+    void bobs_set_param(const std::vector<double> &param, const std::vector<double> &loglik_const);
 
     // The pullback of gaussian_approximation at its mode d_x (device_ga_pullback.cpp, ga_pullback.hip; gmrfx_ga_pullback): from the
     // cotangents of the mode (d_mubar, n) and of the posterior precision (d_Qbar, nnz on the pattern), either nullable, those of the

@@ -8,6 +8,11 @@
 // decisions. A step of the loop is ONE forest-wide launch masked to the members it concerns; a member that has stopped is masked out
 // of every launch that writes its slices, its hess slice above all: every later forest factorisation then reproduces its factor bit
 // for bit (a member's factor depends on its own values only), so it ends holding the factor of its own last iterate.
+// CONSTRAINTS (gmrfx_batch_constrained_gaussian_approximation). With a batch constraint held every step is projected,
+// s_k <- s_k - At_k W_k^-1 (A s_k), where the plain loop projects it: after the refactorize_update_solve of an iterate and after each
+// chord solve of the frozen finish, by the masked launches of constraint.hip (bcon_project). bcon_prepare runs once per iterate, forest
+// wide: a stopped member's factor is reproduced bit for bit, so its At_k, W_k and B_k are too, and it ends holding the operands of its
+// own last iterate. A member whose W_k fails is read on the host and masked out before any correction launch; it stops alone.
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -64,6 +69,18 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     HC(hipStreamSynchronize(stream));
     bfisher_ = std::move(f);
     bprior_map_ok_ = -1;
+}
+
+void Device::bobs_set_param(const std::vector<double> &param, const std::vector<double> &loglik_const) {
+    HC(hipSetDevice(device));
+    const size_t nb = (size_t)nbatch_;
+    if (!bobs_held() || param.size() != nb || loglik_const.size() != nb) throw std::invalid_argument("batch_obs_set_param: the parameters do not belong to this handle");
+    std::vector<double> lp(nb);
+    for (size_t k = 0; k < nb; k++) lp[k] = fisher_logparam(bfisher_.family, param[k]);
+    HC(hipStreamSynchronize(stream));      // nothing in flight may still read the previous values
+    HC(hipMemcpy(bfisher_.param, param.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    HC(hipMemcpy(bfisher_.logparam, lp.data(), nb * sizeof(double), hipMemcpyHostToDevice));
+    bfisher_.loglik_const = loglik_const;
 }
 
 // Design form, what it adds to bobs_set: the tables of design_upload once, ONE data set by observation, and every member's work:
@@ -159,7 +176,7 @@ void Device::batch_fisher_eval(const BEvalIO &io, double *out_host) {
 }
 
 int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, double *result, double *totals, double *dec_trace, double *alpha_trace,
-                                         long long *info) {
+                                         long long *info, long long *cinfo, double *residual) {
     HC(hipSetDevice(device));
     if (!io.d_x || !result) throw std::invalid_argument("batch_gaussian_approximation: x / result is null");
     if (o.max_iter < 0 || o.max_ls < 0) throw std::invalid_argument("batch_gaussian_approximation: max_iter / max_linesearch_iter is negative");
@@ -183,7 +200,10 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
         else if (io.d_mu) HC(hipMemcpyAsync(dst, io.d_mu + k * io.smu, nbytes, hipMemcpyDeviceToDevice, stream));
         else HC(hipMemsetAsync(dst, 0, nbytes, stream));
         if (info) info[k] = 0;
+        if (cinfo) cinfo[k] = 0;
+        if (residual) residual[k] = std::nan("");
     }
+    const bool constrained = bcon_.m > 0;
     const long long tl = o.max_iter + 1;
     for (long long q = 0; q < tl * nb; q++) {
         if (dec_trace) dec_trace[q] = std::nan("");
@@ -194,6 +214,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
                     long long iters = 0; bool frozen = false; };
     std::vector<Member> m((size_t)nb);
     double tot_fact = 0, tot_solve = 0, tot_eval = 0;
+    bool wfail = false;      // some member's W_k = A Q_k^-1 A' was not positive definite
     std::vector<double> ev(2 * (size_t)nb), st(4 * (size_t)nb), al((size_t)nb, 1.0), obj_accept((size_t)nb), stepinf((size_t)nb);
     std::vector<long long> binfo((size_t)nb);
     const unsigned char *d_mask = reinterpret_cast<const unsigned char *>(bfisher_.ctl.get() + nb);
@@ -231,6 +252,8 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
         mk.status = status; mk.iters = iters; mk.frozen = frozen;
         HC(hipMemcpyAsync(io.d_x + k * io.sx, x + k * n, nbytes, hipMemcpyDeviceToDevice, stream));
     };
+    // a member's constraint status: -1 beside a failed factorisation, 1 + the failing pivot of its W_k
+    auto con_failed = [&](int k, long long c) { if (cinfo) cinfo[k] = c; };
     std::vector<unsigned char> run((size_t)nb, 1), mask((size_t)nb);
     for (long long iter = 1; iter <= o.max_iter && any(run); iter++) {
         bfisher_ctl(nullptr, run);
@@ -245,12 +268,29 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
             mk.nfact += 1; mk.nsolve += 1;
             if (binfo[(size_t)k] != 0) {
                 if (info) info[k] = binfo[(size_t)k];
+                con_failed(k, -1);
                 stop(k, kFailed, xk, iter - 1, false);
                 run[(size_t)k] = 0;
             }
             mk.alpha_prev = mk.alpha;
         }
         if (!any(run)) break;
+        if (constrained) {
+            // the step - At_k W_k^-1 (A step) of _workspace_constrain_with_matrix, on the operands of the factor in hand. The status
+            // words are read before any correction is launched: a member whose W_k failed stops alone, masked out before
+            // k_con_apply can see its NaN L_c^-1 (cinfo = -1 is a failed factorisation: the pivot report above has dealt with it)
+            const std::vector<long long> &ci = bcon_prepare_members();
+            for (int k = 0; k < nb; k++)
+                if (run[(size_t)k] && ci[(size_t)k] > 0) {
+                    con_failed(k, ci[(size_t)k]);
+                    stop(k, kFailed, xk, iter - 1, false);
+                    run[(size_t)k] = 0;
+                    wfail = true;
+                }
+            if (!any(run)) break;
+            bfisher_ctl(nullptr, run);
+            bcon_project(step, n, d_mask);
+        }
         if (adaptive) {
             // _ga_line_search per member, in rounds: a round forms the candidates of the members still searching and evaluates them
             bool have_inf = false;
@@ -327,6 +367,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
                 eval(xf, n, score, nullptr, fire);
                 solve(score, N, 1, xk, N, true, 0);
                 tot_solve += 1;
+                if (constrained) bcon_project(xk, n, d_mask);      // (the same factor: the operands of this iterate; the mask is `fire`)
                 for (int k = 0; k < nb; k++)
                     if (fire[(size_t)k]) m[(size_t)k].nsolve += 1;
                 if (j == 1) {
@@ -373,8 +414,13 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
         for (int k = 0; k < nb; k++) {
             if (m[(size_t)k].status == kFailed) continue;
             m[(size_t)k].nfact += 1;
-            if (binfo[(size_t)k] != 0) { if (info) info[k] = binfo[(size_t)k]; rc = 1; }
+            if (binfo[(size_t)k] != 0) { if (info) info[k] = binfo[(size_t)k]; con_failed(k, -1); rc = 1; }
         }
+    }
+    if (constrained && residual && any_ok) {
+        for (int k = 0; k < nb; k++) mask[(size_t)k] = m[(size_t)k].status != kFailed;
+        bfisher_ctl(nullptr, mask);
+        bcon_residual(io.d_x, io.sx, d_mask, mask.data(), residual);
     }
     HC(hipStreamSynchronize(stream));
     HC(hipGetLastError());
@@ -385,7 +431,7 @@ int Device::batch_gaussian_approximation(const BGaIO &io, const GaOpts &o, doubl
         std::copy(r, r + 10, result + 10 * k);
     }
     if (totals) { totals[0] = tot_fact; totals[1] = tot_solve; totals[2] = tot_eval; }
-    return rc;
+    return wfail ? (rc | 2) : rc;
 }
 
 }  // namespace gmrfx

@@ -300,6 +300,33 @@ void Device::bcon_correct(double *d_X, long long ldx, long long sx, long long nv
     HC(hipGetLastError());
 }
 
+void Device::bcon_project(double *d_S, long long stride, const unsigned char *d_active) {
+    HC(hipSetDevice(device));
+    BConDev &b = bcon_;
+    const int m = b.m, nb = nbatch_;
+    const long long n = nmember_;
+    if (m <= 0) return;
+    con_reserve_cols(bcon_, 1, nbatch_);        // (bcon_prepare has reserved more)
+    launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_S, n, 1, b.part, nullptr, nullptr, b.R, nb, stride, d_active);
+    launch_con_apply(stream, b.B, b.Linv, b.R, nullptr, d_S, n, (int)n, m, 1, nb, stride, n, d_active);
+}
+
+void Device::bcon_residual(const double *d_x, long long sx, const unsigned char *d_active, const unsigned char *active_host, double *out_host) {
+    HC(hipSetDevice(device));
+    BConDev &b = bcon_;
+    const int m = b.m, nb = nbatch_;
+    if (m <= 0) return;
+    con_reserve_cols(bcon_, 1, nbatch_);
+    launch_con_ax(stream, b.rowptr, b.col, b.val, b.choff, b.maxchunks, m, d_x, nmember_, 1, b.part, b.e, nullptr, b.R, nb, sx, d_active);
+    launch_batch_con_maxabs(stream, b.R, m, nb, d_active, b.stat + nb);
+    std::vector<double> r((size_t)nb);
+    HC(hipMemcpyAsync(r.data(), b.stat + nb, (size_t)nb * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    for (int k = 0; k < nb; k++)
+        if (!active_host || active_host[k]) out_host[k] = r[(size_t)k];
+}
+
 void Device::bcon_quad(const double *d_x, double *quad_host) {
     HC(hipSetDevice(device));
     BConDev &b = bcon_;

@@ -109,6 +109,8 @@ void launch_transpose(hipStream_t st, const double *src, double *dst, long long 
 // constraint.hip -- linear equality constraints A x = e (m <= 64 sparse rows; At, B: n x m column-major, ld n)
 // nb members (batched handles; a plain handle is one): member k's At / B at + k n m, Linv at + k m m, R at + k m cols, part at
 // + k choff[m] cols, X at + k sx, mu at + k smu, add at + k m
+// active (launch_con_ax, launch_con_apply): nb bytes on the device, nullable = all; a member whose byte is 0 is skipped by every
+// workgroup before its first load and nothing of it is written (X, R, part)
 constexpr int kConChunk = 4096;        // entries of a row of A per partial sum of A X (fixed: the sums' order depends on it)
 constexpr int kConColTile = 8;         // columns of X per workgroup of the reduction
 constexpr int kConApplyGroups = 2048;  // row-tile workgroups of the correction kernel per column block (they walk the tiles)
@@ -117,17 +119,19 @@ void launch_con_scatter(hipStream_t st, const long long *rowptr, const int *col,
 // R[r + j m] = (A X)[r, j] (- e[r]) (+ add[r]); part: choff[m] k doubles, choff = prefix sum of the rows' chunk counts
 void launch_con_ax(hipStream_t st, const long long *rowptr, const int *col, const double *val, const int *choff, int maxchunks, int m,
                    const double *X, long long ldx, int k, double *part, const double *e, const double *add, double *R, int nb = 1,
-                   long long sx = 0);
+                   long long sx = 0, const unsigned char *active = nullptr);
 void launch_con_trsm(hipStream_t st, const double *At, const double *Linv, int n, int m, double *B, int nb = 1);
 void launch_con_var(hipStream_t st, const double *B, int n, int m, double *sig, int nb = 1);
 // X <- X (+ mu) - B (Linv R); m = 0 with a mean: X += mu
 void launch_con_apply(hipStream_t st, const double *B, const double *Linv, const double *R, const double *mu, double *X, long long ldx, int n,
-                      int m, int k, int nb = 1, long long sx = 0, long long smu = 0);
+                      int m, int k, int nb = 1, long long sx = 0, long long smu = 0, const unsigned char *active = nullptr);
 // per member k < nb, one workgroup each: L_c L_c' = W_k (column-major m x m at W + k m m) -> Linv (row-major, + k m m), logdet[k],
 // cinfo[k] = 0, 1 + failing pivot, or -1 when finfo[k] != 0 (finfo nullable); a failed member gets NaN
 void launch_batch_con_chol(hipStream_t st, const double *W, int m, int nb, const long long *finfo, double *Linv, double *logdet, long long *cinfo);
 // members with cinfo[k] = -1: NaN into their nat doubles of At and nw doubles of W
 void launch_batch_con_void(hipStream_t st, const long long *cinfo, double *At, long long nat, double *W, int nw, int nb);
+// out[k] = max_r |R[k m + r]| for the members of active (nbatch bytes on the device, nullable = all)
+void launch_batch_con_maxabs(hipStream_t st, const double *R, int m, int nb, const unsigned char *active, double *out);
 // quad[k] = |Linv_k r_k|^2, r_k = m values at R + k sr
 void launch_batch_con_quad(hipStream_t st, const double *Linv, const double *R, long long sr, int m, int nb, double *quad);
 

@@ -88,6 +88,7 @@ EXPORTS = [
     "gmrfx_batch_set_prior", "gmrfx_batch_obs_set", "gmrfx_batch_obs_info", "gmrfx_batch_fisher_eval", "gmrfx_batch_fisher_eval_dev",
     "gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev",
     "gmrfx_batch_obs_set_design", "gmrfx_batch_obs_hess_map", "gmrfx_batch_obs_design_info",
+    "gmrfx_batch_obs_set_param", "gmrfx_batch_constrained_gaussian_approximation", "gmrfx_batch_constrained_gaussian_approximation_dev",
 ]
 
 
@@ -283,6 +284,9 @@ def lib(cdll=C.CDLL):
         L.gmrfx_batch_fisher_eval_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, i64, vp]
         for nm in ("gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev"):
             getattr(L, nm).argtypes = [vp, vp, i64, vp, i64, i64, i64, dbl, dbl, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_obs_set_param.argtypes = [vp, vp]
+        for nm in ("gmrfx_batch_constrained_gaussian_approximation", "gmrfx_batch_constrained_gaussian_approximation_dev"):
+            getattr(L, nm).argtypes = [vp, vp, i64, vp, i64, i64, i64, dbl, dbl, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         for nm in EXPORTS[2:]:
             if nm not in ("gmrfx_destroy", "gmrfx_device_ptr"):
                 getattr(L, nm).restype = i32

@@ -1,7 +1,7 @@
 """MI355XBatchLaplace -- a batched handle with the non-Gaussian path: one observation data set, one prior precision and one
 likelihood parameter per member, Fisher scoring and the Gaussian approximation for all members in one pass over the forest
 (include/gmrfx.h: gmrfx_batch_set_prior, gmrfx_batch_obs_set, gmrfx_batch_obs_set_design, gmrfx_batch_fisher_eval,
-gmrfx_batch_gaussian_approximation). The hyper-parameter sweep of a model with Poisson, binomial or similar observations: one Laplace
+gmrfx_batch_gaussian_approximation, gmrfx_batch_constrained_gaussian_approximation while set_constraints holds a constraint). The hyper-parameter sweep of a model with Poisson, binomial or similar observations: one Laplace
 approximation per theta_k. The observations sit on nodes (set_observations) or are seen through a sparse design matrix, eta = A x + b
 (set_design_observations: points inside mesh triangles, intercepts, group effects)."""
 from __future__ import annotations
@@ -92,6 +92,16 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         nz = np.ascontiguousarray(Ac.data, dtype=np.float64)
         check(lib().gmrfx_batch_obs_set_design(self._h, fam, yy.size, ptr(cp), ptr(rv), ptr(nz), 0, ptr(off), ptr(yy), ptr(ax), ptr(pp)), self._h)
 
+    def set_param(self, param) -> None:
+        """The members' likelihood parameters (sigma, r, phi) replaced in place (gmrfx_batch_obs_set_param): a scalar, or an array of
+        length B. The data set and, in design form, the plan stay as they are; works while a constraint is held, where
+        set_observations is refused."""
+        pp = np.asarray(param, dtype=np.float64)
+        pp = np.full(self.nbatch, float(pp)) if pp.ndim == 0 else np.ascontiguousarray(pp).reshape(-1)
+        if pp.size != self.nbatch:
+            raise ValueError("param must be a scalar or have one entry per member")
+        check(lib().gmrfx_batch_obs_set_param(self._h, ptr(pp)), self._h)
+
     def observations_hess_map(self) -> np.ndarray:
         """0-based positions into ONE member's values of the entries of A' D A, ascending (gmrfx_batch_obs_hess_map): the order of the
         Hessian values fisher_eval and gaussian_approximation return per member in design form."""
@@ -158,8 +168,27 @@ class MI355XBatchLaplace(MI355XBatchBackend):
                                                 ptr(out)), self._h)
         return out[0].copy(), out[1].copy()
 
-    def _ga_info(self, res, totals, dec, alp, info, rc):
-        return {"iterations": res[0].astype(np.int64), "converged": res[1] != 0, "alpha": res[2].copy(), "decrement": res[3].copy(),
+    def _ga_call(self, dev: bool, head, tail):
+        """the loop's entry point for the handle's state: the constrained one while set_constraints holds a constraint. Returns
+        (rc, cinfo, residual), the last two None without a constraint."""
+        L = lib()
+        if self._con_m() > 0:
+            ci, rs = np.zeros(self.nbatch, np.int64), np.full(self.nbatch, np.nan)
+            fn = L.gmrfx_batch_constrained_gaussian_approximation_dev if dev else L.gmrfx_batch_constrained_gaussian_approximation
+            return fn(*head, *tail, ptr(ci), ptr(rs)), ci, rs
+        fn = L.gmrfx_batch_gaussian_approximation_dev if dev else L.gmrfx_batch_gaussian_approximation
+        return fn(*head, *tail), None, None
+
+    @staticmethod
+    def _laplace_state(res, cinfo, refactorize_final):
+        """what laplace_terms() keeps of the last loop: energy and loglik at the modes; at_modes: a constraint was held and the handle
+        was left factorised at the modes (logdet_W is then that of the modes); failed: the members whose constraint status is not 0"""
+        return {"energy": res[8].copy(), "loglik": res[9].copy(), "at_modes": cinfo is not None and bool(refactorize_final),
+                "failed": None if cinfo is None else cinfo != 0}
+
+    def _ga_info(self, res, totals, dec, alp, info, rc, cinfo=None, residual=None):
+        con = {} if cinfo is None else {"cinfo": cinfo, "residual": residual}
+        return {**con, "iterations": res[0].astype(np.int64), "converged": res[1] != 0, "alpha": res[2].copy(), "decrement": res[3].copy(),
                 "factorizations": res[4].astype(np.int64), "solves": res[5].astype(np.int64), "merit_evaluations": res[6].astype(np.int64),
                 "frozen_finish": res[7] != 0, "energy": res[8].copy(), "loglik": res[9].copy(), "info": info.copy(),
                 "dec_trace": [dec[~np.isnan(dec[:, k]), k].copy() for k in range(self.nbatch)],
@@ -174,7 +203,10 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         and (cnt, B) in design form (the values of A' D_k A at the mode, in the order of observations_hess_map()). info holds
         per-member arrays (iterations, converged, alpha, decrement, factorizations, solves, merit_evaluations, frozen_finish, energy,
         loglik, info; dec_trace and alpha_trace as lists of arrays) and the forest-level `totals`. A member whose factorisation failed
-        does not raise: info["info"][k] > 0, X[:, k] is its last accepted iterate and H[:, k] is NaN; the others are complete."""
+        does not raise: info["info"][k] > 0, X[:, k] is its last accepted iterate and H[:, k] is NaN; the others are complete.
+        While set_constraints holds a constraint every step is projected onto A s = 0 (gmrfx_batch_constrained_gaussian_approximation;
+        x0 or the mean must satisfy A x = e) and info gains cinfo (0, 1 + the failing pivot of W_k, -1 beside a failed
+        factorisation) and residual (max |A x_k - e|, NaN for a failed member)."""
         mu, smu = self._points(mean, "mean", shared_ok=True)
         xs, sx0 = self._points(x0, "x0")
         hl = self._hess_len()
@@ -184,14 +216,14 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         dec, alp = (np.full((max_iter + 1, self.nbatch), np.nan, order="F") for _ in range(2))
         info = np.zeros(self.nbatch, np.int64)
         flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
-        rc = lib().gmrfx_batch_gaussian_approximation(self._h, ptr(mu), smu, ptr(xs), sx0, max_iter, max_linesearch_iter, float(mean_change_tol),
-                                                      float(newton_dec_tol), flags, ptr(X), self.n, ptr(H), hl, ptr(res), ptr(totals),
-                                                      ptr(dec), ptr(alp), ptr(info))
+        rc, ci, rs = self._ga_call(False, (self._h, ptr(mu), smu, ptr(xs), sx0, max_iter, max_linesearch_iter, float(mean_change_tol),
+                                           float(newton_dec_tol), flags),
+                                   (ptr(X), self.n, ptr(H), hl, ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info)))
         self._info = info.copy()
         if rc != ERR_NOT_POSDEF:
             check(rc, self._h)
-        self._laplace = (res[8].copy(), res[9].copy())
-        return X, H, self._ga_info(res, totals, dec, alp, info, rc)
+        self._laplace = self._laplace_state(res, ci, refactorize_final)
+        return X, H, self._ga_info(res, totals, dec, alp, info, rc, ci, rs)
 
     def gaussian_approximation_dev(self, d_x: int, sx: int, d_hess: int = 0, sh: int = 0, d_mu: int = 0, smu: int = 0, d_x0: int = 0, sx0: int = 0,
                                    max_iter: int = 50, mean_change_tol: float = 1e-4, newton_dec_tol: float = 1e-5, adaptive_stepsize: bool = True,
@@ -205,19 +237,26 @@ class MI355XBatchLaplace(MI355XBatchBackend):
         dec, alp = (np.full((max_iter + 1, self.nbatch), np.nan, order="F") for _ in range(2))
         info = np.zeros(self.nbatch, np.int64)
         flags = MI355XBackend._ga_flags(adaptive_stepsize, step_recovery, predictive_convergence, refactorize_final)
-        rc = lib().gmrfx_batch_gaussian_approximation_dev(self._h, d_mu or None, smu, d_x0 or None, sx0 or self.n, max_iter, max_linesearch_iter,
-                                                          float(mean_change_tol), float(newton_dec_tol), flags, d_x, sx, d_hess or None,
-                                                          sh or self._hess_len(), ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info))
+        rc, ci, rs = self._ga_call(True, (self._h, d_mu or None, smu, d_x0 or None, sx0 or self.n, max_iter, max_linesearch_iter,
+                                          float(mean_change_tol), float(newton_dec_tol), flags),
+                                   (d_x, sx, d_hess or None, sh or self._hess_len(), ptr(res), ptr(totals), ptr(dec), ptr(alp), ptr(info)))
         self._info = info.copy()
         if rc != ERR_NOT_POSDEF:
             check(rc, self._h)
-        self._laplace = (res[8].copy(), res[9].copy())
-        return self._ga_info(res, totals, dec, alp, info, rc)
+        self._laplace = self._laplace_state(res, ci, refactorize_final)
+        return self._ga_info(res, totals, dec, alp, info, rc, ci, rs)
 
     def laplace_terms(self) -> dict:
         """energy and loglik at the modes of the last gaussian_approximation and logdet of the factor in hand, per member. With
         log det Q_p,k the Laplace marginal likelihood of member k is loglik - energy' + (log det Q_p,k - logdet) / 2, where energy' is
-        the energy plus mu' Q_p,k mu / 2 (zero for a zero prior mean). After refactorize_final=True the factor is that of the mode."""
+        the energy plus mu' Q_p,k mu / 2 (zero for a zero prior mean). After refactorize_final=True the factor is that of the mode.
+        With a constraint held and refactorize_final=True the dict gains logdet_W (B,): log det(A Q_post,k^-1 A') at the modes
+        (constraint_info), NaN for the members that failed."""
         if getattr(self, "_laplace", None) is None:
             raise ValueError("laplace_terms: gaussian_approximation has not been called")
-        return {"energy": self._laplace[0].copy(), "loglik": self._laplace[1].copy(), "logdet": self.logdet()}
+        st = self._laplace
+        out = {"energy": st["energy"].copy(), "loglik": st["loglik"].copy(), "logdet": self.logdet()}
+        if st["at_modes"] and self._con_m() > 0:
+            ci = self.constraint_info(check_posdef=False)
+            out["logdet_W"] = np.where(st["failed"] | (ci["cinfo"] != 0), np.nan, ci["logdet_W"])
+        return out

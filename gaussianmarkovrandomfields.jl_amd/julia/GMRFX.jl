@@ -979,6 +979,20 @@ function set_observations!(bb::MI355XBatch, family::Integer, y::Vector{Float64},
         bb.h.ptr, Int32(family), length(y), idx, Int32(1), y, ax, param), bb.h)
     return nothing
 end
+# the members' parameters (sigma, r, phi) replaced in place (gmrfx_batch_obs_set_param): no data goes up, no plan is rebuilt; works while
+# a constraint is held, where set_observations! is refused
+function set_param!(bb::MI355XBatch, param::Vector{Float64})
+    length(param) == bb.nbatch || throw(DimensionMismatch("param must have one entry per member"))
+    GC.@preserve param check(ccall((:gmrfx_batch_obs_set_param, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, param), bb.h)
+    return nothing
+end
+# rows of the batch constraint held (0: none)
+function _con_m(bb::MI355XBatch)
+    m = Ref{Int64}(0)
+    check(ccall((:gmrfx_batch_constraints_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+        bb.h.ptr, m, C_NULL, C_NULL, C_NULL, C_NULL), bb.h)
+    return m[]
+end
 # The same data set observed through eta = A x + offset (gmrfx_batch_obs_set_design): A as Julia holds it (CSC, 1-based), nobs x n of the
 # MEMBER. Replaces the node form; call set_prior! again afterwards, it installs the members' maps. fisher_eval and gaussian_approximation
 # then return cnt Hessian values per member, in the order of observations_hess_map(bb).
@@ -1034,7 +1048,10 @@ function fisher_eval(bb::MI355XBatch, X::Matrix{Float64}; mean::Union{Nothing, M
 end
 # The Gaussian approximation of every member: (X, H, result 10 x nbatch, totals, dec_trace, alpha_trace, info). A member whose
 # factorisation failed does not throw: info[k] > 0, X[:, k] its last accepted iterate, H[:, k] NaN. H: n x nbatch in node form, cnt x nbatch
-# in design form.
+# in design form. The tuple always has nine entries: the last two are cinfo and residual, `nothing` each without a constraint (callers that
+# destructure the first seven are unaffected). While set_constraints! holds a constraint the loop is
+# gmrfx_batch_constrained_gaussian_approximation (every step projected onto A s = 0): cinfo is 0, 1 + the failing pivot of W_k, or -1
+# beside a failed factorisation; residual is max |A x_k - e| per member, NaN for a failed one.
 function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Float64}} = nothing, x0::Union{Nothing, Matrix{Float64}} = nothing,
                                 max_iter::Integer = 50, max_linesearch_iter::Integer = 10, mean_change_tol::Real = 1e-4,
                                 newton_dec_tol::Real = 1e-5, flags::Integer = 7)
@@ -1047,6 +1064,17 @@ function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Flo
     inf = zeros(Int64, bb.nbatch)
     mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
     xs = x0 === nothing ? Ptr{Float64}(C_NULL) : pointer(x0)
+    if _con_m(bb) > 0
+        cinf = zeros(Int64, bb.nbatch); res = fill(NaN, bb.nbatch)
+        rc = GC.@preserve mean x0 X H result totals dec alp inf cinf res ccall((:gmrfx_batch_constrained_gaussian_approximation, LIB), Int32,
+            (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+             Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+            bb.h.ptr, mu, bb.n, xs, bb.n, Int64(max_iter), Int64(max_linesearch_iter), Float64(mean_change_tol), Float64(newton_dec_tol),
+            Int32(flags), X, bb.n, H, hl, result, totals, dec, alp, inf, cinf, res)
+        bb.info .= inf
+        rc == 5 || check(rc, bb.h)          # GMRFX_ERR_NOT_POSDEF: reported per member in info and cinfo
+        return X, H, result, totals, dec, alp, inf, cinf, res
+    end
     rc = GC.@preserve mean x0 X H result totals dec alp inf ccall((:gmrfx_batch_gaussian_approximation, LIB), Int32,
         (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Int64, Int64, Float64, Float64, Int32, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
@@ -1054,7 +1082,7 @@ function gaussian_approximation(bb::MI355XBatch; mean::Union{Nothing, Matrix{Flo
         Int32(flags), X, bb.n, H, hl, result, totals, dec, alp, inf)
     bb.info .= inf
     rc == 5 || check(rc, bb.h)          # GMRFX_ERR_NOT_POSDEF: reported per member in info
-    return X, H, result, totals, dec, alp, inf
+    return X, H, result, totals, dec, alp, inf, nothing, nothing
 end
 
 # deepcopy(bb) (Newton loops copy their caches) reaches the owning Handle: a copy of a handle is a clone of the native one

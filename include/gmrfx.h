@@ -772,21 +772,42 @@ int32_t gmrfx_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, co
  *                            stopped member's values no longer change, so without flag bit 3 it ends holding the factor of its own last
  *                            iterate; with it, one more forest factorisation at H(x_k) covers every member that did not fail. Design
  *                            form: hess has cnt entries per member (sh >= cnt); a plan with cnt = 0 runs with Q_post = Q_p.
+ *   gmrfx_batch_obs_set_param    replaces the members' parameters (sigma, r, phi) of the likelihood in place, in node or design form: the
+ *                            validation of gmrfx_batch_obs_set on every param[k], loglik_const per member in long double from the data
+ *                            the handle keeps. No data goes up and no plan is rebuilt; a following evaluation has the bits it has after
+ *                            a full gmrfx_batch_obs_set with the same parameters. Works with a batch constraint held and on symbolic_only
+ *                            handles. INVALID_ARG without a likelihood or with a null param.
+ *   gmrfx_batch_constrained_gaussian_approximation   the same loop under the batch constraint A x = e of gmrfx_batch_constraints_set
+ *                            (Besag, RW1, RW2, BYM2 under sum-to-zero): every step is projected, s_k <- s_k - At_k W_k^-1 (A s_k), where
+ *                            the plain loop projects it under gmrfx_constraints_set -- once per iterate and once per chord step of the
+ *                            frozen finish -- with At_k, W_k refreshed per iterate for all members in one forest solve. The arguments of
+ *                            gmrfx_batch_gaussian_approximation, then cinfo (nbatch, nullable): 0, 1 + the failing pivot of W_k, or -1
+ *                            beside a failed factorisation; residual (host, nbatch, nullable): max_r |(A x_k - e)_r| of the members that
+ *                            did not fail, NaN for the others. The iterates keep A x_k = A x0_k, so x0 (or mu) must satisfy the
+ *                            constraint for the modes to. A member whose W_k fails stops alone like one whose factorisation fails: x_k its
+ *                            last accepted iterate, everybody else complete; GMRFX_ERR_NOT_POSDEF when any member failed either way.
+ *                            INVALID_ARG when no batch constraint is held (call gmrfx_batch_gaussian_approximation) or a plain one is,
+ *                            then every refusal of the unconstrained call. gmrfx_batch_set_prior accepts a handle holding a batch
+ *                            constraint; gmrfx_batch_obs_set[_design], gmrfx_batch_fisher_eval and gmrfx_batch_gaussian_approximation[_dev]
+ *                            keep refusing one: the unconstrained loop would silently ignore the constraint.
  * No atomics; bit-reproducible; the host and the _dev forms agree bit for bit; a member's results do not depend on the other members.
  * Device memory: the data set (17 n bytes), the member's row structure, 6 n nbatch doubles of work vectors on the first loop. Design
  * form: the plan's tables and the data set once, (2 nobs + ncc + nct + design blocks) nbatch doubles of evaluation work (ncc + nct: the
  * chunks of the columns and term lists longer than 512 entries), (5 n + cnt) nbatch doubles of work vectors on the first loop.
  * Errors (INVALID_ARG with a message, nothing changed): a sharded handle, more than 65535 members, a constraint set (gmrfx_constraints_set
- * or gmrfx_batch_constraints_set), a plain handle holding the design form of gmrfx_obs_set_design, null x / out / result, a stride below n
+ * everywhere; gmrfx_batch_constraints_set for gmrfx_batch_obs_set[_design], gmrfx_batch_fisher_eval and the unconstrained loop; none held
+ * for the constrained loop), a plain handle holding the design form of gmrfx_obs_set_design, null x / out / result, a stride below n
  * (smu = 0 excepted; hess: below cnt in design form), no likelihood, no prior, a prior whose map is not the likelihood's.
  * GMRFX_ERR_NO_DEVICE for symbolic_only handles after these checks.
- * LIMITS: no constraints, no batched pullback or predictive scores (left to follow-ups); nbatch <= 65535; n < 2^31. */
+ * LIMITS: constraints through gmrfx_batch_constrained_gaussian_approximation only (one A and e for all members, m <= 64 rows); no batched
+ * pullback or predictive scores (left to follow-ups); nbatch <= 65535; n < 2^31. */
 int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval /* nnz x nbatch */);
 int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *indices /* nobs, nullable */, int32_t index_base,
                             const double *y /* nobs */, const double *aux /* nobs, nullable */, const double *param /* nbatch */);
 int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, const int64_t *colptr /* n + 1 */, const int64_t *rowval,
                                    const double *nzval, int32_t index_base, const double *offset /* nobs, nullable */,
                                    const double *y /* nobs */, const double *aux /* nobs, nullable */, const double *param /* nbatch */);
+int32_t gmrfx_batch_obs_set_param(gmrfx_handle *h, const double *param /* nbatch */);
 int32_t gmrfx_batch_obs_hess_map(const gmrfx_handle *h, int64_t *map /* nullable; cnt values, index base 0 */, int64_t cap, int64_t *cnt);
 int32_t gmrfx_batch_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms);
 int32_t gmrfx_batch_obs_info(const gmrfx_handle *h, int32_t *family, int64_t *nobs, double *loglik_const /* nbatch */);
@@ -806,6 +827,18 @@ int32_t gmrfx_batch_gaussian_approximation_dev(gmrfx_handle *h, const double *d_
                                                int32_t flags, double *d_x, int64_t sx, double *d_hess, int64_t sh, double *result /* host */,
                                                double *totals /* host */, double *dec_trace /* host */, double *alpha_trace /* host */,
                                                int64_t *info);
+int32_t gmrfx_batch_constrained_gaussian_approximation(gmrfx_handle *h, const double *mu /* nullable */, int64_t smu, const double *x0 /* nullable */,
+                                                       int64_t sx0, int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                                       double newton_dec_tol, int32_t flags, double *x, int64_t sx, double *hess /* nullable */,
+                                                       int64_t sh, double *result /* host, 10 x nbatch */, double *totals /* host, 3, nullable */,
+                                                       double *dec_trace /* host, (max_iter + 1) x nbatch, nullable */, double *alpha_trace /* same */,
+                                                       int64_t *info /* nbatch, nullable */, int64_t *cinfo /* nbatch, nullable */,
+                                                       double *residual /* host, nbatch, nullable */);
+int32_t gmrfx_batch_constrained_gaussian_approximation_dev(gmrfx_handle *h, const double *d_mu, int64_t smu, const double *d_x0, int64_t sx0,
+                                                           int64_t max_iter, int64_t max_linesearch_iter, double mean_change_tol,
+                                                           double newton_dec_tol, int32_t flags, double *d_x, int64_t sx, double *d_hess, int64_t sh,
+                                                           double *result /* host */, double *totals /* host */, double *dec_trace /* host */,
+                                                           double *alpha_trace /* host */, int64_t *info, int64_t *cinfo, double *residual /* host */);
 
 /* ---- The pullback of the Gaussian approximation (implicit-function rule) -------------------------------------------------------------
  * Reverse-mode rule of gaussian_approximation(prior, obs_lik) at its mode x (src/workspace/autodiff.jl:140-202; for plain GMRFs

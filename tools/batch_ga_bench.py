@@ -17,7 +17,11 @@ N(0, 1 / 0.01) prior, every row of A observes it with weight 1 (n + 1 nodes; the
 zeros; the dense intercept column is pinned to the end of the elimination order, PinDenseColumns). gmrfx_batch_obs_set_design once, then
 gmrfx_batch_set_prior + gmrfx_batch_gaussian_approximation_dev per sweep, against ONE plain handle whose design likelihood is set once
 (the plan does not depend on theta) and which takes gmrfx_set_prior + gmrfx_gaussian_approximation_dev per member.
-usage: tools/batch_ga_bench.py [--design] [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
+--constraint: a Besag model on a g x g torus plus 1e-6 I under a sum-to-zero constraint, Poisson counts on every
+node, B = 50 precisions. gmrfx_batch_set_prior + gmrfx_batch_constrained_gaussian_approximation_dev per sweep on a batched handle holding
+the constraint, against the same 50 approximations on ONE plain handle under gmrfx_constraints_set (gmrfx_set_prior +
+gmrfx_gaussian_approximation_dev per member; the data set goes in once). Output: profiles/batch_ga_con_bench.json by default.
+usage: tools/batch_ga_bench.py [--design | --constraint] [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
 import argparse
 import json
 import os
@@ -134,6 +138,80 @@ def design(a):
     return row
 
 
+def torus_besag(g, eps=1e-6):
+    """graph Laplacian of the g x g periodic lattice + eps I (the intrinsic CAR model of the reference's besag.jl, regularised)"""
+    idx = np.arange(g * g).reshape(g, g)
+    r = np.concatenate([idx.ravel(), idx.ravel()])
+    c = np.concatenate([np.roll(idx, -1, axis=0).ravel(), np.roll(idx, -1, axis=1).ravel()])
+    W = sp.coo_matrix((np.ones(len(r)), (r, c)), shape=(g * g, g * g))
+    W = (W + W.T).tocsc()
+    Q = sp.csc_matrix(sp.diags(np.asarray(W.sum(axis=1)).ravel()) - W + eps * sp.identity(g * g))
+    Q.sort_indices()
+    return Q
+
+
+def constraint(a):
+    B, g = a.batch, a.grid
+    M = torus_besag(g)
+    n = M.shape[0]
+    rng = np.random.default_rng(g)
+    taus = np.exp(rng.uniform(np.log(0.2), np.log(20.0), B))
+    NZ = np.asfortranarray(np.stack([t * M.data for t in taus], axis=1))
+    z = rng.standard_normal(n)
+    rate = 20.0
+    y = rng.poisson(rate * np.exp(z - z.mean())).astype(float)
+    aux = np.full(n, np.log(rate))
+    A, e = sp.csr_matrix(np.ones((1, n))), np.zeros(1)
+    dpos = diag_positions(M)
+    kw = dict(refactorize_final=True)
+    pts = np.stack(np.meshgrid(np.arange(g, dtype=float), np.arange(g, dtype=float), indexing="ij"), axis=-1).reshape(n, 2)
+    bb = gmrfx.MI355XBatchLaplace(M, B, coords=pts, device=0)
+    bb.set_observations("poisson", y, aux=aux, param=0.0)
+    bb.set_constraints(A, e)
+    perm = bb.ordering_permutation()
+    dX = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    dX0 = torch.zeros(n * B, dtype=torch.float64, device="cuda:0")
+    torch.cuda.synchronize()
+    res = {}
+
+    def batched():
+        bb.set_prior(NZ)
+        res["b"] = bb.gaussian_approximation_dev(dX.data_ptr(), n, d_x0=dX0.data_ptr(), sx0=n, **kw)
+    t_b = timed(batched, a.reps, a.warmup)
+    Xb = dX.cpu().numpy().reshape(B, n).copy()
+
+    plain = gmrfx.MI355XBackend(M, ordering=perm, device=0, factorize=False)
+    plain.set_observations("poisson", y, aux=aux)
+    plain.set_constraints(A, e)
+    dx = torch.empty(n * B, dtype=torch.float64, device="cuda:0")
+    its = np.zeros(B, np.int64)
+
+    def sequential():
+        for k in range(B):
+            plain.set_prior(NZ[:, k], dpos)
+            i = plain.gaussian_approximation_dev(dx.data_ptr() + 8 * k * n, d_x0=dX0.data_ptr(), **kw)
+            its[k] = i["iterations"]
+    t_s = timed(sequential, a.reps, a.warmup)
+    Xs = dx.cpu().numpy().reshape(B, n).copy()
+    plain.close()
+
+    ib = res["b"]
+    assert np.array_equal(ib["iterations"], its), (ib["iterations"], its)
+    assert (ib["cinfo"] == 0).all() and (ib["info"] == 0).all()
+    assert t_b["median_ms"] <= t_s["median_ms"], "the batched constrained route is slower than the plain route of the same run"
+    row = {"tool": "tools/batch_ga_bench.py --constraint", "device": torch.cuda.get_device_name(0), "source_tree_hash": _lib.source_tree_hash(),
+           "n": n, "grid": g, "B": B, "m": 1, "family": "poisson", "reps": a.reps, "warmup": a.warmup,
+           "batched_constrained": t_b, "one_plain_handle_sequential": t_s,
+           "ms_per_member_batched": t_b["median_ms"] / B, "ms_per_member_sequential": t_s["median_ms"] / B,
+           "speedup_vs_sequential": t_s["median_ms"] / t_b["median_ms"],
+           "iterations": ib["iterations"].tolist(), "iteration_counts_agree": True, "converged": bool(ib["converged"].all()), "totals": ib["totals"],
+           "sum_member_factorizations": int(ib["factorizations"].sum()), "max_residual": float(np.nanmax(ib["residual"])),
+           "max_abs_mode_diff": float(np.abs(Xb - Xs).max())}
+    print(json.dumps(row), flush=True)
+    bb.close()
+    return row
+
+
 def diag_positions(Q):
     out = np.empty(Q.shape[0], np.int64)
     for j in range(Q.shape[0]):
@@ -163,10 +241,13 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--design", action="store_true")
+    ap.add_argument("--constraint", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    if a.design:
-        row = design(a)
+    if a.design or a.constraint:
+        row = constraint(a) if a.constraint else design(a)
+        if a.constraint and a.out is None:
+            a.out = os.path.join(ROOT, "profiles", "batch_ga_con_bench.json")
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as f:
