@@ -277,7 +277,7 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
     """S: dense symmetric prior precision, Ad: dense design matrix (nobs x n), A: dense constraint matrix or None. Returns the dict of
     fisher_ref.newton_loop plus `margins`: (kind, distance from the threshold, scale) of every comparison -- a merit against obj_accept
     with the merit's noise floor 64 eps max(|energy| + |loglik|, 1) as scale, the convergence and look-ahead tests with their tolerance
-    -- and hess_dense = A' D A at the mode."""
+    --, tiny: (alpha |step|_inf, dec_tol / 1000) of every tiny-step comparison, rounds as in fisher_ref.newton_loop, and hess_dense = A' D A at the mode."""
     n = S.shape[0]
     S, Ad = np.asarray(S, dtype), np.asarray(Ad, dtype)
     mu = np.zeros(n, dtype) if mu is None else np.asarray(mu, dtype)
@@ -286,7 +286,7 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
     c = dtype(ref.loglik_const(obs.family, obs.y, obs.aux, obs.param)[0])
     A = None if A is None else np.asarray(A, dtype)
     cnt = {"fact": 0, "solve": 0, "merit": 0}
-    events, margins, floor = [], [], [0.0]
+    events, margins, tiny, floor, rounds = [], [], [], [0.0], []
 
     def point(x):
         g, d, lo, _ = ref.pointwise(obs.family, Ad @ x + bb, obs.y, obs.aux, obs.param, dtype)
@@ -313,13 +313,14 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
         return {"x": x, "hess_dense": point(x)[1], "iterations": iters, "converged": converged, "alpha": float(alpha), "dec": float(dec),
                 "factorizations": cnt["fact"], "solves": cnt["solve"], "merit_evaluations": cnt["merit"], "frozen": frozen,
                 "dec_trace": np.array(dec_trace, dtype), "alpha_trace": np.array(alpha_trace, np.float64), "events": events,
-                "margins": margins, "Qk": Qk}
+                "margins": margins, "tiny": tiny, "rounds": rounds, "Qk": Qk}
 
     x_k = mu.copy() if x0 is None else np.asarray(x0, dtype).copy()
     alpha, dec_prev, dec = dtype(1), dtype(0), dtype("nan")
     dec_trace, alpha_trace = [], []
     Qk = S
     for it in range(1, max_iter + 1):
+        rounds.append([0, 0, 0])
         g, H, ll_k = point(x_k)
         en_k = energy(x_k)
         Qk = S - H
@@ -332,6 +333,7 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
             obj_accept = (en_k - ll_k) + 64 * EPS * max(abs(en_k) + abs(ll_k), 1)
             done = False
             if retry_full and alpha < 1:
+                rounds[-1][0] = 1
                 x_full = x_k - step
                 if merit(x_full, obj_accept) <= obj_accept:
                     x_new, alpha, done = x_full, dtype(1), True
@@ -342,12 +344,14 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
                 accept = False
                 x_new = x_k - alpha * step
                 for _ in range(max_ls):
+                    rounds[-1][1] += 1
                     cand = x_k - alpha * step
                     if merit(cand, obj_accept) <= obj_accept:
                         x_new, alpha, accept = cand, np.sqrt(alpha), True
                         break
                     alpha = alpha * dtype(0.1)
                     events.append("backtrack")
+                    tiny.append((float(alpha * np.abs(step).max()), dec_tol / 1000))
                     if alpha * np.abs(step).max() < dec_tol / 1000:
                         x_new, accept = cand, True
                         events.append("tiny_step_exit")
@@ -373,6 +377,7 @@ def newton_loop(S, mu, obs, Ad, b=None, x0=None, A=None, dtype=np.float64, max_i
                 events.append("lookahead_fire")
                 x, ok = x_new.copy(), True
                 for j in (1, 2, 3):
+                    rounds[-1][2] += 1
                     gs = (S @ x - h) - point(x)[0]
                     st = solve_step(Qk, gs)
                     if j == 1:

@@ -248,8 +248,10 @@ def _solve(Qk, B):
 def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_ls=10, mean_tol=1e-4, dec_tol=1e-5, adaptive=True,
                 retry_full=True, predictive=True):
     """S: dense symmetric prior precision. Returns a dict: x (the mode), hess, iterations, converged, alpha, dec, factorizations, solves,
-    merit_evaluations, frozen, dec_trace, alpha_trace, events (the branches taken, in order). The merit's noise floor uses the float64
-    eps in every dtype: the long-double run follows the decisions a float64 loop is meant to take, with exact-er numbers."""
+    merit_evaluations, frozen, dec_trace, alpha_trace, events (the branches taken, in order), margins ((kind, distance from the threshold,
+    scale) of every merit comparison, as tests/fisher_design_ref.py: newton_loop records them) and tiny ((alpha |step|_inf, dec_tol / 1000)
+    of every tiny-step comparison) and rounds ([full-step retry 0 / 1, probes of the search, chord solves] per iterate). The merit's noise floor uses the float64 eps in every dtype: the long-double run follows the
+    decisions a float64 loop is meant to take, with exact-er numbers."""
     n = S.shape[0]
     S = np.asarray(S, dtype)
     mu = np.zeros(n, dtype) if mu is None else np.asarray(mu, dtype)
@@ -258,7 +260,7 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
     c = dtype(loglik_const(obs.family, obs.y, obs.aux, obs.param)[0])
     A = None if A is None else np.asarray(A, dtype)
     cnt = {"fact": 0, "solve": 0, "merit": 0}
-    events = []
+    events, margins, tiny, floor, rounds = [], [], [], [0.0], []
 
     def point(x):
         g, d = np.zeros(n, dtype), np.zeros(n, dtype)
@@ -269,9 +271,11 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
     def energy(x):
         return x @ (S @ x) / 2 - x @ h
 
-    def merit(x):
+    def merit(x, accept):
         cnt["merit"] += 1
-        return energy(x) - point(x)[2]
+        m = energy(x) - point(x)[2]
+        margins.append(("merit", float(abs(m - accept)), floor[0]))
+        return m
 
     def solve_step(Qk, rhs):
         cnt["solve"] += 1
@@ -287,12 +291,14 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
     def result(x, iters, converged, frozen):
         return {"x": x, "hess": point(x)[1], "iterations": iters, "converged": converged, "alpha": float(alpha), "dec": float(dec),
                 "factorizations": cnt["fact"], "solves": cnt["solve"], "merit_evaluations": cnt["merit"], "frozen": frozen,
-                "dec_trace": np.array(dec_trace, dtype), "alpha_trace": np.array(alpha_trace, np.float64), "events": events}
+                "dec_trace": np.array(dec_trace, dtype), "alpha_trace": np.array(alpha_trace, np.float64), "events": events,
+                "margins": margins, "tiny": tiny, "rounds": rounds}
 
     x_k = mu.copy() if x0 is None else np.asarray(x0, dtype).copy()
     alpha, dec_prev, dec = dtype(1), dtype(0), dtype("nan")
     dec_trace, alpha_trace = [], []
     for it in range(1, max_iter + 1):
+        rounds.append([0, 0, 0])
         g, d, ll_k = point(x_k)
         en_k = energy(x_k)
         Qk = S - np.diag(d)
@@ -301,11 +307,13 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
         step = solve_step(Qk, score)
         alpha_prev = alpha
         if adaptive:
+            floor[0] = float(64 * EPS * max(abs(en_k) + abs(ll_k), 1))
             obj_accept = (en_k - ll_k) + 64 * EPS * max(abs(en_k) + abs(ll_k), 1)
             done = False
             if retry_full and alpha < 1:
+                rounds[-1][0] = 1
                 x_full = x_k - step
-                if merit(x_full) <= obj_accept:
+                if merit(x_full, obj_accept) <= obj_accept:
                     x_new, alpha, done = x_full, dtype(1), True
                     events.append("retry_full_accept")
                 else:
@@ -314,12 +322,14 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
                 accept = False
                 x_new = x_k - alpha * step
                 for _ in range(max_ls):
+                    rounds[-1][1] += 1
                     cand = x_k - alpha * step
-                    if merit(cand) <= obj_accept:
+                    if merit(cand, obj_accept) <= obj_accept:
                         x_new, alpha, accept = cand, np.sqrt(alpha), True
                         break
                     alpha = alpha * dtype(0.1)
                     events.append("backtrack")
+                    tiny.append((float(alpha * np.abs(step).max()), dec_tol / 1000))
                     if alpha * np.abs(step).max() < dec_tol / 1000:
                         x_new, accept = cand, True
                         events.append("tiny_step_exit")
@@ -340,6 +350,7 @@ def newton_loop(S, mu, obs, x0=None, A=None, dtype=np.float64, max_iter=50, max_
             events.append("lookahead_fire")
             x, ok = x_new.copy(), True
             for j in (1, 2, 3):
+                rounds[-1][2] += 1
                 gs = neg_score(x)
                 st = solve_step(Qk, gs)
                 if j == 1:
