@@ -27,6 +27,27 @@ static void bf_check_stride(const std::string &who, const char *what, int64_t s,
     if (s < n) throw std::invalid_argument(who + what + ": member stride smaller than " + len);
 }
 
+// nobs = 0 of either form: the batch likelihood is dropped, on the device and on the host
+static int32_t bf_clear(gmrfx_handle *h) {
+    if (h->D) h->D->bobs_set(h->rsym, BObsHost{});
+    h->bobs = BObsHost{};
+    return GMRFX_OK;
+}
+// Every check of gmrfx_obs_set (or gmrfx_obs_set_design) on the values, member by member, with the member's loglik_const in long double
+// each; o (its family and nobs set) takes the parameters, the constants and the one data set.
+static void bf_fill_members(BObsHost &o, const std::string &who, int64_t nb, const double *y, const double *aux, const double *param) {
+    o.param.resize((size_t)nb); o.loglik_const.resize((size_t)nb);
+    for (int64_t k = 0; k < nb; k++) {
+        const std::string wk = who + "member " + std::to_string(k) + ": ";
+        obs_check_operands(wk, o.family, y, aux, param[k]);
+        ObsHost ok;
+        obs_fill_values(ok, wk, o.family, o.nobs, y, aux, param[k]);
+        o.param[(size_t)k] = param[k];
+        o.loglik_const[(size_t)k] = ok.loglik_const;
+        if (k == nb - 1) { o.y = std::move(ok.y); o.aux = std::move(ok.aux); }
+    }
+}
+
 extern "C" int32_t gmrfx_batch_set_prior(gmrfx_handle *h, const double *prior_nzval) {
     return guarded(h, [&]() -> int32_t {
         const std::string who = "batch_set_prior: ";
@@ -55,11 +76,7 @@ extern "C" int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t 
         const std::string who = "batch_obs_set: ";
         bf_check_handle(h, who);
         const int64_t n = bf_n(h), nb = h->nbatch;
-        if (nobs == 0) {
-            if (h->D) h->D->bobs_set(h->rsym, BObsHost{});
-            h->bobs = BObsHost{};
-            return GMRFX_OK;
-        }
+        if (nobs == 0) return bf_clear(h);
         obs_check_family(who, family);
         if (nobs < 0 || nobs > n) throw std::invalid_argument(who + "nobs outside [0, n]");
         check_index_base(index_base, who.c_str());
@@ -76,16 +93,7 @@ extern "C" int32_t gmrfx_batch_obs_set(gmrfx_handle *h, int32_t family, int64_t 
             o.idx[(size_t)k] = i;
         }
         o.family = family; o.nobs = nobs;
-        o.param.resize((size_t)nb); o.loglik_const.resize((size_t)nb);
-        for (int64_t k = 0; k < nb; k++) {          // every check of gmrfx_obs_set, member by member; loglik_const in long double each
-            const std::string wk = who + "member " + std::to_string(k) + ": ";
-            obs_check_operands(wk, family, y, aux, param[k]);
-            ObsHost ok;
-            obs_fill_values(ok, wk, family, nobs, y, aux, param[k]);
-            o.param[(size_t)k] = param[k];
-            o.loglik_const[(size_t)k] = ok.loglik_const;
-            if (k == nb - 1) { o.y = std::move(ok.y); o.aux = std::move(ok.aux); }
-        }
+        bf_fill_members(o, who, nb, y, aux, param);
         if (h->D) {
             bf_ensure_batch(h);
             if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
@@ -106,11 +114,7 @@ extern "C" int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, i
         const std::string who = "batch_obs_set_design: ";
         bf_check_handle(h, who);
         const int64_t n = bf_n(h), nb = h->nbatch;
-        if (nobs == 0) {
-            if (h->D) h->D->bobs_set(h->rsym, BObsHost{});
-            h->bobs = BObsHost{};
-            return GMRFX_OK;
-        }
+        if (nobs == 0) return bf_clear(h);
         obs_check_family(who, family);
         if (nobs < 0) throw std::invalid_argument(who + "nobs is negative");
         check_index_base(index_base, who.c_str());
@@ -121,16 +125,7 @@ extern "C" int32_t gmrfx_batch_obs_set_design(gmrfx_handle *h, int32_t family, i
         if (!param) throw std::invalid_argument(who + "param is null (one value per member)");
         BObsHost o;
         o.family = family; o.nobs = nobs;
-        o.param.resize((size_t)nb); o.loglik_const.resize((size_t)nb);
-        for (int64_t k = 0; k < nb; k++) {          // every check of gmrfx_obs_set_design on the values, member by member
-            const std::string wk = who + "member " + std::to_string(k) + ": ";
-            obs_check_operands(wk, family, y, aux, param[k]);
-            ObsHost ok;
-            obs_fill_values(ok, wk, family, nobs, y, aux, param[k]);
-            o.param[(size_t)k] = param[k];
-            o.loglik_const[(size_t)k] = ok.loglik_const;
-            if (k == nb - 1) { o.y = std::move(ok.y); o.aux = std::move(ok.aux); }
-        }
+        bf_fill_members(o, who, nb, y, aux, param);
         if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
         auto plan = std::make_shared<DesignPlan>();
         design_build_plan(h->rsym, n, bf_nnz(h), nobs, colptr, rowval, nzval, index_base, offset, *plan);

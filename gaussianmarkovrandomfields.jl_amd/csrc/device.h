@@ -11,6 +11,7 @@
 
 #include "device_plan.h"
 #include "fisher_design_plan.h"
+#include "ga_rules.h"
 #include "rbmc_plan.h"
 #include "resource.h"
 
@@ -94,15 +95,13 @@ struct ObsByNode { std::vector<double> y, aux; std::vector<unsigned char> mask; 
 ObsByNode obs_by_node(size_t n, long long nobs, const std::vector<long long> &idx, const std::vector<double> &y, const std::vector<double> &aux);
 // the log r the negative binomial's stable forms take beside r (fisher_point.h); the other families do not read it
 inline double fisher_logparam(int family, double param) { return family == 4 ? std::log(param) : 0.0; }
-// _merit_atol (condition/gaussian_approximation.jl:245): the line search's slack on the merit, for both loops
-inline double merit_atol(double scale) { return 64.0 * 2.220446049250313e-16 * std::max(scale, 1.0); }
 
 constexpr long long kNoPpa = (long long)0x8000000000000000ull;
 struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoPpa; };
 // Where one sweep pass runs: a stream and the right-hand-side buffers it works in (X: the pass's columns in elimination order,
 // X2: y of the big fronts, W: the update vectors). The sweep drivers take it as a parameter; nothing selects a lane by state.
 struct SweepLane { hipStream_t st; double *X, *X2, *W; };
-constexpr size_t kTableMinBytes = 8;      // the constraint / RBMC tables' size rule: 8 bytes at least (+ the 16 of slack)
+struct FisherMembers;      // (kernels.h)
 class Device {
 public:
     Device() = default;
@@ -269,13 +268,12 @@ public:
     // Design form (device_fisher.cpp, fisher_design.hip): eta = A x + b, score = (Q_p x - h) - A' g(eta), d_hess = the hess_len() values
     // sum_t w_t d(eta_{i_t}) of A' D A in map order; needs set_prior with exactly the map of the plan.
     void fisher_eval(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host);
-    // The Fisher-scoring loop of the reference (src/workspace/gaussian_approximation.jl:230-313 with _ga_line_search, _predict_converged
-    // and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409), control flow on the host, every vector in HBM.
-    // flags: bit 0 adaptive_stepsize, 1 retry_full, 2 predictive_convergence, 3 leave the handle factorised at Q_prior - H(x_final).
+    // The Fisher-scoring loop of the reference (src/workspace/gaussian_approximation.jl:230-313), control flow on the host, every vector
+    // in HBM; its decisions (_ga_line_search, _predict_converged, _frozen_finish) are the functions of ga_rules.h, GaOpts with its flags too.
     // d_x0 nullable (= mu, or 0); d_x: n out; d_hess: n out, nullable. result[8], dec_trace / alpha_trace (max_iter + 1, nullable): host.
     // Returns 0, 1 when a factorisation failed (*info = 1 + the failing step; d_x = the last accepted iterate), 2 when the
     // constraint's W = A Q^-1 A' did.
-    struct GaOpts { long long max_iter, max_ls; double mean_tol, dec_tol; int flags; };
+    using GaOpts = gmrfx::GaOpts;
     int gaussian_approximation(const RbmcSym &sym, const double *d_mu, const double *d_x0, const GaOpts &o, double *d_x, double *d_hess,
                                double *result, double *dec_trace, double *alpha_trace, long long *info);
 
@@ -609,44 +607,57 @@ private:
         int ncc = 0, nct = 0;
     };
     void design_upload(const std::shared_ptr<const DesignPlan> &plan, DesignTables &t);
-    // Fisher-scoring state: the likelihood by node (y, aux, mask: n each), the evaluation's partial sums (2 per workgroup) and results
+    // Fisher-scoring state, ONE data set for `members` members (fisher_build). Node form: y, aux, mask by node (n each), part = one
+    // (energy, loglik) pair per workgroup and member. Design form: y / aux by observation (mask unused), the tables above once, and per
+    // member g, d (nobs each), the chunk sums cpart (ncc + nct), the energy partials (part: design_blocks(n)) and the loglik partials
+    // (lpart: design_blocks(nobs)). Either form: spart = the loop's reductions (4 per chunk and member), out = 6 per member (2 of every
+    // member's evaluation, then 4 of every member's reductions) with its pinned copy, work = the loop's five vectors and the Hessian
+    // (5 n + hess_len per member, on first use).
+    // The handle keeps two, independent of each other. fisher_ (gmrfx_obs_set): one member, its parameter and the log by value, the
+    // rows of sym_rows_. bfisher_ (gmrfx_batch_obs_set; a plain handle's is a batch of one): the members' parameters and their logs on
+    // the device, the member's own row structure (the forest's first n rows), nnz = the member's stride in the priors' values, and the
+    // loop's control words (ctl: `members` step lengths, then `members` mask bytes) with their pinned copy.
     struct FisherDev : DesignTables {
-        DevBuf<double> y, aux, part, out, spart, work;      // spart: the loop's reductions; work: its six vectors (on first use)
+        int family = 0, members = 1, n = 0;                  // n: a member's nodes
+        double param = 0, logparam = 0;                    // by value (fisher_); 0 where param_k / logparam_k hold one per member
+        long long nnz = 0;
+        std::vector<double> loglik_const;                    // one per member
+        DevBuf<double> y, aux, part, out, spart, work;
         DevBuf<unsigned char> mask;
-        PinnedBuf<double> h_out;                             // 2 of the evaluation, then 4 of the reductions
-        int family = 0;
-        double param = 0, loglik_const = 0;
-        // design form: y / aux by observation (mask unused), the tables above, g and d by observation, the chunk and loglik partial sums
+        PinnedBuf<double> h_out;
         DevBuf<double> g, d, lpart, cpart;
-    } fisher_;
-    // the same for the members of a batch: ONE data set by node and the member's row structure (the forest's first n_member rows), the
-    // members' parameters and their logs, the partial sums (2 per workgroup and 4 per chunk, per member), the results (6 per member:
-    // 2 of the evaluation, then 4 of the reductions) with their pinned copy, the loop's control words (nbatch step lengths, then
-    // nbatch mask bytes) with theirs, and the loop's six work vectors of the forest's length (on first use)
-    // Design form (gmrfx_batch_obs_set_design): y / aux by observation (mask unused), the tables once, and per member g, d (nobs each),
-    // the chunk sums (ncc + nct), the energy partials (part: design_blocks(n_member)) and the loglik partials (lpart: design_blocks(nobs));
-    // the Hessian has cnt entries per member and the work area 5 n nbatch + cnt nbatch doubles.
-    struct BFisherDev : DesignTables {
-        DevBuf<double> y, aux, param, logparam, part, out, spart, work, ctl;
-        DevBuf<unsigned char> mask;
+        DevBuf<double> param_k, logparam_k, ctl;
         DevBuf<long long> rp;
         DevBuf<int> col, pos;
-        PinnedBuf<double> h_out, h_ctl;
-        std::vector<double> loglik_const;
-        int family = 0;
-        DevBuf<double> g, d, lpart, cpart;
-    } bfisher_;
-    void bobs_set_design(const BObsHost &o, BFisherDev &f);      // (what the design form adds to bobs_set)
+        PinnedBuf<double> h_ctl;
+    } fisher_, bfisher_;
+    // what a likelihood is built from: the data by node, or by observation with the plan (design non-null), and one parameter with its
+    // loglik_const per member. rows non-null: the batch slot (parameters, rows and control words on the device), n its member's nodes.
+    struct FisherSource {
+        int family;
+        const ObsByNode *by_node;
+        const std::vector<double> *y, *aux;
+        std::shared_ptr<const DesignPlan> design;
+        const std::vector<double> &param, &loglik_const;
+    };
+    FisherDev fisher_build(const FisherSource &src, size_t n, const RbmcSym *rows);
+    // An evaluation of every member of a slot on the row structure `rows`: member k's point at d_x + k sx, mean at d_mu + k smu
+    // (nullable), score at + k ss, hess at + k sh (either nullable), d_active (device, nullable = all) its mask and active (host,
+    // nullable) the same bytes: out_host[2 k ..] = {energy, loglik with the member's loglik_const} of the members it names. The one
+    // place FisherEval and FisherDesign are filled. Synchronises.
+    struct FisherRows { const long long *rp; const int *col, *pos; };
+    struct FisherIO { const double *d_x; long long sx; const double *d_mu; long long smu; double *d_score, *d_hess; long long ss, sh; const unsigned char *d_active; };
+    void fisher_launch(FisherDev &f, const FisherRows &rows, const FisherIO &io, const unsigned char *active, double *out_host);
+    // the loop's four reductions {sum a b, sum (c - d)^2, sum d^2, max |b|} of the members of m, to the host: out4[4 k ..] for the
+    // members `active` names (host, nullable = all). Synchronises.
+    void fisher_stats(FisherDev &f, const FisherMembers &m, const double *a, const double *b, const double *c, const double *d,
+                      const unsigned char *active, double *out4);
     // the map gmrfx_batch_set_prior installed: false: the forest's diagonal (node form), true: the replicated map of a design plan;
     // bprior_map_ok_: -1 not compared with the plan in place since then, 0 / 1 (also reset by bobs_set)
     bool bprior_design_ = false;
     int bprior_map_ok_ = -1;
     void bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask);
     void bfisher_check_prior();
-    // the members' evaluation (BEvalIO, its mask already on the device: d_active) into bfisher_.h_out, 2 per member; synchronises
-    // (score at + k ss, hess at + k sh)
-    void bfisher_eval(const double *d_x, long long sx, const double *d_mu, long long smu, const unsigned char *d_active, double *d_score,
-                      double *d_hess, long long ss, long long sh);
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
     // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
     struct GapDev {
@@ -667,12 +678,10 @@ private:
         PinnedBuf<double> h_out, h_quad;
     } pred_;
     void pred_tables(const ObsHost &o);
-    void fisher_check_map(const RbmcSym &sym);
+    void fisher_check_map(const RbmcSym &sym, const char *who);
     std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
     int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
     int prior_design_ = -1;               // the same against the map of the design plan (also reset by obs_set)
-    void obs_set_design(const ObsHost &o, FisherDev &f);
-    void fisher_eval_design(const RbmcSym &sym, const double *d_x, const double *d_mu, double *d_score, double *d_hess, double *out_host);
     void grad_tables();
     void grad_drop_constraint() { grad_.acolptr.reset(); grad_.arow.reset(); grad_.aval.reset(); grad_.Bt.reset(); grad_.bt_serial = 0; }   // (behind a synchronisation)
     void grad_constraint_tables(const ConHost &A, int m, const double *d_B, int nb, long long n);

@@ -15,31 +15,6 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-// fisher_eval's refusals about the prior and its map, without an evaluation
-void Device::fisher_check_map(const RbmcSym &sym) {
-    if (!d_prior_) throw std::invalid_argument("ga_pullback: gmrfx_set_prior has not been called");
-    const long long n = S_->n;
-    if (fisher_.design) {
-        const DesignPlan &P = *fisher_.design;
-        if (prior_design_ < 0) prior_design_ = (hmap_cnt_ == P.cnt && std::equal(P.map.begin(), P.map.end(), h_hmap_.begin())) ? 1 : 0;
-        if (!prior_design_)
-            throw std::invalid_argument("ga_pullback: the map of gmrfx_set_prior is not the map of gmrfx_obs_hess_map (the positions of A' D A, design form)");
-        return;
-    }
-    if (prior_diag_ < 0) {
-        prior_diag_ = hmap_cnt_ == n ? 1 : 0;
-        for (long long i = 0; i < n && prior_diag_; i++)
-            if (h_hmap_[(size_t)i] != sym.diag[(size_t)i]) prior_diag_ = 0;
-    }
-    if (!prior_diag_) throw std::invalid_argument("ga_pullback: the map of gmrfx_set_prior is not the position of (i, i) for every i (diagonal Hessians only)");
-}
-
-template <class T, class U> static void gap_up(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) {
-    static_assert(sizeof(T) == sizeof(U), "gap_up copies bytes");
-    dst.alloc(src.size(), ledger, kTableMinBytes);
-    if (!src.empty()) hip_check(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
-}
-
 // The plan's transposed term table on the device (design form; 12 B per term): uploaded by whichever of gmrfx_ga_pullback and
 // gmrfx_predictor_marginals needs it first, kept until obs_set drops the pullback's state.
 void Device::gap_term_table() {
@@ -48,9 +23,9 @@ void Device::gap_term_table() {
     DevBuf<long long> optr;      // built aside: an upload that fails half-way leaves nothing behind
     DevBuf<int> oidx;
     DevBuf<double> ow;
-    gap_up(optr, P->optr, &bytes_total);
-    gap_up(oidx, P->oidx, &bytes_total);
-    gap_up(ow, P->ow, &bytes_total);
+    dev_upload(optr, P->optr, &bytes_total);
+    dev_upload(oidx, P->oidx, &bytes_total);
+    dev_upload(ow, P->ow, &bytes_total);
     gap_.optr = std::move(optr); gap_.oidx = std::move(oidx); gap_.ow = std::move(ow);
 }
 
@@ -81,7 +56,7 @@ int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, l
     const bool project = io.flags & 1, refactor = io.flags & 2;
     if (!io.d_mubar && !io.d_Qbar) throw std::invalid_argument("ga_pullback: mubar and Qbar are both null");
     if (project && con_.m <= 0) throw std::invalid_argument("ga_pullback: flag bit 0 (project lambda) needs a constraint (gmrfx_constraints_set)");
-    fisher_check_map(sym);
+    fisher_check_map(sym, "ga_pullback");
     if (info) *info = 0;
     const size_t nb = (size_t)n * sizeof(double);
     if (refactor) {

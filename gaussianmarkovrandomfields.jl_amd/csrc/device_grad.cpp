@@ -17,11 +17,6 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-template <class T> static void grad_up(DevBuf<T> &dst, const std::vector<T> &src, double *ledger) {
-    dst.alloc(src.size(), ledger, kTableMinBytes);
-    if (!src.empty()) HC(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-}
-
 // The tables that depend on the symbolic structure only: built on the first call, kept for the handle's life, on its books.
 void Device::grad_tables() {
     if (grad_.zoff) return;
@@ -39,8 +34,8 @@ void Device::grad_tables() {
             w[(size_t)p] = i == j ? 1 : ((S.in_use ? i > j : i < j) ? 2 : 0);
         }
     GradDev g;        // built aside: an upload that fails half-way leaves nothing behind
-    grad_up(g.zoff, off, &bytes_total);
-    grad_up(g.wgt, w, &bytes_total);
+    dev_upload(g.zoff, off, &bytes_total);
+    dev_upload(g.wgt, w, &bytes_total);
     const size_t nb = batched() ? (size_t)nbatch_ : 1;
     g.r.alloc((size_t)nm * nb, &bytes_total, kTableMinBytes);
     g.ybar.alloc(nb, &bytes_total, kTableMinBytes);
@@ -76,9 +71,9 @@ void Device::grad_constraint_tables(const ConHost &A, int m, const double *d_B, 
         DevBuf<long long> dcp;
         DevBuf<int> dar;
         DevBuf<double> dav;
-        grad_up(dcp, cp, &bytes_total);
-        grad_up(dar, ar, &bytes_total);
-        grad_up(dav, av, &bytes_total);
+        dev_upload(dcp, cp, &bytes_total);
+        dev_upload(dar, ar, &bytes_total);
+        dev_upload(dav, av, &bytes_total);
         grad_.acolptr = std::move(dcp); grad_.arow = std::move(dar); grad_.aval = std::move(dav);
         grad_.bt_serial = 0;
     }

@@ -16,12 +16,6 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-template <class T, class U> static void pred_up(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) {
-    static_assert(sizeof(T) == sizeof(U), "pred_up copies bytes");
-    dst.alloc(src.size(), ledger, kTableMinBytes);
-    if (!src.empty()) hip_check(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
-}
-
 void obs_pointwise_const(const ObsHost &o, double *out) {
     const long double p = (long double)o.param;
     for (long long k = 0; k < o.nobs; k++)
@@ -36,12 +30,12 @@ void Device::pred_tables(const ObsHost &o) {
     PredDev p;       // built aside: an upload that fails half-way leaves nothing behind
     std::vector<double> c(nobs);
     obs_pointwise_const(o, c.data());
-    pred_up(p.c, c, &bytes_total);
-    if (o.design) pred_up(p.hmap, o.design->map, &bytes_total);
+    dev_upload(p.c, c, &bytes_total);
+    if (o.design) dev_upload(p.hmap, o.design->map, &bytes_total);
     else {
         std::vector<int> idx(nobs);
         for (size_t k = 0; k < nobs; k++) idx[k] = (int)o.idx[k];
-        pred_up(p.idx, idx, &bytes_total);
+        dev_upload(p.idx, idx, &bytes_total);
     }
     p.part.alloc(4 * (size_t)design_blocks((long long)nobs), &bytes_total, kTableMinBytes);
     p.out.alloc(4, &bytes_total, kTableMinBytes);

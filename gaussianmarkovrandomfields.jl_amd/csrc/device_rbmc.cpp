@@ -16,21 +16,14 @@ namespace gmrfx {
 
 #define HC(x) hip_check((x), #x)
 
-// dst = a device copy of src (converted to T), on the handle's books
-template <class T, class U> static void rb_up(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) {
-    std::vector<T> tmp(src.begin(), src.end());
-    dst.alloc(tmp.size(), ledger, kTableMinBytes);
-    if (!tmp.empty()) HC(hipMemcpy(dst, tmp.data(), tmp.size() * sizeof(T), hipMemcpyHostToDevice));
-}
-
 void Device::sym_rows_upload(const RbmcSym &sym) {
     if (sym_rows_.rp) return;
     if (S_->nnz_in > INT_MAX || (long long)sym.col.size() > (1ll << 40)) throw std::invalid_argument("rbmc: Q has too many stored entries for 32-bit positions");
     SymRowsDev d;        // built aside: an upload that fails half-way leaves nothing behind
-    rb_up(d.rp, sym.rowptr, &bytes_total);      // n + 1
-    rb_up(d.col, sym.col, &bytes_total);
-    rb_up(d.pos, sym.pos, &bytes_total);
-    rb_up(d.dpos, sym.diag, &bytes_total);      // n
+    dev_upload(d.rp, sym.rowptr, &bytes_total);      // n + 1
+    dev_upload(d.col, sym.col, &bytes_total);
+    dev_upload(d.pos, std::vector<int>(sym.pos.begin(), sym.pos.end()), &bytes_total);        // (32-bit positions: checked above)
+    dev_upload(d.dpos, std::vector<int>(sym.diag.begin(), sym.diag.end()), &bytes_total);     // n
     sym_rows_ = std::move(d);
 }
 
@@ -55,15 +48,15 @@ void Device::rbmc_upload_plan(const RbmcPlan &plan) {
     rb_.plan = RbmcPlanDev();
     if (plan.loc.size() > (size_t)1 << 40) throw std::invalid_argument("rbmc: plan too large");
     RbmcPlanDev d;
-    rb_up(d.bptr, plan.block_ptr, &bytes_total);
-    rb_up(d.eptr, plan.eptr, &bytes_total);
-    rb_up(d.rows, plan.rows, &bytes_total);
-    rb_up(d.ns, plan.n_interior, &bytes_total);
-    rb_up(d.loc, plan.loc, &bytes_total);
-    rb_up(d.owner, plan.owner, &bytes_total);
+    dev_upload(d.bptr, plan.block_ptr, &bytes_total);
+    dev_upload(d.eptr, plan.eptr, &bytes_total);
+    dev_upload(d.rows, plan.rows, &bytes_total);
+    dev_upload(d.ns, plan.n_interior, &bytes_total);
+    dev_upload(d.loc, plan.loc, &bytes_total);
+    dev_upload(d.owner, plan.owner, &bytes_total);
     for (int c = 0; c < kRbmcClasses; c++) {
         d.cnt[c] = (int)plan.order[c].size();
-        if (d.cnt[c]) rb_up(d.order[c], plan.order[c], &bytes_total);
+        if (d.cnt[c]) dev_upload(d.order[c], plan.order[c], &bytes_total);
     }
     // global scratch of the two large classes, by workgroup of a launch: Q_BB (512 x 512) and R (rows x kRbmcW)
     const size_t wg3 = (size_t)std::min(d.cnt[3], rbmc_class_chunk(3)), wg2 = (size_t)std::min(d.cnt[2], rbmc_class_chunk(2));

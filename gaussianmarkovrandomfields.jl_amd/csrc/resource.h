@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <utility>
+#include <vector>
 
 namespace gmrfx {
 
@@ -56,6 +57,16 @@ private:
     size_t bytes_ = 0;
     double *ledger_ = nullptr;
 };
+
+constexpr size_t kTableMinBytes = 8;      // the size rule of a handle's tables: 8 bytes at least (+ the 16 of slack)
+// dst = a device copy of count entries of src, on the ledger's books (an element type of the same size is copied as bytes:
+// std::int64_t and long long, std::uint8_t and unsigned char)
+template <class T, class U> void dev_upload(DevBuf<T> &dst, const U *src, size_t count, double *ledger) {
+    static_assert(sizeof(T) == sizeof(U), "dev_upload copies bytes");
+    dst.alloc(count, ledger, kTableMinBytes);
+    if (count > 0) hip_check(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy");
+}
+template <class T, class U> void dev_upload(DevBuf<T> &dst, const std::vector<U> &src, double *ledger) { dev_upload(dst, src.data(), src.size(), ledger); }
 
 // Page-locked host memory of cap() elements.
 template <class T> class PinnedBuf {

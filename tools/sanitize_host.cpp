@@ -5,6 +5,7 @@
 // sources as the product, driven through the C ABI with symbolic_only handles (no GPU is touched; the HIP kernel
 // launch wrappers stay unresolved and are never called). Exit code 0 = clean. Run by tests/test_sanitizers.py.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <vector>
 
 #include "../gaussianmarkovrandomfields.jl_amd/csrc/device_plan.h"
+#include "../gaussianmarkovrandomfields.jl_amd/csrc/ga_rules.h"
 #include "../include/gmrfx.h"
 
 // 19-point pattern of (5-point Laplacian)^2 on an nx x ny grid, both triangles, 0-based
@@ -355,6 +357,81 @@ static void check_level_plans(const gmrfx::Symbolic &S, const std::vector<gmrfx:
     }
 }
 
+// The decisions of the Fisher-scoring loop (ga_rules.h), driven alone with scripted numbers: both loops of the device take them from here.
+static void check_ga_rules() {
+    using namespace gmrfx;
+    const double eps = 2.220446049250313e-16, inf = INFINITY;
+    const GaOpts o{10, 5, 1e-4, 1e-3, 1 | 2 | 4}, plain{10, 5, 1e-4, 1e-3, 0}, refactors{1, 1, 0, 0, 8};
+    EXPECT(o.adaptive() && o.retry_full() && o.predictive() && !o.refactor_final() && !plain.adaptive() && refactors.refactor_final());
+    // acceptance: the bound is the merit plus 64 eps max(|energy| + |loglik|, 1); a merit at the bound accepts, one ulp above rejects
+    const double e[2] = {3.0, 1.0}, small[2] = {0.25, -0.125};
+    const double bound = ga_line_search_bound(e);
+    EXPECT(ga_merit(e) == 2.0 && bound == 2.0 + 256 * eps && ga_line_search_bound(small) == 0.375 + 64 * eps && merit_atol(0.0) == 64 * eps);
+    GaMember m;
+    EXPECT(m.alpha == 1.0 && m.alpha_prev == 1.0 && m.dec_prev == 0.0 && std::isnan(m.dec) && m.status == kGaRun && !m.frozen && m.iters == 0);
+    EXPECT(ga_line_search_probe(m, bound, bound) && m.alpha == 1.0);                                   // (sqrt(1) = 1)
+    // the step lengths 1 -> 0.1 -> 0.01 -> accept -> 0.1
+    EXPECT(!ga_line_search_probe(m, std::nextafter(bound, inf), bound) && m.alpha == 0.1);
+    EXPECT(!ga_line_search_probe(m, std::nan(""), bound) && m.alpha == 0.1 * 0.1);                      // (a NaN merit backtracks)
+    EXPECT(ga_line_search_probe(m, 2.0, bound) && m.alpha == std::sqrt(0.1 * 0.1) && std::fabs(m.alpha - 0.1) < 1e-16);
+    // the full-step retry: only under its flag and only below the full step; accepted, it sets the full step
+    EXPECT(ga_line_search_retries_full(o, m) && !ga_line_search_retries_full(plain, m));
+    EXPECT(!ga_line_search_full_step(m, std::nextafter(bound, inf), bound) && m.alpha < 1.0 && !ga_line_search_full_step(m, std::nan(""), bound));
+    EXPECT(ga_line_search_full_step(m, bound, bound) && m.alpha == 1.0 && !ga_line_search_retries_full(o, m));
+    // the tiny-step exit: alpha |step|_inf against dec_tol / 1000, both sides
+    const double tiny = o.dec_tol / 1000;
+    EXPECT(!ga_line_search_tiny_step(o, m, tiny) && ga_line_search_tiny_step(o, m, std::nextafter(tiny, 0.0)));
+    m.alpha = 0.5;
+    EXPECT(!ga_line_search_tiny_step(o, m, 2 * tiny) && ga_line_search_tiny_step(o, m, std::nextafter(2 * tiny, 0.0)) && !ga_line_search_tiny_step(o, m, std::nan("")));
+    // convergence, each condition alone: the decrement, the mean change, the mean change relative to |x| (floored at 1e-10: x = 0 is
+    // no division by zero)
+    auto verdict = [&](const GaOpts &op, GaMember &mm, long long iter, double dec, double diff2, double x2) {
+        const double st[4] = {dec, diff2, x2, 7.0};
+        const GaVerdict v = ga_iterate_verdict(op, mm, iter, st);
+        EXPECT(mm.dec == dec || (std::isnan(dec) && std::isnan(mm.dec)));       // the verdict records dec, and dec_prev is the caller's
+        return v;
+    };
+    GaMember c;
+    EXPECT(verdict(plain, c, 1, std::nextafter(1e-3, 0.0), 1.0, 1.0) == kGaConverges && verdict(plain, c, 1, 1e-3, 1.0, 1.0) == kGaContinue);
+    EXPECT(verdict(plain, c, 1, 1.0, 25e-10, 0.0) == kGaConverges && verdict(plain, c, 1, 1.0, 4e-8, 0.0) == kGaContinue);      // (sqrt: 5e-5, 2e-4)
+    EXPECT(verdict(plain, c, 1, 1.0, 1.0, 1e10) == kGaConverges && verdict(plain, c, 1, 1.0, 1.0, 1e6) == kGaContinue);        // (1e-5, 1e-3)
+    const GaOpts floor_only{10, 5, 0.0, 0.0, 0};       // nothing is below a tolerance of 0: 0 / max(0, 1e-10) = 0, not NaN
+    EXPECT(verdict(floor_only, c, 1, 1.0, 0.0, 0.0) == kGaContinue && verdict(plain, c, 1, std::nan(""), 1.0, 1.0) == kGaContinue && c.dec_prev == 0.0);
+    // the look-ahead: dec (dec / dec_prev)^2 < dec_tol, under its flag, after the first iterate, and both step lengths exactly 1
+    auto ahead = [&](const GaOpts &op, long long iter, double alpha, double alpha_prev, double dec_prev) {
+        GaMember p;
+        p.alpha = alpha; p.alpha_prev = alpha_prev; p.dec_prev = dec_prev;
+        return verdict(op, p, iter, 1e-2, 1.0, 1.0);
+    };
+    EXPECT(ahead(o, 2, 1.0, 1.0, 0.1) == kGaLooksAhead);                    // 1e-2 (1e-1)^2 = 1e-4
+    EXPECT(ahead(o, 1, 1.0, 1.0, 0.1) == kGaContinue && ahead(plain, 2, 1.0, 1.0, 0.1) == kGaContinue);
+    EXPECT(ahead(o, 2, std::nextafter(1.0, 0.0), 1.0, 0.1) == kGaContinue && ahead(o, 2, 1.0, std::nextafter(1.0, 0.0), 0.1) == kGaContinue);
+    EXPECT(ahead(o, 2, 1.0, 1.0, 0.02) == kGaContinue);                     // 1e-2 (0.5)^2 = 2.5e-3
+    // the chord step of the frozen finish decides by !(dec < tol): a NaN does not converge it, and only a deciding step is recorded
+    GaMember f;
+    f.dec = 0.5;
+    EXPECT(!frozen_finish_decides(o, f, std::nan("")) && f.dec == 0.5 && !frozen_finish_decides(o, f, 1e-3) && f.dec == 0.5);
+    EXPECT(frozen_finish_decides(o, f, 5e-4) && f.dec == 5e-4 && kFrozenFinishSteps == 3);
+    // the counters and the eight-number row
+    GaMember r;
+    r.alpha = 0.25;
+    ga_iterate_begun(r);
+    ga_iterate_begun(r);
+    r.alpha = 0.5; r.dec = 1e-5; r.nmerit = 7;
+    EXPECT(r.alpha_prev == 0.25 && r.nfact == 2 && r.nsolve == 2);
+    ga_stop(r, kGaConverged, 3, true);
+    double row[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
+    ga_result_row(r, row);
+    const double want[9] = {3, 1, 0.5, 1e-5, 2, 2, 7, 1, -1};
+    EXPECT(std::equal(row, row + 9, want));
+    ga_stop(r, kGaMaxIter, 10, false);
+    ga_result_row(r, row);
+    EXPECT(row[0] == 10 && row[1] == 0 && row[7] == 0);
+    ga_stop(r, kGaFailed, 2, false);
+    ga_result_row(r, row);
+    EXPECT(row[0] == 2 && row[1] == 0 && row[7] == 0);
+}
+
 // the device tables of every rank of a (sharded, world > 1) analysis, with and without the tile records (GMRFX_SYRK_XCD=0)
 static void device_plans(const std::vector<int64_t> &cp, const std::vector<int64_t> &ri, const double *coords, int64_t n, int world) {
     for (int rank = 0; rank < world; rank++) {
@@ -390,6 +467,7 @@ int main() {
     sharded_handles(cp, ri, xy.data(), n, 4);
     sharded_handles(cp, ri, xy.data(), n, 8);      // the width the driver scales to
     check_launch_edges();
+    check_ga_rules();
     device_plans(cp, ri, xy.data(), n, 1);
     device_plans(cp, ri, xy.data(), n, 2);         // owner columns, foreign parents, other ranks' children
     // distinct handles are used concurrently from different host threads (WorkspacePool contract)
