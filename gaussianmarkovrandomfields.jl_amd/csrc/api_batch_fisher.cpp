@@ -324,3 +324,69 @@ extern "C" int32_t gmrfx_batch_constrained_gaussian_approximation_dev(gmrfx_hand
     return bf_ga_impl(h, d_mu, smu, d_x0, sx0, max_iter, max_linesearch_iter, mean_change_tol, newton_dec_tol, flags, d_x, sx, d_hess, sh, result,
                       totals, dec_trace, alpha_trace, info, true, true, cinfo, residual);
 }
+
+// ---- the pullback of the Gaussian approximation for every member (Device::batch_ga_pullback; csrc/ga_pullback.hip) -------------------
+// The middle link of gmrfx_batch_logpdf_grad -> gmrfx_batch_ga_pullback -> gmrfx_batch_pattern_dot: cotangents and outputs dense per
+// member, as the two neighbours have them; x and mu with member strides, as gmrfx_batch_fisher_eval.
+static int32_t bf_pullback_impl(gmrfx_handle *h, const double *x, int64_t sx, const double *mu, int64_t smu, const double *mubar, const double *Qbar,
+                                int32_t flags, double *Qbar_prior, double *mubar_prior, double *lambda, double *out, int64_t *info, bool dev) {
+    return guarded(h, [&]() -> int32_t {
+        const std::string who = "batch_ga_pullback: ";
+        bf_check_handle(h, who, true);
+        if (!x) throw std::invalid_argument(who + "x is null");
+        if (!out) throw std::invalid_argument(who + "out is null");
+        const int64_t n = bf_n(h), nnz = bf_nnz(h), nb = h->nbatch;
+        bf_check_stride(who, "x", sx, n);
+        if (mu) bf_check_stride(who, "mu", smu, n, true);
+        if (flags < 0 || flags > 3) throw std::invalid_argument(who + "unknown flag bits");
+        if (!mubar && !Qbar) throw std::invalid_argument(who + "mubar and Qbar are both null");
+        if (!Qbar_prior && !mubar_prior && !lambda) throw std::invalid_argument(who + "every output is null");
+        if ((flags & 1) && h->bcon.m <= 0)
+            throw std::invalid_argument(who + "flag bit 0 (project lambda) needs a batch constraint (gmrfx_batch_constraints_set)");
+        if (h->bobs.nobs == 0) throw std::invalid_argument(who + "no observation likelihood is set (gmrfx_batch_obs_set)");
+        if (int32_t e = need_batch(h, !(flags & 2))) return e;
+        if (!h->rsym.built) rbmc_build_sym(h->S, h->rsym);
+        std::vector<double> res(2 * (size_t)nb, 0.0);
+        std::vector<long long> inf((size_t)nb, 0);
+        if (dev)
+            h->D->batch_ga_pullback(h->rsym, Device::BGapIO{x, sx, mu, smu, mubar, Qbar, flags, Qbar_prior, mubar_prior, lambda}, res.data(), inf.data());
+        else {
+            DevBlock bx, bm, bb, bq, oq, om, ol;
+            stage_up(h, bx, x, n, n, 1, sx, nb);
+            if (mu) stage_up(h, bm, mu, n, n, 1, smu, smu == 0 ? 1 : nb);
+            if (mubar) stage_up(h, bb, mubar, n * nb);
+            if (Qbar) stage_up(h, bq, Qbar, nnz * nb);
+            if (Qbar_prior) stage_alloc(h, oq, nnz * nb);
+            if (mubar_prior) stage_alloc(h, om, n * nb);
+            if (lambda) stage_alloc(h, ol, n * nb);
+            h->D->batch_ga_pullback(h->rsym, Device::BGapIO{bx, n, mu ? bm.get() : nullptr, smu == 0 ? 0 : n, mubar ? bb.get() : nullptr,
+                                                            Qbar ? bq.get() : nullptr, flags, Qbar_prior ? oq.get() : nullptr,
+                                                            mubar_prior ? om.get() : nullptr, lambda ? ol.get() : nullptr},
+                                    res.data(), inf.data());
+            if (Qbar_prior && nnz > 0) stage_down(h, oq, Qbar_prior, nnz * nb, nnz * nb, 1);
+            if (mubar_prior) stage_down(h, om, mubar_prior, n * nb, n * nb, 1);
+            if (lambda) stage_down(h, ol, lambda, n * nb, n * nb, 1);
+        }
+        std::copy(res.begin(), res.end(), out);
+        if (info) { std::copy(inf.begin(), inf.end(), info); return GMRFX_OK; }
+        // a failed member has NaN in its own outputs; without info the return code says so
+        for (int64_t k = 0; k < nb; k++) {
+            if (inf[(size_t)k] == 0) continue;
+            h->err = who + "member " + std::to_string(k) + ": " +
+                     (inf[(size_t)k] < 0 ? "Q_prior - H(x) is not positive definite (its factorisation failed)"
+                                         : "A Q^-1 A' is not positive definite (rank-deficient constraint matrix)");
+            return GMRFX_ERR_NOT_POSDEF;
+        }
+        return GMRFX_OK;
+    });
+}
+extern "C" int32_t gmrfx_batch_ga_pullback(gmrfx_handle *h, const double *x, int64_t sx, const double *mu, int64_t smu, const double *mubar,
+                                           const double *Qbar, int32_t flags, double *Qbar_prior, double *mubar_prior, double *lambda, double *out,
+                                           int64_t *info) {
+    return bf_pullback_impl(h, x, sx, mu, smu, mubar, Qbar, flags, Qbar_prior, mubar_prior, lambda, out, info, false);
+}
+extern "C" int32_t gmrfx_batch_ga_pullback_dev(gmrfx_handle *h, const double *d_x, int64_t sx, const double *d_mu, int64_t smu, const double *d_mubar,
+                                               const double *d_Qbar, int32_t flags, double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda,
+                                               double *out, int64_t *info) {
+    return bf_pullback_impl(h, d_x, sx, d_mu, smu, d_mubar, d_Qbar, flags, d_Qbar_prior, d_mubar_prior, d_lambda, out, info, true);
+}

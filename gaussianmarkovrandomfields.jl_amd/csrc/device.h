@@ -317,6 +317,16 @@ public:
     // factorisation failed (*info = 1 + the failing step), 2 when the constraint's W did.
     struct GapIO { const double *d_x, *d_mu, *d_mubar, *d_Qbar; int flags; double *d_Qbar_prior, *d_mubar_prior, *d_lambda; };
     int ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info);
+    // The same for every member of a batched handle (gmrfx_batch_ga_pullback), forest-wide, one launch per step: member k's mode at
+    // d_x + k sx, prior mean at d_mu + k smu (nullable; smu = 0: one mean), cotangents and outputs dense per member (n / nnz_member
+    // each). Needs the batch likelihood and the prior of gmrfx_batch_set_prior. Bit 0 projects with the BATCH constraint (a held
+    // constraint without the bit: the plain solve); bit 1 evaluates every member's Hessian at its x and refactorises the forest first.
+    // out_host: 2 per member; info_host (nbatch, nullable): 0, -1 when member k's factorisation failed, 1 + the failing pivot when its
+    // W_k did -- such a member is masked out of every launch, its requested output slices and its two results are NaN, nobody
+    // else's are touched. Returns 0, or 1 when some member failed. One synchronisation behind the last launch.
+    struct BGapIO { const double *d_x; long long sx; const double *d_mu; long long smu; const double *d_mubar, *d_Qbar; int flags;
+                    double *d_Qbar_prior, *d_mubar_prior, *d_lambda; };
+    int batch_ga_pullback(const RbmcSym &sym, const BGapIO &io, double *out_host, long long *info_host);
 
     // ---- the linear predictor's marginals and the predictive scores (device_predictive.cpp, predictive.hip) -------------------------
     // Per observation, in the caller's order (the indices of gmrfx_obs_set / the rows of A): the mean of the linear predictor at d_x
@@ -659,15 +669,31 @@ private:
     void bfisher_ctl(const std::vector<double> *alpha, const std::vector<unsigned char> &mask);
     void bfisher_check_prior();
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
-    // of the plan, the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two parameter sums, the result
+    // of the plan (ONE copy), and per member the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two
+    // parameter sums, the result
     struct GapDev {
         DevBuf<long long> optr;
         DevBuf<int> oidx;
         DevBuf<double> ow, work, part, out;
         PinnedBuf<double> h_out;
-    } gap_;
-    void gap_tables();
+    } gap_, bgap_;               // of fisher_ (obs_set drops it) and of bfisher_ (bobs_set does): sized for the slot's members
+    void gap_tables(const FisherDev &f, GapDev &g);
     void gap_term_table();       // the plan's transposed term table alone (also what gmrfx_predictor_marginals needs of the pullback's state)
+    void gap_term_table(const FisherDev &f, GapDev &g);
+    // The launch sequence of the pullback for the members of a likelihood slot (f with its state g), the ONE place the kernels'
+    // arguments are filled: xbar, the forest solve, the projection (project: 0 none, 1 the plain constraint, 2 the batch constraint;
+    // its operands prepared by the caller), the outputs, the two results per member. The factor in hand is the one to solve with.
+    // hmap / colptr / row / rows: the MEMBER's slice of the Hessian map, its pattern and its symmetric rows; d_active (device, nullable
+    // = all) and active (host) name the members that take part: the others get NaN in their output slices and results.
+    struct GapRun {
+        const long long *hmap, *colptr;
+        const int *row;
+        FisherRows rows;
+        long long sx, smu;
+        int project;
+        const unsigned char *d_active, *active;
+    };
+    void gap_launch(FisherDev &f, GapDev &g, const GapRun &r, const GapIO &io, double *out_host);
     // predictive state, built on the first gmrfx_predictor_marginals / gmrfx_predictive_scores for the likelihood in place (obs_set
     // drops it): the observed nodes in the caller's order (node form, 4 nobs bytes), the constants c (8 nobs), the plan's map (design
     // form, 8 cnt), the scores' partial sums (4 per workgroup), totals and quadrature rule

@@ -42,6 +42,7 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     }
     HC(hipStreamSynchronize(stream));
     bfisher_ = std::move(f);
+    bgap_ = GapDev{};        // (the batched pullback's tables belong to the likelihood: rebuilt on its next call)
     bprior_map_ok_ = -1;
 }
 

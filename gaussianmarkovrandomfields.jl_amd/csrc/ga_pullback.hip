@@ -19,6 +19,16 @@
 // a chunk's thread adds entries t, t + 256 and the 256 sums meet in a fixed LDS tree; workgroup partials are added by a fixed strided
 // loop and tree. Every operand is read and written one double at a time: nothing depends on alignment. Contraction is off in the
 // whole file; every fused multiply-add is written as one.
+// MEMBERS (batched handles, gmrfx_batch_ga_pullback). Every kernel takes a member index from its grid (blockIdx.y; blockIdx.x in
+// k_gap_final) and member strides: ONE copy of A by rows and columns, the chunk tables, the transposed term table, the data set (y, aux,
+// offset, mask), the member's pattern, its symmetric rows and its slice of the Hessian map; member k's G and Qbar_prior at + k sg, its
+// point at + k sx, its mean at + k smu (0: one mean), its cotangents, work vectors and outputs at their own strides, t at + k nobs, its
+// chunk sums at + k sc, its partial sums at + k gap_obs_blocks(...), its result at out[k]. A per-member scalar is the by-value argument
+// unless its device array is non-null. A workgroup never spans two members and a member's sums are formed in the order above whatever
+// the other members hold: member k's results have the bits of a plain handle of Q_p,k and param[k]. A plain handle is one member, grid
+// (blocks, 1), strides 0, scalars by value. INACTIVE MEMBERS (active non-null and active[k] == 0): every workgroup of the member returns
+// on its first statement, uniform over the workgroup and ahead of every barrier and load; nothing of the member is written.
+// k_gap_copy carries a vector of every active member (or NaN into those of the inactive ones: the slices of a member whose factor failed).
 // SELECTION MATRICES. With A = rows of the identity and no offset every sum has one term of weight 1: eta, t and xbar have the bits
 // of the node form, and so has everything behind the solve.
 #include <hip/hip_runtime.h>
@@ -47,144 +57,175 @@ __device__ __forceinline__ void gap_block_sum(double *sh, int cnt, double *dst) 
 }
 
 __global__ __launch_bounds__(kGapNode) void k_gap_point_node(const GapPoint a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     __shared__ double sp[kGapNode];
     const long long i = (long long)blockIdx.x * kGapNode + threadIdx.x;
     double p = 0.0;
     if (i < a.n) {
         double t = 0.0;
         if (a.mask[i]) {
-            const double c = a.G[a.hmap[i]];
+            const double c = a.G[(long long)k * a.sg + a.hmap[i]];
             double d3, gp, dp;
-            fisher_point_pullback(a.family, a.x[i], a.y[i], a.aux ? a.aux[i] : 0.0, a.param, a.logparam, d3, gp, dp);
+            fisher_point_pullback(a.family, a.x[(long long)k * a.sx + i], a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                                  a.logparam_k ? a.logparam_k[k] : a.logparam, d3, gp, dp);
             t = c * d3;
             p = c * dp;
         }
-        a.xbar[i] = (a.mubar ? a.mubar[i] : 0.0) - t;
+        a.xbar[(long long)k * a.sw + i] = (a.mubar ? a.mubar[(long long)k * a.sm + i] : 0.0) - t;
     }
     sp[threadIdx.x] = p;
-    gap_block_sum(sp, kGapNode, a.ppart + blockIdx.x);
+    gap_block_sum(sp, kGapNode, a.ppart + ((long long)k * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(256) void k_gap_point(const GapPoint a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     __shared__ double sp[kDesignRows];
     const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
     const long long i = (long long)blockIdx.x * kDesignRows + g;
     double p = 0.0;
     if (i < a.nobs) {           // (a whole lane group takes the branch together)
+        const double *x = a.x + (long long)k * a.sx, *G = a.G + (long long)k * a.sg;
         double s = 0.0, c = 0.0;
         const long long q1 = a.arp[i + 1], o1 = a.optr[i + 1];
-        for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], a.x[a.acol[q]], s);
-        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) c = __builtin_fma(a.ow[q], a.G[a.hmap[a.oidx[q]]], c);
+        for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], x[a.acol[q]], s);
+        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) c = __builtin_fma(a.ow[q], G[a.hmap[a.oidx[q]]], c);
         s = gap_group_sum(s);
         c = gap_group_sum(c);
         if (l == 0) {
             const double eta = a.offset ? s + a.offset[i] : s;
             double d3, gp, dp;
-            fisher_point_pullback(a.family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, a.param, a.logparam, d3, gp, dp);
-            a.t[i] = c * d3;
+            fisher_point_pullback(a.family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                                  a.logparam_k ? a.logparam_k[k] : a.logparam, d3, gp, dp);
+            a.t[(long long)k * a.nobs + i] = c * d3;
             p = c * dp;
         }
     }
     if (l == 0) sp[g] = p;
-    gap_block_sum(sp, kDesignRows, a.ppart + blockIdx.x);
+    gap_block_sum(sp, kDesignRows, a.ppart + ((long long)k * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(256) void k_gap_chunks(const GapGather a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     __shared__ double sh[256];
     const int b = blockIdx.x, tid = threadIdx.x;
+    const double *t_k = a.t + (long long)k * a.st;
     const long long p0 = a.chs[b];
     const int len = a.chl[b];
     double s = 0.0;
-    for (int t = tid; t < len; t += 256) s = __builtin_fma(a.acv[p0 + t], a.t[a.arow[p0 + t]], s);
+    for (int t = tid; t < len; t += 256) s = __builtin_fma(a.acv[p0 + t], t_k[a.arow[p0 + t]], s);
     sh[tid] = s;
-    gap_block_sum(sh, 256, a.cpart + b);
+    gap_block_sum(sh, 256, a.cpart + ((long long)k * a.sc + b));
 }
 
 __global__ __launch_bounds__(256) void k_gap_gather(const GapGather a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
     const long long j = (long long)blockIdx.x * kDesignRows + g;
     if (j >= a.n) return;       // (a whole lane group leaves together)
+    const double *t_k = a.t + (long long)k * a.st, *cpart = a.cpart + (long long)k * a.sc;
     const long long p0 = a.acp[j], p1 = a.acp[j + 1];
     double s = 0.0;
     if (p1 - p0 <= kDesignChunk)
-        for (long long q = p0 + l; q < p1; q += kDesignLanes) s = __builtin_fma(a.acv[q], a.t[a.arow[q]], s);
+        for (long long q = p0 + l; q < p1; q += kDesignLanes) s = __builtin_fma(a.acv[q], t_k[a.arow[q]], s);
     else
-        for (int c = a.cchoff[j] + l; c < a.cchoff[j + 1]; c += kDesignLanes) s += a.cpart[c];
+        for (int c = a.cchoff[j] + l; c < a.cchoff[j + 1]; c += kDesignLanes) s += cpart[c];
     s = gap_group_sum(s);
-    if (l == 0) a.xbar[j] = (a.mubar ? a.mubar[j] : 0.0) - s;
+    if (l == 0) a.xbar[(long long)k * a.sw + j] = (a.mubar ? a.mubar[(long long)k * a.sm + j] : 0.0) - s;
 }
 
 __global__ __launch_bounds__(256) void k_gap_pattern(const GapPattern a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     const int g = threadIdx.x / kGradLanes, l = threadIdx.x % kGradLanes, n = a.n;
+    const double *lam = a.lam + (long long)k * a.sw, *x = a.x + (long long)k * a.sx;
+    const double *mu = a.mu ? a.mu + (long long)k * a.smu : nullptr, *G = a.G ? a.G + (long long)k * a.sg : nullptr;
+    double *out = a.out + (long long)k * a.sg;
     for (int t = 0; t < kGradColsPerGroup; t++) {
         const long long j = (long long)blockIdx.x * kGradCols + t * (256 / kGradLanes) + g;      // neighbouring groups walk neighbouring columns
         if (j >= n) continue;
-        const double lj = a.lam[j], rj = a.x[j] - (a.mu ? a.mu[j] : 0.0);
+        const double lj = lam[j], rj = x[j] - (mu ? mu[j] : 0.0);
         const long long p1 = a.colptr[j + 1];
         for (long long p = a.colptr[j] + l; p < p1; p += kGradLanes) {
             const int i = a.row[p];
-            const double ri = a.x[i] - (a.mu ? a.mu[i] : 0.0);
-            a.out[p] = (a.G ? a.G[p] : 0.0) - 0.5 * (a.lam[i] * rj + lj * ri);
+            const double ri = x[i] - (mu ? mu[i] : 0.0);
+            out[p] = (G ? G[p] : 0.0) - 0.5 * (lam[i] * rj + lj * ri);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_gap_mean(int n, const long long *__restrict__ rp, const int *__restrict__ col, const int *__restrict__ pos,
-                                                  const double *__restrict__ val, const double *__restrict__ lam, double *__restrict__ out) {
+__global__ __launch_bounds__(256) void k_gap_mean(const GapMean a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     const int g = threadIdx.x / kGradLanes, l = threadIdx.x % kGradLanes;
     const long long i = (long long)blockIdx.x * kGradRows + g;
-    if (i >= n) return;         // (a whole lane group leaves together)
+    if (i >= a.n) return;       // (a whole lane group leaves together)
+    const double *__restrict__ val = a.val + (long long)k * a.nnz, *__restrict__ lam = a.lam + (long long)k * a.sw;
     double s = 0.0;
-    const long long q1 = rp[i + 1];
-    for (long long q = rp[i] + l; q < q1; q += kGradLanes) s = __builtin_fma(val[pos[q]], lam[col[q]], s);
+    const long long q1 = a.rp[i + 1];
+    for (long long q = a.rp[i] + l; q < q1; q += kGradLanes) s = __builtin_fma(val[a.pos[q]], lam[a.col[q]], s);
 #pragma unroll
     for (int sh = kGradLanes / 2; sh > 0; sh >>= 1) s += __shfl_xor(s, sh, kGradLanes);
-    if (l == 0) out[i] = s;
+    if (l == 0) a.out[(long long)k * a.so + i] = s;
 }
 
 __global__ __launch_bounds__(kGapNode) void k_gap_param_node(const GapParam a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     __shared__ double sp[kGapNode];
     const long long i = (long long)blockIdx.x * kGapNode + threadIdx.x;
     double p = 0.0;
     if (i < a.n && a.mask[i]) {
         double d3, gp, dp;
-        fisher_point_pullback(a.family, a.x[i], a.y[i], a.aux ? a.aux[i] : 0.0, a.param, a.logparam, d3, gp, dp);
-        p = a.lam[i] * gp;
+        fisher_point_pullback(a.family, a.x[(long long)k * a.sx + i], a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                              a.logparam_k ? a.logparam_k[k] : a.logparam, d3, gp, dp);
+        p = a.lam[(long long)k * a.sw + i] * gp;
     }
     sp[threadIdx.x] = p;
-    gap_block_sum(sp, kGapNode, a.gpart + blockIdx.x);
+    gap_block_sum(sp, kGapNode, a.gpart + ((long long)k * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(256) void k_gap_param(const GapParam a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     __shared__ double sp[kDesignRows];
     const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
     const long long i = (long long)blockIdx.x * kDesignRows + g;
     double p = 0.0;
     if (i < a.nobs) {
+        const double *x = a.x + (long long)k * a.sx, *lam = a.lam + (long long)k * a.sw;
         double s = 0.0, e = 0.0;
         const long long q1 = a.arp[i + 1];
         for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) {
-            const int k = a.acol[q];
-            e = __builtin_fma(a.aval[q], a.x[k], e);
-            s = __builtin_fma(a.aval[q], a.lam[k], s);
+            const int c = a.acol[q];
+            e = __builtin_fma(a.aval[q], x[c], e);
+            s = __builtin_fma(a.aval[q], lam[c], s);
         }
         e = gap_group_sum(e);
         s = gap_group_sum(s);
         if (l == 0) {
             const double eta = a.offset ? e + a.offset[i] : e;
             double d3, gp, dp;
-            fisher_point_pullback(a.family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, a.param, a.logparam, d3, gp, dp);
+            fisher_point_pullback(a.family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                                  a.logparam_k ? a.logparam_k[k] : a.logparam, d3, gp, dp);
             p = s * gp;
         }
     }
     if (l == 0) sp[g] = p;
-    gap_block_sum(sp, kDesignRows, a.gpart + blockIdx.x);
+    gap_block_sum(sp, kDesignRows, a.gpart + ((long long)k * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(kFisherFinal) void k_gap_final(const double *__restrict__ gpart, int ng, const double *__restrict__ ppart, int np,
-                                                            double *__restrict__ out) {
+                                                            const unsigned char *__restrict__ active, double *__restrict__ out) {
+    const int k = blockIdx.x;
+    if (active && !active[k]) return;
     __shared__ double sg[kFisherFinal], sp[kFisherFinal];
     const int tid = threadIdx.x;
+    gpart += (long long)k * ng;
+    ppart += (long long)k * np;
     double g = 0.0, p = 0.0;
     for (int b = tid; b < ng; b += kFisherFinal) g += gpart[b];
     for (int b = tid; b < np; b += kFisherFinal) p += ppart[b];
@@ -194,36 +235,55 @@ __global__ __launch_bounds__(kFisherFinal) void k_gap_final(const double *__rest
         if (tid < st) { sg[tid] += sg[tid + st]; sp[tid] += sp[tid + st]; }
         __syncthreads();
     }
-    if (tid == 0) out[0] = sg[0] - sp[0];
+    if (tid == 0) out[k] = sg[0] - sp[0];
 }
 
-void launch_gap_point(hipStream_t st, const GapPoint &a, bool design) {
-    if (a.n <= 0 || a.nobs <= 0) return;
+// the active members' vectors copied (src non-null), or the INACTIVE members' filled with NaN (src null)
+__global__ __launch_bounds__(256) void k_gap_copy(long long n, const double *__restrict__ src, long long ss, double *__restrict__ dst, long long sd,
+                                                  const unsigned char *__restrict__ active) {
+    const int k = blockIdx.y;
+    const bool on = !active || active[k];
+    if (on != (src != nullptr)) return;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[(long long)k * sd + i] = src ? src[(long long)k * ss + i] : __builtin_nan("");
+}
+
+void launch_gap_point(hipStream_t st, const GapPoint &a, bool design, int nbatch) {
+    if (a.n <= 0 || a.nobs <= 0 || nbatch <= 0) return;
     const unsigned nb = (unsigned)gap_obs_blocks(design, a.n, a.nobs);
-    if (design) hipLaunchKernelGGL(k_gap_point, dim3(nb), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_gap_point_node, dim3(nb), dim3(kGapNode), 0, st, a);
+    if (design) hipLaunchKernelGGL(k_gap_point, dim3(nb, (unsigned)nbatch), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_gap_point_node, dim3(nb, (unsigned)nbatch), dim3(kGapNode), 0, st, a);
 }
-void launch_gap_gather(hipStream_t st, const GapGather &a) {
-    if (a.n <= 0) return;
-    if (a.ncc > 0) hipLaunchKernelGGL(k_gap_chunks, dim3((unsigned)a.ncc), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_gap_gather, dim3((unsigned)design_blocks(a.n)), dim3(256), 0, st, a);
+void launch_gap_gather(hipStream_t st, const GapGather &a, int nbatch) {
+    if (a.n <= 0 || nbatch <= 0) return;
+    if (a.ncc > 0) hipLaunchKernelGGL(k_gap_chunks, dim3((unsigned)a.ncc, (unsigned)nbatch), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_gap_gather, dim3((unsigned)design_blocks(a.n), (unsigned)nbatch), dim3(256), 0, st, a);
 }
-void launch_gap_pattern(hipStream_t st, const GapPattern &a) {
-    if (a.n <= 0) return;
-    hipLaunchKernelGGL(k_gap_pattern, dim3((unsigned)cdiv(a.n, kGradCols)), dim3(256), 0, st, a);
+void launch_gap_pattern(hipStream_t st, const GapPattern &a, int nbatch) {
+    if (a.n <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_pattern, dim3((unsigned)cdiv(a.n, kGradCols), (unsigned)nbatch), dim3(256), 0, st, a);
 }
-void launch_gap_mean(hipStream_t st, int n, const long long *rp, const int *col, const int *pos, const double *val, const double *lam, double *out) {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_gap_mean, dim3((unsigned)cdiv(n, kGradRows)), dim3(256), 0, st, n, rp, col, pos, val, lam, out);
+void launch_gap_mean(hipStream_t st, const GapMean &a, int nbatch) {
+    if (a.n <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_mean, dim3((unsigned)cdiv(a.n, kGradRows), (unsigned)nbatch), dim3(256), 0, st, a);
 }
-void launch_gap_param(hipStream_t st, const GapParam &a, bool design) {
-    if (a.n <= 0 || a.nobs <= 0) return;
+void launch_gap_param(hipStream_t st, const GapParam &a, bool design, int nbatch) {
+    if (a.n <= 0 || a.nobs <= 0 || nbatch <= 0) return;
     const unsigned nb = (unsigned)gap_obs_blocks(design, a.n, a.nobs);
-    if (design) hipLaunchKernelGGL(k_gap_param, dim3(nb), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_gap_param_node, dim3(nb), dim3(kGapNode), 0, st, a);
+    if (design) hipLaunchKernelGGL(k_gap_param, dim3(nb, (unsigned)nbatch), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_gap_param_node, dim3(nb, (unsigned)nbatch), dim3(kGapNode), 0, st, a);
 }
-void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, double *out) {
-    hipLaunchKernelGGL(k_gap_final, dim3(1), dim3(kFisherFinal), 0, st, gpart, ng, ppart, np, out);
+void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, const unsigned char *active, int nbatch, double *out) {
+    if (nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_final, dim3((unsigned)nbatch), dim3(kFisherFinal), 0, st, gpart, ng, ppart, np, active, out);
+}
+void launch_gap_copy(hipStream_t st, long long n, const double *src, long long ss, double *dst, long long sd, const unsigned char *active, int nbatch) {
+    if (n <= 0 || nbatch <= 0 || !src) return;
+    hipLaunchKernelGGL(k_gap_copy, dim3((unsigned)((n + 255) / 256), (unsigned)nbatch), dim3(256), 0, st, n, src, ss, dst, sd, active);
+}
+void launch_gap_fill_failed(hipStream_t st, long long n, double *dst, long long sd, const unsigned char *active, int nbatch) {
+    if (n <= 0 || nbatch <= 0 || !active) return;
+    hipLaunchKernelGGL(k_gap_copy, dim3((unsigned)((n + 255) / 256), (unsigned)nbatch), dim3(256), 0, st, n, (const double *)nullptr, 0LL, dst, sd, active);
 }
 
 }  // namespace gmrfx

@@ -314,14 +314,18 @@ struct FisherDesign {
 // inactive members' pairs are left
 void launch_fisher_design(hipStream_t st, const FisherDesign &a, int nbatch, double *out);
 
-// ga_pullback.hip -- the array arithmetic of the implicit-function rule of the Gaussian approximation (gmrfx_ga_pullback). The solve
-// in the middle is the handle's own; these are the kernels on either side of it. Node form: one thread per node, kGapNode nodes per
-// workgroup. Design form: the lane-group layout of fisher_design.hip (kDesignLanes lanes per row of A / per node, kDesignRows per
-// workgroup), the columns of A cut into chunks by the same design_chunks() rule. The pattern and mean kernels have the layout of
-// k_grad_pattern / k_grad_mubar (device_plan.h: kGradLanes, kGradCols, kGradRows).
+// ga_pullback.hip -- the array arithmetic of the implicit-function rule of the Gaussian approximation (gmrfx_ga_pullback,
+// gmrfx_batch_ga_pullback). The solve in the middle is the handle's own; these are the kernels on either side of it. Node form: one
+// thread per node, kGapNode nodes per workgroup. Design form: the lane-group layout of fisher_design.hip (kDesignLanes lanes per row of
+// A / per node, kDesignRows per workgroup), the columns of A cut into chunks by the same design_chunks() rule. The pattern and mean
+// kernels have the layout of k_grad_pattern / k_grad_mubar (device_plan.h: kGradLanes, kGradCols, kGradRows).
+// nbatch members (a plain handle is one, strides 0, scalars by value, nobody masked): the member in the grid's second dimension
+// (the first in k_gap_final), ONE copy of every table, the data set and the member's slice of the Hessian map; per-member cotangents,
+// points, work vectors and partial sums. A workgroup never spans two members; active (nbatch bytes, nullable = all): a member whose
+// byte is 0 is skipped by every workgroup before its first load, and nothing of it is written.
 constexpr int kGapNode = 256;
 inline int gap_node_blocks(int n) { return (n + kGapNode - 1) / kGapNode; }
-// workgroups of the per-observation kernels (k_gap_point*, k_gap_param*), and so the partial sums each of them leaves
+// workgroups of the per-observation kernels (k_gap_point*, k_gap_param*), and so the partial sums each of them leaves per member
 inline int gap_obs_blocks(bool design, long long n, long long nobs) { return design ? design_blocks(nobs) : gap_node_blocks((int)n); }
 struct GapPoint {
     int n, nobs, family;
@@ -339,9 +343,14 @@ struct GapPoint {
     double param, logparam;
     double *t;                   // design form, nobs: t_i = c_i d3_i
     double *xbar;                // node form: mubar_i - t_i, n
-    double *ppart;               // sum of c_i dp_i per workgroup
+    double *ppart;               // sum of c_i dp_i per workgroup; member k's at + k gap_obs_blocks(...)
+    // the members, behind what one member needs (a plain handle leaves them zero): member k's G at + k sg (hmap is the MEMBER's slice:
+    // positions in one member's values), x at + k sx, mubar at + k sm, t at + k nobs, xbar at + k sw
+    long long sg, sx, sm, sw;
+    const double *param_k, *logparam_k;  // nullable: one per member, in place of param / logparam
+    const unsigned char *active; // nullable = all
 };
-void launch_gap_point(hipStream_t st, const GapPoint &a, bool design);
+void launch_gap_point(hipStream_t st, const GapPoint &a, bool design, int nbatch);
 struct GapGather {
     int n, ncc;
     const long long *acp;        // A by columns
@@ -352,19 +361,35 @@ struct GapGather {
     const int *chl;
     const double *t, *mubar;     // mubar nullable
     double *cpart, *xbar;
+    // the members: member k's t at + k st, mubar at + k sm, cpart at + k sc, xbar at + k sw
+    long long st, sm, sc, sw;
+    const unsigned char *active;
 };
-void launch_gap_gather(hipStream_t st, const GapGather &a);
+void launch_gap_gather(hipStream_t st, const GapGather &a, int nbatch);
 struct GapPattern {
     int n;
-    const long long *colptr;     // the pattern of Q
+    const long long *colptr;     // the MEMBER's pattern of Q
     const int *row;
     const double *G;             // nullable: 0
     const double *lam, *x, *mu;  // mu nullable
     double *out;                 // nnz; may be G itself
+    // the members: member k's G and out at + k sg, lam at + k sw, x at + k sx, mu at + k smu (0: one mean for all)
+    long long sg, sw, sx, smu;
+    const unsigned char *active;
 };
-void launch_gap_pattern(hipStream_t st, const GapPattern &a);
-// out_i = sum_q val[pos[q]] lam[col[q]] over row i of Symmetric(Q) (RbmcSym)
-void launch_gap_mean(hipStream_t st, int n, const long long *rp, const int *col, const int *pos, const double *val, const double *lam, double *out);
+void launch_gap_pattern(hipStream_t st, const GapPattern &a, int nbatch);
+// out_i = sum_q val[pos[q]] lam[col[q]] over row i of the member's Symmetric(Q) (RbmcSym); member k's val at + k nnz, lam at + k sw,
+// out at + k so
+struct GapMean {
+    int n;
+    const long long *rp;
+    const int *col, *pos;
+    const double *val, *lam;
+    double *out;
+    long long nnz, sw, so;
+    const unsigned char *active;
+};
+void launch_gap_mean(hipStream_t st, const GapMean &a, int nbatch);
 struct GapParam {
     int n, nobs, family;
     const double *lam, *x;
@@ -374,11 +399,19 @@ struct GapParam {
     const int *acol;
     const double *aval, *offset;
     double param, logparam;
-    double *gpart;               // sum of (A lam)_i gp_i per workgroup
+    double *gpart;               // sum of (A lam)_i gp_i per workgroup; member k's at + k gap_obs_blocks(...)
+    // the members: member k's lam at + k sw, x at + k sx
+    long long sw, sx;
+    const double *param_k, *logparam_k;
+    const unsigned char *active;
 };
-void launch_gap_param(hipStream_t st, const GapParam &a, bool design);
-// out[0] = sum gpart - sum ppart (np / ng = 0: that sum is 0)
-void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, double *out);
+void launch_gap_param(hipStream_t st, const GapParam &a, bool design, int nbatch);
+// out[k] = sum of member k's gpart - sum of its ppart (np / ng = 0: that sum is 0); one workgroup per member, inactive members' left
+void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, const unsigned char *active, int nbatch, double *out);
+// dst_k = src_k (n entries; member k's at + k sd / + k ss) for the active members; dst_k = NaN for the INACTIVE ones (gap_fill_failed:
+// what a member whose factorisation or W_k failed gets in its output slices)
+void launch_gap_copy(hipStream_t st, long long n, const double *src, long long ss, double *dst, long long sd, const unsigned char *active, int nbatch);
+void launch_gap_fill_failed(hipStream_t st, long long n, double *dst, long long sd, const unsigned char *active, int nbatch);
 
 // predictive.hip -- the marginals of the linear predictor (gmrfx_predictor_marginals) and the quadrature scores over them
 // (gmrfx_predictive_scores). Node form: one thread per observation, kPredNode per workgroup. Design form and the scores: the lane-group

@@ -89,6 +89,7 @@ EXPORTS = [
     "gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev",
     "gmrfx_batch_obs_set_design", "gmrfx_batch_obs_hess_map", "gmrfx_batch_obs_design_info",
     "gmrfx_batch_obs_set_param", "gmrfx_batch_constrained_gaussian_approximation", "gmrfx_batch_constrained_gaussian_approximation_dev",
+    "gmrfx_batch_ga_pullback", "gmrfx_batch_ga_pullback_dev",
 ]
 
 
@@ -268,6 +269,8 @@ def lib(cdll=C.CDLL):
         L.gmrfx_gaussian_approximation_dev.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]
         L.gmrfx_ga_pullback.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.gmrfx_ga_pullback_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.gmrfx_batch_ga_pullback.argtypes = [vp, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_ga_pullback_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]
         L.gmrfx_obs_design_rows.argtypes = [vp, vp, vp, vp]
         L.gmrfx_obs_pointwise_const.argtypes = [vp, vp]
         L.gmrfx_predictor_marginals.argtypes = [vp, vp, i32, vp, vp, vp]

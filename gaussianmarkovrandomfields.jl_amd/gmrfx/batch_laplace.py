@@ -260,3 +260,42 @@ class MI355XBatchLaplace(MI355XBatchBackend):
             ci = self.constraint_info(check_posdef=False)
             out["logdet_W"] = np.where(st["failed"] | (ci["cinfo"] != 0), np.nan, ci["logdet_W"])
         return out
+
+    # -- the pullback of the Gaussian approximation, per member (include/gmrfx.h "The same pullback for every member of a batched handle")
+    def ga_pullback(self, X, mean=None, mubar=None, Qbar=None, project: bool = False, refactorize: bool = False,
+                    want_Qbar_prior: bool = True, want_mubar_prior: bool = True, want_lambda: bool = True):
+        """The implicit-function rule at every member's mode (gmrfx_batch_ga_pullback), the link between logpdf_grad and pattern_dot.
+        X (n, B); mean (n,) for every member or (n, B); mubar (n, B) / Qbar (nnz, B, on the pattern, as logpdf_grad returns it): the
+        cotangents of the posterior means / precisions, either None (zero). Returns (Qbar_prior (nnz, B), mubar_prior (n, B), lam
+        (n, B), param (B,), check (B,), info (B,)); the arrays not asked for are None. project: lam_k is projected with the batch
+        constraint; refactorize: every member is factorised at Q_p,k - H(x_k) first (otherwise the handle holds those factors:
+        gaussian_approximation with refactorize_final=True). A member whose factorisation (info[k] = -1) or W_k (1 + the failing
+        pivot) failed does not raise: its columns, param[k] and check[k] are NaN, the others are complete."""
+        Xf, sx = self._points(X, "X")
+        mu, smu = self._points(mean, "mean", shared_ok=True)
+        mb, _ = self._points(mubar, "mubar")
+        qb = None if Qbar is None else self._values(Qbar)
+        qp = np.empty((self._nnz, self.nbatch), order="F") if want_Qbar_prior else None
+        mp = np.empty((self.n, self.nbatch), order="F") if want_mubar_prior else None
+        lam = np.empty((self.n, self.nbatch), order="F") if want_lambda else None
+        out = np.empty((2, self.nbatch), order="F")
+        info = np.zeros(self.nbatch, np.int64)
+        flags = int(bool(project)) | (int(bool(refactorize)) << 1)
+        rc = lib().gmrfx_batch_ga_pullback(self._h, ptr(Xf), sx, ptr(mu), smu, ptr(mb), ptr(qb), flags, ptr(qp), ptr(mp), ptr(lam), ptr(out),
+                                           ptr(info))
+        check(rc, self._h)
+        return qp, mp, lam, out[0].copy(), out[1].copy(), info
+
+    def ga_pullback_dev(self, d_x: int, sx: int, d_mu: int = 0, smu: int = 0, d_mubar: int = 0, d_Qbar: int = 0, d_Qbar_prior: int = 0,
+                        d_mubar_prior: int = 0, d_lambda: int = 0, project: bool = False, refactorize: bool = False):
+        """Device pointers (0 = absent): member k's x at + k sx, mu at + k smu (0: one mean), mubar / mubar_prior / lambda at + k n,
+        Qbar / Qbar_prior at + k nnz; d_Qbar_prior may be d_Qbar. Returns (param (B,), check (B,), info (B,))."""
+        if not d_x:
+            raise ValueError("ga_pullback_dev: null pointer")
+        out = np.empty((2, self.nbatch), order="F")
+        info = np.zeros(self.nbatch, np.int64)
+        flags = int(bool(project)) | (int(bool(refactorize)) << 1)
+        rc = lib().gmrfx_batch_ga_pullback_dev(self._h, d_x, sx, d_mu or None, smu, d_mubar or None, d_Qbar or None, flags, d_Qbar_prior or None,
+                                               d_mubar_prior or None, d_lambda or None, ptr(out), ptr(info))
+        check(rc, self._h)
+        return out[0].copy(), out[1].copy(), info

@@ -953,6 +953,27 @@ function pattern_dot(bb::MI355XBatch, G::Matrix{Float64}, J::Array{Float64, 3})
     return out
 end
 
+# The pullback of gaussian_approximation for every member (gmrfx_batch_ga_pullback): the link between logpdf_grad(bb, ...) and
+# pattern_dot(bb, ...). X n x nbatch (the modes); mean n x nbatch; mubar n x nbatch and Qbar nnz x nbatch as logpdf_grad returns them,
+# either `nothing`. Returns (Qbar_prior nnz x nbatch, mubar_prior, lambda n x nbatch, param_bar, lambda' xbar (nbatch each), info):
+# info[k] = 0, -1 (member k's factorisation failed) or 1 + the failing pivot of W_k; such a member's columns and results are NaN.
+function ga_pullback(bb::MI355XBatch, X::Matrix{Float64}; mean::Union{Nothing, Matrix{Float64}} = nothing,
+                     mubar::Union{Nothing, Matrix{Float64}} = nothing, Qbar::Union{Nothing, Matrix{Float64}} = nothing,
+                     project::Bool = false, refactorize::Bool = false)
+    size(X) == (bb.n, bb.nbatch) && (mean === nothing || size(mean) == (bb.n, bb.nbatch)) && (mubar === nothing || size(mubar) == (bb.n, bb.nbatch)) &&
+        (Qbar === nothing || size(Qbar) == (bb.nnz, bb.nbatch)) || throw(DimensionMismatch("X, mean, mubar must be n x nbatch, Qbar nnz x nbatch"))
+    qp = Matrix{Float64}(undef, bb.nnz, bb.nbatch); mp = Matrix{Float64}(undef, bb.n, bb.nbatch); lam = Matrix{Float64}(undef, bb.n, bb.nbatch)
+    out = zeros(2, bb.nbatch); inf = zeros(Int64, bb.nbatch)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    mb = mubar === nothing ? Ptr{Float64}(C_NULL) : pointer(mubar)
+    qb = Qbar === nothing ? Ptr{Float64}(C_NULL) : pointer(Qbar)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    GC.@preserve X mean mubar Qbar qp mp lam out inf check(ccall((:gmrfx_batch_ga_pullback, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, X, bb.n, mu, bb.n, mb, qb, flags, qp, mp, lam, out, inf), bb.h)
+    return qp, mp, lam, out[1, :], out[2, :], inf
+end
+
 # max(diag Sigma_k - rowsum(B_k^2), 0) of every member: n x nbatch; without a constraint selinv_diag(bb)
 function constrained_var(bb::MI355XBatch)
     out = Matrix{Float64}(undef, bb.n, bb.nbatch)

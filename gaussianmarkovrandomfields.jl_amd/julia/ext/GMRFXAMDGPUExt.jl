@@ -194,6 +194,29 @@ function ga_pullback_dev!(b::MI355XBackend, x::ROCVector{Float64}; mean::Union{N
     check(code, b.h)
     return out[1], out[2]
 end
+# the same for the members of a batch (gmrfx_batch_ga_pullback_dev): X / mean / mubar / mubar_prior / lambda n x B, Qbar / Qbar_prior nnz x B
+# (Qbar_prior may be Qbar itself: the Qbar of logpdf_grad_dev! goes in, pattern_dot_dev takes it on); returns (param_bar, lambda' xbar, info)
+function ga_pullback_dev!(bb::MI355XBatch, X::ROCMatrix{Float64}; mean::Union{Nothing, ROCMatrix{Float64}} = nothing,
+                          mubar::Union{Nothing, ROCMatrix{Float64}} = nothing, Qbar::Union{Nothing, ROCMatrix{Float64}} = nothing,
+                          Qbar_prior::Union{Nothing, ROCMatrix{Float64}} = nothing, mubar_prior::Union{Nothing, ROCMatrix{Float64}} = nothing,
+                          lambda::Union{Nothing, ROCMatrix{Float64}} = nothing, project::Bool = false, refactorize::Bool = false)
+    size(X, 1) == bb.n && size(X, 2) == bb.nbatch || throw(DimensionMismatch("X must be n x nbatch"))
+    for a in (mubar, mubar_prior, lambda)
+        a === nothing || (size(a) == (bb.n, bb.nbatch) && stride(a, 2) == bb.n) || throw(DimensionMismatch("mubar / mubar_prior / lambda must be dense n x nbatch"))
+    end
+    for a in (Qbar, Qbar_prior)
+        a === nothing || (size(a) == (bb.nnz, bb.nbatch) && stride(a, 2) == bb.nnz) || throw(DimensionMismatch("Qbar / Qbar_prior must be dense nnz x nbatch"))
+    end
+    AMDGPU.synchronize()
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : devptr(a)
+    out = zeros(2, bb.nbatch); inf = zeros(Int64, bb.nbatch)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    smu = mean === nothing ? 0 : stride(mean, 2)
+    GC.@preserve X mean mubar Qbar Qbar_prior mubar_prior lambda out inf check(ccall((:gmrfx_batch_ga_pullback_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, devptr(X), stride(X, 2), p(mean), smu, p(mubar), p(Qbar), flags, p(Qbar_prior), p(mubar_prior), p(lambda), out, inf), bb.h)
+    return out[1, :], out[2, :], inf
+end
 # the members of a batch: Qbar nnz x B, mubar / Z / mean n x B; returns info
 function logpdf_grad_dev!(Qbar::ROCMatrix{Float64}, mubar::ROCMatrix{Float64}, bb::MI355XBatch, Z::ROCMatrix{Float64}, ybar::Vector{Float64};
                           mean::Union{Nothing, ROCMatrix{Float64}} = nothing, d_nz::Union{Nothing, ROCMatrix{Float64}} = nothing)

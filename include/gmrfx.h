@@ -885,6 +885,45 @@ int32_t gmrfx_ga_pullback_dev(gmrfx_handle *h, const double *d_x, const double *
                               double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda, double *out /* host, 2 */);
 int32_t gmrfx_obs_design_rows(const gmrfx_handle *h, int64_t *ptr /* nobs + 1 */, int64_t *pos /* terms */, double *w /* terms */);
 
+/* ---- The same pullback for every member of a batched handle ------------------------------------------------------------------------------
+ * The middle link of the batched gradient chain gmrfx_batch_logpdf_grad_dev -> gmrfx_batch_ga_pullback_dev -> gmrfx_batch_pattern_dot_dev:
+ * the formulas of gmrfx_ga_pullback, member by member, with Q_p,k the values of gmrfx_batch_set_prior, the ONE likelihood of
+ * gmrfx_batch_obs_set / gmrfx_batch_obs_set_design (node or design form) and param[k]. ONE forest solve and one launch per step for
+ * all members.
+ * STRIDES. Member k's mode at x + k sx (sx >= n) and prior mean at mu + k smu (smu >= n, or 0: one mean for all), as in
+ * gmrfx_batch_fisher_eval. The cotangents and the outputs are dense per member, as gmrfx_batch_logpdf_grad has them: mubar, mubar_prior
+ * and lambda at + k n, Qbar and Qbar_prior at + k nnz (nnz of the member's pattern); the Qbar of gmrfx_batch_logpdf_grad_dev is passed
+ * straight in and Qbar_prior straight on to gmrfx_batch_pattern_dot_dev. Qbar_prior may be Qbar itself. out[2 k], out[2 k + 1]: member
+ * k's parameter cotangent and lam_k' xbar_k.
+ * FLAGS. Bit 0: lam_k <- lam_k - A~_k' W_k^-1 (A lam_k) with the batch constraint (gmrfx_batch_constraints_set). A handle that holds a
+ * batch constraint is not refused without the bit: bit clear is the plain solve, as on a plain handle. Bit 1: one batched evaluation of
+ * every member's Hessian at its x, then the forest's gmrfx_refactorize_update; without it the handle must hold the factor of every
+ * Q_p,k - H(x_k) already -- gmrfx_batch_gaussian_approximation with its flag bit 3 leaves it.
+ * INFO (host, nbatch, nullable), the convention of gmrfx_batch_logpdf_grad: 0; -1 when member k's factorisation failed (under bit 1, or
+ * held); 1 + the failing pivot when its W_k did (bit 0). Such a member is masked out of every launch: its requested output slices and
+ * its two entries of out are NaN, nothing else of it is touched, and every other member is computed as if it were not there. With info
+ * NULL such a member makes the call return GMRFX_ERR_NOT_POSDEF; the healthy members' outputs are written all the same.
+ * BITS. No atomics; member k's sums are formed in the plain call's orders whatever the other members hold. Without bit 0, member k's
+ * outputs and its two results have the bits of gmrfx_ga_pullback on a plain handle of Q_p,k, param[k], x_k, mu_k and its cotangents,
+ * whichever members share the batch; host and _dev forms agree bit for bit, whatever the alignment of the operands (8 bytes suffice).
+ * Under bit 0 the preparation of W_k is the batch constraint's own (see gmrfx_batch_constraints_set): close to, not bitwise, the plain one.
+ * Work memory on the device, allocated on the first call, on the handle's books and dropped with the likelihood by
+ * gmrfx_batch_obs_set*: nbatch (2 n + nobs) doubles, the partial sums and nbatch results, and in design form ONE transposed term table
+ * (12 B per term); under bit 1 the loop's work area (5 n + hess_len doubles per member) if the loop has not allocated it yet.
+ * Errors: INVALID_ARG for x or out null, sx < n, smu neither 0 nor >= n, unknown flag bits, mubar and Qbar both null, every output
+ * null, bit 0 without a batch constraint, no batch likelihood (a plain handle that has none among them), no prior or a map that is not
+ * the likelihood's, a sharded handle, a plain constraint set or a plain design likelihood held -- all before GMRFX_ERR_NO_DEVICE on
+ * symbolic_only handles where they need no device state; GMRFX_ERR_NOT_FACTORIZED without bit 1 before the first factorisation;
+ * GMRFX_ERR_NOT_POSDEF as above. gmrfx_ga_pullback keeps refusing batched handles.
+ * LIMITS: nbatch <= 65535 (the member is the second dimension of the launch grid); otherwise those of gmrfx_ga_pullback. */
+int32_t gmrfx_batch_ga_pullback(gmrfx_handle *h, const double *x, int64_t sx, const double *mu /* nullable */, int64_t smu /* 0: one mean for all */,
+                                const double *mubar /* n x nbatch, nullable */, const double *Qbar /* nnz x nbatch, nullable */, int32_t flags,
+                                double *Qbar_prior /* nnz x nbatch, nullable */, double *mubar_prior /* n x nbatch, nullable */,
+                                double *lambda /* n x nbatch, nullable */, double *out /* host, 2 x nbatch */, int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_ga_pullback_dev(gmrfx_handle *h, const double *d_x, int64_t sx, const double *d_mu, int64_t smu, const double *d_mubar,
+                                    const double *d_Qbar, int32_t flags, double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda,
+                                    double *out /* host, 2 x nbatch */, int64_t *info /* host, nbatch, nullable */);
+
 /* ---- Linear-predictor marginals and predictive scores ----------------------------------------------------------------------------------
  * What follows a fit: linear_predictor_marginals(ga, obs_lik) of the reference (src/linear_predictor_marginals.jl:58-195, with the
  * constraint correction and clamp of _subtract_constraint_correction!, :189-195) and pointwise_loglik (src/observation_models/

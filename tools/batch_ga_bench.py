@@ -21,7 +21,14 @@ gmrfx_batch_set_prior + gmrfx_batch_gaussian_approximation_dev per sweep, agains
 node, B = 50 precisions. gmrfx_batch_set_prior + gmrfx_batch_constrained_gaussian_approximation_dev per sweep on a batched handle holding
 the constraint, against the same 50 approximations on ONE plain handle under gmrfx_constraints_set (gmrfx_set_prior +
 gmrfx_gaussian_approximation_dev per member; the data set goes in once). Output: profiles/batch_ga_con_bench.json by default.
-usage: tools/batch_ga_bench.py [--design | --constraint] [--grid 100] [--batch 50] [--reps 15] [--warmup 3] [--out profiles/batch_ga_bench.json]"""
+--pullback [--design]: the gradient chain of the sweep, dL/dtheta_k of -logpdf(posterior_k, x*_k) for every member with
+theta_k scaling member k's prior: gmrfx_batch_set_prior + gmrfx_batch_gaussian_approximation_dev (flag bit 3) ->
+gmrfx_batch_logpdf_grad_dev (ybar = -1) -> gmrfx_batch_ga_pullback_dev (Qbar_prior over Qbar) -> gmrfx_batch_pattern_dot_dev, against
+the same chain run B times on ONE plain handle (gmrfx_set_prior + gmrfx_gaussian_approximation_dev -> gmrfx_logpdf_grad_dev ->
+gmrfx_ga_pullback_dev -> gmrfx_pattern_dot_dev per member). Node case and, with --design, the design case above (3 n points and an
+intercept). Whether the B gradients of both routes agree bit for bit is reported (gradients_same_bits). Output: profiles/batch_ga_pullback_bench[_design].json.
+usage: tools/batch_ga_bench.py [--design | --constraint | --pullback [--design]] [--grid 100] [--batch 50] [--reps 15] [--warmup 3]
+                               [--out profiles/batch_ga_bench.json]"""
 import argparse
 import json
 import os
@@ -138,6 +145,71 @@ def design(a):
     return row
 
 
+def pullback(a):
+    """the batched gradient chain against the plain chain member by member (module docstring)"""
+    B, g = a.batch, a.grid
+    if a.design:
+        Qs, pts, A, y = design_problem(g, B, np.random.default_rng(g))
+        order = dict(ordering=gmrfx.PinDenseColumns())
+    else:
+        Qs, pts = members(g, B, np.random.default_rng(g))
+        A, y, order = None, np.random.default_rng(1).poisson(20.0, Qs[0].shape[0]).astype(float), {}
+    n, nnz = Qs[0].shape[0], Qs[0].nnz
+    NZ = np.asfortranarray(np.stack([Q.data for Q in Qs], axis=1))
+    dev = "cuda:0"
+    kw = dict(refactorize_final=True)
+    bb = gmrfx.MI355XBatchLaplace(Qs[0], B, coords=pts, device=0, **order)
+    if a.design:
+        bb.set_design_observations("poisson", y, A, param=0.0)
+    else:
+        bb.set_observations("poisson", y, param=0.0)
+    perm = bb.ordering_permutation()
+    dX, dX0 = torch.empty(n * B, dtype=torch.float64, device=dev), torch.zeros(n * B, dtype=torch.float64, device=dev)
+    dG = torch.empty(nnz * B, dtype=torch.float64, device=dev)
+    dJ = torch.from_numpy(np.ascontiguousarray(NZ.T).reshape(-1)).to(dev)          # dQ_k / dtheta_k at theta_k = 1: Q_k itself
+    torch.cuda.synchronize()
+    res = {}
+
+    def batched():
+        bb.set_prior(NZ)
+        res["ga"] = bb.gaussian_approximation_dev(dX.data_ptr(), n, d_x0=dX0.data_ptr(), sx0=n, **kw)
+        bb.logpdf_grad_dev(dX.data_ptr(), n, -1.0, d_Qbar=dG.data_ptr(), d_mu=dX.data_ptr())
+        res["info"] = bb.ga_pullback_dev(dX.data_ptr(), n, 0, 0, 0, dG.data_ptr(), dG.data_ptr(), 0, 0)[2]
+        res["grad"] = bb.pattern_dot_dev(dG.data_ptr(), dJ.data_ptr(), nnz, nnz, 1)[0].copy()
+    t_b = timed(batched, a.reps, a.warmup)
+    assert (res["info"] == 0).all() and res["ga"]["converged"].all()
+
+    plain = gmrfx.MI355XBackend(Qs[0], ordering=perm, device=0, factorize=False)
+    if a.design:
+        plain.set_design_observations("poisson", y, A)
+        hmap = plain.observations_hess_map()
+    else:
+        plain.set_observations("poisson", y)
+        hmap = diag_positions(Qs[0])
+    dx, dg = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(nnz, dtype=torch.float64, device=dev)
+    grad = np.zeros(B)
+
+    def sequential():
+        for k in range(B):
+            plain.set_prior(NZ[:, k], hmap)
+            plain.gaussian_approximation_dev(dx.data_ptr(), d_x0=dX0.data_ptr(), **kw)
+            plain.logpdf_grad_dev(dx.data_ptr(), d_Qbar=dg.data_ptr(), d_mu=dx.data_ptr(), ybar=-1.0)
+            plain.ga_pullback_dev(dx.data_ptr(), 0, 0, dg.data_ptr(), dg.data_ptr(), 0, 0)
+            grad[k] = plain.pattern_dot_dev(dg.data_ptr(), dJ.data_ptr() + 8 * k * nnz, nnz, 1)[0]
+    t_s = timed(sequential, a.reps, a.warmup)
+    plain.close()
+    same = bool(np.array_equal(grad.view(np.int64), res["grad"].view(np.int64)))
+    row = {"tool": "tools/batch_ga_bench.py --pullback" + (" --design" if a.design else ""), "device": torch.cuda.get_device_name(0),
+           "source_tree_hash": _lib.source_tree_hash(), "n": n, "nnz": int(nnz), "nobs": int(len(y)), "grid": g, "B": B, "family": "poisson",
+           "reps": a.reps, "warmup": a.warmup, "batched_chain": t_b, "one_plain_handle_chain_sequential": t_s,
+           "ms_per_member_batched": t_b["median_ms"] / B, "ms_per_member_sequential": t_s["median_ms"] / B,
+           "speedup_vs_sequential": t_s["median_ms"] / t_b["median_ms"], "gradients_same_bits": same,
+           "gradients_max_rel_diff": float(np.max(np.abs(grad - res["grad"]) / np.abs(grad))), "iterations": res["ga"]["iterations"].tolist()}
+    print(json.dumps(row), flush=True)
+    bb.close()
+    return row
+
+
 def torus_besag(g, eps=1e-6):
     """graph Laplacian of the g x g periodic lattice + eps I (the intrinsic CAR model of the reference's besag.jl, regularised)"""
     idx = np.arange(g * g).reshape(g, g)
@@ -242,8 +314,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--design", action="store_true")
     ap.add_argument("--constraint", action="store_true")
+    ap.add_argument("--pullback", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.pullback:
+        row = pullback(a)
+        out = a.out or os.path.join(ROOT, "profiles", "batch_ga_pullback_bench_design.json" if a.design else "batch_ga_pullback_bench.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(row, f, indent=1)
+        return
     if a.design or a.constraint:
         row = constraint(a) if a.constraint else design(a)
         if a.constraint and a.out is None:

@@ -16,7 +16,12 @@ around the solve (the time is measured, the bytes are not):
           + 24 n (lam, x, mu gathered);  mean 16 nnz_sym + 8 (n + 1) + 16 n
   design  point 12 nnz(A) + 12 terms + 8 terms (G gathered through the map) + 16 (nobs + 1) + nobs (8 y + 8 aux + 8 t) + 8 n;
           gather 12 nnz(A) + 12 (n + 1) + 8 nobs + 16 n;  pattern and mean as above
-usage: tools/ga_pullback_bench.py [--design [--nobs 1000000]] [--grid 1000] [--reps 15] [--warmup 3] [--out profiles/ga_pullback_bench[_design].json]"""
+--old PATH/TO/libgmrfx.so: an A/B of gmrfx_ga_pullback_dev between this build and another one (the parent commit's), alternating in
+ONE process, each with its own handle on the same problem: --rounds medians per side. The rule, set beforehand: the new median lies
+inside the other build's min .. max; the outputs must have its bits. --first: whose handle is created first (it is part of the
+measurement: DESIGN.md section 6m). Written to profiles/ga_pullback_ab[_design].json.
+usage: tools/ga_pullback_bench.py [--design [--nobs 1000000]] [--grid 1000] [--reps 15] [--warmup 3] [--old LIB [--rounds 4] [--first old|new]]
+                                  [--out profiles/ga_pullback_bench[_design].json]"""
 import argparse
 import json
 import os
@@ -35,6 +40,48 @@ from gmrfx import _lib, spde  # noqa: E402
 from fisher_bench import timed  # noqa: E402
 
 
+def ab(a, libs, handles, A, y, aux, Q, cols, ins, outs, res):
+    """the plain call on both builds, alternating; the old build's handle gets the likelihood and prior the new one has"""
+    dx, dm, db, dG = ins
+    oq, om, ol = outs
+    _lib.use(libs["old"])
+    bo = handles["old"]
+    if a.design:
+        bo.set_design_observations("poisson", y, A, aux=aux)
+        bo.set_prior(Q.data, bo.observations_hess_map())
+    else:
+        bo.set_observations("poisson", y, aux=aux)
+        bo.set_prior(Q.data, np.flatnonzero(Q.indices == cols).astype(np.int64))
+    medians, bits, results = {"old": [], "new": []}, {}, {}
+    for tag in ("old", "new"):
+        _lib.use(libs[tag])
+        results[tag] = handles[tag].ga_pullback_dev(dx.data_ptr(), dm.data_ptr(), db.data_ptr(), dG.data_ptr(), oq.data_ptr(), om.data_ptr(),
+                                                    ol.data_ptr(), refactorize=True)
+        torch.cuda.synchronize()
+        bits[tag] = [t.cpu().numpy().copy() for t in (oq, om, ol)]
+    for r in range(a.rounds):
+        for tag in (("old", "new") if r % 2 == 0 else ("new", "old")):
+            _lib.use(libs[tag])
+            be = handles[tag]
+            t = timed(lambda: be.ga_pullback_dev(dx.data_ptr(), dm.data_ptr(), db.data_ptr(), dG.data_ptr(), oq.data_ptr(), om.data_ptr(), 0),
+                      a.reps, a.warmup)
+            medians[tag].append(t["median_ms"])
+    for tag in ("old", "new"):          # every handle is destroyed by the library that made it (close() goes to the library in use)
+        _lib.use(libs[tag])
+        handles[tag].close()
+    _lib.use(libs["new"])
+    old, new = medians["old"], medians["new"]
+    res.update({"tool": "tools/ga_pullback_bench.py --old", "rounds": a.rounds, "handle_created_first": a.first, "old_median_ms": old, "new_median_ms": new,
+                "new_inside_old_min_max": bool(min(old) <= float(np.median(new)) <= max(old)),
+                "new_median_above_old_max_ms": float(np.median(new)) - max(old),
+                "same_bits": bool(all(np.array_equal(u.view(np.int64), v.view(np.int64)) for u, v in zip(bits["old"], bits["new"]))
+                                  and results["old"] == results["new"])})
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=1000)
@@ -42,17 +89,32 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--design", action="store_true")
     ap.add_argument("--nobs", type=int, default=1000000)
+    ap.add_argument("--old", default=None, help="another build of libgmrfx.so: A/B of gmrfx_ga_pullback_dev against it")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--first", choices=("old", "new"), default="old", help="whose handle is created first (DESIGN.md 6m: it is part of the measurement)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "ga_pullback_bench_design.json" if a.design else "ga_pullback_bench.json")
+        stem = "ga_pullback_ab" if a.old else "ga_pullback_bench"
+        a.out = os.path.join(ROOT, "profiles", stem + ("_design.json" if a.design else ".json"))
     mesh = spde.grid_mesh_2d(a.grid, a.grid, jitter=0.25, seed=0)
     Q = sp.csc_matrix(spde.matern_precision(mesh, smoothness=0, range_=0.2))
     Q = sp.csc_matrix((Q + Q.T) * 0.5)
     Q.sort_indices()
     n, nnz = Q.shape[0], Q.nnz
     rng = np.random.default_rng(0)
+    libs = {"new": _lib.lib()}
+    if a.old:
+        libs["old"] = _lib.load_from(a.old)
+    if a.old and a.first == "old":
+        _lib.use(libs["old"])
+        be_old = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+        _lib.use(libs["new"])
     be = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+    if a.old and a.first == "new":
+        _lib.use(libs["old"])
+        be_old = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+        _lib.use(libs["new"])
     dev = torch.device("cuda:0")
     cols = np.repeat(np.arange(n), np.diff(Q.indptr))
     S = sp.csr_matrix(sp.triu(Q) + sp.triu(Q, 1).T)
@@ -89,6 +151,8 @@ def main():
     assert Gs.nnz == nnz
     dx, dm, db, dG = (torch.from_numpy(v).to(dev) for v in (x, mu, mubar, G))
     oq, om, ol, dl = (torch.empty(k, dtype=torch.float64, device=dev) for k in (nnz, n, n, n))
+    if a.old:
+        return ab(a, libs, {"new": be, "old": be_old}, A, y, aux, Q, cols, (dx, dm, db, dG), (oq, om, ol), res)
     be.ga_pullback_dev(dx.data_ptr(), dm.data_ptr(), db.data_ptr(), dG.data_ptr(), oq.data_ptr(), om.data_ptr(), ol.data_ptr(), refactorize=True)
     diag = np.flatnonzero(Q.indices == cols)
 
