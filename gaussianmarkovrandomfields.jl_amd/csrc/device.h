@@ -340,6 +340,23 @@ public:
     // lpd, lcpo, elp, vlp per observation (device, each nullable) and their totals out4_host, computed either way.
     struct ScoreIO { const double *d_mu, *d_v; int K; const double *z, *w; double *d_lpd, *d_lcpo, *d_elp, *d_vlp; };
     void predictive_scores(const ObsHost &o, const ScoreIO &io, double *out4_host);
+    // The same for every member of a batched handle (gmrfx_batch_predictor_marginals, gmrfx_batch_predictive_scores), forest-wide, one
+    // launch per step: member k's mean at d_x + k sx, outputs dense per member (nobs each, member stride nobs). Needs the batch
+    // likelihood; the variance needs the forest's factorisation (the selected inverse is computed if absent). Bit 0 subtracts the
+    // BATCH constraint's correction per member and clamps (a held constraint without the bit is ignored). info_host (nbatch): 0, -1
+    // when member k's factorisation failed, 1 + the failing pivot when its W_k did (bit 0) -- such a member is masked out of every
+    // launch and gets NaN in its requested slices, nobody else's are touched; without d_v_eta no factor is looked at and nobody is
+    // masked. Returns 0, or 1 when some member failed. One synchronisation behind the last launch.
+    struct BPredIO { const double *d_x; long long sx; int flags; double *d_mu_eta, *d_v_eta, *d_pll; };
+    int batch_predictor_marginals(const RbmcSym &sym, const BObsHost &o, const BPredIO &io, long long *info_host);
+    // d_mu / d_v and the four outputs: nobs x nbatch; out_host: 4 per member. A member whose factorisation failed (when the handle
+    // holds one) is masked as above: info_host[k] = -1, NaN in its slices and totals.
+    int batch_predictive_scores(const BObsHost &o, const ScoreIO &io, double *out_host, long long *info_host);
+    // The mixture of the members' predictive distributions (gmrfx_batch_predictive_mixture; k_pred_mixture): w = nbatch weights omega_k,
+    // then nbatch logs of them (-inf: the member is never read), as the C ABI rounded them; d_mu, d_v, d_lpd (nullable): nobs x nbatch;
+    // the three outputs nobs each, nullable; *out_host = the sum of mix_lpd (NaN without d_lpd).
+    struct MixIO { const double *d_mu, *d_v, *d_lpd; double *d_mix_mu, *d_mix_v, *d_mix_lpd; };
+    void batch_predictive_mixture(const BObsHost &o, const std::vector<double> &w, const MixIO &io, double *out_host);
 
     bool factorized = false, selinv_valid = false;
     bool inverse_pending = false;   // dense inverses of the big fronts are computed lazily, on a side stream
@@ -696,14 +713,30 @@ private:
     void gap_launch(FisherDev &f, GapDev &g, const GapRun &r, const GapIO &io, double *out_host);
     // predictive state, built on the first gmrfx_predictor_marginals / gmrfx_predictive_scores for the likelihood in place (obs_set
     // drops it): the observed nodes in the caller's order (node form, 4 nobs bytes), the constants c (8 nobs), the plan's map (design
-    // form, 8 cnt), the scores' partial sums (4 per workgroup), totals and quadrature rule
+    // form, 8 cnt), the scores' partial sums (4 per workgroup), totals and quadrature rule. The batch slot (bpred_, of bfisher_;
+    // bobs_set and bobs_set_param drop it): the same tables once, c as ONE column (sc = 0; families 1, 2, 3) or one per member (sc =
+    // nobs; the families with a parameter), partial sums and totals per member, the member's diagonal positions (node form, 4 n bytes,
+    // on the first variance) and the mixture's weights with their pinned copy.
     struct PredDev {
-        DevBuf<int> idx;
+        long long nobs = 0, sc = 0;
+        int members = 1;
+        DevBuf<int> idx, dpos;
         DevBuf<long long> hmap;
-        DevBuf<double> c, part, out, quad;
-        PinnedBuf<double> h_out, h_quad;
-    } pred_;
+        DevBuf<double> c, part, out, quad, mixw;
+        PinnedBuf<double> h_out, h_quad, h_mixw;
+    } pred_, bpred_;
     void pred_tables(const ObsHost &o);
+    void bpred_tables(const BObsHost &o);
+    // what pred_tables and bpred_tables build alike, aside: the observation order or the plan's map, c (cols columns), the work of
+    // `members` members
+    PredDev pred_build(long long nobs, const std::vector<long long> &idx, const DesignPlan *plan, const std::vector<double> &c, int members);
+    // The launches of the marginals and of the scores for the members of a likelihood slot (f with its pullback state g, whose term
+    // table the design form reads, and its predictive state p), the ONE place the kernels' arguments are filled. Both only enqueue.
+    // dpos: the member's diagonal positions; B (m columns; m = 0: no correction): member k's at + k sb; sz: the member's stride in
+    // the offset table of Z; d_active (device, nullable = all): the members that take part.
+    struct PredRun { const int *dpos; const double *B; int m; long long sx, sz, sb, so; const unsigned char *d_active; };
+    void pred_marg_launch(const FisherDev &f, const GapDev &g, const PredDev &p, const PredRun &r, const PredIO &io);
+    void pred_score_launch(const FisherDev &f, PredDev &p, const ScoreIO &io, long long stride, const unsigned char *d_active);
     void fisher_check_map(const RbmcSym &sym, const char *who);
     std::vector<long long> h_hmap_;       // host copy of set_prior's map: fisher_eval checks that it is the diagonal's
     int prior_diag_ = -1;                 // -1: not looked at since set_prior, 0 / 1: the map is (not) "position of (i, i) for every i"
@@ -721,6 +754,8 @@ void hip_check(hipError_t e, const char *what);
 
 // out[k] = the term of observation k's log density that does not depend on x (obs_const.h), rounded to double; no device
 void obs_pointwise_const(const ObsHost &o, double *out);
+// the same at param[k] of every member, out: nobs x members (the families without a parameter repeat one column)
+void bobs_pointwise_const(const BObsHost &o, double *out);
 
 // slicing of a column-major n x nrhs host array for the page-locked staging ring (device.cpp: host_upload / host_download)
 struct HostIoPlan { long long cols_per = 1, ppc = 1, rows_per = 0, slot_doubles = 0, nsl = 0, reserve = 0; };

@@ -43,6 +43,7 @@ void Device::bobs_set(const RbmcSym &sym, const BObsHost &o) {
     HC(hipStreamSynchronize(stream));
     bfisher_ = std::move(f);
     bgap_ = GapDev{};        // (the batched pullback's tables belong to the likelihood: rebuilt on its next call)
+    bpred_ = PredDev{};      // (and so do the batched predictive calls')
     bprior_map_ok_ = -1;
 }
 
@@ -56,6 +57,7 @@ void Device::bobs_set_param(const std::vector<double> &param, const std::vector<
     HC(hipMemcpy(bfisher_.param_k, param.data(), nb * sizeof(double), hipMemcpyHostToDevice));
     HC(hipMemcpy(bfisher_.logparam_k, lp.data(), nb * sizeof(double), hipMemcpyHostToDevice));
     bfisher_.loglik_const = loglik_const;
+    bpred_ = PredDev{};      // (the constants of the pointwise log density belong to the parameters: rebuilt on the next predictive call)
 }
 
 void Device::bset_prior(const double *prior_nzval, const std::vector<long long> &map, bool design) {

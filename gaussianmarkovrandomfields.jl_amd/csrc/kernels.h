@@ -413,10 +413,15 @@ void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double 
 void launch_gap_copy(hipStream_t st, long long n, const double *src, long long ss, double *dst, long long sd, const unsigned char *active, int nbatch);
 void launch_gap_fill_failed(hipStream_t st, long long n, double *dst, long long sd, const unsigned char *active, int nbatch);
 
-// predictive.hip -- the marginals of the linear predictor (gmrfx_predictor_marginals) and the quadrature scores over them
-// (gmrfx_predictive_scores). Node form: one thread per observation, kPredNode per workgroup. Design form and the scores: the lane-group
-// layout of fisher_design.hip (kDesignLanes lanes per observation, kDesignRows observations per workgroup of 256 threads).
-constexpr int kPredNode = 256, kPredMaxNodes = 64, kPredNodesPerLane = kPredMaxNodes / kDesignLanes;
+// predictive.hip -- the marginals of the linear predictor (gmrfx_predictor_marginals, gmrfx_batch_predictor_marginals), the quadrature
+// scores over them (gmrfx_predictive_scores, gmrfx_batch_predictive_scores) and the mixture of the members' predictive distributions
+// (gmrfx_batch_predictive_mixture). Node form: one thread per observation, kPredNode per workgroup. Design form and the scores: the
+// lane-group layout of fisher_design.hip (kDesignLanes lanes per observation, kDesignRows observations per workgroup of 256 threads).
+// nbatch members (a plain handle is one, strides 0, scalars by value, nobody masked): the member in the grid's second dimension (the
+// first in k_pred_final), ONE copy of every table and of the data set; per-member points, selected inverse, B, constants, outputs and
+// partial sums. A workgroup never spans two members; active (nbatch bytes, nullable = all): a member whose byte is 0 is skipped by
+// every workgroup before its first load, and nothing of it is written.
+constexpr int kPredNode = 256, kPredMaxNodes = 64, kPredNodesPerLane = kPredMaxNodes / kDesignLanes, kPredMix = 256;
 struct PredMarg {
     int n, nobs, m, family;      // m: columns of B to subtract (0: no correction, no clamp)
     const double *x;             // the posterior mean, n
@@ -436,8 +441,14 @@ struct PredMarg {
     const double *c;             // the constant of every observation's log density, nobs
     double param, logparam;
     double *mu_eta, *v_eta, *pll;        // nobs each, each nullable
+    // the members, behind what one member needs (a plain handle leaves them zero): member k's x at + k sx, its entries of zoff at
+    // + k sz (dpos and hmap are the MEMBER's: positions in one member's values; the offsets themselves are absolute), B at + k sb,
+    // c at + k sc (0: one column for all), mu_eta / v_eta / pll at + k so
+    long long sx, sz, sb, sc, so;
+    const double *param_k, *logparam_k;  // nullable: one per member, in place of param / logparam
+    const unsigned char *active; // nullable = all
 };
-void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design);
+void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design, int nbatch);
 struct PredScores {
     int nobs, K, family;
     const double *mu, *v;        // nobs each
@@ -447,8 +458,26 @@ struct PredScores {
     double param, logparam;
     double *lpd, *lcpo, *elp, *vlp;      // nobs each, each nullable
     double *part;                // 4 per workgroup
+    // the members: member k's mu and v at + k sm, c at + k sc (0: one column for all), lpd / lcpo / elp / vlp at + k so, part at
+    // + 4 k design_blocks(nobs)
+    long long sm, sc, so;
+    const double *param_k, *logparam_k;
+    const unsigned char *active;
 };
-// out4 (device) = the totals of lpd, lcpo, elp, vlp
-void launch_pred_scores(hipStream_t st, const PredScores &a, double *out4);
+// out4 (device) = member k's totals of lpd, lcpo, elp, vlp at + 4 k; inactive members' are left
+void launch_pred_scores(hipStream_t st, const PredScores &a, int nbatch, double *out4);
+// The mixture over the members with weights omega_k (w: nbatch weights, then nbatch logs of them; a member whose log is -inf is never
+// read): mix_mu = sum omega mu, mix_v = sum omega (v + (mu - mix_mu)^2), mix_lpd = log sum exp(log omega + lpd). mu, v, lpd (nullable):
+// nobs x nbatch, member stride nobs; mix_* nobs each, nullable. One thread per observation, members in ascending order. With lpd:
+// part gets 4 per workgroup (the sum of mix_lpd, then zeros) and out4[0] their total in the order of k_pred_final.
+struct PredMix {
+    int nobs, nbatch;
+    const double *w;
+    const double *mu, *v, *lpd;
+    double *mix_mu, *mix_v, *mix_lpd;
+    double *part;
+};
+inline int pred_mix_blocks(long long nobs) { return (int)((nobs + kPredMix - 1) / kPredMix); }
+void launch_pred_mixture(hipStream_t st, const PredMix &a, double *out4);
 
 }  // namespace gmrfx

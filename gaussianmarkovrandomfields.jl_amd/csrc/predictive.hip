@@ -22,6 +22,13 @@
 // (which leaves the sum in every lane); the squares of the correction are added for l = 0, 1, ... in that order; the 16 observations of
 // a workgroup meet in a fixed LDS tree, the workgroups in a fixed strided loop and tree. Every operand is read and written one double
 // at a time: nothing depends on alignment. Contraction is off in the whole file; every fused multiply-add is written as one.
+// MEMBERS (batched handles, gmrfx_batch_predictor_marginals / gmrfx_batch_predictive_scores). Every kernel takes a member index from its
+// grid (blockIdx.y; blockIdx.x in k_pred_final) and offsets what belongs to the member by the strides of its argument record: the point,
+// its entries of the offset table of Z (the offsets are absolute: the forest's panels are one array), its block of B, its column of the
+// constants, its outputs and partial sums. The tables, the data set and the quadrature rule are one copy. A plain handle launches one
+// member with every stride zero and null param_k / active: the same loads, the same arithmetic, the same bits.
+//   k_pred_mixture   one thread per observation, the members in ascending order: the weighted mixture of the members' predictive
+//                    distributions (gmrfx_batch_predictive_mixture); its total through k_pred_final
 // SELECTION MATRICES. With A = rows of the identity and no offset every sum has one term of weight 1: mu_eta, v_eta (corrected or
 // not) and pll have the bits of the node form.
 #include <hip/hip_runtime.h>
@@ -54,63 +61,81 @@ __device__ __forceinline__ double pred_loglik(int family, double eta, double y, 
 }
 
 __global__ __launch_bounds__(kPredNode) void k_pred_node(const PredMarg a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     const long long i = (long long)blockIdx.x * kPredNode + threadIdx.x;
     if (i >= a.nobs) return;
+    const long long o = (long long)k * a.so + i;
     const int j = a.idx[i];
-    const double mu = a.x[j];
-    if (a.mu_eta) a.mu_eta[i] = mu;
+    const double mu = a.x[(long long)k * a.sx + j];
+    if (a.mu_eta) a.mu_eta[o] = mu;
     if (a.v_eta) {
-        double v = a.Z[a.zoff[a.dpos[j]]];
+        double v = a.Z[a.zoff[(long long)k * a.sz + a.dpos[j]]];
         if (a.m > 0) {
+            const double *__restrict__ B = a.B + (long long)k * a.sb;
             double s = 0.0;
-            for (int l = 0; l < a.m; l++) { const double b = a.B[j + (long long)l * a.n]; s = __builtin_fma(b, b, s); }
+            for (int l = 0; l < a.m; l++) { const double b = B[j + (long long)l * a.n]; s = __builtin_fma(b, b, s); }
             v = pred_clamp(v, s);
         }
-        a.v_eta[i] = v;
+        a.v_eta[o] = v;
     }
-    if (a.pll) a.pll[i] = pred_loglik(a.family, mu, a.y[j], a.aux ? a.aux[j] : 0.0, a.param, a.logparam, a.c[i]);
+    if (a.pll)
+        a.pll[o] = pred_loglik(a.family, mu, a.y[j], a.aux ? a.aux[j] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                               a.logparam_k ? a.logparam_k[k] : a.logparam, a.c[(long long)k * a.sc + i]);
 }
 
 __global__ __launch_bounds__(256) void k_pred_design(const PredMarg a) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
     const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
     const long long i = (long long)blockIdx.x * kDesignRows + g;
     if (i >= a.nobs) return;         // (a whole lane group leaves together)
+    const long long o = (long long)k * a.so + i;
+    const double *__restrict__ x = a.x + (long long)k * a.sx;
     const long long q0 = a.arp[i], q1 = a.arp[i + 1];
     double s = 0.0;
-    for (long long q = q0 + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], a.x[a.acol[q]], s);
+    for (long long q = q0 + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], x[a.acol[q]], s);
     s = pred_group_sum(s);
     const double mu = a.offset ? s + a.offset[i] : s;
-    if (l == 0 && a.mu_eta) a.mu_eta[i] = mu;
+    if (l == 0 && a.mu_eta) a.mu_eta[o] = mu;
     if (a.v_eta) {
+        const long long *__restrict__ zoff = a.zoff + (long long)k * a.sz;
         double v = 0.0;
         const long long o1 = a.optr[i + 1];
-        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) v = __builtin_fma(a.ow[q], a.Z[a.zoff[a.hmap[a.oidx[q]]]], v);
+        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) v = __builtin_fma(a.ow[q], a.Z[zoff[a.hmap[a.oidx[q]]]], v);
         v = pred_group_sum(v);
         if (a.m > 0) {
+            const double *__restrict__ B = a.B + (long long)k * a.sb;
             double corr = 0.0;
-            for (int k = 0; k < a.m; k++) {
-                const double *__restrict__ Bk = a.B + (long long)k * a.n;
+            for (int c = 0; c < a.m; c++) {
+                const double *__restrict__ Bc = B + (long long)c * a.n;
                 double ab = 0.0;
-                for (long long q = q0 + l; q < q1; q += kDesignLanes) ab = __builtin_fma(a.aval[q], Bk[a.acol[q]], ab);
+                for (long long q = q0 + l; q < q1; q += kDesignLanes) ab = __builtin_fma(a.aval[q], Bc[a.acol[q]], ab);
                 ab = pred_group_sum(ab);
                 corr = __builtin_fma(ab, ab, corr);
             }
             v = pred_clamp(v, corr);
         }
-        if (l == 0) a.v_eta[i] = v;
+        if (l == 0) a.v_eta[o] = v;
     }
-    if (l == 0 && a.pll) a.pll[i] = pred_loglik(a.family, mu, a.y[i], a.aux ? a.aux[i] : 0.0, a.param, a.logparam, a.c[i]);
+    if (l == 0 && a.pll)
+        a.pll[o] = pred_loglik(a.family, mu, a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
+                               a.logparam_k ? a.logparam_k[k] : a.logparam, a.c[(long long)k * a.sc + i]);
 }
 
 __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
     __shared__ double sp[4][kDesignRows];
+    const int m = blockIdx.y;
+    if (a.active && !a.active[m]) return;       // (the whole workgroup: nobody waits at the barriers below)
     const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
     const long long i = (long long)blockIdx.x * kDesignRows + g;
     double lpd = 0.0, lcpo = 0.0, elp = 0.0, vlp = 0.0;
     if (i < a.nobs) {           // (a whole lane group takes the branch together)
-        const double mu = a.mu[i], v = a.v[i];
+        const long long o = (long long)m * a.so + i;
+        const double mu = a.mu[(long long)m * a.sm + i], v = a.v[(long long)m * a.sm + i];
         const long long j = a.idx ? a.idx[i] : i;
-        const double y = a.y[j], aux = a.aux ? a.aux[j] : 0.0, c = a.c[i];
+        const double y = a.y[j], aux = a.aux ? a.aux[j] : 0.0, c = a.c[(long long)m * a.sc + i];
+        const double param = a.param_k ? a.param_k[m] : a.param, logparam = a.logparam_k ? a.logparam_k[m] : a.logparam;
         const double s = sqrt(v);
         double lk[kPredNodesPerLane], wk[kPredNodesPerLane];
         double M = -INFINITY, Mn = -INFINITY, e = 0.0;
@@ -120,7 +145,7 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
             lk[t] = 0.0; wk[t] = 0.0;
             if (k < a.K) {
                 wk[t] = a.w[k];
-                lk[t] = pred_loglik(a.family, __builtin_fma(s, a.z[k], mu), y, aux, a.param, a.logparam, c);
+                lk[t] = pred_loglik(a.family, __builtin_fma(s, a.z[k], mu), y, aux, param, logparam, c);
                 M = fmax(M, lk[t]);
                 Mn = fmax(Mn, -lk[t]);
                 e = __builtin_fma(wk[t], lk[t], e);
@@ -147,10 +172,10 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
         lcpo = Mn == INFINITY ? -INFINITY : -(Mn + log(sc));
         if (!(v >= 0.0)) lpd = lcpo = elp = vlp = NAN;          // (a NaN or negative variance)
         if (l == 0) {
-            if (a.lpd) a.lpd[i] = lpd;
-            if (a.lcpo) a.lcpo[i] = lcpo;
-            if (a.elp) a.elp[i] = elp;
-            if (a.vlp) a.vlp[i] = vlp;
+            if (a.lpd) a.lpd[o] = lpd;
+            if (a.lcpo) a.lcpo[o] = lcpo;
+            if (a.elp) a.elp[o] = elp;
+            if (a.vlp) a.vlp[o] = vlp;
         }
     }
     if (l == 0) { sp[0][g] = lpd; sp[1][g] = lcpo; sp[2][g] = elp; sp[3][g] = vlp; }
@@ -162,11 +187,17 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
         }
         __syncthreads();
     }
-    if (threadIdx.x < 4) a.part[4 * (long long)blockIdx.x + threadIdx.x] = sp[threadIdx.x][0];
+    if (threadIdx.x < 4) a.part[4 * ((long long)m * gridDim.x + blockIdx.x) + threadIdx.x] = sp[threadIdx.x][0];
 }
 
-__global__ __launch_bounds__(kFisherFinal) void k_pred_final(const double *__restrict__ part, int nb, double *__restrict__ out) {
+// one workgroup per member: member k's nb partial quadruples at part + 4 k nb, its totals at out + 4 k
+__global__ __launch_bounds__(kFisherFinal) void k_pred_final(const double *__restrict__ part, int nb, const unsigned char *__restrict__ active,
+                                                             double *__restrict__ out) {
     __shared__ double sh[4][kFisherFinal];
+    const int k = blockIdx.x;
+    if (active && !active[k]) return;
+    part += 4 * (long long)k * nb;
+    out += 4 * (long long)k;
     const int tid = threadIdx.x;
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int b = tid; b < nb; b += kFisherFinal) {
@@ -186,17 +217,89 @@ __global__ __launch_bounds__(kFisherFinal) void k_pred_final(const double *__res
     if (tid < 4) out[tid] = sh[tid][0];
 }
 
-void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design) {
-    if (a.nobs <= 0) return;
-    if (design) hipLaunchKernelGGL(k_pred_design, dim3((unsigned)design_blocks(a.nobs)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_pred_node, dim3((unsigned)((a.nobs + kPredNode - 1) / kPredNode)), dim3(kPredNode), 0, st, a);
+// The mixture of the members' predictive distributions, one thread per observation, the members in ascending order. The first included
+// member's term is a plain product and every later one a fused multiply-add onto it, so one member of weight 1 hands its inputs through
+// bit for bit. An excluded member (log omega = -inf) is never read; an included member's NaN propagates (fmax alone would drop it from
+// the maximum: it is carried beside it). The workgroup's sum of mix_lpd: a fixed LDS tree over its kPredMix threads.
+__global__ __launch_bounds__(kPredMix) void k_pred_mixture(const PredMix a) {
+    __shared__ double sh[kPredMix];
+    const long long i = (long long)blockIdx.x * kPredMix + threadIdx.x;
+    const double *__restrict__ om = a.w, *__restrict__ lw = a.w + a.nbatch;
+    double total = 0.0;
+    if (i < a.nobs) {
+        if (a.mix_mu || a.mix_v) {
+            double mm = 0.0;
+            bool first = true;
+            for (int k = 0; k < a.nbatch; k++) {
+                if (lw[k] == -INFINITY) continue;
+                const double mu = a.mu[(long long)k * a.nobs + i];
+                mm = first ? om[k] * mu : __builtin_fma(om[k], mu, mm);
+                first = false;
+            }
+            if (a.mix_mu) a.mix_mu[i] = mm;
+            if (a.mix_v) {
+                double mv = 0.0;
+                first = true;
+                for (int k = 0; k < a.nbatch; k++) {
+                    if (lw[k] == -INFINITY) continue;
+                    const double d = a.mu[(long long)k * a.nobs + i] - mm;
+                    const double t = __builtin_fma(d, d, a.v[(long long)k * a.nobs + i]);
+                    mv = first ? om[k] * t : __builtin_fma(om[k], t, mv);
+                    first = false;
+                }
+                a.mix_v[i] = mv;
+            }
+        }
+        if (a.lpd) {
+            double M = -INFINITY, bad = 0.0;
+            for (int k = 0; k < a.nbatch; k++) {
+                if (lw[k] == -INFINITY) continue;
+                const double t = lw[k] + a.lpd[(long long)k * a.nobs + i];
+                if (t != t) bad = t;
+                M = fmax(M, t);
+            }
+            double r = M;
+            if (bad != bad) r = bad;
+            else if (M != -INFINITY) {
+                double s = 0.0;
+                for (int k = 0; k < a.nbatch; k++) {
+                    if (lw[k] == -INFINITY) continue;
+                    s += exp(lw[k] + a.lpd[(long long)k * a.nobs + i] - M);
+                }
+                r = M + log(s);
+            }
+            if (a.mix_lpd) a.mix_lpd[i] = r;
+            total = r;
+        }
+    }
+    if (!a.lpd) return;
+    sh[threadIdx.x] = total;
+    __syncthreads();
+    for (int st = kPredMix / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) sh[threadIdx.x] += sh[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) a.part[4 * (long long)blockIdx.x + threadIdx.x] = threadIdx.x == 0 ? sh[0] : 0.0;
 }
 
-void launch_pred_scores(hipStream_t st, const PredScores &a, double *out4) {
-    if (a.nobs <= 0) return;
+void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design, int nbatch) {
+    if (a.nobs <= 0 || nbatch <= 0) return;
+    if (design) hipLaunchKernelGGL(k_pred_design, dim3((unsigned)design_blocks(a.nobs), (unsigned)nbatch), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_pred_node, dim3((unsigned)((a.nobs + kPredNode - 1) / kPredNode), (unsigned)nbatch), dim3(kPredNode), 0, st, a);
+}
+
+void launch_pred_scores(hipStream_t st, const PredScores &a, int nbatch, double *out4) {
+    if (a.nobs <= 0 || nbatch <= 0) return;
     const int nb = design_blocks(a.nobs);
-    hipLaunchKernelGGL(k_pred_scores, dim3((unsigned)nb), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_pred_final, dim3(1), dim3(kFisherFinal), 0, st, a.part, nb, out4);
+    hipLaunchKernelGGL(k_pred_scores, dim3((unsigned)nb, (unsigned)nbatch), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_pred_final, dim3((unsigned)nbatch), dim3(kFisherFinal), 0, st, a.part, nb, a.active, out4);
+}
+
+void launch_pred_mixture(hipStream_t st, const PredMix &a, double *out4) {
+    if (a.nobs <= 0 || a.nbatch <= 0) return;
+    const int nb = pred_mix_blocks(a.nobs);
+    hipLaunchKernelGGL(k_pred_mixture, dim3((unsigned)nb), dim3(kPredMix), 0, st, a);
+    if (a.lpd) hipLaunchKernelGGL(k_pred_final, dim3(1), dim3(kFisherFinal), 0, st, a.part, nb, (const unsigned char *)nullptr, out4);
 }
 
 }  // namespace gmrfx

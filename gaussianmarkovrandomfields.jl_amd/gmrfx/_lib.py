@@ -85,6 +85,9 @@ EXPORTS = [
     "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
     "gmrfx_obs_pointwise_const", "gmrfx_predictor_marginals", "gmrfx_predictor_marginals_dev",
     "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
+    "gmrfx_batch_obs_pointwise_const", "gmrfx_batch_predictor_marginals", "gmrfx_batch_predictor_marginals_dev",
+    "gmrfx_batch_predictive_scores", "gmrfx_batch_predictive_scores_dev",
+    "gmrfx_batch_predictive_mixture", "gmrfx_batch_predictive_mixture_dev",
     "gmrfx_batch_set_prior", "gmrfx_batch_obs_set", "gmrfx_batch_obs_info", "gmrfx_batch_fisher_eval", "gmrfx_batch_fisher_eval_dev",
     "gmrfx_batch_gaussian_approximation", "gmrfx_batch_gaussian_approximation_dev",
     "gmrfx_batch_obs_set_design", "gmrfx_batch_obs_hess_map", "gmrfx_batch_obs_design_info",
@@ -277,6 +280,13 @@ def lib(cdll=C.CDLL):
         L.gmrfx_predictor_marginals_dev.argtypes = [vp, vp, i32, vp, vp, vp]
         L.gmrfx_predictive_scores.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.gmrfx_predictive_scores_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_obs_pointwise_const.argtypes = [vp, vp]
+        L.gmrfx_batch_predictor_marginals.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+        L.gmrfx_batch_predictor_marginals_dev.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+        L.gmrfx_batch_predictive_scores.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_predictive_scores_dev.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_predictive_mixture.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gmrfx_batch_predictive_mixture_dev.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gmrfx_batch_set_prior.argtypes = [vp, vp]
         L.gmrfx_batch_obs_set.argtypes = [vp, i32, i64, vp, i32, vp, vp, vp]
         L.gmrfx_batch_obs_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i64), vp]

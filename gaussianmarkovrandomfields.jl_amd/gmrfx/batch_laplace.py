@@ -299,3 +299,109 @@ class MI355XBatchLaplace(MI355XBatchBackend):
                                                d_mubar_prior or None, d_lambda or None, ptr(out), ptr(info))
         check(rc, self._h)
         return out[0].copy(), out[1].copy(), info
+
+    # -- what follows the fit, per member (include/gmrfx.h "The same read-outs for every member of a batched handle")
+    def _nobs(self) -> int:
+        nobs = self.observations_info()["nobs"]
+        if nobs <= 0:
+            raise ValueError("no observation likelihood is set (set_observations / set_design_observations)")
+        return nobs
+
+    def _per_obs(self, a, what: str):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != (self._nobs(), self.nbatch):
+            raise ValueError(f"{what} must have shape (nobs, nbatch) = ({self._nobs()}, {self.nbatch}), got {a.shape}")
+        return np.asfortranarray(a)
+
+    def observations_pointwise_const(self) -> np.ndarray:
+        """c (nobs, B): the terms of every observation's log density that do not depend on x, at every member's param
+        (gmrfx_batch_obs_pointwise_const); no device needed."""
+        c = np.empty((self._nobs(), self.nbatch), order="F")
+        check(lib().gmrfx_batch_obs_pointwise_const(self._h, ptr(c)), self._h)
+        return c
+
+    def predictor_marginals(self, X, constraint_correction: bool = False, want_mean: bool = True, want_var: bool = True, want_pll: bool = True):
+        """(mu_eta, v_eta, pll, info): mean and variance of every member's linear predictor and the log density at the mean, (nobs, B)
+        each in the caller's observation order (gmrfx_batch_predictor_marginals); X (n, B) the members' modes. The variance needs the
+        factors of the modes (gaussian_approximation with refactorize_final=True). constraint_correction: every member's variance gets
+        the correction and clamp of the batch constraint. A member whose factorisation (info[k] = -1) or W_k (1 + the failing pivot)
+        failed does not raise: its columns are NaN, the others are complete. The arrays not asked for are None."""
+        Xf, sx = self._points(X, "X")
+        nobs = self._nobs()
+        mu, v, pll = (np.empty((nobs, self.nbatch), order="F") if want else None for want in (want_mean, want_var, want_pll))
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_predictor_marginals(self._h, ptr(Xf), sx, int(bool(constraint_correction)), ptr(mu), ptr(v), ptr(pll), ptr(info)),
+              self._h)
+        return mu, v, pll, info
+
+    def predictor_marginals_dev(self, d_x: int, sx: int, d_mu_eta: int = 0, d_v_eta: int = 0, d_pll: int = 0, constraint_correction: bool = False):
+        """Device pointers (0 = not wanted): member k's x at + k sx, outputs (nobs, B) with member stride nobs. Returns info (B,)."""
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_predictor_marginals_dev(self._h, d_x or None, sx, int(bool(constraint_correction)), d_mu_eta or None, d_v_eta or None,
+                                                        d_pll or None, ptr(info)), self._h)
+        return info
+
+    batch_predictor_marginals = predictor_marginals
+    batch_predictor_marginals_dev = predictor_marginals_dev
+
+    @staticmethod
+    def _rule(nodes, weights, K: int):
+        if nodes is None or weights is None:
+            nodes, weights = MI355XBackend.gauss_hermite(K)
+        z = np.ascontiguousarray(nodes, dtype=np.float64).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if z.size != w.size:
+            raise ValueError("nodes and weights must have the same length")
+        return z, w
+
+    def predictive_scores(self, mu_eta, v_eta, K: int = 32, nodes=None, weights=None):
+        """The quadrature scores of every member over eta_ik ~ N(mu_eta_ik, v_eta_ik) (gmrfx_batch_predictive_scores; the rule of
+        MI355XBackend.gauss_hermite(K) unless nodes and weights are given): a dict of lpd, lcpo, elp, vlp (nobs, B), totals (4, B)
+        in that order, and info (B,) (-1: the member's factorisation failed; its columns and totals are NaN)."""
+        mu, v = self._per_obs(mu_eta, "mu_eta"), self._per_obs(v_eta, "v_eta")
+        z, w = self._rule(nodes, weights, K)
+        arrs = [np.empty(mu.shape, order="F") for _ in range(4)]
+        out = np.empty((4, self.nbatch), order="F")
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_predictive_scores(self._h, ptr(mu), ptr(v), z.size, ptr(z), ptr(w), *(ptr(a) for a in arrs), ptr(out), ptr(info)),
+              self._h)
+        return {"lpd": arrs[0], "lcpo": arrs[1], "elp": arrs[2], "vlp": arrs[3], "totals": out, "info": info}
+
+    def predictive_scores_dev(self, d_mu_eta: int, d_v_eta: int, K: int = 32, nodes=None, weights=None, d_lpd: int = 0, d_lcpo: int = 0,
+                              d_elp: int = 0, d_vlp: int = 0):
+        """Device pointers, (nobs, B) with member stride nobs (outputs: 0 = not wanted). Returns (totals (4, B), info (B,))."""
+        z, w = self._rule(nodes, weights, K)
+        out = np.empty((4, self.nbatch), order="F")
+        info = np.zeros(self.nbatch, np.int64)
+        check(lib().gmrfx_batch_predictive_scores_dev(self._h, d_mu_eta or None, d_v_eta or None, z.size, ptr(z), ptr(w), d_lpd or None,
+                                                      d_lcpo or None, d_elp or None, d_vlp or None, ptr(out), ptr(info)), self._h)
+        return out, info
+
+    def _logw(self, logw):
+        lw = np.ascontiguousarray(logw, dtype=np.float64).reshape(-1)
+        if lw.size != self.nbatch:
+            raise ValueError("logw must have one entry per member")
+        return lw
+
+    def predictive_mixture(self, logw, mu_eta, v_eta, lpd=None):
+        """The predictive distribution integrated over the members with weights proportional to exp(logw) (B unnormalised log weights,
+        -inf excludes a member; gmrfx_batch_predictive_mixture): (mix_mu, mix_v, mix_lpd, total), (nobs,) each and the sum of mix_lpd;
+        without lpd the last two are None."""
+        lw = self._logw(logw)
+        mu, v = self._per_obs(mu_eta, "mu_eta"), self._per_obs(v_eta, "v_eta")
+        lp = None if lpd is None else self._per_obs(lpd, "lpd")
+        nobs = mu.shape[0]
+        mm, mv = np.empty(nobs), np.empty(nobs)
+        ml = None if lp is None else np.empty(nobs)
+        out = np.full(1, np.nan)
+        check(lib().gmrfx_batch_predictive_mixture(self._h, ptr(lw), ptr(mu), ptr(v), ptr(lp), ptr(mm), ptr(mv), ptr(ml), ptr(out)), self._h)
+        return mm, mv, ml, (None if lp is None else float(out[0]))
+
+    def predictive_mixture_dev(self, logw, d_mu_eta: int, d_v_eta: int, d_lpd: int = 0, d_mix_mu: int = 0, d_mix_v: int = 0, d_mix_lpd: int = 0):
+        """Device pointers: inputs (nobs, B) with member stride nobs, outputs (nobs,) (0 = not wanted). Returns the sum of mix_lpd
+        (NaN without d_lpd)."""
+        lw = self._logw(logw)
+        out = np.full(1, np.nan)
+        check(lib().gmrfx_batch_predictive_mixture_dev(self._h, ptr(lw), d_mu_eta or None, d_v_eta or None, d_lpd or None, d_mix_mu or None,
+                                                       d_mix_v or None, d_mix_lpd or None, ptr(out)), self._h)
+        return float(out[0])

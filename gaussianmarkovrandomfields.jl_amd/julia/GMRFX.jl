@@ -974,6 +974,58 @@ function ga_pullback(bb::MI355XBatch, X::Matrix{Float64}; mean::Union{Nothing, M
     return qp, mp, lam, out[1, :], out[2, :], inf
 end
 
+# What follows the fit, for every member (gmrfx_batch_predictor_marginals, gmrfx_batch_predictive_scores, gmrfx_batch_predictive_mixture):
+# X n x nbatch (the modes); every per-observation array nobs x nbatch. info[k] = 0, -1 (member k's factorisation failed) or 1 + the
+# failing pivot of W_k; such a member's columns (and totals) are NaN.
+function batch_nobs(bb::MI355XBatch)
+    fam = Ref{Int32}(0); nobs = Ref{Int64}(0); c = zeros(bb.nbatch)
+    GC.@preserve c check(ccall((:gmrfx_batch_obs_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ptr{Float64}), bb.h.ptr, fam, nobs, c), bb.h)
+    return Int(nobs[])
+end
+function observations_pointwise_const(bb::MI355XBatch)
+    c = Matrix{Float64}(undef, batch_nobs(bb), bb.nbatch)
+    GC.@preserve c check(ccall((:gmrfx_batch_obs_pointwise_const, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), bb.h.ptr, c), bb.h)
+    return c
+end
+function predictor_marginals(bb::MI355XBatch, X::Matrix{Float64}; constraint_correction::Bool = false)
+    size(X) == (bb.n, bb.nbatch) || throw(DimensionMismatch("X must be n x nbatch"))
+    nobs = batch_nobs(bb)
+    mu = Matrix{Float64}(undef, nobs, bb.nbatch); v = Matrix{Float64}(undef, nobs, bb.nbatch); pll = Matrix{Float64}(undef, nobs, bb.nbatch)
+    inf = zeros(Int64, bb.nbatch)
+    GC.@preserve X mu v pll inf check(ccall((:gmrfx_batch_predictor_marginals, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, X, bb.n, Int32(constraint_correction), mu, v, pll, inf), bb.h)
+    return mu, v, pll, inf
+end
+function predictive_scores(bb::MI355XBatch, mu_eta::Matrix{Float64}, v_eta::Matrix{Float64}, nodes::Vector{Float64}, weights::Vector{Float64})
+    nobs = batch_nobs(bb)
+    size(mu_eta) == (nobs, bb.nbatch) && size(v_eta) == (nobs, bb.nbatch) && length(nodes) == length(weights) ||
+        throw(DimensionMismatch("mu_eta / v_eta must be nobs x nbatch, nodes / weights must pair up"))
+    lpd = Matrix{Float64}(undef, nobs, bb.nbatch); lcpo = Matrix{Float64}(undef, nobs, bb.nbatch)
+    elp = Matrix{Float64}(undef, nobs, bb.nbatch); vlp = Matrix{Float64}(undef, nobs, bb.nbatch)
+    out = zeros(4, bb.nbatch); inf = zeros(Int64, bb.nbatch)
+    GC.@preserve mu_eta v_eta nodes weights lpd lcpo elp vlp out inf check(ccall((:gmrfx_batch_predictive_scores, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}),
+        bb.h.ptr, mu_eta, v_eta, length(nodes), nodes, weights, lpd, lcpo, elp, vlp, out, inf), bb.h)
+    return (lpd = lpd, lcpo = lcpo, elp = elp, vlp = vlp), out, inf
+end
+# the predictive distribution integrated over the members with weights proportional to exp(logw) (-Inf excludes a member):
+# (mix_mu, mix_v, mix_lpd, sum of mix_lpd); without lpd the last two are `nothing`
+function predictive_mixture(bb::MI355XBatch, logw::Vector{Float64}, mu_eta::Matrix{Float64}, v_eta::Matrix{Float64},
+                            lpd::Union{Nothing, Matrix{Float64}} = nothing)
+    nobs = batch_nobs(bb)
+    length(logw) == bb.nbatch && size(mu_eta) == (nobs, bb.nbatch) && size(v_eta) == (nobs, bb.nbatch) &&
+        (lpd === nothing || size(lpd) == (nobs, bb.nbatch)) || throw(DimensionMismatch("logw must have nbatch entries, the arrays nobs x nbatch"))
+    mm = Vector{Float64}(undef, nobs); mv = Vector{Float64}(undef, nobs); ml = Vector{Float64}(undef, nobs)
+    out = zeros(1)
+    lp = lpd === nothing ? Ptr{Float64}(C_NULL) : pointer(lpd)
+    mlp = lpd === nothing ? Ptr{Float64}(C_NULL) : pointer(ml)
+    GC.@preserve logw mu_eta v_eta lpd mm mv ml out check(ccall((:gmrfx_batch_predictive_mixture, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+        bb.h.ptr, logw, mu_eta, v_eta, lp, mm, mv, mlp, out), bb.h)
+    return mm, mv, (lpd === nothing ? nothing : ml), (lpd === nothing ? nothing : out[1])
+end
+
 # max(diag Sigma_k - rowsum(B_k^2), 0) of every member: n x nbatch; without a constraint selinv_diag(bb)
 function constrained_var(bb::MI355XBatch)
     out = Matrix{Float64}(undef, bb.n, bb.nbatch)

@@ -978,6 +978,67 @@ int32_t gmrfx_predictive_scores_dev(gmrfx_handle *h, const double *d_mu_eta, con
                                     const double *w /* host, K */, double *d_lpd, double *d_lcpo, double *d_elp, double *d_vlp,
                                     double *out /* host, 4 */);
 
+/* ---- The same read-outs for every member of a batched handle, and the mixture over the sweep ----------------------------------------------
+ * After gmrfx_batch_gaussian_approximation (flag bit 3: the forest holds the factor of every Q_post,k) the formulas above, member by
+ * member, with the ONE likelihood of gmrfx_batch_obs_set / gmrfx_batch_obs_set_design and param[k]: one launch per step for all
+ * members, the member in the launch grid. A plain handle that holds a batch likelihood is a batch of one.
+ * LAYOUT. Member k's mean at x + k sx (sx >= n). Every per-observation array is nobs x nbatch, column k member k's (stride nobs):
+ * mu_eta, v_eta, pll, the inputs and the four outputs of the scores, the inputs of the mixture. out of the scores: 4 per member.
+ * gmrfx_batch_obs_pointwise_const: c_ik = the term of gmrfx_obs_pointwise_const at param[k], nobs x nbatch (the families without a
+ * parameter repeat one column; the device keeps one column for them and nobs x nbatch for Normal, NegBin and Gamma). The device's
+ * table is dropped by gmrfx_batch_obs_set_param and gmrfx_batch_obs_set*: the next call rebuilds it.
+ * FLAGS (marginals). Bit 0: member k's v_eta gets the BATCH constraint's correction with its own B_k (read where
+ * gmrfx_batch_constraints_set keeps it, no transposed copy) and the clamp. A held constraint without the bit is ignored.
+ * INFO (host, nbatch, nullable), the convention of gmrfx_batch_ga_pullback: 0; -1 when member k's factorisation failed; 1 + the
+ * failing pivot when its W_k did (bit 0). Such a member is masked out of every launch: NaN in its requested slices (and its four
+ * totals), nothing else of it is touched, everybody else is complete; the call returns GMRFX_OK. The marginals look at the factor only
+ * when v_eta is asked for: without it every member gets its mu_eta and pll. The scores read no factor; where the handle holds one, a
+ * member whose factor failed is reported and masked all the same.
+ * BITS. No atomics. Without bit 0 member k's results (and its four totals) have the bits of the plain calls on a plain handle
+ * factorised at Q_post,k with param[k], whichever members share the batch, in host or _dev form, whatever the alignment (8 bytes
+ * suffice) -- given that the member's selected inverse has the plain handle's bits. Under bit 0 the preparation of W_k is the batch
+ * constraint's own: close to, not bitwise, the plain one.
+ *
+ * gmrfx_batch_predictive_mixture: the predictive distribution integrated over the members with weights omega_k proportional to
+ * exp(logw_k) (logw: host, nbatch, unnormalised; -inf excludes a member). The library forms omega_k = exp(logw_k - max) / sum in long
+ * double and rounds omega_k and log omega_k to double. Per observation, the members in ascending k:
+ *   mix_mu_i  = sum_k omega_k mu_ik            mix_v_i = sum_k omega_k (v_ik + (mu_ik - mix_mu_i)^2)
+ *   mix_lpd_i = M_i + log sum_k exp(log omega_k + lpd_ik - M_i),  M_i = max_k (log omega_k + lpd_ik)      (-inf when M_i is)
+ * lpd nullable (then mix_lpd is not computed and out[0] is NaN); mix_mu, mix_v, mix_lpd: nobs each, each nullable. out[0] (host,
+ * nullable): sum_i mix_lpd_i, through per-workgroup partials and one final workgroup in a fixed order. An excluded member is never
+ * read (its NaN does no harm); an included member's NaN propagates. One member with logw = [0] returns its inputs bit for bit, with
+ * one exception of sign: a v_eta or lpd entry of -0.0 comes back as +0.0 (0 + -0.0 in the sums); mu_eta keeps its sign of zero. No
+ * atomics; bit-reproducible; shifting every logw by a constant that is exact in double changes nothing.
+ * Device memory, on the first call after gmrfx_batch_obs_set*, on the handle's books: the tables of the plain calls once (c as above),
+ * 32 bytes of partial sums per 16 observations and member, 4 n bytes (node form, for v_eta), 16 nbatch bytes of weights.
+ * Errors: INVALID_ARG (with a message, nothing written) for x null, sx < n, every output null, unknown flag bits, bit 0 without a batch
+ * constraint, no batch likelihood, a sharded handle, more than 65535 members, a plain constraint or a plain design likelihood held;
+ * for the scores mu_eta / v_eta / out null and a refused quadrature rule; for the mixture logw / mu_eta / v_eta null, every output
+ * null, mix_lpd without lpd, a NaN or +inf weight, every member excluded. Then GMRFX_ERR_NO_DEVICE, then GMRFX_ERR_NOT_FACTORIZED when
+ * v_eta is asked for before the first factorisation. gmrfx_predictor_marginals and gmrfx_predictive_scores keep refusing batched handles.
+ * LIMITS: nbatch <= 65535; n, nobs < 2^31; K <= 64; unsharded handles. */
+int32_t gmrfx_batch_obs_pointwise_const(const gmrfx_handle *h, double *out /* nobs x nbatch */);
+int32_t gmrfx_batch_predictor_marginals(gmrfx_handle *h, const double *x, int64_t sx, int32_t flags, double *mu_eta /* nobs x nbatch, nullable */,
+                                        double *v_eta /* nobs x nbatch, nullable */, double *pll /* nobs x nbatch, nullable */,
+                                        int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_predictor_marginals_dev(gmrfx_handle *h, const double *d_x, int64_t sx, int32_t flags, double *d_mu_eta, double *d_v_eta,
+                                            double *d_pll, int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_predictive_scores(gmrfx_handle *h, const double *mu_eta /* nobs x nbatch */, const double *v_eta /* nobs x nbatch */, int64_t K,
+                                      const double *z /* host, K */, const double *w /* host, K */, double *lpd /* nobs x nbatch, nullable */,
+                                      double *lcpo /* nobs x nbatch, nullable */, double *elp /* nobs x nbatch, nullable */,
+                                      double *vlp /* nobs x nbatch, nullable */, double *out /* host, 4 x nbatch */,
+                                      int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_predictive_scores_dev(gmrfx_handle *h, const double *d_mu_eta, const double *d_v_eta, int64_t K, const double *z /* host, K */,
+                                          const double *w /* host, K */, double *d_lpd, double *d_lcpo, double *d_elp, double *d_vlp,
+                                          double *out /* host, 4 x nbatch */, int64_t *info /* host, nbatch, nullable */);
+int32_t gmrfx_batch_predictive_mixture(gmrfx_handle *h, const double *logw /* host, nbatch */, const double *mu_eta /* nobs x nbatch */,
+                                       const double *v_eta /* nobs x nbatch */, const double *lpd /* nobs x nbatch, nullable */,
+                                       double *mix_mu /* nobs, nullable */, double *mix_v /* nobs, nullable */, double *mix_lpd /* nobs, nullable */,
+                                       double *out /* host, 1, nullable */);
+int32_t gmrfx_batch_predictive_mixture_dev(gmrfx_handle *h, const double *logw /* host, nbatch */, const double *d_mu_eta, const double *d_v_eta,
+                                           const double *d_lpd, double *d_mix_mu, double *d_mix_v, double *d_mix_lpd,
+                                           double *out /* host, 1, nullable */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,7 +21,13 @@ A byte MODEL (not a measurement; the kernels are not timed apart from their call
   marginals, node form    nobs (4 idx + 8 x + 4 dpos + 8 zoff + 8 Z + 8 y + 8 aux + 8 c + 24 out)      (gathers through L2)
   marginals, design form  12 nnz(A) + 8 (nobs + 1) + 8 nnz(A) (x) + terms (12 + 8 hmap + 8 zoff + 8 Z) + 8 (nobs + 1) + nobs (8 b + 8 y + 8 aux + 8 c + 24 out)
   scores                  nobs (8 mu + 8 v + 8 y + 8 aux + 8 c + 32 out) (+ 4 nobs idx in node form); K exponentials and logarithms per observation
-usage: tools/predictive_bench.py [--design [--nobs 1000000]] [--grid 1000] [--nodes 32] [--reps 15] [--warmup 3] [--out profiles/predictive_bench[_design].json]"""
+--old PATH/TO/libgmrfx.so: an A/B of gmrfx_predictor_marginals_dev and gmrfx_predictive_scores_dev between this build and another one
+(the parent commit's), alternating in one process on the same operands: --rounds (4) medians of --reps per side and call, the order
+within a round alternating; --first old|new: whose handle is created first (it is part of the measurement). Reported per
+call: both sides' medians, whether the new median lies inside the old min .. max, and whether the seven output arrays and the four
+totals of both builds have the same bits. Output: profiles/predictive_ab[_design].json.
+usage: tools/predictive_bench.py [--design [--nobs 1000000]] [--grid 1000] [--nodes 32] [--reps 15] [--warmup 3]
+                                 [--old LIB [--rounds 4] [--first old|new]] [--out profiles/predictive_bench[_design].json]"""
 import argparse
 import json
 import os
@@ -67,6 +73,50 @@ def host_scores(mu, v, y, aux, c, z, w):
     return lpd, lcpo, elp, vlp, (lpd.sum(), lcpo.sum(), elp.sum(), vlp.sum())
 
 
+def ab(a, libs, handles, setup, Q, ptrs, z, w, res):
+    """the two plain calls on both builds, alternating; each handle is set up, factorised and inverted by the library that made it"""
+    dx, outs = ptrs
+    p = [t.data_ptr() for t in outs]
+    calls = {"marginals_dev": lambda be: be.predictor_marginals_dev(dx.data_ptr(), p[0], p[1], p[2]),
+             "scores_dev": lambda be: be.predictive_scores_dev(p[0], p[1], z, w, p[3], p[4], p[5], p[6])}
+    medians = {c: {"old": [], "new": []} for c in calls}
+    bits, totals = {}, {}
+    for tag in ("old", "new"):
+        _lib.use(libs[tag])
+        be = handles[tag]
+        setup(be)
+        be.refactorize_values(Q.data)
+        be.selinv_compute_dev()
+        calls["marginals_dev"](be)
+        totals[tag] = calls["scores_dev"](be)
+        torch.cuda.synchronize()
+        bits[tag] = [t.cpu().numpy().copy() for t in outs]
+    same = True
+    for r in range(a.rounds):
+        for tag in (("old", "new") if r % 2 == 0 else ("new", "old")):
+            _lib.use(libs[tag])
+            be = handles[tag]
+            for c, fn in calls.items():
+                medians[c][tag].append(timed(lambda: fn(be), a.reps, a.warmup)["median_ms"])
+            torch.cuda.synchronize()       # the parent's bits in every run: the arrays the timed calls left
+            same = same and all(np.array_equal(t.cpu().numpy().view(np.int64), u.view(np.int64)) for t, u in zip(outs, bits["old"]))
+    for tag in ("old", "new"):          # every handle is destroyed by the library that made it (close() goes to the library in use)
+        _lib.use(libs[tag])
+        handles[tag].close()
+    _lib.use(libs["new"])
+    res.update({"tool": "tools/predictive_bench.py --old", "rounds": a.rounds, "handle_created_first": a.first})
+    for c in calls:
+        old, new = medians[c]["old"], medians[c]["new"]
+        res[c] = {"old_median_ms": old, "new_median_ms": new, "new_inside_old_min_max": bool(min(old) <= float(np.median(new)) <= max(old)),
+                  "new_median_above_old_max_ms": float(np.median(new)) - max(old)}
+    res["same_bits"] = bool(same and all(np.array_equal(u.view(np.int64), v.view(np.int64)) for u, v in zip(bits["old"], bits["new"]))
+                            and totals["old"] == totals["new"])
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--grid", type=int, default=1000)
@@ -75,10 +125,14 @@ def main():
     ap.add_argument("--nodes", type=int, default=32)
     ap.add_argument("--design", action="store_true")
     ap.add_argument("--nobs", type=int, default=1000000)
+    ap.add_argument("--old", default=None, help="another build of libgmrfx.so: A/B of the two plain calls against it")
+    ap.add_argument("--rounds", type=int, default=4)
+    ap.add_argument("--first", choices=("old", "new"), default="old", help="whose handle is created first (DESIGN.md 6m: it is part of the measurement)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "predictive_bench_design.json" if a.design else "predictive_bench.json")
+        stem = "predictive_ab" if a.old else "predictive_bench"
+        a.out = os.path.join(ROOT, "profiles", stem + ("_design.json" if a.design else ".json"))
     mesh = spde.grid_mesh_2d(a.grid, a.grid, jitter=0.25, seed=0)
     Q = sp.csc_matrix(spde.matern_precision(mesh, smoothness=0, range_=0.2))
     Q = sp.csc_matrix((Q + Q.T) * 0.5)
@@ -86,7 +140,19 @@ def main():
     n = Q.shape[0]
     rng = np.random.default_rng(0)
     dev = torch.device("cuda:0")
+    libs = {"new": _lib.lib()}
+    be_old = None
+    if a.old:
+        libs["old"] = _lib.load_from(a.old)
+    if a.old and a.first == "old":
+        _lib.use(libs["old"])
+        be_old = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+        _lib.use(libs["new"])
     be = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+    if a.old and a.first == "new":
+        _lib.use(libs["old"])
+        be_old = gmrfx.MI355XBackend(Q, coords=mesh.points, device=0, factorize=False)
+        _lib.use(libs["new"])
     z, w = be.gauss_hermite(a.nodes)
     x = 0.3 * rng.standard_normal(n)
     if a.design:
@@ -102,12 +168,19 @@ def main():
         idx = rng.permutation(n)
     y = rng.poisson(3.0, nobs).astype(float)
     aux = rng.uniform(-0.5, 0.5, nobs)
-    if a.design:
-        be.set_design_observations("poisson", y, A, offset=b, aux=aux)
-    else:
-        be.set_observations("poisson", y, indices=idx, aux=aux)
+    def setup(h):
+        if a.design:
+            h.set_design_observations("poisson", y, A, offset=b, aux=aux)
+        else:
+            h.set_observations("poisson", y, indices=idx, aux=aux)
+    if not a.old:
+        setup(be)
     res = {"n": n, "nobs": nobs, "K": a.nodes, "design": bool(a.design), "reps": a.reps, "warmup": a.warmup,
            "source_tree_hash": _lib.source_tree_hash()}
+    if a.old:
+        dx = torch.from_numpy(x).to(dev)
+        outs = [torch.empty(nobs, dtype=torch.float64, device=dev) for _ in range(7)]
+        return ab(a, libs, {"new": be, "old": be_old}, setup, Q, (dx, outs), z, w, res)
     if a.design:
         info = be.observations_design_info()
         res.update({"nnz_A": info["nnz"], "terms": info["terms"]})
