@@ -89,9 +89,16 @@ void Device::init(const Symbolic &S, int dev) {
     ev_inv_.create(hipEventDisableTiming);
     for (auto &ev : ev_) ev.create();
     for (auto &l : ev_lane_) for (auto &ev : l) ev.create();
-    h_info_.alloc(2);
+    {
+        int khz = 0;
+        HC(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device));
+        if (khz <= 0) throw std::runtime_error("the device reports no wall clock rate");
+        wall_clock_khz_ = khz;
+    }
+    // the pivot word (+ one of padding), then a pair of 64-bit clock stamps per SYRK slot: one slot per level at most
+    h_info_.alloc(kInfoWords + 4 * (long long)S.nlevels);
+    std::fill_n((int *)h_info_, kInfoWords + 4 * (long long)S.nlevels, 0);
     h_info_[0] = INT_MAX;
-    h_info_[1] = 0;
     ev_ready_.create(hipEventDisableTiming);
     ev_ready2_.create(hipEventDisableTiming);
     ev_done1_.create(hipEventDisableTiming);
@@ -157,8 +164,20 @@ void Device::upload(const Symbolic &S) {
     if (!P.inv_lvl_list.empty()) d_inv_lvl_list_ = up(P.inv_lvl_list);
     for (const auto &off : P.inv_lvl_toff) d_inv_lvl_toff_.push_back(up(off));
     d_syrk_recs_ = up(P.syrk_recs); d_fwd_recs_ = up(P.fwd_recs); d_arec_ = up(P.arec);
-    ev_syrk_.resize(2 * (size_t)S.nlevels);
-    for (auto &e : ev_syrk_) e.create();
+    {
+        // where the tiles of k_syrk_cb_rec leave their times (two words each), and per level its tiles and its SYRK slot: the slots
+        // go to the levels with big fronts that have trailing rows, in level order (factor_levels counts them the same way)
+        std::vector<SyrkLevelTimes> lt(levels_.size());
+        int slot = 0;
+        for (size_t l = 0; l < levels_.size(); l++) {
+            const LevelInfo &L = levels_[l];
+            const long long end = l + 1 < levels_.size() ? levels_[l + 1].syrk_off : (long long)P.syrk_recs.size();
+            const bool timed = L.nbig() > 0 && L.max_trail > 0;
+            lt[l] = SyrkLevelTimes{L.syrk_off, env_.syrk_xcd && timed ? (int)(end - L.syrk_off) : 0, timed ? slot++ : -1};
+        }
+        d_syrk_level_times_ = up(lt);
+        d_syrk_times_ = dalloc<unsigned long long>(2 * P.syrk_recs.size());
+    }
 
     // INVARIANT (pair loads): the kernels that read operand rows in 16-byte pairs (sweep_front.hip, k_syrk_cb_rec, selinv.hip)
     // may read ONE double past a column's last row; for the last column of the last panel that is element l_size_ of the
@@ -170,7 +189,7 @@ void Device::upload(const Symbolic &S) {
     d_L_ = dalloc<double>((size_t)l_size_ + kChunkSlack);
     d_cb_ = dalloc<double>((size_t)S.cb_arena);
     d_nz_ = dalloc<double>((size_t)S.nnz_in);
-    d_info_ = dalloc<int>(2);
+    d_info_ = dalloc<int>((size_t)kInfoWords + 4 * (size_t)S.nlevels);      // (the same layout as h_info_)
     d_part_ = dalloc<double>(1024 + 8);
     HC(hipMemsetAsync(d_L_, 0, ((size_t)l_size_ + kChunkSlack) * sizeof(double) + kPairSlackBytes, stream));
     HC(hipStreamSynchronize(stream));
@@ -508,25 +527,28 @@ bool Device::factor_panel_chains(const LevelInfo &L) {
     return two;
 }
 
-// The contribution blocks of a level's big fronts (children gathered + L21 L21'), between the level's pair of timing events.
+// The contribution blocks of a level's big fronts (children gathered + L21 L21'). The level's launches read the device's wall
+// clock themselves -- k_syrk_cb_rec per tile (reduced behind the last level, factor_levels), the others straight into slot `slot`
+// of the stamps behind the pivot word (kernel_common.h, stamp_begin / stamp_end) --: earliest start, latest end over their
+// workgroups, with nothing on the stream between the launches and their neighbours (syrk_ms()).
 void Device::factor_contribution_blocks(const LevelInfo &L, int slot) {
     const int *list = d_levellist_ + L.first + L.nsmall;
     const int nf = L.nbig();
-    HC(hipEventRecord(ev_syrk_[2 * slot], stream));
+    unsigned long long *stamp = syrk_stamps(d_info_) + 2 * slot;
+    unsigned long long *times = d_syrk_times_ + 2 * L.syrk_off;       // k_syrk_cb_rec: per tile; factor_levels reduces them into the slot
     // levels of HUGE fronts (3-D problems): the children's extend-add alone, then the product on 128 x 128 staged tiles
     const bool huge = env_.syrk_xcd && !sharded() && L.max_trail >= 4096 && L.max_cols >= 1024;
     // levels of wide fronts (the product dominates the tile): the software-pipelined product loop (factor_kernels.hip, k_syrk_cb_rec<true>;
     // same sums in the same order: a level's choice does not show in the bits)
-    if (env_.syrk_xcd) launch_syrk_cb_recs(stream, ds_, d_syrk_recs_ + L.syrk_off, L.syrk_split, L.syrk_per, d_L_, d_cb_, huge ? 1 : 0, L.max_cols >= env_.syrk_piped_min);
-    else launch_syrk_cb(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_);
-    if (huge) launch_syrk_big(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_);
-    HC(hipEventRecord(ev_syrk_[2 * slot + 1], stream));
+    if (env_.syrk_xcd) launch_syrk_cb_recs(stream, ds_, d_syrk_recs_ + L.syrk_off, L.syrk_split, L.syrk_per, d_L_, d_cb_, times, huge ? 1 : 0, L.max_cols >= env_.syrk_piped_min);
+    else launch_syrk_cb(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_, stamp);
+    if (huge) launch_syrk_big(stream, ds_, list, nf, L.max_trail, d_L_, d_cb_, stamp);       // (the slot spans both launches)
 }
 
 void Device::factor_levels(int lo, int hi, bool record_level_events) {
     if (lo == 0) {
-        const int big = INT_MAX;
-        HC(hipMemcpyAsync(d_info_, &big, sizeof(int), hipMemcpyHostToDevice, stream));
+        // the pivot word = "no failure", every SYRK slot = (start: all ones, end: 0), in one small launch
+        launch_factor_reset(stream, d_info_, syrk_stamps(d_info_), S_->nlevels);
         syrk_launches = 0;
         // whole small subtrees first (one workgroup each), then the level schedule of everything above
         for (int k = 0, off = 0; k < 3; off += nsub_cls_[k], k++)
@@ -561,6 +583,8 @@ void Device::factor_levels(int lo, int hi, bool record_level_events) {
         }
         if (record_level_events) HC(hipEventRecord(ev_flevel_[lev], stream));      // the panels of this level are final: its sweep may start
     }
+    // the tile times of the levels' SYRK launches into their slots: one launch behind the last level
+    if (nsy > (int)syrk_launches && env_.syrk_xcd) launch_syrk_reduce(stream, d_syrk_level_times_ + lo, hi - lo, d_syrk_times_, syrk_stamps(d_info_));
     syrk_launches = nsy;
     if (lo == 0 && nzp_pending_) { HC(hipStreamWaitEvent(stream, ev_nzp_, 0)); nzp_pending_ = false; }     // (see above)
     if (env_.level_mark) level_event(stream, 0, hi);
@@ -730,7 +754,7 @@ void Device::enqueue_factor_tail() {
     HC(hipEventRecord(ev_[1], stream));
     HC(hipEventRecord(ev_fact_, stream));
     fact_event_valid_ = true;
-    HC(hipMemcpyAsync(h_info_, d_info_, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HC(hipMemcpyAsync(h_info_, d_info_, info_bytes(syrk_launches), hipMemcpyDeviceToHost, stream));     // (the SYRK stamps ride along)
 }
 // behind the synchronisation. `factorized` is set HERE for every caller, once the synchronisation has succeeded: a call that
 // throws on the way leaves the handle as it found it. (decide_inverse_cap returns at once when the cap is decided -- always so in
@@ -742,7 +766,7 @@ void Device::finish_factor() {
     float ms = 0;
     HC(hipEventElapsedTime(&ms, ev_[0], ev_[1]));
     ms_factor = ms;
-    syrk_times_pending_ = true;      // the per-launch event times are only read when somebody asks for the statistics
+    syrk_times_pending_ = true;      // the per-launch stamps are only summed when somebody asks for the statistics
     factorized = true;
     selinv_valid = false;
 }
@@ -782,6 +806,7 @@ void Device::refactorize_phase(const double *d_nzval, int phase) {
         if (lev >= nl) throw std::invalid_argument("refactorize phase beyond the last level");
         factor_levels(lev, lev + 1, false);
     }
+    syrk_times_pending_ = true;      // (the slots accumulate over the phases as syrk_launches does; syrk_ms() fetches them)
     HC(hipEventRecord(ev_[1], stream));
     if (!async_phases_) {
         HC(hipStreamSynchronize(stream));
@@ -910,12 +935,17 @@ void Device::refactorize_update_solve(const double *h, bool h_on_device, const d
 double Device::syrk_ms() {
     if (syrk_times_pending_) {
         HC(hipSetDevice(device));
-        ms_syrk = 0;
-        for (long long k = 0; k < syrk_launches; k++) {
-            float t = 0;
-            HC(hipEventElapsedTime(&t, ev_syrk_[2 * k], ev_syrk_[2 * k + 1]));
-            ms_syrk += t;
+        if (!info_cached_ && syrk_launches > 0) {
+            // (the phases of a sharded factorisation leave the stamps on the device; asynchronous phases / an external main
+            //  stream: the factorisation may still run)
+            HC(hipStreamSynchronize(stream));
+            HC(hipMemcpy(syrk_stamps(h_info_), syrk_stamps(d_info_), info_bytes(syrk_launches) - info_bytes(0), hipMemcpyDeviceToHost));
         }
+        const unsigned long long *stamp = syrk_stamps(h_info_);
+        unsigned long long ticks = 0;
+        for (long long k = 0; k < syrk_launches; k++)
+            if (stamp[2 * k + 1] > stamp[2 * k]) ticks += stamp[2 * k + 1] - stamp[2 * k];       // (a slot nobody stamped: start all ones, end 0)
+        ms_syrk = (double)ticks / wall_clock_khz_;
         syrk_times_pending_ = false;
     }
     return ms_syrk;

@@ -102,6 +102,7 @@ struct FrontArg { int on, s, c, r, ld, first; long long pp; long long ppa = kNoP
 // X2: y of the big fronts, W: the update vectors). The sweep drivers take it as a parameter; nothing selects a lane by state.
 struct SweepLane { hipStream_t st; double *X, *X2, *W; };
 struct FisherMembers;      // (kernels.h)
+struct SyrkLevelTimes;     // (kernels.h)
 class Device {
 public:
     Device() = default;
@@ -366,8 +367,8 @@ public:
     double ms_inv_decide = 0;      // host wall time of the one-time inverse-cap decision (decide_inverse_cap), 0 before / without it
     int inv_cap() const { return inv_cap_; }
     bool syrk_times_pending_ = false;
-    double syrk_ms();                 // summed HIP-event time of the SYRK launches of the last factorisation (read lazily)
-    double ms_syrk = 0, syrk_flops = 0;   // dominant kernel (k_syrk_cb): live HIP-event time per refactorisation, flops
+    double syrk_ms();                 // summed device time of the SYRK launches of the last factorisation (read lazily)
+    double ms_syrk = 0, syrk_flops = 0;   // dominant kernel (k_syrk_cb): device wall-clock stamps of its own workgroups per refactorisation, flops
     long long syrk_launches = 0;
     double bytes_total = 0;
     int device = 0;
@@ -408,6 +409,17 @@ private:
     // Members are destroyed in reverse order of declaration: the streams (own_stream_, stream2, stream3 above, stream_io_ here) are
     // declared before every buffer and event of the handle, so that those are released first and the streams last.
     Stream stream_io_;                // copy stream of the pipelined call's host I/O
+    // The events by their uses (all in device.cpp):
+    //   stream-to-stream hand-offs, only ever the argument of hipStreamWaitEvent on this device: ev_fact_, ev_inv_, ev_ready_,
+    //                 ev_ready2_, ev_done1_, ev_nzp0_, ev_nzp_, ev_flevel_[*]
+    //   host-waited:  ev_logdet_, ev_ring_[*], ev_bdiag_ (hipEventSynchronize); ev_up_, ev_x_, ev_qf_ (they order copies to / from
+    //                 host memory that the host reads or reuses behind them)
+    //   times read:   ev_[*], ev_lane_[*][*] (some of them are waited for by a stream as well), ev_level_[*] (GMRFX_LEVEL_MARK),
+    //                 con_ev_, bcon_ev_, rb_ev_: default flags
+    // The constraint, Fisher, RBMC and selected-inversion paths fork no stream of their own. MEASURED and not adopted (DESIGN.md
+    // section 5, "SYRK times from device stamps"): the hand-offs created with hipEventDisableTiming | hipEventReleaseToDevice
+    // (a device-scope release instead of the system-scope one) -- the step within its run-to-run spread either way; they stay
+    // hipEventDisableTiming alone.
     Event ev_fact_, ev_inv_;
     // the arena of the tables that live as long as the handle (append-only, released by the destructor)
     template <class T> T *dalloc(size_t count);
@@ -431,6 +443,8 @@ private:
     Event ev_nzp_, ev_nzp0_;
     AsmRec *d_arec_ = nullptr;          // one per position of the level lists (Symbolic::levellist order)
     SyrkTile *d_syrk_recs_ = nullptr;   // one record per contribution-block tile, level by level, in hand-out order
+    unsigned long long *d_syrk_times_ = nullptr;        // two device wall-clock words per record: the tile's start and end (k_syrk_cb_rec)
+    SyrkLevelTimes *d_syrk_level_times_ = nullptr;      // one per level: its records and its SYRK slot (k_syrk_reduce)
     EnvKnobs env_;                  // the environment's knobs (device_plan.h), read by init
     FrontView *d_frec_ = nullptr, *d_frec2_ = nullptr, *d_sel_frec_ = nullptr;   // geometry records parallel to the level lists
     int *d_levellist2_ = nullptr;   // per level: the big fronts re-ordered [even positions..., odd positions...] (two-stream panel chains)
@@ -502,7 +516,13 @@ private:
     std::vector<long long *> d_inv_lvl_toff_;                  // per stage: offsets into d_invT_, aligned with d_inv_lvl_list_
     void invert_level(hipStream_t st, int lev);
     bool fact_event_valid_ = false;   // ev_fact_ was recorded at the end of the last factorisation
-    PinnedBuf<int> h_info_;           // the pivot report of the last factorisation
+    // the pivot report of the last factorisation, then its SYRK stamps: kInfoWords ints (the pivot word + padding to 8 bytes), then
+    // per SYRK slot two 64-bit device wall-clock values (earliest start, latest end). d_info_ has the same layout; one copy brings both.
+    static constexpr int kInfoWords = 2;
+    PinnedBuf<int> h_info_;
+    static unsigned long long *syrk_stamps(int *info) { return reinterpret_cast<unsigned long long *>(info + kInfoWords); }
+    static size_t info_bytes(long long slots) { return kInfoWords * sizeof(int) + 2 * (size_t)slots * sizeof(unsigned long long); }
+    double wall_clock_khz_ = 0;       // hipDeviceAttributeWallClockRate: ticks per millisecond of the stamps
     PinnedBuf<double> h_qf_;          // quadratic forms of refactorize_logpdf
     Event ev_qf_;
     void prepare_quadform(long long nvec);
@@ -544,7 +564,6 @@ private:
     long long qf_cap_ = 0;
     bool nz_held_ = false;    // d_nz_ holds the values of the factorisation
     Event ev_[8];
-    std::vector<Event> ev_syrk_;        // begin/end event of every k_syrk_cb launch
     long long l_size_ = 0, sum_trail_ = 0;
     // batched handles (set_batch): members, member size / values; device partials + results of batch_diag / batch_quadform, pinned copies
     int nbatch_ = 1;

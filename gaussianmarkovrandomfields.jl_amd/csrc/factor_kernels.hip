@@ -1,6 +1,8 @@
 // factor_kernels.hip -- HIP kernels (gfx950 / CDNA4) of the numeric factorisation of the multifrontal supernodal Cholesky: assembly,
 // the panel chain below the diagonal block (TRSM, GEMM), the contribution-block SYRKs, the 128 x 128 tile of huge fronts; their
 // launch wrappers (the variant and geometry of a launch: choose_*, device_plan.h). Memory layout and MFMA maps: kernel_common.h.
+#include <climits>
+
 #include "kernel_common.h"
 
 namespace gmrfx {
@@ -536,8 +538,11 @@ __global__ __launch_bounds__(256) void k_gemm_nt(DevSym S, const FrontView *__re
 // epilogue stores LDS tile minus accumulators. No zero-fill, no read-modify-write of CB in HBM.
 // (Reference form on a plain 3-D grid, front x tile row x tile column: GMRFX_SYRK_XCD=0. The product path is
 // k_syrk_cb_rec below -- same arithmetic, tiles handed out per XCD from self-contained records.)
+// STAMP: the level's launch, timed (stamp_begin / stamp_end, kernel_common.h); the distributed fronts' launches are not, and keep
+// the code they had (with the stamps the compiler takes 102 registers instead of 76: 3 waves per SIMD instead of 4).
+template <bool STAMP>
 __global__ __launch_bounds__(256) void k_syrk_cb(DevSym S, const int *__restrict__ list, const double *__restrict__ L,
-                                                 double *__restrict__ CB, int cyc_w, int cyc_r, int cyc_b0) {
+                                                 double *__restrict__ CB, int cyc_w, int cyc_r, int cyc_b0, unsigned long long *stamp) {
     __shared__ double Tl[64 * 65];
     const int s = list[blockIdx.z], bi = blockIdx.x, bj = blockIdx.y;
     const int c = S.sfirst[s + 1] - S.sfirst[s];
@@ -547,6 +552,8 @@ __global__ __launch_bounds__(256) void k_syrk_cb(DevSym S, const int *__restrict
     // distributed front (cyc_w > 0): this rank computes the 256-column blocks of the contribution block it owns -- block q on
     // position (cyc_b0 + q) mod cyc_w of the group, cyc_b0 = the panel's blocks (the dealing continues behind the panel)
     if (cyc_w > 0 && (cyc_b0 + (bj >> 2)) % cyc_w != cyc_r) return;
+    // every workgroup with a tile stamps (the grid is a plain one: no workgroup is known to be the first or the last to run)
+    if (STAMP) stamp_begin(stamp, (unsigned long long)wall_clock64());
     const int ld = S.ld[s];
     const double *A = L + S.panelptr[s] + c;
     double *C = CB + S.cbptr[s];
@@ -600,7 +607,7 @@ __global__ __launch_bounds__(256) void k_syrk_cb(DevSym S, const int *__restrict
     }
     const int wave = tid >> 6, lane = tid & 63;
     const int i0 = ti0 + (wave & 1) * 32, j0 = tj0 + (wave >> 1) * 32;
-    if (i0 >= m || j0 >= m || j0 > i0 + 31) return;
+    if (i0 >= m || j0 >= m || j0 > i0 + 31) return;       // (never wave 0, whose first lane stamps the end)
     const int lm = lane & 15, lk = lane >> 4;
     d4 acc[2][2];
 #pragma unroll
@@ -620,6 +627,7 @@ __global__ __launch_bounds__(256) void k_syrk_cb(DevSym S, const int *__restrict
                 const int j = j0 + a * 16 + lk + 4 * rr, i = i0 + b * 16 + lm;
                 if (i < m && j < m && i >= j) C[i + (long long)j * m] = Tl[(i - ti0) + (j - tj0) * 65] - acc[a][b][rr];
             }
+    if (STAMP) stamp_end(stamp);
 }
 
 // The product form of the same tile, driven by one 128-byte record per tile (SyrkTile, device.h) and handed out per
@@ -634,13 +642,20 @@ __global__ __launch_bounds__(256) void k_syrk_cb(DevSym S, const int *__restrict
 struct SyrkOps { d2u a[2], b[2]; };       // the operands of two k-steps (rows in pairs): one stage of the pipelined product loop
 template <bool PIPED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k_syrk_cb_rec(DevSym S, const SyrkTile *__restrict__ recs, const SyrkSplit split,
-                                                     const double *__restrict__ L, double *__restrict__ CB, int noprod) {
+                                                     const double *__restrict__ L, double *__restrict__ CB, int noprod,
+                                                     unsigned long long *__restrict__ times) {
     // noprod: the children's extend-add only -- the product follows as its own launch on 128 x 128 staged tiles (k_syrk_big: the
     // huge fronts of 3-D problems)
     __shared__ double Tl[64 * 65];
     const int x = blockIdx.x & 7;
     const int t = split.start[x] + (int)(blockIdx.x >> 3);
     if (t >= split.start[x + 1]) return;
+    // the launch's time (Device::syrk_ms): every tile leaves the device wall clock of its start and of its end in its own two words
+    // of `times`, by one plain store behind its last one; k_syrk_reduce turns a level's tiles into the launch's slot behind the
+    // last level. (No atomics here: a launch has ~1000 tiles that start and end together, and atomics execute at the memory side,
+    // one address after the other -- measured, one atomic minimum and one maximum per tile into the launch's slot: k_syrk_cb_rec
+    // 3.35 -> 4.05 ms per step.)
+    const unsigned long long t_begin = (unsigned long long)wall_clock64();
     const SyrkTile T = recs[t];
     const int c = T.c, m = T.m, ld = T.ld, bi = T.bi, bj = T.bj;
     const double *A = L + T.pa;
@@ -826,7 +841,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             __syncthreads();
         }
     }
-    if (!live) return;
+    if (!live) return;       // (never wave 0 -- a tile's first 32 x 32 part reaches the lower triangle --, whose first lane stamps the end)
     // rows i, i + 1 of column j leave together (16 bytes) wherever both lie inside the lower triangle
 #pragma unroll
     for (int a = 0; a < 2; a++)
@@ -844,6 +859,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
                 }
             }
         }
+    if (tid == 0) *(ulonglong2 *)(times + 2 * (long long)(t)) = make_ulonglong2(t_begin, (unsigned long long)wall_clock64());
 }
 
 // The same update for the HUGE fronts of 3-D problems (round 5): 128 x 128 workgroup tiles, operands staged through LDS -- 16 k
@@ -943,13 +959,56 @@ __global__ __launch_bounds__(512) void k_gemm_nt_big(const FrontView *__restrict
 // cfg 4 the one-pass kernel's 64 x 64 tiles stream K = 8 000-16 000 columns of both operands per tile (8 flop per byte: it ran at
 // ~34 TFLOP/s, 3.5 of the 5.1 s); a 128 x 128 tile halves the operand bytes per flop. The extra read-modify-write of the block
 // (m^2 doubles twice) is milliseconds against seconds there.
-__global__ __launch_bounds__(512) void k_syrk_big(DevSym S, const int *__restrict__ list, const double *__restrict__ L, double *__restrict__ CB) {
+__global__ __launch_bounds__(512) void k_syrk_big(DevSym S, const int *__restrict__ list, const double *__restrict__ L, double *__restrict__ CB,
+                                                  unsigned long long *stamp) {
     const int s = list[blockIdx.z];
     const int c = S.sfirst[s + 1] - S.sfirst[s];
     const int r = (int)(S.rowptr[s + 1] - S.rowptr[s]);
     const int m = r - c;
     if (m <= 0) return;
+    // every workgroup of the lower triangle stamps (those without a tile leave gemm_nt_big_tile at once: all of it inside the launch)
+    const bool stamps = stamp && blockIdx.y <= blockIdx.x;
+    if (stamps) stamp_begin(stamp, (unsigned long long)wall_clock64());
     gemm_nt_big_tile(L + S.panelptr[s] + c, S.ld[s], CB + S.cbptr[s], m, m, m, c);
+    if (stamps) stamp_end(stamp);
+}
+
+// Behind the last level of a factorisation (or of a phase of one): the tile times of k_syrk_cb_rec, level by level, into the
+// levels' slots -- earliest start, latest end. One workgroup per level; the atomics (two per level) meet what k_syrk_big stamped
+// into the same slot.
+__global__ __launch_bounds__(256) void k_syrk_reduce(const SyrkLevelTimes *__restrict__ lev, const unsigned long long *__restrict__ times,
+                                                     unsigned long long *__restrict__ stamps) {
+    __shared__ unsigned long long lo[256], hi[256];
+    const SyrkLevelTimes r = lev[blockIdx.x];
+    if (r.slot < 0 || r.cnt <= 0) return;
+    unsigned long long a = ~0ull, b = 0ull;
+    for (int k = threadIdx.x; k < r.cnt; k += 256) {
+        const ulonglong2 v = *(const ulonglong2 *)(times + 2 * (r.off + k));
+        a = min(a, v.x); b = max(b, v.y);
+    }
+    lo[threadIdx.x] = a; hi[threadIdx.x] = b;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            lo[threadIdx.x] = min(lo[threadIdx.x], lo[threadIdx.x + w]);
+            hi[threadIdx.x] = max(hi[threadIdx.x], hi[threadIdx.x + w]);
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        atomicMin(stamps + 2 * r.slot, lo[0]);
+        atomicMax(stamps + 2 * r.slot + 1, hi[0]);
+    }
+}
+
+// The words a factorisation reports through, before its first launch: the pivot word = INT_MAX ("no pivot failed"), the SYRK
+// slots = (all ones, 0) for the atomic minimum / maximum of the stamps.
+__global__ __launch_bounds__(256) void k_factor_reset(int *__restrict__ info, unsigned long long *__restrict__ stamps, int nslots) {
+    if (threadIdx.x == 0) *info = INT_MAX;
+    for (int k = threadIdx.x; k < nslots; k += 256) {
+        stamps[2 * k] = ~0ull;
+        stamps[2 * k + 1] = 0ull;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -976,24 +1035,32 @@ void launch_assemble_cyclic(hipStream_t st, const DevSym &S, const int *list, in
                             int cyc_w, int cyc_r, bool compact) {
     hipLaunchKernelGGL(k_assemble<1>, dim3(odd(ncols), 1), dim3(256), 0, st, S, list, nzval, L, CB, cyc_w, cyc_r, compact ? 1 : 0);
 }
-void launch_syrk_cb(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB) {
+void launch_factor_reset(hipStream_t st, int *info, unsigned long long *stamps, int nslots) {
+    hipLaunchKernelGGL(k_factor_reset, dim3(1), dim3(256), 0, st, info, stamps, nslots);
+}
+void launch_syrk_cb(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB, unsigned long long *stamp) {
     if (nfronts <= 0 || max_trail <= 0) return;
-    hipLaunchKernelGGL(k_syrk_cb, dim3(odd(cdiv(max_trail, 64)), odd(cdiv(max_trail, 64)), nfronts), dim3(256), 0, st, S, list, L, CB, 0, 0, 0);
+    hipLaunchKernelGGL(k_syrk_cb<true>, dim3(odd(cdiv(max_trail, 64)), odd(cdiv(max_trail, 64)), nfronts), dim3(256), 0, st, S, list, L, CB, 0, 0, 0, stamp);
 }
 void launch_syrk_cb_cyclic(hipStream_t st, const DevSym &S, const int *list, int trail, const double *L, double *CB, int cyc_w, int cyc_r, int cyc_b0) {
     if (trail <= 0) return;
-    hipLaunchKernelGGL(k_syrk_cb, dim3(odd(cdiv(trail, 64)), odd(cdiv(trail, 64)), 1), dim3(256), 0, st, S, list, L, CB, cyc_w, cyc_r, cyc_b0);
+    hipLaunchKernelGGL(k_syrk_cb<false>, dim3(odd(cdiv(trail, 64)), odd(cdiv(trail, 64)), 1), dim3(256), 0, st, S, list, L, CB, cyc_w, cyc_r, cyc_b0,
+                       (unsigned long long *)nullptr);
 }
 void launch_syrk_cb_recs(hipStream_t st, const DevSym &S, const SyrkTile *recs, const SyrkSplit &split, int per_xcd, const double *L, double *CB,
-                         int noprod, bool piped) {
+                         unsigned long long *times, int noprod, bool piped) {
     if (per_xcd <= 0) return;
-    if (piped) hipLaunchKernelGGL(k_syrk_cb_rec<true>, dim3(8 * (unsigned)per_xcd), dim3(256), 0, st, S, recs, split, L, CB, noprod);
-    else hipLaunchKernelGGL(k_syrk_cb_rec<false>, dim3(8 * (unsigned)per_xcd), dim3(256), 0, st, S, recs, split, L, CB, noprod);
+    if (piped) hipLaunchKernelGGL(k_syrk_cb_rec<true>, dim3(8 * (unsigned)per_xcd), dim3(256), 0, st, S, recs, split, L, CB, noprod, times);
+    else hipLaunchKernelGGL(k_syrk_cb_rec<false>, dim3(8 * (unsigned)per_xcd), dim3(256), 0, st, S, recs, split, L, CB, noprod, times);
 }
-void launch_syrk_big(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB) {
+void launch_syrk_reduce(hipStream_t st, const SyrkLevelTimes *lev, int nlev, const unsigned long long *times, unsigned long long *stamps) {
+    if (nlev <= 0) return;
+    hipLaunchKernelGGL(k_syrk_reduce, dim3((unsigned)nlev), dim3(256), 0, st, lev, times, stamps);
+}
+void launch_syrk_big(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB, unsigned long long *stamp) {
     if (nfronts <= 0 || max_trail <= 0) return;
     const int nt = cdiv(max_trail, 128);
-    hipLaunchKernelGGL(k_syrk_big, dim3(odd(nt), odd(nt), nfronts), dim3(512), 0, st, S, list, L, CB);
+    hipLaunchKernelGGL(k_syrk_big, dim3(odd(nt), odd(nt), nfronts), dim3(512), 0, st, S, list, L, CB, stamp);
 }
 void launch_trsm(hipStream_t st, const DevSym &S, const FrontView *frec, int nactive, int kb, int mode, int max_rows_below,
                  double *L, double *Yh, const long long *yoff, const FrontArg &fa) {

@@ -20,6 +20,18 @@ namespace gmrfx {
 // a kernel with the grid, block and dynamic LDS that a choice function of device_plan.h returned
 #define GMRFX_LAUNCH(kernel, c, st, ...) hipLaunchKernelGGL(kernel, dim3((c).gx, (c).gy, (c).gz), dim3((c).block), (c).lds, st, __VA_ARGS__)
 
+// The time of a launch from the device's own wall clock instead of a pair of events on its stream (Device::syrk_ms): a slot of two
+// 64-bit words, slot[0] = the earliest start and slot[1] = the latest end over the workgroups that stamp it (k_factor_reset sets the
+// slot to all ones / 0; several launches may share one). One lane per workgroup, a plain device-scope atomic each way, nothing
+// waits for either: for launches of few, long workgroups (k_syrk_big) and the reference form k_syrk_cb -- k_syrk_cb_rec, ~1000
+// short tiles that start and end together, stores its times per tile instead (factor_kernels.hip). slot == nullptr: untimed.
+__device__ __forceinline__ void stamp_begin(unsigned long long *slot, unsigned long long t0) {
+    if (slot && threadIdx.x == 0) atomicMin(slot, t0);
+}
+__device__ __forceinline__ void stamp_end(unsigned long long *slot) {
+    if (slot && threadIdx.x == 0) atomicMax(slot + 1, (unsigned long long)wall_clock64());
+}
+
 // two doubles that are only known to be 8-byte aligned (one 16-byte load; the hardware takes unaligned addresses)
 typedef double gmrfx_d2u __attribute__((ext_vector_type(2), aligned(8)));
 typedef double gmrfx_d4 __attribute__((ext_vector_type(4)));

@@ -14,15 +14,24 @@ namespace gmrfx {
 void launch_gather_values(hipStream_t st, const double *nzval, const int *qsrc, double *out, long long cnt);
 void launch_assemble(hipStream_t st, const DevSym &S, const int *list, const AsmRec *arec, const double *nzp, int nfronts, int max_cols, int max_rows,
                      const double *nzval, double *L, double *CB);
-void launch_syrk_cb(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB);
+// info[0] = INT_MAX (no pivot failed), stamps[2 k] = all ones, stamps[2 k + 1] = 0 for the nslots SYRK slots: one launch of one workgroup
+void launch_factor_reset(hipStream_t st, int *info, unsigned long long *stamps, int nslots);
+// The time of the SYRK launches (Device::syrk_ms) from the device's wall clock. stamp (k_syrk_cb, k_syrk_big): the launch's slot of
+// two words -- earliest start, latest end over its workgroups (kernel_common.h, stamp_begin / stamp_end; one atomic each per
+// workgroup); launches that share a slot span it together. times (k_syrk_cb_rec): two words per tile of the level, start and
+// end, plain stores; launch_syrk_reduce takes them into the slots behind the last level.
+void launch_syrk_cb(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB, unsigned long long *stamp);
 // The same tiles from self-contained records, one contiguous run per XCD (workgroup id mod 8 = XCD): see k_syrk_cb_rec.
 void launch_syrk_cb_recs(hipStream_t st, const DevSym &S, const SyrkTile *recs, const SyrkSplit &split, int per_xcd, const double *L, double *CB,
-                         int noprod = 0, bool piped = false);
+                         unsigned long long *times, int noprod = 0, bool piped = false);
+// lev[0 .. nlev): per level the first tile (index into `times` / 2), the number of tiles and the slot (-1: none)
+struct SyrkLevelTimes { long long off; int cnt, slot; };
+void launch_syrk_reduce(hipStream_t st, const SyrkLevelTimes *lev, int nlev, const unsigned long long *times, unsigned long long *stamps);
 // piped: the product loop in three stages of two k-steps, each requested two stages ahead (levels whose widest front has at least
 // kSyrkPipedMinCols columns, device_plan.h; measured on cfg 2, round 6: k_syrk_cb_rec 3.60-3.69 -> 3.37-3.45 ms per step with 32 / 64 / 128 /
 // 200 / 300 alike, 600: 3.56)
 // CB -= L21 L21' on 128 x 128 LDS-staged tiles (behind a gather-only pass: noprod = 1), for levels of huge fronts
-void launch_syrk_big(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB);
+void launch_syrk_big(hipStream_t st, const DevSym &S, const int *list, int nfronts, int max_trail, const double *L, double *CB, unsigned long long *stamp);
 // blocks at most 32 columns wide, factorisation only (k_trsm<0, 0>'s arithmetic on half the registers)
 void launch_trsm_narrow(hipStream_t st, const FrontView *frec, int nactive, int kb, int max_rows_below, double *L);
 void launch_trsm(hipStream_t st, const DevSym &S, const FrontView *frec, int nactive, int kb, int mode, int max_rows_below,

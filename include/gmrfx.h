@@ -89,8 +89,10 @@ typedef struct gmrfx_stats {
             ms_logdet, ms_selinv;
     int64_t last_nrhs;
     int64_t fail_col;              /* -1, or first (permuted, 0-based) non-positive pivot   */
-    /* the dominant kernel of the factorisation (contribution-block SYRK, k_syrk_cb): summed HIP-event
-     * time of its launches in the most recent refactorisation, their number, and the flops they do
+    /* the dominant kernel of the factorisation (contribution-block SYRK, k_syrk_cb): summed device
+     * time of its launches in the most recent refactorisation -- per launch the latest end minus the
+     * earliest start that its own workgroups read from the device's wall clock (no event on the
+     * stream) --, their number, and the flops they do
      * (sum over big fronts of c m (m + 1), m = r - c: lower triangle only)                  */
     double  ms_syrk, syrk_flops;
     int64_t syrk_launches;
