@@ -10,6 +10,8 @@ static int32_t ga_pullback_impl(gmrfx_handle *h, const double *x, const double *
         if (!x) throw std::invalid_argument("ga_pullback: x is null");
         if (!out) throw std::invalid_argument("ga_pullback: out is null");
         if (h->obs.nobs == 0) throw std::invalid_argument("ga_pullback: no observation likelihood is set (gmrfx_obs_set)");
+        if (!h->obs.comp.empty())
+            throw std::invalid_argument("ga_pullback: composite likelihoods are not supported (one parameter cotangent per component is needed; gmrfx_obs_set_composite)");
         if (flags < 0 || flags > 3) throw std::invalid_argument("ga_pullback: unknown flag bits");
         if (!mubar && !Qbar) throw std::invalid_argument("ga_pullback: mubar and Qbar are both null");
         if (!Qbar_prior && !mubar_prior && !lambda) throw std::invalid_argument("ga_pullback: every output is null");

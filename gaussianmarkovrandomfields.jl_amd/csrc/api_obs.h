@@ -1,5 +1,5 @@
 // api_obs.h -- what the entry points that set an observation likelihood share (api_fisher.cpp: gmrfx_obs_set, gmrfx_obs_set_design;
-// api_batch_fisher.cpp: gmrfx_batch_obs_set): the checks of family, operands and values, and the constant of the log-likelihood.
+// api_composite.cpp: gmrfx_obs_set_composite; api_batch_fisher.cpp: gmrfx_batch_obs_set): the checks of family, operands and values, and the constant of the log-likelihood.
 #pragma once
 #include <cmath>
 
@@ -11,23 +11,28 @@
 //   Normal  nobs (-1/2 log 2 pi - log sigma)          Poisson  -sum lgamma(y + 1)          Bernoulli  0
 //   Binomial  sum lgamma(n + 1) - lgamma(y + 1) - lgamma(n - y + 1)
 //   NegBin  sum lgamma(y + r) - lgamma(r) - lgamma(y + 1) + r log r          Gamma  nobs (phi log phi - lgamma(phi)) + (phi - 1) sum log y
-inline double obs_loglik_const(int f, long long nobs_, const std::vector<double> &ys, const std::vector<double> &aux, double param) {
+// over the nobs observations at ys (aux: read by the binomial family alone), before the rounding to double: a composite likelihood
+// (gmrfx_obs_set_composite) adds its components' in long double
+inline long double obs_loglik_const_ld(int f, long long nobs_, const double *ys, const double *aux /* null: the family has none */, double param) {
     long double c = 0.0L;
     const long double p = (long double)param, nobs = (long double)nobs_;
     switch (f) {
         case 0: c = nobs * obs_const_shared(f, p); break;
-        case 1: for (double y : ys) c += obs_const_own(f, y, 0.0L, p); break;
+        case 1: for (long long k = 0; k < nobs_; k++) c += obs_const_own(f, ys[k], 0.0L, p); break;
         case 3:
-            for (size_t k = 0; k < ys.size(); k++) c += obs_const_own(f, ys[k], aux[k], p);
+            for (long long k = 0; k < nobs_; k++) c += obs_const_own(f, ys[k], aux[k], p);
             break;
-        case 4: for (double y : ys) c += obs_const_own(f, y, 0.0L, p); break;
+        case 4: for (long long k = 0; k < nobs_; k++) c += obs_const_own(f, ys[k], 0.0L, p); break;
         case 5:
             c = nobs * obs_const_shared(f, p);
-            for (double y : ys) c += obs_const_own(f, y, 0.0L, p);
+            for (long long k = 0; k < nobs_; k++) c += obs_const_own(f, ys[k], 0.0L, p);
             break;
         default: break;
     }
-    return (double)c;
+    return c;
+}
+inline double obs_loglik_const(int f, long long nobs_, const std::vector<double> &ys, const std::vector<double> &aux, double param) {
+    return (double)obs_loglik_const_ld(f, (long long)ys.size(), ys.data(), aux.data(), param);
 }
 inline double obs_loglik_const(const ObsHost &o) { return obs_loglik_const(o.family, o.nobs, o.y, o.aux, o.param); }
 
@@ -48,20 +53,22 @@ inline void obs_check_operands(const std::string &who, int32_t family, const dou
     if (family == 3 && !aux) throw std::invalid_argument(who + "the binomial family needs aux (the number of trials)");
     obs_check_param(who, family, param);
 }
+inline bool obs_family_reads_aux(int32_t family) { return family == 1 || family == 3 || family == 4; }      // (the others have no auxiliary number)
+// one observation's values under its family (aux: null when none is held; at: where, for the message)
+inline void obs_check_value(const std::string &who, int32_t family, double yk, const double *aux, const std::string &at) {
+    if (!std::isfinite(yk)) throw std::invalid_argument(who + "y is not finite" + at);
+    if (aux && !std::isfinite(*aux)) throw std::invalid_argument(who + "aux is not finite" + at);
+    if (family >= 1 && family <= 4 && yk < 0.0) throw std::invalid_argument(who + "negative count" + at);
+    if (family == 2 && yk > 1.0) throw std::invalid_argument(who + "a Bernoulli observation above 1" + at);
+    if (family == 3 && !(*aux >= 0.0 && yk <= *aux)) throw std::invalid_argument(who + "y exceeds the number of trials" + at);
+    if (family == 5 && !(yk > 0.0)) throw std::invalid_argument(who + "a Gamma observation must be positive" + at);
+}
 // y, aux, param and loglik_const of o, observation by observation
 inline void obs_fill_values(ObsHost &o, const std::string &who, int32_t family, int64_t nobs, const double *y, const double *aux, double param) {
     o.family = family; o.nobs = nobs; o.param = param;
     o.y.assign(y, y + nobs);
-    if (aux && family != 0 && family != 2 && family != 5) o.aux.assign(aux, aux + nobs);      // (the others have no auxiliary number)
-    for (int64_t k = 0; k < nobs; k++) {
-        const double yk = o.y[(size_t)k];
-        const std::string at = " (observation " + std::to_string(k) + ")";
-        if (!std::isfinite(yk)) throw std::invalid_argument(who + "y is not finite" + at);
-        if (!o.aux.empty() && !std::isfinite(o.aux[(size_t)k])) throw std::invalid_argument(who + "aux is not finite" + at);
-        if (family >= 1 && family <= 4 && yk < 0.0) throw std::invalid_argument(who + "negative count" + at);
-        if (family == 2 && yk > 1.0) throw std::invalid_argument(who + "a Bernoulli observation above 1" + at);
-        if (family == 3 && !(o.aux[(size_t)k] >= 0.0 && yk <= o.aux[(size_t)k])) throw std::invalid_argument(who + "y exceeds the number of trials" + at);
-        if (family == 5 && !(yk > 0.0)) throw std::invalid_argument(who + "a Gamma observation must be positive" + at);
-    }
+    if (aux && obs_family_reads_aux(family)) o.aux.assign(aux, aux + nobs);
+    for (int64_t k = 0; k < nobs; k++)
+        obs_check_value(who, family, o.y[(size_t)k], o.aux.empty() ? nullptr : &o.aux[(size_t)k], " (observation " + std::to_string(k) + ")");
     o.loglik_const = obs_loglik_const(o);
 }

@@ -70,6 +70,18 @@ struct ConHost {
 // 5 Gamma / log (param phi). idx: the observed nodes, 0-based, in the caller's order; y and aux (empty: none) go with them.
 // design (gmrfx_obs_set_design): non-null when the likelihood is observed through eta = A x + b; idx is then empty and y / aux go
 // with the rows of A.
+// comp (gmrfx_obs_set_composite): non-empty when the rows of A belong to several components, each with a family and a parameter of its
+// own; family is then kObsComposite, param unused, aux one value per row (0 on the rows of components without one; empty: none given)
+// and loglik_const the sum of the components'.
+constexpr int kObsFamilies = 6, kObsMaxComponents = 16, kObsComposite = -2;
+struct ObsComponents {
+    std::vector<int> family;                 // ncomp
+    std::vector<double> param, loglik_const; // ncomp each: the component's parameter and its constant over its own rows
+    std::vector<long long> rowptr;           // ncomp + 1: component c owns rows rowptr[c] .. rowptr[c + 1]
+    bool empty() const { return family.empty(); }
+    size_t size() const { return family.size(); }
+};
+struct ObsComp;
 struct ObsHost {
     int family = 0;
     long long nobs = 0;
@@ -77,8 +89,8 @@ struct ObsHost {
     std::vector<double> y, aux;
     double param = 0, loglik_const = 0;      // the sum of the terms of loglik that do not depend on x (long double on the host)
     std::shared_ptr<const DesignPlan> design;
+    ObsComponents comp;
 };
-constexpr int kObsFamilies = 6;
 // The likelihood of a batched handle (gmrfx_batch_obs_set): ONE data set (idx, y, aux as in ObsHost) and one parameter per member, with
 // the member's loglik_const; nobs = 0: none. A plain handle keeps one too, as a batch of one, beside the ObsHost of gmrfx_obs_set.
 constexpr int kBatchFisherMaxMembers = 65535;      // the member is the second dimension of the launch grid
@@ -260,6 +272,8 @@ public:
     // obs_set expands y, aux and the observed mask to length-n arrays on the device (nobs = 0: drops them), built aside: a failed
     // upload leaves the previous likelihood in place.
     void obs_set(const ObsHost &o);
+    // the parameters of the composite in place replaced (gmrfx_obs_composite_set_param): C.param and the new total constant
+    void obs_composite_set_param(const ObsComponents &C, double loglik_const);
     bool obs_held() const { return (bool)fisher_.y; }
     // entries of the Hessian vector of fisher_eval / gaussian_approximation: n in node form, the map's cnt in design form
     long long hess_len() const { return fisher_.design ? fisher_.design->cnt : S_->n; }
@@ -673,6 +687,13 @@ private:
         PinnedBuf<double> h_out;
         DevBuf<double> g, d, lpart, cpart;
         DevBuf<double> param_k, logparam_k, ctl;
+        // a composite likelihood (fisher_ only; ncomp = 0: a single family): the component of every observation and the component
+        // table, cpar = ncomp parameters, then their ncomp logs
+        int ncomp = 0;
+        DevBuf<unsigned char> comp;
+        DevBuf<int> cfamily;
+        DevBuf<double> cpar;
+        ObsComp comp_table() const;      // (kernels.h; device_fisher.cpp)
         DevBuf<long long> rp;
         DevBuf<int> col, pos;
         PinnedBuf<double> h_ctl;
@@ -685,6 +706,7 @@ private:
         const std::vector<double> *y, *aux;
         std::shared_ptr<const DesignPlan> design;
         const std::vector<double> &param, &loglik_const;
+        const ObsComponents *comp = nullptr;      // a composite likelihood (design form, one member)
     };
     FisherDev fisher_build(const FisherSource &src, size_t n, const RbmcSym *rows);
     // An evaluation of every member of a slot on the row structure `rows`: member k's point at d_x + k sx, mean at d_mu + k smu

@@ -70,6 +70,7 @@ void Device::design_upload(const std::shared_ptr<const DesignPlan> &plan, Design
 // evaluation's and the loop's work per member. The batch slot (rows non-null) adds what a plain likelihood passes by value or takes
 // from the handle: the members' parameters and their logs, the member's rows (the forest's first n: columns and positions of member 0
 // are the member's own) and the control words.
+static std::vector<double> fisher_comp_params(const ObsComponents &C);
 Device::FisherDev Device::fisher_build(const FisherSource &src, size_t n, const RbmcSym *rows) {
     FisherDev f;
     const size_t nb = src.param.size();
@@ -101,6 +102,15 @@ Device::FisherDev Device::fisher_build(const FisherSource &src, size_t n, const 
         dev_upload(f.y, *src.y, &bytes_total);
         if (!src.aux->empty()) dev_upload(f.aux, *src.aux, &bytes_total);
         design_upload(src.design, f);
+        if (src.comp) {
+            const ObsComponents &C = *src.comp;
+            std::vector<unsigned char> comp(nobs);
+            for (size_t c = 0; c < C.size(); c++) std::fill(comp.begin() + C.rowptr[c], comp.begin() + C.rowptr[c + 1], (unsigned char)c);
+            f.ncomp = (int)C.size();
+            dev_upload(f.comp, comp, &bytes_total);
+            dev_upload(f.cfamily, C.family, &bytes_total);
+            dev_upload(f.cpar, fisher_comp_params(C), &bytes_total);
+        }
         f.g.alloc(nobs * nb, &bytes_total, kTableMinBytes);
         f.d.alloc(nobs * nb, &bytes_total, kTableMinBytes);
         f.cpart.alloc((size_t)(f.ncc + f.nct) * nb, &bytes_total, kTableMinBytes);
@@ -116,6 +126,14 @@ Device::FisherDev Device::fisher_build(const FisherSource &src, size_t n, const 
     return f;
 }
 
+// the component table's parameters as the device holds them: the ncomp parameters, then their logs (fisher_logparam)
+static std::vector<double> fisher_comp_params(const ObsComponents &C) {
+    std::vector<double> p(C.param);
+    for (size_t c = 0; c < C.size(); c++) p.push_back(fisher_logparam(C.family[c], C.param[c]));
+    return p;
+}
+ObsComp Device::FisherDev::comp_table() const { return ObsComp{comp, cfamily, cpar.get(), cpar.get() + ncomp}; }
+
 void Device::obs_set(const ObsHost &o) {
     HC(hipSetDevice(device));
     if (sharded() || many_members()) throw std::invalid_argument("obs_set: batched and sharded handles are not supported");
@@ -125,13 +143,27 @@ void Device::obs_set(const ObsHost &o) {
         if (o.design && ((long long)n != o.design->n || n > (size_t)INT_MAX)) throw std::invalid_argument("obs_set_design: the plan does not belong to this handle");
         const ObsByNode b = o.design ? ObsByNode{} : obs_by_node(n, o.nobs, o.idx, o.y, o.aux);
         const std::vector<double> param{o.param}, loglik_const{o.loglik_const};
-        f = fisher_build(FisherSource{o.family, &b, &o.y, &o.aux, o.design, param, loglik_const}, n, nullptr);
+        if (!o.comp.empty() && (!o.design || o.comp.rowptr.size() != o.comp.size() + 1 || o.comp.rowptr.back() != o.nobs))
+            throw std::invalid_argument("obs_set_composite: the components do not belong to this likelihood");
+        f = fisher_build(FisherSource{o.family, &b, &o.y, &o.aux, o.design, param, loglik_const, o.comp.empty() ? nullptr : &o.comp}, n, nullptr);
     }
     HC(hipStreamSynchronize(stream));        // (an evaluation in flight on an external stream still reads the old arrays)
     fisher_ = std::move(f);
     gap_ = GapDev{};         // (the pullback's tables belong to the likelihood: rebuilt on its next call)
     pred_ = PredDev{};       // (and so do the predictive calls')
     prior_design_ = -1;
+}
+
+// The parameters of the composite in place: the table's 2 ncomp doubles and the constant. The plan, the component bytes and every
+// other table stay; the cached pointwise constants belong to the parameters and are rebuilt on the next predictive call.
+void Device::obs_composite_set_param(const ObsComponents &C, double loglik_const) {
+    HC(hipSetDevice(device));
+    if (fisher_.ncomp <= 0 || (size_t)fisher_.ncomp != C.size()) throw std::invalid_argument("obs_composite_set_param: no composite likelihood is set");
+    const std::vector<double> p = fisher_comp_params(C);
+    HC(hipStreamSynchronize(stream));      // nothing in flight may still read the previous values
+    HC(hipMemcpy(fisher_.cpar, p.data(), p.size() * sizeof(double), hipMemcpyHostToDevice));
+    fisher_.loglik_const.assign(1, loglik_const);
+    pred_ = PredDev{};
 }
 
 void Device::fisher_launch(FisherDev &f, const FisherRows &rows, const FisherIO &io, const unsigned char *active, double *out_host) {
@@ -152,7 +184,8 @@ void Device::fisher_launch(FisherDev &f, const FisherRows &rows, const FisherIO 
         a.epart = f.part; a.lpart = f.lpart;
         a.nnz = f.nnz; a.sx = io.sx; a.smu = io.smu; a.ss = io.ss; a.sh = io.sh;
         a.param_k = f.param_k; a.logparam_k = f.logparam_k; a.active = io.d_active;
-        launch_fisher_design(stream, a, f.members, f.out);
+        if (f.ncomp > 0) launch_fisher_design_comp(stream, a, f.comp_table(), f.members, f.out);
+        else launch_fisher_design(stream, a, f.members, f.out);
     } else {
         auto a = FisherEval{};
         a.n = f.n; a.family = f.family;

@@ -20,6 +20,12 @@ namespace gmrfx {
 #define HC(x) hip_check((x), #x)
 
 void obs_pointwise_const(const ObsHost &o, double *out) {
+    for (size_t c = 0; c < o.comp.size(); c++) {        // a composite: every row under its own component
+        const long double p = (long double)o.comp.param[c];
+        for (long long k = o.comp.rowptr[c]; k < o.comp.rowptr[c + 1]; k++)
+            out[k] = (double)obs_const_term(o.comp.family[c], o.y[(size_t)k], o.aux.empty() ? 0.0 : o.aux[(size_t)k], p);
+    }
+    if (!o.comp.empty()) return;
     const long double p = (long double)o.param;
     for (long long k = 0; k < o.nobs; k++)
         out[k] = (double)obs_const_term(o.family, o.y[(size_t)k], o.aux.empty() ? 0.0 : o.aux[(size_t)k], p);
@@ -97,7 +103,8 @@ void Device::pred_marg_launch(const FisherDev &f, const GapDev &g, const PredDev
     a.mu_eta = io.d_mu_eta; a.v_eta = io.d_v_eta; a.pll = io.d_pll;
     a.sx = r.sx; a.sz = r.sz; a.sb = r.sb; a.sc = p.sc; a.so = r.so;
     a.param_k = f.param_k; a.logparam_k = f.logparam_k; a.active = r.d_active;
-    launch_pred_marginals(stream, a, (bool)f.design, p.members);
+    if (f.ncomp > 0) launch_pred_marginals_comp(stream, a, f.comp_table(), p.members);
+    else launch_pred_marginals(stream, a, (bool)f.design, p.members);
 }
 
 void Device::pred_score_launch(const FisherDev &f, PredDev &p, const ScoreIO &io, long long stride, const unsigned char *d_active) {
@@ -114,7 +121,8 @@ void Device::pred_score_launch(const FisherDev &f, PredDev &p, const ScoreIO &io
     a.part = p.part;
     a.sm = stride; a.sc = p.sc; a.so = stride;
     a.param_k = f.param_k; a.logparam_k = f.logparam_k; a.active = d_active;
-    launch_pred_scores(stream, a, p.members, p.out);
+    if (f.ncomp > 0) launch_pred_scores_comp(stream, a, f.comp_table(), p.members, p.out);
+    else launch_pred_scores(stream, a, p.members, p.out);
     HC(hipMemcpyAsync(p.h_out, p.out, 4 * (size_t)p.members * sizeof(double), hipMemcpyDeviceToHost, stream));
 }
 

@@ -7,6 +7,8 @@
 //   hess[p] = sum_t w_t d_{i_t}(eta_{i_t})             the hvals of gmrfx_refactorize_update under the map of gmrfx_obs_hess_map
 //   energy  = sum_j (0.5 x_j (Q_p x)_j - x_j h_j),  loglik = sum_i l_i(eta_i)
 //   k_design_eta     a lane group per row of A: eta_i, then g_i, d_i and l_i (fisher_point.h); one loglik partial per workgroup
+//   k_design_eta_comp  the same row pass for a composite likelihood (gmrfx_obs_set_composite): the row's family and parameter come from
+//                    the component table (ObsComp), one byte per observation naming the component
 //   k_design_chunks  one workgroup per chunk of kDesignChunk entries of a long column of A (sum A_ij g_i; when the score is wanted) or
 //                    term list (sum w_t d_i; when the Hessian is)
 //   k_design_score   a lane group per node: the pass of k_fisher_eval over Symmetric(Q_p) (fisher_gather.h), then the gather over column j of A
@@ -73,6 +75,41 @@ __global__ __launch_bounds__(256) void k_design_eta(const FisherDesign a) {
             double gi, di;
             fisher_point(a.family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, a.param_k ? a.param_k[k] : a.param,
                          a.logparam_k ? a.logparam_k[k] : a.logparam, gi, di, ll);
+            a.g[(long long)k * a.nobs + i] = gi;
+            a.d[(long long)k * a.nobs + i] = di;
+        }
+    }
+    if (l == 0) sl[g] = ll;
+    __syncthreads();
+    for (int st = kDesignRows / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) sl[threadIdx.x] += sl[threadIdx.x + st];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) a.lpart[(long long)k * gridDim.x + blockIdx.x] = sl[0];
+}
+
+// k_design_eta for a composite likelihood: the same statements, except that lane 0 takes the row's (family, param, logparam) from the
+// component table in device memory. KEEP THE TWO IN STEP: the body is written twice because sharing it through an inlined function
+// gives k_design_eta another instruction schedule; the one-component test of tests/test_gpu_composite.py compares
+// their bits.
+__global__ __launch_bounds__(256) void k_design_eta_comp(const FisherDesign a, const ObsComp t) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
+    __shared__ double sl[kDesignRows];
+    const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
+    const long long i = (long long)blockIdx.x * kDesignRows + g;
+    double ll = 0.0;
+    if (i < a.nobs) {           // (a whole lane group takes the branch together)
+        const double *x = a.x + (long long)k * a.sx;
+        double s = 0.0;
+        const long long q1 = a.arp[i + 1];
+        for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], x[a.acol[q]], s);
+        s = design_group_sum(s);
+        if (l == 0) {
+            const double eta = a.offset ? s + a.offset[i] : s;
+            const int c = t.comp[i];
+            double gi, di;
+            fisher_point(t.family[c], eta, a.y[i], a.aux ? a.aux[i] : 0.0, t.param[c], t.logparam[c], gi, di, ll);
             a.g[(long long)k * a.nobs + i] = gi;
             a.d[(long long)k * a.nobs + i] = di;
         }
@@ -172,17 +209,23 @@ __global__ __launch_bounds__(kFisherFinal) void k_design_final(const double *__r
     if (tid == 0) { out[2 * (long long)k] = se[0]; out[2 * (long long)k + 1] = sl[0]; }
 }
 
-void launch_fisher_design(hipStream_t st, const FisherDesign &a, int nbatch, double *out) {
+// t null: a single family (k_design_eta); non-null: a composite (k_design_eta_comp)
+static void design_launches(hipStream_t st, const FisherDesign &a, const ObsComp *t, int nbatch, double *out) {
     if (a.n <= 0 || a.nobs <= 0 || nbatch <= 0) return;
     const int ne = design_blocks(a.n), nl = design_blocks(a.nobs);
     const unsigned nb = (unsigned)nbatch;
-    hipLaunchKernelGGL(k_design_eta, dim3((unsigned)nl, nb), dim3(256), 0, st, a);
+    if (t) hipLaunchKernelGGL(k_design_eta_comp, dim3((unsigned)nl, nb), dim3(256), 0, st, a, *t);
+    else hipLaunchKernelGGL(k_design_eta, dim3((unsigned)nl, nb), dim3(256), 0, st, a);
     // the chunk sums of the long columns feed the score only, those of the long term lists the Hessian only
     const int c0 = a.score ? 0 : a.ncc, c1 = a.hess ? a.ncc + a.nct : a.ncc;
     if ((a.score || a.hess) && c1 > c0) hipLaunchKernelGGL(k_design_chunks, dim3((unsigned)(c1 - c0), nb), dim3(256), 0, st, a, c0);
     hipLaunchKernelGGL(k_design_score, dim3((unsigned)ne, nb), dim3(256), 0, st, a);
     if (a.hess && a.cnt > 0) hipLaunchKernelGGL(k_design_hess, dim3((unsigned)design_blocks(a.cnt), nb), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_design_final, dim3(nb), dim3(kFisherFinal), 0, st, a.epart, ne, a.lpart, nl, a.active, out);
+}
+void launch_fisher_design(hipStream_t st, const FisherDesign &a, int nbatch, double *out) { design_launches(st, a, nullptr, nbatch, out); }
+void launch_fisher_design_comp(hipStream_t st, const FisherDesign &a, const ObsComp &t, int nbatch, double *out) {
+    design_launches(st, a, &t, nbatch, out);
 }
 
 }  // namespace gmrfx

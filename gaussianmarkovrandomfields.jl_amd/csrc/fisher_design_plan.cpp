@@ -14,16 +14,15 @@ namespace gmrfx {
 
 static constexpr i64 kDesignIndexLimit = (i64)1 << 31;
 
-void design_check_sizes(i64 n, i64 nobs, i64 nnz) {
+void design_check_sizes(i64 n, i64 nobs, i64 nnz, const std::string &who) {
     if (n >= kDesignIndexLimit || nobs >= kDesignIndexLimit || nnz >= kDesignIndexLimit)
-        throw std::invalid_argument("obs_set_design: n, nobs or nnz(A) is 2^31 or above");
+        throw std::invalid_argument(who + "n, nobs or nnz(A) is 2^31 or above");
 }
 
 void design_build_plan(const RbmcSym &R, i64 n, i64 nnzq, i64 nobs, const int64_t *colptr, const int64_t *rowval, const double *nzval,
-                       int index_base, const double *offset, DesignPlan &out) {
-    const std::string who = "obs_set_design: ";
+                       int index_base, const double *offset, DesignPlan &out, const std::string &who) {
     const i64 nnz = colptr[n] - index_base;
-    design_check_sizes(n, nobs, nnz);
+    design_check_sizes(n, nobs, nnz, who);
     DesignPlan P;
     P.n = n; P.nobs = nobs; P.nnz = nnz;
     P.cptr.resize((size_t)n + 1);

@@ -4,6 +4,7 @@
 // linearly_transformed.jl:313-340: loggrad = A' g, loghessian = A' D A) and _sparse_hessian_map (src/workspace/gaussian_approximation.jl:73-129).
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "rbmc_plan.h"
@@ -31,12 +32,12 @@ struct DesignPlan {
 };
 
 // Throws std::invalid_argument when n, nobs or nnz(A) is 2^31 or above: before anything of that length is read.
-void design_check_sizes(i64 n, i64 nobs, i64 nnz);
+void design_check_sizes(i64 n, i64 nobs, i64 nnz, const std::string &who = "obs_set_design: ");
 // A: nobs x n in CSC with ptr[0] == index_base and a monotone colptr (the caller has checked both). Throws std::invalid_argument
 // (P unchanged) for a row index outside [0, nobs), unsorted or repeated row indices within a column, a non-finite value of A or
 // offset, a pair (j, k) of pattern(A'A) that Q does not store (the first one, named in the caller's index base), and for n, nobs,
-// nnz(A) or the term count at 2^31 or above. nnzq: stored entries of Q.
+// nnz(A) or the term count at 2^31 or above. nnzq: stored entries of Q. who: the prefix of the messages (the entry point's name).
 void design_build_plan(const RbmcSym &R, i64 n, i64 nnzq, i64 nobs, const int64_t *colptr, const int64_t *rowval, const double *nzval,
-                       int index_base, const double *offset, DesignPlan &P);
+                       int index_base, const double *offset, DesignPlan &P, const std::string &who = "obs_set_design: ");
 
 }  // namespace gmrfx

@@ -322,6 +322,18 @@ struct FisherDesign {
 // nbatch members (a plain handle: 1): out[2 k] = member k's energy, out[2 k + 1] = its sum of the x-dependent terms of loglik (device);
 // inactive members' pairs are left
 void launch_fisher_design(hipStream_t st, const FisherDesign &a, int nbatch, double *out);
+// A composite likelihood (gmrfx_obs_set_composite): the rows of A belong to ncomp <= kObsMaxComponents components, each with a family
+// and a parameter of its own. comp[i]: the component of observation i (one byte beside the >= 20 a row reads); family / param /
+// logparam: ncomp each, in device memory (a lane-varying index into a by-value array would send the array to scratch). The kernels
+// that take one read the row's (family, param, logparam) there and ignore those of their first argument; everything else is the
+// single-family kernel's: same lane groups, same order of summation, same trees.
+struct ObsComp {
+    const unsigned char *comp;   // nobs
+    const int *family;           // ncomp
+    const double *param, *logparam;
+};
+// the same launch sequence with k_design_eta_comp in place of k_design_eta (the other four kernels never read the family)
+void launch_fisher_design_comp(hipStream_t st, const FisherDesign &a, const ObsComp &t, int nbatch, double *out);
 
 // ga_pullback.hip -- the array arithmetic of the implicit-function rule of the Gaussian approximation (gmrfx_ga_pullback,
 // gmrfx_batch_ga_pullback). The solve in the middle is the handle's own; these are the kernels on either side of it. Node form: one
@@ -458,6 +470,8 @@ struct PredMarg {
     const unsigned char *active; // nullable = all
 };
 void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design, int nbatch);
+// a composite likelihood (design form only): k_pred_design_comp; a.c holds every observation's constant under its own component
+void launch_pred_marginals_comp(hipStream_t st, const PredMarg &a, const ObsComp &t, int nbatch);
 struct PredScores {
     int nobs, K, family;
     const double *mu, *v;        // nobs each
@@ -475,6 +489,7 @@ struct PredScores {
 };
 // out4 (device) = member k's totals of lpd, lcpo, elp, vlp at + 4 k; inactive members' are left
 void launch_pred_scores(hipStream_t st, const PredScores &a, int nbatch, double *out4);
+void launch_pred_scores_comp(hipStream_t st, const PredScores &a, const ObsComp &t, int nbatch, double *out4);      // (a.idx null: by observation)
 // The mixture over the members with weights omega_k (w: nbatch weights, then nbatch logs of them; a member whose log is -inf is never
 // read): mix_mu = sum omega mu, mix_v = sum omega (v + (mu - mix_mu)^2), mix_lpd = log sum exp(log omega + lpd). mu, v, lpd (nullable):
 // nobs x nbatch, member stride nobs; mix_* nobs each, nullable. One thread per observation, members in ascending order. With lpd:

@@ -15,6 +15,8 @@
 //   k_pred_node      one thread per observation
 //   k_pred_design    a lane group per row of A; (a_i B)_l: one lane-group sum per column l of B, squares added in the order of l
 //   k_pred_scores    a lane group per observation, lane l owns the nodes l, l + 16, l + 32, l + 48; one partial of each total per workgroup
+//   k_pred_design_comp, k_pred_scores_comp   the same two for a composite likelihood (gmrfx_obs_set_composite): l_i under the family and
+//                    parameter of observation i's component (kernels.h: ObsComp), c_i from the per-component constants
 //   k_pred_final     the four totals: a strided loop over the workgroups' partials and a tree, as k_fisher_final
 // B is read where the constraint keeps it (n x m column-major, stride n between columns): a row of A touches a few nodes, so a
 // transposed copy (8 n m bytes more, a launch per factorisation) would save nothing a lane group could use.
@@ -123,7 +125,54 @@ __global__ __launch_bounds__(256) void k_pred_design(const PredMarg a) {
                                a.logparam_k ? a.logparam_k[k] : a.logparam, a.c[(long long)k * a.sc + i]);
 }
 
-__global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
+// k_pred_design for a composite likelihood (kernels.h: ObsComp): the same statements -- mean and variance do not depend on the family
+// -- except that lane 0 takes the row's (family, param, logparam) from the component table. KEEP THE TWO IN STEP: the body is written
+// twice because sharing it through an inlined function gives k_pred_design another instruction schedule; the
+// one-component test of tests/test_gpu_composite.py compares their bits.
+__global__ __launch_bounds__(256) void k_pred_design_comp(const PredMarg a, const ObsComp t) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
+    const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
+    const long long i = (long long)blockIdx.x * kDesignRows + g;
+    if (i >= a.nobs) return;         // (a whole lane group leaves together)
+    const long long o = (long long)k * a.so + i;
+    const double *__restrict__ x = a.x + (long long)k * a.sx;
+    const long long q0 = a.arp[i], q1 = a.arp[i + 1];
+    double s = 0.0;
+    for (long long q = q0 + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], x[a.acol[q]], s);
+    s = pred_group_sum(s);
+    const double mu = a.offset ? s + a.offset[i] : s;
+    if (l == 0 && a.mu_eta) a.mu_eta[o] = mu;
+    if (a.v_eta) {
+        const long long *__restrict__ zoff = a.zoff + (long long)k * a.sz;
+        double v = 0.0;
+        const long long o1 = a.optr[i + 1];
+        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) v = __builtin_fma(a.ow[q], a.Z[zoff[a.hmap[a.oidx[q]]]], v);
+        v = pred_group_sum(v);
+        if (a.m > 0) {
+            const double *__restrict__ B = a.B + (long long)k * a.sb;
+            double corr = 0.0;
+            for (int c = 0; c < a.m; c++) {
+                const double *__restrict__ Bc = B + (long long)c * a.n;
+                double ab = 0.0;
+                for (long long q = q0 + l; q < q1; q += kDesignLanes) ab = __builtin_fma(a.aval[q], Bc[a.acol[q]], ab);
+                ab = pred_group_sum(ab);
+                corr = __builtin_fma(ab, ab, corr);
+            }
+            v = pred_clamp(v, corr);
+        }
+        if (l == 0) a.v_eta[o] = v;
+    }
+    if (l == 0 && a.pll) {
+        const int c = t.comp[i];
+        a.pll[o] = pred_loglik(t.family[c], mu, a.y[i], a.aux ? a.aux[i] : 0.0, t.param[c], t.logparam[c], a.c[(long long)k * a.sc + i]);
+    }
+}
+
+// k_pred_scores and k_pred_scores_comp (COMP: the observation's family and parameter from the component table; every lane of the group
+// reads its observation's component, the same address). COMP = false reads no table.
+template <bool COMP>
+__device__ __forceinline__ void pred_scores_rows(const PredScores &a, const ObsComp &tab) {
     __shared__ double sp[4][kDesignRows];
     const int m = blockIdx.y;
     if (a.active && !a.active[m]) return;       // (the whole workgroup: nobody waits at the barriers below)
@@ -135,7 +184,15 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
         const double mu = a.mu[(long long)m * a.sm + i], v = a.v[(long long)m * a.sm + i];
         const long long j = a.idx ? a.idx[i] : i;
         const double y = a.y[j], aux = a.aux ? a.aux[j] : 0.0, c = a.c[(long long)m * a.sc + i];
-        const double param = a.param_k ? a.param_k[m] : a.param, logparam = a.logparam_k ? a.logparam_k[m] : a.logparam;
+        int family;
+        double param, logparam;
+        if constexpr (COMP) {
+            const int cm = tab.comp[i];
+            family = tab.family[cm]; param = tab.param[cm]; logparam = tab.logparam[cm];
+        } else {
+            family = a.family;
+            param = a.param_k ? a.param_k[m] : a.param; logparam = a.logparam_k ? a.logparam_k[m] : a.logparam;
+        }
         const double s = sqrt(v);
         double lk[kPredNodesPerLane], wk[kPredNodesPerLane];
         double M = -INFINITY, Mn = -INFINITY, e = 0.0;
@@ -145,7 +202,7 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
             lk[t] = 0.0; wk[t] = 0.0;
             if (k < a.K) {
                 wk[t] = a.w[k];
-                lk[t] = pred_loglik(a.family, __builtin_fma(s, a.z[k], mu), y, aux, param, logparam, c);
+                lk[t] = pred_loglik(family, __builtin_fma(s, a.z[k], mu), y, aux, param, logparam, c);
                 M = fmax(M, lk[t]);
                 Mn = fmax(Mn, -lk[t]);
                 e = __builtin_fma(wk[t], lk[t], e);
@@ -189,6 +246,8 @@ __global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) {
     }
     if (threadIdx.x < 4) a.part[4 * ((long long)m * gridDim.x + blockIdx.x) + threadIdx.x] = sp[threadIdx.x][0];
 }
+__global__ __launch_bounds__(256) void k_pred_scores(const PredScores a) { pred_scores_rows<false>(a, ObsComp{}); }
+__global__ __launch_bounds__(256) void k_pred_scores_comp(const PredScores a, const ObsComp t) { pred_scores_rows<true>(a, t); }
 
 // one workgroup per member: member k's nb partial quadruples at part + 4 k nb, its totals at out + 4 k
 __global__ __launch_bounds__(kFisherFinal) void k_pred_final(const double *__restrict__ part, int nb, const unsigned char *__restrict__ active,
@@ -286,6 +345,18 @@ void launch_pred_marginals(hipStream_t st, const PredMarg &a, bool design, int n
     if (a.nobs <= 0 || nbatch <= 0) return;
     if (design) hipLaunchKernelGGL(k_pred_design, dim3((unsigned)design_blocks(a.nobs), (unsigned)nbatch), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_pred_node, dim3((unsigned)((a.nobs + kPredNode - 1) / kPredNode), (unsigned)nbatch), dim3(kPredNode), 0, st, a);
+}
+
+void launch_pred_marginals_comp(hipStream_t st, const PredMarg &a, const ObsComp &t, int nbatch) {
+    if (a.nobs <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_pred_design_comp, dim3((unsigned)design_blocks(a.nobs), (unsigned)nbatch), dim3(256), 0, st, a, t);
+}
+
+void launch_pred_scores_comp(hipStream_t st, const PredScores &a, const ObsComp &t, int nbatch, double *out4) {
+    if (a.nobs <= 0 || nbatch <= 0) return;
+    const int nb = design_blocks(a.nobs);
+    hipLaunchKernelGGL(k_pred_scores_comp, dim3((unsigned)nb, (unsigned)nbatch), dim3(256), 0, st, a, t);
+    hipLaunchKernelGGL(k_pred_final, dim3((unsigned)nbatch), dim3(kFisherFinal), 0, st, a.part, nb, a.active, out4);
 }
 
 void launch_pred_scores(hipStream_t st, const PredScores &a, int nbatch, double *out4) {

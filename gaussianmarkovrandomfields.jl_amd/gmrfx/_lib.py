@@ -82,6 +82,7 @@ EXPORTS = [
     "gmrfx_obs_set", "gmrfx_obs_info", "gmrfx_fisher_eval", "gmrfx_fisher_eval_dev",
     "gmrfx_gaussian_approximation", "gmrfx_gaussian_approximation_dev",
     "gmrfx_obs_set_design", "gmrfx_obs_hess_map", "gmrfx_obs_design_info",
+    "gmrfx_obs_set_composite", "gmrfx_obs_composite_info", "gmrfx_obs_composite_set_param",
     "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
     "gmrfx_obs_pointwise_const", "gmrfx_predictor_marginals", "gmrfx_predictor_marginals_dev",
     "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
@@ -266,6 +267,9 @@ def lib(cdll=C.CDLL):
         L.gmrfx_obs_set_design.argtypes = [vp, i32, i64, vp, vp, vp, i32, vp, vp, vp, dbl]
         L.gmrfx_obs_hess_map.argtypes = [vp, C.POINTER(i64), vp]
         L.gmrfx_obs_design_info.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64)]
+        L.gmrfx_obs_set_composite.argtypes = [vp, i32, vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp]
+        L.gmrfx_obs_composite_info.argtypes = [vp, C.POINTER(i32), vp, vp, vp, vp]
+        L.gmrfx_obs_composite_set_param.argtypes = [vp, vp]
         L.gmrfx_fisher_eval.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gmrfx_fisher_eval_dev.argtypes = [vp, vp, vp, vp, vp, vp]
         L.gmrfx_gaussian_approximation.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]

@@ -406,6 +406,40 @@ function set_design_observations!(b::MI355XBackend, family::Union{Symbol, Intege
         b.h.ptr, Int32(fam), length(y), A.colptr, A.rowval, A.nzval, Int32(1), poff, y, paux, Float64(param)), b.h)
     return b
 end
+# A composite likelihood (gmrfx_obs_set_composite; the reference's CompositeObservationModel): `families` and `params` per component,
+# A the stacked design matrix [A_1; ...; A_C] and `rows` the components' row counts in that order; y, offset and aux go with A's rows.
+# The map, set_prior!, fisher_eval, gaussian_approximation_device and the predictive calls are those of the design form.
+function set_composite_observations!(b::MI355XBackend, families::Vector{<:Union{Symbol, Integer}}, rows::Vector{<:Integer}, y::Vector{Float64},
+                                     A::SparseMatrixCSC{Float64, Int64}; params::Vector{Float64} = zeros(length(families)),
+                                     offset::Union{Nothing, Vector{Float64}} = nothing, aux::Union{Nothing, Vector{Float64}} = nothing)
+    fam = Int32[f isa Symbol ? getfield(OBS_FAMILIES, f) : Int(f) for f in families]
+    length(rows) == length(fam) == length(params) || throw(DimensionMismatch("families, rows and params must have one entry per component"))
+    rowptr = Int64[0; cumsum(rows)]
+    size(A) == (length(y), b.n) && rowptr[end] == length(y) || throw(DimensionMismatch("A must be nobs x n, with nobs = sum(rows)"))
+    (offset === nothing || length(offset) == length(y)) && (aux === nothing || length(aux) == length(y)) ||
+        throw(DimensionMismatch("offset / aux must have one entry per observation"))
+    poff = offset === nothing ? Ptr{Float64}(C_NULL) : pointer(offset)
+    paux = aux === nothing ? Ptr{Float64}(C_NULL) : pointer(aux)
+    GC.@preserve fam params rowptr y A offset aux check(ccall((:gmrfx_obs_set_composite, LIB), Int32,
+        (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}),
+        b.h.ptr, Int32(length(fam)), fam, params, rowptr, length(y), A.colptr, A.rowval, A.nzval, Int32(1), poff, y, paux), b.h)
+    return b
+end
+function composite_info(b::MI355XBackend)
+    nc = Ref{Int32}(0)
+    check(ccall((:gmrfx_obs_composite_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                b.h.ptr, nc, C_NULL, C_NULL, C_NULL, C_NULL), b.h)
+    fam = Vector{Int32}(undef, nc[]); par = Vector{Float64}(undef, nc[]); rp = Vector{Int64}(undef, nc[] + 1); c = Vector{Float64}(undef, nc[])
+    nc[] > 0 && check(ccall((:gmrfx_obs_composite_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}),
+                            b.h.ptr, nc, fam, par, rp, c), b.h)
+    return (family = fam, param = par, rowptr = nc[] > 0 ? rp : Int64[], loglik_const = c)
+end
+function set_composite_param!(b::MI355XBackend, params::Vector{Float64})
+    length(params) == length(composite_info(b).family) || throw(DimensionMismatch("params must have one entry per component"))
+    check(ccall((:gmrfx_obs_composite_set_param, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), b.h.ptr, params), b.h)
+    return b
+end
 function observations_design_info(b::MI355XBackend)
     a = Ref{Int64}(0); c = Ref{Int64}(0); t = Ref{Int64}(0)
     check(ccall((:gmrfx_obs_design_info, LIB), Int32, (Ptr{Cvoid}, Ref{Int64}, Ref{Int64}, Ref{Int64}), b.h.ptr, a, c, t), b.h)

@@ -705,6 +705,46 @@ int32_t gmrfx_obs_set_design(gmrfx_handle *h, int32_t family, int64_t nobs, cons
                              const double *aux /* nobs, nullable */, double param);
 int32_t gmrfx_obs_hess_map(const gmrfx_handle *h, int64_t *cnt, int64_t *map /* nullable; cnt values, index base 0 */);
 int32_t gmrfx_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cnt, int64_t *terms);
+/* ---- composite likelihoods: several observation families on one handle (CompositeObservationModel / CompositeLikelihood,
+ * src/observation_models/composite/: loglik, loggrad and loghessian are sums over the components, pointwise_loglik their
+ * concatenation) -- Normal measurements next to Poisson counts, a Bernoulli presence part next to a Gamma amount part, two Normal data
+ * sets with different sigmas ----------------------------------------------------------------------------------------------------------
+ * gmrfx_obs_set_composite: A is the STACKED nobs x n design matrix [A_1; ...; A_C] in CSC, exactly as gmrfx_obs_set_design takes it
+ * (offset, y and aux go with its rows; a component observed at nodes is a block of identity rows, and two components may observe the
+ * same nodes). Component c owns rows rowptr[c] .. rowptr[c + 1] (index base 0): rowptr[0] = 0, rowptr[ncomp] = nobs, strictly
+ * increasing (no empty component), 1 <= ncomp <= GMRFX_OBS_MAX_COMPONENTS. family[c]: one of the six ids of gmrfx_obs_set; param[c]:
+ * that component's sigma / r / phi, ignored for the families without one. aux has one value per row; it is read and validated only on
+ * the rows of Poisson, Binomial and NegBinomial components (the other rows may hold anything, NaN included); NULL is refused when a
+ * Binomial component exists. Every check and refusal of gmrfx_obs_set_design applies, the value checks per component under that
+ * component's family; the messages name the component and the observation;
+ * what is refused about A carries the entry point's name and the column). Refused in addition (INVALID_ARG, a message, nothing
+ * changed): ncomp out of range, a null family / param / rowptr, a rowptr that does not start at 0, is not strictly increasing or does
+ * not end at nobs.
+ * loglik_const is the sum of the components' constants over their own rows, taken in component order in long double; gmrfx_obs_info
+ * returns the total and family = GMRFX_OBS_COMPOSITE, gmrfx_obs_composite_info the components (ncomp = 0 when none is set; family,
+ * param, loglik_const: ncomp values, one per component, rowptr ncomp + 1; each nullable). The plan, the map and the term tables are those of
+ * gmrfx_obs_set_design on the same A: gmrfx_obs_hess_map, gmrfx_obs_design_info, gmrfx_obs_design_rows and gmrfx_set_prior with that
+ * map work unchanged; one component gives the state of gmrfx_obs_set_design and every result bit for bit. Setting any of the three
+ * forms replaces the others; gmrfx_obs_set with nobs = 0 removes the likelihood; gmrfx_clone carries the composite; symbolic_only
+ * handles validate it and give the constants and the map.
+ * gmrfx_obs_composite_set_param replaces the parameters in place (the positivity checks again; on refusal nothing is changed) and
+ * recomputes the constants and the cached pointwise constants; the plan and the device tables are untouched.
+ * On a handle holding a composite gmrfx_fisher_eval[_dev], gmrfx_gaussian_approximation[_dev] (with and without a constraint set),
+ * gmrfx_obs_pointwise_const, gmrfx_predictor_marginals[_dev] and gmrfx_predictive_scores[_dev] run the composite: every row's g, d and
+ * l under its own component (csrc/fisher_design.hip: k_design_eta_comp, one byte per observation and a table of ncomp entries in
+ * device memory; csrc/predictive.hip), every sum in the order of the design form. No atomics; bit-reproducible; the host and the _dev
+ * forms agree bit for bit. gmrfx_ga_pullback[_dev] is refused (INVALID_ARG): its single parameter cotangent has no composite meaning.
+ * The batched entry points refuse the handle as they refuse the design form.
+ * LIMITS: plain handles; at most 16 components; pointwise exponential-family components only. */
+#define GMRFX_OBS_MAX_COMPONENTS 16
+#define GMRFX_OBS_COMPOSITE (-2)
+int32_t gmrfx_obs_set_composite(gmrfx_handle *h, int32_t ncomp, const int32_t *family /* ncomp */, const double *param /* ncomp */,
+                                const int64_t *rowptr /* ncomp + 1, index base 0 */, int64_t nobs, const int64_t *colptr /* n + 1 */,
+                                const int64_t *rowval, const double *nzval, int32_t index_base, const double *offset /* nobs, nullable */,
+                                const double *y /* nobs */, const double *aux /* nobs, nullable */);
+int32_t gmrfx_obs_composite_info(const gmrfx_handle *h, int32_t *ncomp, int32_t *family, double *param, int64_t *rowptr,
+                                 double *loglik_const /* ncomp: per component */);
+int32_t gmrfx_obs_composite_set_param(gmrfx_handle *h, const double *param /* ncomp */);
 /* The loop itself: gaussian_approximation(prior::WorkspaceGMRF, obs_lik) of the reference (src/workspace/gaussian_approximation.jl:191-313)
  * with _ga_line_search, _predict_converged and _frozen_finish of src/arithmetic/condition/gaussian_approximation.jl:231-409 restated
  * line by line in host C++; every vector (x_k, step, score, hess, the line search's candidates) stays in HBM, the host reads a handful
