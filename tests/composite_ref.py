@@ -1,11 +1,12 @@
 """References for composite likelihoods (gmrfx_obs_set_composite; csrc/fisher_design.hip: k_design_eta_comp), no device.
 
 A composite is the design form with a family and a parameter per ROW. The restatement therefore is the design form's own
-(tests/fisher_design_ref.py: eval_ref, eval_f64, bounds, newton_loop; tests/predictive_ref.py is not needed: mean and variance do not
-depend on the family), run with fisher_ref.pointwise and fisher_ref.loglik_const dispatched per component: `restated()` puts a proxy of
-fisher_ref in fisher_design_ref's place for the duration of a call, which hands a CompObs to the per-component rule and everything else
-through. Nothing of either module is edited. The bounds are those of fisher_design_ref.bounds: a row's g, d and l have the error of
-their own family whatever the neighbouring rows hold, so the derivation there carries over term by term.
+(tests/fisher_design_ref.py: eval_ref, eval_f64, bounds, newton_loop; mu_eta and v_eta of the predictive calls do not depend on the
+family, but pll and the four scores do: their restatement per component is tests/composite_predictive_ref.py), run with
+fisher_ref.pointwise and fisher_ref.loglik_const dispatched per component: `restated()` puts a proxy of fisher_ref in
+fisher_design_ref's place for the duration of a call, which hands a CompObs to the per-component rule and everything else through.
+Nothing of either module is edited. The bounds are those of fisher_design_ref.bounds: a row's g, d and l have the error of their own
+family whatever the neighbouring rows hold, so the derivation there carries over term by term.
 
 MUTANTS: deliberately wrong composites, each of which must leave the bounds on at least one case (tests/test_composite_host.py).
 
