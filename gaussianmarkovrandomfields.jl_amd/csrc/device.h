@@ -332,6 +332,11 @@ public:
     // factorisation failed (*info = 1 + the failing step), 2 when the constraint's W did.
     struct GapIO { const double *d_x, *d_mu, *d_mubar, *d_Qbar; int flags; double *d_Qbar_prior, *d_mubar_prior, *d_lambda; };
     int ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info);
+    // The same for a composite likelihood (gmrfx_ga_pullback_composite): param_bar_host gets one parameter cotangent per component
+    // (0.0 for a component whose family has no parameter), *check_host (nullable) lam' xbar. The unchanged kernels, the solve and the
+    // projection are launched as ga_pullback launches them; k_gap_point_comp, k_gap_param_comp and k_gap_final_comp take the place
+    // of the three that read a family.
+    int ga_pullback_composite(const RbmcSym &sym, const GapIO &io, double *param_bar_host, double *check_host, long long *info);
     // The same for every member of a batched handle (gmrfx_batch_ga_pullback), forest-wide, one launch per step: member k's mode at
     // d_x + k sx, prior mean at d_mu + k smu (nullable; smu = 0: one mean), cotangents and outputs dense per member (n / nnz_member
     // each). Needs the batch likelihood and the prior of gmrfx_batch_set_prior. Bit 0 projects with the BATCH constraint (a held
@@ -693,6 +698,8 @@ private:
         DevBuf<unsigned char> comp;
         DevBuf<int> cfamily;
         DevBuf<double> cpar;
+        std::vector<long long> crowptr;  // host: ncomp + 1 row offsets (the pullback's component tiling is built from them)
+        std::vector<int> cfam;           // host: ncomp families
         ObsComp comp_table() const;      // (kernels.h; device_fisher.cpp)
         DevBuf<long long> rp;
         DevBuf<int> col, pos;
@@ -729,11 +736,17 @@ private:
     // pullback state, built on the first gmrfx_ga_pullback for the likelihood in place (obs_set drops it): the transposed term table
     // of the plan (ONE copy), and per member the work vectors xbar, lam (n each) and t (nobs, design form), the partial sums of the two
     // parameter sums, the result
+    // A composite (gap_ only): the component tiling of kernels.h: GapTiles -- bptr and the row offsets on the device, nblk workgroups;
+    // part holds 2 nblk partial sums and out / h_out ncomp results. Uploaded with the first composite pullback, dropped by obs_set
+    // with the rest; gmrfx_obs_composite_set_param leaves them (only the parameter table changes).
     struct GapDev {
         DevBuf<long long> optr;
         DevBuf<int> oidx;
         DevBuf<double> ow, work, part, out;
         PinnedBuf<double> h_out;
+        DevBuf<int> bptr;
+        DevBuf<long long> crow;
+        int nblk = 0;
     } gap_, bgap_;               // of fisher_ (obs_set drops it) and of bfisher_ (bobs_set does): sized for the slot's members
     void gap_tables(const FisherDev &f, GapDev &g);
     void gap_term_table();       // the plan's transposed term table alone (also what gmrfx_predictor_marginals needs of the pullback's state)
@@ -752,6 +765,10 @@ private:
         const unsigned char *d_active, *active;
     };
     void gap_launch(FisherDev &f, GapDev &g, const GapRun &r, const GapIO &io, double *out_host);
+    // what ga_pullback and ga_pullback_composite do ahead of their launches: the argument checks (messages prefixed "who: "), the
+    // factorisation of Q_prior - H(x) under bit 1, the constraint's operands under bit 0, the pattern and the symmetric rows.
+    // Returns 0, 1 (factorisation failed, *info = 1 + the step) or 2 (the constraint's W failed).
+    int gap_prepare(const RbmcSym &sym, const GapIO &io, long long *info, const char *who);
     // predictive state, built on the first gmrfx_predictor_marginals / gmrfx_predictive_scores for the likelihood in place (obs_set
     // drops it): the observed nodes in the caller's order (node form, 4 nobs bytes), the constants c (8 nobs), the plan's map (design
     // form, 8 cnt), the scores' partial sums (4 per workgroup), totals and quadrature rule. The batch slot (bpred_, of bfisher_;

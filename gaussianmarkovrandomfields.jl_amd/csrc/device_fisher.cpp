@@ -107,6 +107,8 @@ Device::FisherDev Device::fisher_build(const FisherSource &src, size_t n, const 
             std::vector<unsigned char> comp(nobs);
             for (size_t c = 0; c < C.size(); c++) std::fill(comp.begin() + C.rowptr[c], comp.begin() + C.rowptr[c + 1], (unsigned char)c);
             f.ncomp = (int)C.size();
+            f.crowptr = C.rowptr;
+            f.cfam = C.family;
             dev_upload(f.comp, comp, &bytes_total);
             dev_upload(f.cfamily, C.family, &bytes_total);
             dev_upload(f.cpar, fisher_comp_params(C), &bytes_total);

@@ -40,10 +40,22 @@ void Device::gap_tables(const FisherDev &f, GapDev &g) {
     gap_term_table(f, g);
     DevBuf<double> work, part, out;      // built aside, as the table
     PinnedBuf<double> h_out;
+    // a composite: the component tiling's workgroups and one result per component (kernels.h: GapTiles)
+    DevBuf<int> bptr;
+    DevBuf<long long> crow;
+    size_t nblk = (size_t)gap_obs_blocks(P != nullptr, (long long)n, (long long)nobs), nout = 1;
+    if (f.ncomp > 0) {
+        std::vector<int> b((size_t)f.ncomp + 1);
+        nblk = (size_t)gap_comp_tiles(f.crowptr.data(), f.ncomp, b.data());
+        nout = (size_t)f.ncomp;
+        dev_upload(bptr, b, &bytes_total);
+        dev_upload(crow, f.crowptr, &bytes_total);
+    }
     work.alloc(nb * (2 * n + nobs), &bytes_total, kTableMinBytes);
-    part.alloc(2 * nb * (size_t)gap_obs_blocks(P != nullptr, (long long)n, (long long)nobs), &bytes_total, kTableMinBytes);
-    out.alloc(nb, &bytes_total, kTableMinBytes);
-    h_out.alloc((long long)nb);
+    part.alloc(2 * nb * nblk, &bytes_total, kTableMinBytes);
+    out.alloc(nb * nout, &bytes_total, kTableMinBytes);
+    h_out.alloc((long long)(nb * nout));
+    g.bptr = std::move(bptr); g.crow = std::move(crow); g.nblk = (int)nblk;
     g.part = std::move(part); g.out = std::move(out); g.h_out = std::move(h_out); g.work = std::move(work);
 }
 
@@ -129,17 +141,17 @@ void Device::gap_launch(FisherDev &f, GapDev &g, const GapRun &r, const GapIO &i
     }
 }
 
-int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info) {
-    HC(hipSetDevice(device));
-    if (sharded() || many_members()) throw std::invalid_argument("ga_pullback: batched and sharded handles are not supported");
-    if (!io.d_x || !out_host) throw std::invalid_argument("ga_pullback: x / out is null");
-    if (!obs_held()) throw std::invalid_argument("ga_pullback: no observation likelihood is set (gmrfx_obs_set)");
+int Device::gap_prepare(const RbmcSym &sym, const GapIO &io, long long *info, const char *who) {
+    const std::string w = std::string(who) + ": ";
+    if (sharded() || many_members()) throw std::invalid_argument(w + "batched and sharded handles are not supported");
+    if (!io.d_x) throw std::invalid_argument(w + "x / out is null");
+    if (!obs_held()) throw std::invalid_argument(w + "no observation likelihood is set (gmrfx_obs_set)");
     const long long n = S_->n;
-    if (n > INT_MAX) throw std::invalid_argument("ga_pullback: more than 2^31 - 1 nodes");
+    if (n > INT_MAX) throw std::invalid_argument(w + "more than 2^31 - 1 nodes");
     const bool project = io.flags & 1, refactor = io.flags & 2;
-    if (!io.d_mubar && !io.d_Qbar) throw std::invalid_argument("ga_pullback: mubar and Qbar are both null");
-    if (project && con_.m <= 0) throw std::invalid_argument("ga_pullback: flag bit 0 (project lambda) needs a constraint (gmrfx_constraints_set)");
-    fisher_check_map(sym, "ga_pullback");
+    if (!io.d_mubar && !io.d_Qbar) throw std::invalid_argument(w + "mubar and Qbar are both null");
+    if (project && con_.m <= 0) throw std::invalid_argument(w + "flag bit 0 (project lambda) needs a constraint (gmrfx_constraints_set)");
+    fisher_check_map(sym, who);
     if (info) *info = 0;
     if (refactor) {
         // Q_prior - H(x): the evaluation's Hessian values, then the update the loop's last step does under its flag bit 3
@@ -154,9 +166,90 @@ int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, l
     if (project && !con_prepare()) return 2;      // (the operands of the factor in hand: nothing of the rule has been launched yet)
     if (io.d_Qbar_prior) prepare_quadform(0);     // (the pattern of Q on the device)
     if (io.d_mubar_prior) sym_rows_upload(sym);
+    return 0;
+}
+
+int Device::ga_pullback(const RbmcSym &sym, const GapIO &io, double *out_host, long long *info) {
+    HC(hipSetDevice(device));
+    if (!out_host) throw std::invalid_argument("ga_pullback: x / out is null");
+    if (fisher_.ncomp > 0) throw std::invalid_argument("ga_pullback: composite likelihoods take gmrfx_ga_pullback_composite");
+    if (const int rc = gap_prepare(sym, io, info, "ga_pullback")) return rc;
     // one member on the handle's own map, pattern and rows: no strides, nobody masked
-    gap_launch(fisher_, gap_, GapRun{d_hmap_, d_in_colptr_, d_in_row_, FisherRows{sym_rows_.rp, sym_rows_.col, sym_rows_.pos}, 0, 0, project ? 1 : 0,
+    gap_launch(fisher_, gap_, GapRun{d_hmap_, d_in_colptr_, d_in_row_, FisherRows{sym_rows_.rp, sym_rows_.col, sym_rows_.pos}, 0, 0, (io.flags & 1) ? 1 : 0,
                                      nullptr, nullptr}, io, out_host);
+    return 0;
+}
+
+// The launch sequence of gap_launch for ONE member of a composite (the batched path is gap_launch's alone): the three kernels that
+// read a family are the composite's, on the component tiling; everything else is launched as there.
+int Device::ga_pullback_composite(const RbmcSym &sym, const GapIO &io, double *param_bar_host, double *check_host, long long *info) {
+    HC(hipSetDevice(device));
+    if (!param_bar_host) throw std::invalid_argument("ga_pullback_composite: param_bar is null");
+    if (fisher_.ncomp <= 0) throw std::invalid_argument("ga_pullback_composite: no composite likelihood is set (gmrfx_obs_set_composite)");
+    if (const int rc = gap_prepare(sym, io, info, "ga_pullback_composite")) return rc;
+    FisherDev &f = fisher_;
+    GapDev &g = gap_;
+    const DesignPlan &P = *f.design;
+    const long long n = f.n, nnz = f.nnz, nobs = P.nobs;
+    const int nc = f.ncomp;
+    bool has_param = false;
+    for (int c = 0; c < nc; c++) has_param = has_param || f.cfam[c] == 0 || f.cfam[c] == 4 || f.cfam[c] == 5;
+    gap_tables(f, g);
+    const ObsComp tab = f.comp_table();
+    const GapTiles tiles{nc, g.bptr, g.crow};
+    double *xbar = g.work, *lam = xbar + n, *t = lam + n;
+    double *gpart = g.part, *ppart = gpart + g.nblk;
+    // ---- xbar = mubar - A' (c . d3) -------------------------------------------------------------------------------------------------
+    if (io.d_Qbar) {
+        auto a = GapPoint{};      // (every field zero, then by name)
+        a.n = (int)n; a.nobs = (int)nobs; a.family = f.family;
+        a.G = io.d_Qbar; a.hmap = d_hmap_; a.x = io.d_x; a.mubar = io.d_mubar;
+        a.y = f.y; a.aux = f.aux;
+        a.arp = f.arp; a.acol = f.acol; a.aval = f.aval; a.offset = f.offset;
+        a.optr = g.optr; a.oidx = g.oidx; a.ow = g.ow;
+        a.t = t; a.xbar = xbar; a.ppart = ppart;
+        a.sg = nnz; a.sm = n; a.sw = n;
+        launch_gap_point_comp(stream, a, tab, tiles, g.nblk, 1);
+        const GapGather b{(int)n, f.ncc, f.acp, f.arow, f.acv, f.cchoff, f.chs, f.chl, t, io.d_mubar, f.cpart, xbar,
+                          nobs, n, (long long)(f.ncc + f.nct), n, nullptr};
+        launch_gap_gather(stream, b, 1);
+    } else launch_gap_copy(stream, n, io.d_mubar, n, xbar, n, nullptr, 1);
+    // ---- lam = Q_post^-1 xbar, projected under bit 0 --------------------------------------------------------------------------------
+    launch_gap_copy(stream, n, xbar, n, lam, n, nullptr, 1);
+    solve(lam, n, 1, lam, n, true, 0);
+    if (io.flags & 1) con_correct(lam, n, 1, nullptr, true);
+    // ---- the outputs ----------------------------------------------------------------------------------------------------------------
+    if (io.d_Qbar_prior) {
+        const GapPattern a{(int)n, d_in_colptr_, d_in_row_, io.d_Qbar, lam, io.d_x, io.d_mu, io.d_Qbar_prior, nnz, n, 0, 0, nullptr};
+        launch_gap_pattern(stream, a, 1);
+    }
+    if (io.d_mubar_prior) {
+        const GapMean a{(int)n, sym_rows_.rp, sym_rows_.col, sym_rows_.pos, d_prior_, lam, io.d_mubar_prior, nnz, n, n, nullptr};
+        launch_gap_mean(stream, a, 1);
+    }
+    if (io.d_lambda) launch_gap_copy(stream, n, lam, n, io.d_lambda, n, nullptr, 1);
+    if (has_param) {
+        auto a = GapParam{};
+        a.n = (int)n; a.nobs = (int)nobs; a.family = f.family;
+        a.lam = lam; a.x = io.d_x;
+        a.y = f.y; a.aux = f.aux;
+        a.arp = f.arp; a.acol = f.acol; a.aval = f.aval; a.offset = f.offset;
+        a.gpart = gpart;
+        a.sw = n;
+        launch_gap_param_comp(stream, a, tab, tiles, g.nblk, 1);
+        launch_gap_final_comp(stream, gpart, ppart, io.d_Qbar != nullptr, tiles, g.nblk, nullptr, 1, g.out);
+        HC(hipMemcpyAsync(g.h_out, g.out, (size_t)nc * sizeof(double), hipMemcpyDeviceToHost, stream));
+    }
+    // lam' xbar by the loop's own reduction (sum a b of launch_fisher_stats)
+    launch_fisher_stats(stream, FisherMembers{(int)n, 1, n, nullptr}, lam, xbar, nullptr, nullptr, f.spart, f.out.get() + 2);
+    HC(hipMemcpyAsync(f.h_out + 2, f.out.get() + 2, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HC(hipStreamSynchronize(stream));
+    HC(hipGetLastError());
+    for (int c = 0; c < nc; c++) {
+        const bool par = f.cfam[c] == 0 || f.cfam[c] == 4 || f.cfam[c] == 5;
+        param_bar_host[c] = par ? g.h_out[c] : 0.0;
+    }
+    if (check_host) *check_host = f.h_out[2];
     return 0;
 }
 

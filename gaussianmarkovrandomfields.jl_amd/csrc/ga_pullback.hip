@@ -15,6 +15,8 @@
 //   k_gap_pattern      a lane group per column of the pattern
 //   k_gap_mean         a lane group per row of Symmetric(Q_p)
 //   k_gap_param_node / k_gap_param   (A lam)_i gp_i (eta_i formed again in the same pass) and its partial per workgroup;  k_gap_final   the two sums
+//   k_gap_point_comp / k_gap_param_comp / k_gap_final_comp   a composite likelihood (gmrfx_ga_pullback_composite): out[c] per component;
+//                      the observations tiled per component (kernels.h: GapTiles), family and parameter from the component table
 // DETERMINISM. No atomics. A lane adds entries q0 + l, q0 + l + 16, ... in that order, the 16 lane sums meet in a fixed xor butterfly;
 // a chunk's thread adds entries t, t + 256 and the 256 sums meet in a fixed LDS tree; workgroup partials are added by a fixed strided
 // loop and tree. Every operand is read and written one double at a time: nothing depends on alignment. Contraction is off in the
@@ -238,6 +240,107 @@ __global__ __launch_bounds__(kFisherFinal) void k_gap_final(const double *__rest
     if (tid == 0) out[k] = sg[0] - sp[0];
 }
 
+// ---- a composite likelihood (gmrfx_ga_pullback_composite; kernels.h: GapTiles, ObsComp) -----------------------------------------------
+// The component of workgroup b: the last c with bptr[c] <= b, by a search over the at most kObsMaxComponents + 1 offsets. Every
+// thread reads the same addresses: the loads are the workgroup's, not the lanes'.
+__device__ __forceinline__ int gap_tile_comp(const GapTiles &w, int b) {
+    int c = 0;
+    while (c + 1 < w.ncomp && b >= w.bptr[c + 1]) c++;
+    return c;
+}
+
+// k_gap_point on the component tiling: the same statements, except the row index and that lane 0 takes (family, param, logparam)
+// of the workgroup's component from the table in device memory. KEEP THE TWO IN STEP: the body is written twice because a shared body
+// gives the single-family kernel another instruction schedule; the one-component test of
+// tests/test_gpu_composite_pullback.py compares their bits.
+__global__ __launch_bounds__(256) void k_gap_point_comp(const GapPoint a, const ObsComp t, const GapTiles w) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
+    __shared__ double sp[kDesignRows];
+    const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
+    const int cm = gap_tile_comp(w, (int)blockIdx.x);
+    const long long i = w.rowptr[cm] + (long long)((int)blockIdx.x - w.bptr[cm]) * kDesignRows + g;
+    double p = 0.0;
+    if (i < w.rowptr[cm + 1]) { // (a whole lane group takes the branch together)
+        const double *x = a.x + (long long)k * a.sx, *G = a.G + (long long)k * a.sg;
+        double s = 0.0, c = 0.0;
+        const long long q1 = a.arp[i + 1], o1 = a.optr[i + 1];
+        for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) s = __builtin_fma(a.aval[q], x[a.acol[q]], s);
+        for (long long q = a.optr[i] + l; q < o1; q += kDesignLanes) c = __builtin_fma(a.ow[q], G[a.hmap[a.oidx[q]]], c);
+        s = gap_group_sum(s);
+        c = gap_group_sum(c);
+        if (l == 0) {
+            const double eta = a.offset ? s + a.offset[i] : s;
+            double d3, gp, dp;
+            fisher_point_pullback(t.family[cm], eta, a.y[i], a.aux ? a.aux[i] : 0.0, t.param[cm], t.logparam[cm], d3, gp, dp);
+            a.t[(long long)k * a.nobs + i] = c * d3;
+            p = c * dp;
+        }
+    }
+    if (l == 0) sp[g] = p;
+    gap_block_sum(sp, kDesignRows, a.ppart + ((long long)k * gridDim.x + blockIdx.x));
+}
+
+// k_gap_param the same way. A component whose family has no parameter (gp = 0 on every row) leaves 0 without walking its rows.
+__global__ __launch_bounds__(256) void k_gap_param_comp(const GapParam a, const ObsComp t, const GapTiles w) {
+    const int k = blockIdx.y;
+    if (a.active && !a.active[k]) return;
+    __shared__ double sp[kDesignRows];
+    const int g = threadIdx.x / kDesignLanes, l = threadIdx.x % kDesignLanes;
+    const int cm = gap_tile_comp(w, (int)blockIdx.x);
+    const int family = t.family[cm];
+    if (family != 0 && family != 4 && family != 5) {        // (uniform over the workgroup, ahead of its barriers)
+        if (threadIdx.x == 0) a.gpart[(long long)k * gridDim.x + blockIdx.x] = 0.0;
+        return;
+    }
+    const long long i = w.rowptr[cm] + (long long)((int)blockIdx.x - w.bptr[cm]) * kDesignRows + g;
+    double p = 0.0;
+    if (i < w.rowptr[cm + 1]) {
+        const double *x = a.x + (long long)k * a.sx, *lam = a.lam + (long long)k * a.sw;
+        double s = 0.0, e = 0.0;
+        const long long q1 = a.arp[i + 1];
+        for (long long q = a.arp[i] + l; q < q1; q += kDesignLanes) {
+            const int c = a.acol[q];
+            e = __builtin_fma(a.aval[q], x[c], e);
+            s = __builtin_fma(a.aval[q], lam[c], s);
+        }
+        e = gap_group_sum(e);
+        s = gap_group_sum(s);
+        if (l == 0) {
+            const double eta = a.offset ? e + a.offset[i] : e;
+            double d3, gp, dp;
+            fisher_point_pullback(family, eta, a.y[i], a.aux ? a.aux[i] : 0.0, t.param[cm], t.logparam[cm], d3, gp, dp);
+            p = s * gp;
+        }
+    }
+    if (l == 0) sp[g] = p;
+    gap_block_sum(sp, kDesignRows, a.gpart + ((long long)k * gridDim.x + blockIdx.x));
+}
+
+// k_gap_final per component: workgroup (c, k) adds the partials of c's workgroups, strided loop then tree as k_gap_final does
+__global__ __launch_bounds__(kFisherFinal) void k_gap_final_comp(const double *__restrict__ gpart, const double *__restrict__ ppart, int has_p,
+                                                                 const GapTiles w, int nblk, const unsigned char *__restrict__ active,
+                                                                 double *__restrict__ out) {
+    const int c = blockIdx.x, k = blockIdx.y;
+    if (active && !active[k]) return;
+    __shared__ double sg[kFisherFinal], sp[kFisherFinal];
+    const int tid = threadIdx.x;
+    const int b0 = w.bptr[c], nb = w.bptr[c + 1] - b0;
+    gpart += (long long)k * nblk + b0;
+    ppart += (long long)k * nblk + b0;
+    double g = 0.0, p = 0.0;
+    for (int b = tid; b < nb; b += kFisherFinal) g += gpart[b];
+    if (has_p)
+        for (int b = tid; b < nb; b += kFisherFinal) p += ppart[b];
+    sg[tid] = g; sp[tid] = p;
+    __syncthreads();
+    for (int st = kFisherFinal / 2; st > 0; st >>= 1) {
+        if (tid < st) { sg[tid] += sg[tid + st]; sp[tid] += sp[tid + st]; }
+        __syncthreads();
+    }
+    if (tid == 0) out[(long long)k * w.ncomp + c] = sg[0] - sp[0];
+}
+
 // the active members' vectors copied (src non-null), or the INACTIVE members' filled with NaN (src null)
 __global__ __launch_bounds__(256) void k_gap_copy(long long n, const double *__restrict__ src, long long ss, double *__restrict__ dst, long long sd,
                                                   const unsigned char *__restrict__ active) {
@@ -276,6 +379,20 @@ void launch_gap_param(hipStream_t st, const GapParam &a, bool design, int nbatch
 void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double *ppart, int np, const unsigned char *active, int nbatch, double *out) {
     if (nbatch <= 0) return;
     hipLaunchKernelGGL(k_gap_final, dim3((unsigned)nbatch), dim3(kFisherFinal), 0, st, gpart, ng, ppart, np, active, out);
+}
+void launch_gap_point_comp(hipStream_t st, const GapPoint &a, const ObsComp &t, const GapTiles &w, int nblk, int nbatch) {
+    if (a.n <= 0 || a.nobs <= 0 || nblk <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_point_comp, dim3((unsigned)nblk, (unsigned)nbatch), dim3(256), 0, st, a, t, w);
+}
+void launch_gap_param_comp(hipStream_t st, const GapParam &a, const ObsComp &t, const GapTiles &w, int nblk, int nbatch) {
+    if (a.n <= 0 || a.nobs <= 0 || nblk <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_param_comp, dim3((unsigned)nblk, (unsigned)nbatch), dim3(256), 0, st, a, t, w);
+}
+void launch_gap_final_comp(hipStream_t st, const double *gpart, const double *ppart, bool has_p, const GapTiles &w, int nblk,
+                           const unsigned char *active, int nbatch, double *out) {
+    if (w.ncomp <= 0 || nbatch <= 0) return;
+    hipLaunchKernelGGL(k_gap_final_comp, dim3((unsigned)w.ncomp, (unsigned)nbatch), dim3(kFisherFinal), 0, st, gpart, ppart, has_p ? 1 : 0, w, nblk,
+                       active, out);
 }
 void launch_gap_copy(hipStream_t st, long long n, const double *src, long long ss, double *dst, long long sd, const unsigned char *active, int nbatch) {
     if (n <= 0 || nbatch <= 0 || !src) return;

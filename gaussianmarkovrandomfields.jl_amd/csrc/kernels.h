@@ -433,6 +433,31 @@ void launch_gap_final(hipStream_t st, const double *gpart, int ng, const double 
 // what a member whose factorisation or W_k failed gets in its output slices)
 void launch_gap_copy(hipStream_t st, long long n, const double *src, long long ss, double *dst, long long sd, const unsigned char *active, int nbatch);
 void launch_gap_fill_failed(hipStream_t st, long long n, double *dst, long long sd, const unsigned char *active, int nbatch);
+// A composite likelihood (gmrfx_ga_pullback_composite): the parameter cotangent is one number per component, so no workgroup's
+// partial sum may mix components. The observations are tiled PER COMPONENT: component c owns workgroups bptr[c] .. bptr[c + 1],
+// bptr[c + 1] - bptr[c] = design_blocks(rows of c); workgroup b of c takes rows rowptr[c] + kDesignRows (b - bptr[c]) .., cut at
+// rowptr[c + 1]. At most design_blocks(nobs) + ncomp - 1 workgroups; one component: the tiling of k_gap_point. bptr (ncomp + 1) and
+// rowptr (ncomp + 1) lie in device memory; a workgroup finds its component by a uniform search over bptr.
+struct GapTiles {
+    int ncomp;
+    const int *bptr;
+    const long long *rowptr;
+};
+// bptr of the tiling above from the components' row offsets (ncomp + 1 entries each); returns the number of workgroups
+inline int gap_comp_tiles(const long long *rowptr, int ncomp, int *bptr) {
+    bptr[0] = 0;
+    for (int c = 0; c < ncomp; c++) bptr[c + 1] = bptr[c] + design_blocks(rowptr[c + 1] - rowptr[c]);
+    return bptr[ncomp];
+}
+// k_gap_point_comp / k_gap_param_comp: the design-form kernels on that tiling with the component's (family, param, logparam) from the
+// table (a.family / a.param / a.logparam and the *_k arrays are ignored); nblk = bptr[ncomp] workgroups and partial sums per member.
+// A component whose family has no parameter leaves 0 in its partials of (A lam) gp without walking its rows.
+void launch_gap_point_comp(hipStream_t st, const GapPoint &a, const ObsComp &t, const GapTiles &w, int nblk, int nbatch);
+void launch_gap_param_comp(hipStream_t st, const GapParam &a, const ObsComp &t, const GapTiles &w, int nblk, int nbatch);
+// out[k ncomp + c] = sum of gpart over c's workgroups - sum of ppart over them (has_p false: that sum is 0), in the order of
+// k_gap_final; one workgroup per component and member, member k's partials at + k nblk
+void launch_gap_final_comp(hipStream_t st, const double *gpart, const double *ppart, bool has_p, const GapTiles &w, int nblk,
+                           const unsigned char *active, int nbatch, double *out);
 
 // predictive.hip -- the marginals of the linear predictor (gmrfx_predictor_marginals, gmrfx_batch_predictor_marginals), the quadrature
 // scores over them (gmrfx_predictive_scores, gmrfx_batch_predictive_scores) and the mixture of the members' predictive distributions

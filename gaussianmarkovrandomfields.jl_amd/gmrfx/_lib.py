@@ -84,6 +84,7 @@ EXPORTS = [
     "gmrfx_obs_set_design", "gmrfx_obs_hess_map", "gmrfx_obs_design_info",
     "gmrfx_obs_set_composite", "gmrfx_obs_composite_info", "gmrfx_obs_composite_set_param",
     "gmrfx_ga_pullback", "gmrfx_ga_pullback_dev", "gmrfx_obs_design_rows",
+    "gmrfx_ga_pullback_composite", "gmrfx_ga_pullback_composite_dev",
     "gmrfx_obs_pointwise_const", "gmrfx_predictor_marginals", "gmrfx_predictor_marginals_dev",
     "gmrfx_predictive_scores", "gmrfx_predictive_scores_dev",
     "gmrfx_batch_obs_pointwise_const", "gmrfx_batch_predictor_marginals", "gmrfx_batch_predictor_marginals_dev",
@@ -276,6 +277,8 @@ def lib(cdll=C.CDLL):
         L.gmrfx_gaussian_approximation_dev.argtypes = [vp, vp, vp, i64, i64, dbl, dbl, i32, vp, vp, vp, vp, vp, C.POINTER(i64)]
         L.gmrfx_ga_pullback.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
         L.gmrfx_ga_pullback_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+        L.gmrfx_ga_pullback_composite.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.gmrfx_ga_pullback_composite_dev.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         L.gmrfx_batch_ga_pullback.argtypes = [vp, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]
         L.gmrfx_batch_ga_pullback_dev.argtypes = [vp, vp, i64, vp, i64, vp, vp, i32, vp, vp, vp, vp, vp]
         L.gmrfx_obs_design_rows.argtypes = [vp, vp, vp, vp]

@@ -2,7 +2,8 @@
 CompositeObservationModel / CompositeLikelihood, src/observation_models/composite/). A CompositeObservations collects the components
 and stacks them into the one design matrix the C ABI takes; the free functions below call the C ABI on a backend's handle. Everything
 after that is the backend's own: set_prior with observations_hess_map(), fisher_eval, gaussian_approximation, predictor_marginals,
-predictive_scores and observations_pointwise_const run the composite unchanged."""
+predictive_scores and observations_pointwise_const run the composite unchanged. The pullback of gaussian_approximation needs one
+parameter cotangent per component: ga_pullback / ga_pullback_dev below (gmrfx_ga_pullback_composite), free functions as the setters are."""
 from __future__ import annotations
 
 import ctypes as C
@@ -85,6 +86,45 @@ def composite_info(backend) -> dict:
     if nc.value > 0:
         check(lib().gmrfx_obs_composite_info(backend._h, C.byref(nc), ptr(fam), ptr(par), ptr(rp), ptr(c)), backend._h)
     return {"family": fam, "param": par, "rowptr": rp if nc.value > 0 else rp[:0], "loglik_const": c}
+
+
+def _flags(backend, project: bool, refactorize: bool) -> int:
+    if refactorize:         # the factor changes: the backend's cached selected inverse no longer belongs to it
+        backend._selinv_cache = None
+        backend._selinv_diag_cache = None
+    return int(bool(project)) | (int(bool(refactorize)) << 1)
+
+
+def ga_pullback(backend, x, mean=None, mubar=None, Qbar=None, project: bool = False, refactorize: bool = False,
+                want_Qbar_prior: bool = True, want_mubar_prior: bool = True, want_lambda: bool = True):
+    """The implicit-function rule at the mode x for the composite on the backend's handle (gmrfx_ga_pullback_composite): the arguments
+    of MI355XBackend.ga_pullback. Returns (Qbar_prior, mubar_prior, lambda, param_bar, lambda' xbar) with param_bar one cotangent per
+    component (0.0 for a component without a parameter); the arrays not asked for are None."""
+    n, nnz = backend.n, backend._nnz
+    xx = np.ascontiguousarray(x, dtype=np.float64)
+    mu, mb, qb = (None if v is None else np.ascontiguousarray(v, dtype=np.float64) for v in (mean, mubar, Qbar))
+    if xx.shape != (n,) or any(v is not None and v.shape != (n,) for v in (mu, mb)) or (qb is not None and qb.shape != (nnz,)):
+        raise ValueError("dimension mismatch")
+    qp = np.empty(nnz) if want_Qbar_prior else None
+    mp = np.empty(n) if want_mubar_prior else None
+    lam = np.empty(n) if want_lambda else None
+    par, chk = np.zeros(max(composite_info(backend)["family"].size, 1)), C.c_double(0.0)
+    rc = lib().gmrfx_ga_pullback_composite(backend._h, ptr(xx), ptr(mu), ptr(mb), ptr(qb), _flags(backend, project, refactorize), ptr(qp), ptr(mp),
+                                           ptr(lam), ptr(par), C.byref(chk))
+    check(rc, backend._h)
+    return qp, mp, lam, par, chk.value
+
+
+def ga_pullback_dev(backend, d_x: int, d_mu: int = 0, d_mubar: int = 0, d_Qbar: int = 0, d_Qbar_prior: int = 0, d_mubar_prior: int = 0,
+                    d_lambda: int = 0, project: bool = False, refactorize: bool = False):
+    """Device pointers (0 = absent); d_Qbar_prior may be d_Qbar. Returns (param_bar, lambda' xbar)."""
+    if not d_x:
+        raise ValueError("ga_pullback_dev: null pointer")
+    par, chk = np.zeros(max(composite_info(backend)["family"].size, 1)), C.c_double(0.0)
+    rc = lib().gmrfx_ga_pullback_composite_dev(backend._h, d_x, d_mu or None, d_mubar or None, d_Qbar or None, _flags(backend, project, refactorize),
+                                               d_Qbar_prior or None, d_mubar_prior or None, d_lambda or None, ptr(par), C.byref(chk))
+    check(rc, backend._h)
+    return par, chk.value
 
 
 def set_composite_param(backend, params) -> None:

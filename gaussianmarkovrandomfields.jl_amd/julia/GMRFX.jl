@@ -530,6 +530,31 @@ function ga_pullback(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, 
     return qp, mp, lam, out[1], out[2]
 end
 function ga_pullback_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
+# The same for a composite likelihood (gmrfx_ga_pullback_composite): param_bar is a vector, one cotangent per component (0.0 for a
+# component without a parameter). Returns (Qbar_prior, mubar_prior, lambda, param_bar, lambda' xbar).
+function ga_pullback_composite(b::MI355XBackend, x::Vector{Float64}; mean::Union{Nothing, Vector{Float64}} = nothing,
+                               mubar::Union{Nothing, Vector{Float64}} = nothing, Qbar::Union{Nothing, Vector{Float64}} = nothing,
+                               project::Bool = false, refactorize::Bool = false)
+    nnz = pattern_nnz(b)
+    length(x) == b.n && (mean === nothing || length(mean) == b.n) && (mubar === nothing || length(mubar) == b.n) &&
+        (Qbar === nothing || length(Qbar) == nnz) || throw(DimensionMismatch("x, mean, mubar need n entries, Qbar nnz"))
+    qp = Vector{Float64}(undef, nnz); mp = Vector{Float64}(undef, b.n); lam = Vector{Float64}(undef, b.n)
+    par = zeros(max(length(composite_info(b).family), 1)); chk = Ref{Float64}(0.0)
+    mu = mean === nothing ? Ptr{Float64}(C_NULL) : pointer(mean)
+    mb = mubar === nothing ? Ptr{Float64}(C_NULL) : pointer(mubar)
+    qb = Qbar === nothing ? Ptr{Float64}(C_NULL) : pointer(Qbar)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    code = GC.@preserve x mean mubar Qbar qp mp lam par ccall((:gmrfx_ga_pullback_composite, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+        b.h.ptr, x, mu, mb, qb, flags, qp, mp, lam, par, chk)
+    if refactorize
+        b.selinv_cache = nothing
+        b.selinv_diag_cache = nothing
+    end
+    check(code, b.h)
+    return qp, mp, lam, par, chk[]
+end
+function ga_pullback_composite_dev! end   # ROCArray method: ext/GMRFXAMDGPUExt.jl
 
 # linear_predictor_marginals(ga, obs_lik) of the reference (src/linear_predictor_marginals.jl:58-195) and pointwise_loglik at the mean,
 # on the device (gmrfx_predictor_marginals; include/gmrfx.h): (mean, variance, pointwise log density) of every observation's linear

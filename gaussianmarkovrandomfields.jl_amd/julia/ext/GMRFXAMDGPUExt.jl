@@ -20,7 +20,7 @@ using AMDGPU
 using LinearAlgebra
 import GMRFX
 import GMRFX: MI355XBackend, LIB, check, refactorize_solve!, backend_solve!, backend_backward_solve!, logpdf_terms
-import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev, fisher_eval_dev!, gaussian_approximation_dev!, ga_pullback_dev!, _ga_flags, _ga_info
+import GMRFX: MI355XBatch, constrained_logpdf_terms, rbmc_var_dev!, logpdf_grad_dev!, pattern_dot_dev, fisher_eval_dev!, gaussian_approximation_dev!, ga_pullback_dev!, ga_pullback_composite_dev!, composite_info, _ga_flags, _ga_info
 import GMRFX: ShardedMI355X, LIB_RCCL, check_rccl, solve!
 import GaussianMarkovRandomFields: refactorize!
 
@@ -193,6 +193,23 @@ function ga_pullback_dev!(b::MI355XBackend, x::ROCVector{Float64}; mean::Union{N
     refactorize && _invalidate!(b)
     check(code, b.h)
     return out[1], out[2]
+end
+# the same for a composite likelihood (gmrfx_ga_pullback_composite_dev); returns (param_bar per component, lambda' xbar)
+function ga_pullback_composite_dev!(b::MI355XBackend, x::ROCVector{Float64}; mean::Union{Nothing, ROCVector{Float64}} = nothing,
+                                    mubar::Union{Nothing, ROCVector{Float64}} = nothing, Qbar::Union{Nothing, ROCVector{Float64}} = nothing,
+                                    Qbar_prior::Union{Nothing, ROCVector{Float64}} = nothing, mubar_prior::Union{Nothing, ROCVector{Float64}} = nothing,
+                                    lambda::Union{Nothing, ROCVector{Float64}} = nothing, project::Bool = false, refactorize::Bool = false)
+    length(x) == b.n || throw(DimensionMismatch("x must have n entries"))
+    AMDGPU.synchronize()
+    p(a) = a === nothing ? Ptr{Float64}(C_NULL) : devptr(a)
+    par = zeros(max(length(composite_info(b).family), 1)); chk = Ref{Float64}(0.0)
+    flags = Int32(project) | (Int32(refactorize) << 1)
+    code = GC.@preserve x mean mubar Qbar Qbar_prior mubar_prior lambda par ccall((:gmrfx_ga_pullback_composite_dev, LIB), Int32,
+        (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ref{Float64}),
+        b.h.ptr, devptr(x), p(mean), p(mubar), p(Qbar), flags, p(Qbar_prior), p(mubar_prior), p(lambda), par, chk)
+    refactorize && _invalidate!(b)
+    check(code, b.h)
+    return par, chk[]
 end
 # the same for the members of a batch (gmrfx_batch_ga_pullback_dev): X / mean / mubar / mubar_prior / lambda n x B, Qbar / Qbar_prior nnz x B
 # (Qbar_prior may be Qbar itself: the Qbar of logpdf_grad_dev! goes in, pattern_dot_dev takes it on); returns (param_bar, lambda' xbar, info)

@@ -733,7 +733,8 @@ int32_t gmrfx_obs_design_info(const gmrfx_handle *h, int64_t *nnz_a, int64_t *cn
  * gmrfx_obs_pointwise_const, gmrfx_predictor_marginals[_dev] and gmrfx_predictive_scores[_dev] run the composite: every row's g, d and
  * l under its own component (csrc/fisher_design.hip: k_design_eta_comp, one byte per observation and a table of ncomp entries in
  * device memory; csrc/predictive.hip), every sum in the order of the design form. No atomics; bit-reproducible; the host and the _dev
- * forms agree bit for bit. gmrfx_ga_pullback[_dev] is refused (INVALID_ARG): its single parameter cotangent has no composite meaning.
+ * forms agree bit for bit. gmrfx_ga_pullback[_dev] is refused (INVALID_ARG): its single parameter cotangent has no composite meaning;
+ * gmrfx_ga_pullback_composite[_dev] (below) returns one per component.
  * The batched entry points refuse the handle as they refuse the design form.
  * LIMITS: plain handles; at most 16 components; pointwise exponential-family components only. */
 #define GMRFX_OBS_MAX_COMPONENTS 16
@@ -965,6 +966,33 @@ int32_t gmrfx_batch_ga_pullback(gmrfx_handle *h, const double *x, int64_t sx, co
 int32_t gmrfx_batch_ga_pullback_dev(gmrfx_handle *h, const double *d_x, int64_t sx, const double *d_mu, int64_t smu, const double *d_mubar,
                                     const double *d_Qbar, int32_t flags, double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda,
                                     double *out /* host, 2 x nbatch */, int64_t *info /* host, nbatch, nullable */);
+
+/* ---- The same pullback for a composite likelihood ---------------------------------------------------------------------------------------
+ * The last link of logpdf_grad_dev -> ga_pullback -> pattern_dot for the joint models of gmrfx_obs_set_composite: the formulas of
+ * gmrfx_ga_pullback with d3, gp and dp of every row taken under the family and parameter of the row's component, and the parameter
+ * cotangent split by component,
+ *   param_bar[c] = sum_{i in rows of c} (A lam)_i gp_i - sum_{i in rows of c} c_i dp_i          ncomp values, on the host
+ *   *check       = lam' xbar                                                                    nullable
+ * param_bar[c] is exactly 0.0 for a Poisson, Bernoulli or Binomial component. x, mu, mubar, Qbar, flags, Qbar_prior, mubar_prior and
+ * lambda are those of gmrfx_ga_pullback; bit 1 factorises Q_prior - H(x) through the composite evaluation. No atomics: a workgroup's
+ * partial sum never mixes components (the observations are tiled per component, csrc/kernels.h: GapTiles), a component's partials
+ * are added in the order gmrfx_ga_pullback adds all of them; results are bit-reproducible, the host and the _dev forms agree bit for
+ * bit, and ONE component gives every array, param_bar[0] and *check of gmrfx_ga_pullback after gmrfx_obs_set_design on the same A
+ * bit for bit. Work memory: that of gmrfx_ga_pullback, at most nobs / 16 + ncomp partial sums twice, ncomp results and 12 (ncomp + 1)
+ * bytes of tiling offsets, uploaded on the first call and dropped when the likelihood is replaced; gmrfx_obs_composite_set_param
+ * leaves it.
+ * Errors, in this order: INVALID_ARG for a sharded or batched handle or a handle without a composite (gmrfx_ga_pullback serves the
+ * single-family likelihoods); INVALID_ARG for x or param_bar null, unknown flag bits, mubar and Qbar both null, every array output
+ * null, bit 0 without a constraint; then GMRFX_ERR_NO_DEVICE, GMRFX_ERR_NOT_FACTORIZED and GMRFX_ERR_NOT_POSDEF as
+ * gmrfx_ga_pullback. A refused call leaves the handle as it was.
+ * LIMITS: plain handles (no batched composite); otherwise those of gmrfx_ga_pullback. */
+int32_t gmrfx_ga_pullback_composite(gmrfx_handle *h, const double *x, const double *mu /* nullable */, const double *mubar /* n, nullable */,
+                                    const double *Qbar /* nnz, nullable */, int32_t flags, double *Qbar_prior /* nnz, nullable */,
+                                    double *mubar_prior /* n, nullable */, double *lambda /* n, nullable */,
+                                    double *param_bar /* host, ncomp */, double *check /* host, 1, nullable */);
+int32_t gmrfx_ga_pullback_composite_dev(gmrfx_handle *h, const double *d_x, const double *d_mu, const double *d_mubar, const double *d_Qbar,
+                                        int32_t flags, double *d_Qbar_prior, double *d_mubar_prior, double *d_lambda,
+                                        double *param_bar /* host, ncomp */, double *check /* host, 1, nullable */);
 
 /* ---- Linear-predictor marginals and predictive scores ----------------------------------------------------------------------------------
  * What follows a fit: linear_predictor_marginals(ga, obs_lik) of the reference (src/linear_predictor_marginals.jl:58-195, with the
